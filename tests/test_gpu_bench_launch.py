@@ -22,7 +22,7 @@ def _bench(args, env=None, timeout=900):
 
 def test_plain_command_starts_its_own_ranks():
     common = ["--steps", "2", "--warmup", "1", "--bases", "48e6", "--no-pmc", "--no-cpu-baseline", "--no-e2e", "--no-k31", "--no-full-index"]
-    r = _bench(["--gpus", "2"] + common, env={"MFX_BENCH_REHEARSE": "1"})
+    r = _bench(["--gpus", "2", "--full"] + common, env={"MFX_BENCH_REHEARSE": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
