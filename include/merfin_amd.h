@@ -250,6 +250,39 @@ int mfx_index_export(const mfx_index *ix, uint64_t *kmers, uint32_t *readV, uint
                      uint64_t *n_out);
 
 /* ------------------------------------------------------------------------ */
+/* Read k-mer counting: the read counts of a run straight from its reads     */
+/* (FASTA / FASTQ records), no k-mer database in between.                   */
+/* ------------------------------------------------------------------------ */
+/* The canonical k-mers of the reads (all k bases ACGT, either case: `meryl count` / kmerIterator) are counted on the device
+ * INTO the k-mers the index holds: a held k-mer's read count grows by its occurrences, any other k-mer is dropped.  The
+ * index must be one whose keys are already what the run asks: a sequence-only index (mfx_index_create_for_seq + claim /
+ * count of the assembly), a path-only index (mfx_index_claim_paths), or for 32 <= k <= 64 a table whose k-mers came from
+ * the assembly only.  Its read side must not have taken counts (a database load, an earlier counter), and takes none from any
+ * other source afterwards.  Its assembly side may come before or after for k <= 31 (updates of claimed k-mers); for 32 <= k <= 64
+ * every add claims, so it must come BEFORE begin.  Counts are exact up to 2^32 - 1 (compact layout: a field reaching 2047 moves to
+ * the side table as a database load does it).  After begin the index takes no more claims (MFX_E_INVAL).
+ *   r = mfx_reads_begin(ix, 0);
+ *   for each batch of records:  mfx_reads_add(r, bases, lens, n);   -- returns once the caller's buffers may be reused
+ *   mfx_reads_end(r, &stats);                                        -- waits, checks the table (MFX_E_FULL), frees r
+ * batch_bases: bases per device batch (0: 64 Mi); a read longer than the room left in a batch is split with a k-1 overlap. */
+typedef struct mfx_reads mfx_reads;
+typedef struct mfx_reads_stats {
+  uint64_t reads, bases;     /* records and bases passed in                                   */
+  uint64_t kmers;            /* valid k-mers of those reads (kmerIterator rules)              */
+  uint64_t counted;          /* of those: k-mers the index answers for, added to their count  */
+  uint64_t dropped;          /* the rest: not claimed (error k-mers, other haplotypes, ...)    */
+  uint64_t saturated;        /* k-mers whose read count ended in the side table (a saturated compact field, or a
+                                quotient-form k-mer kept there beyond its candidate lines)                          */
+  double   seconds_kernel, seconds_copy;
+} mfx_reads_stats;
+mfx_reads *mfx_reads_begin(mfx_index *ix, uint64_t batch_bases);
+/* -min / -max of the run (merfin.C:199-200): applied when the counts are looked up, as for a database; default 0, 2^64 - 1 */
+int        mfx_reads_set_filter(mfx_reads *r, uint64_t minV, uint64_t maxV);
+int        mfx_reads_add(mfx_reads *r, const char *const *bases, const uint64_t *lens, uint64_t n);
+/* out may be NULL; r is freed whatever the result */
+int        mfx_reads_end(mfx_reads *r, mfx_reads_stats *out);
+
+/* ------------------------------------------------------------------------ */
 /* Sequences: replaces the loader callback loadSequence (merfin.C:30-53) +  */
 /* merfinInput::{seq,kiter} (merfin-globals.H:64-65).  All contigs are      */
 /* packed into one HBM buffer once; k-mer extraction happens on the device. */

@@ -49,6 +49,11 @@ INDEX_HEADER_BYTES = 128          # MFX_INDEX_HEADER_BYTES
 VARIANT_MODES = {"filter": 4, "polish": 5, "better": 6, "strict": 7, "loose": 8}
 
 
+class _ReadsStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64), ("counted", C.c_uint64),
+                ("dropped", C.c_uint64), ("saturated", C.c_uint64), ("seconds_kernel", C.c_double), ("seconds_copy", C.c_double)]
+
+
 class _HistResult(C.Structure):
     _fields_ = [("kasm", C.c_uint64), ("kmissing", C.c_uint64), ("koverCpy", C.c_double),
                 ("undrMax", C.c_uint32), ("overMax", C.c_uint32),
@@ -81,6 +86,7 @@ SYMBOLS = [
     "mfx_hist_take_overflow", "mfx_hist_report", "mfx_diag_stream_rates",
     "mfx_pack_bases", "mfx_host_threads_share", "mfx_dump_values", "mfx_dump_contig", "mfx_dump_values_sharded", "mfx_dump_contig_sharded", "mfx_variants_run_sharded", "mfx_vcf_load", "mfx_vcf_free", "mfx_variants_run_vcf", "mfx_vcf_prepare", "mfx_vcf_path_bound", "mfx_index_claim_paths", "mfx_vcf_prepare_path_index", "mfx_completeness", "mfx_completeness_pieces", "mfx_variants_run",
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
+    "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
 ]
 
 
@@ -263,6 +269,11 @@ def load_library():
     L.mfx_hist_allreduce.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     L.mfx_hist_allgather_overflow.argtypes = [vp, vp, u64p, C.c_uint64, u64p, vp]
     L.mfx_hist_result_add_overflow.argtypes = [C.POINTER(_HistResult), u64p, C.c_uint64]
+    L.mfx_reads_begin.restype = vp
+    L.mfx_reads_begin.argtypes = [vp, C.c_uint64]
+    L.mfx_reads_set_filter.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.mfx_reads_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
+    L.mfx_reads_end.argtypes = [vp, C.POINTER(_ReadsStats)]
     _lib = L
     return L
 
@@ -564,6 +575,34 @@ class Index:
 
     def count_asm(self, seqs, stream=None):
         _check(load_library().mfx_index_count_asm(self.h, seqs.h, C.c_void_p(stream or 0)))
+
+    def count_reads(self, reads, batch_bases=0, minV=0, maxV=2**64 - 1, chunk=4096):
+        """read counts straight from reads (mfx_reads_begin / add / end): the canonical k-mers of `reads` (bytes or str
+        records, any case, N breaks a k-mer) are added to the read counts of the k-mers this index holds, the others are
+        dropped.  A sequence-only / path-only index (k > 31: a table of the assembly's k-mers) whose read side has no counts
+        yet.  Returns the counter's statistics as a dict."""
+        L = load_library()
+        recs = [x.encode() if isinstance(x, str) else bytes(x) for x in reads]      # (before begin: a bad record leaves the index as it was)
+        r = _need(L.mfx_reads_begin(self.h, int(batch_bases)))
+        rc = L.mfx_reads_set_filter(r, int(minV), int(maxV))
+        for o in range(0, len(recs), chunk):
+            if rc:
+                break
+            part = recs[o:o + chunk]
+            ptrs = (C.c_char_p * len(part))(*part)
+            lens = (C.c_uint64 * len(part))(*[len(x) for x in part])
+            try:
+                rc = L.mfx_reads_add(r, ptrs, lens, len(part))
+            except BaseException:
+                L.mfx_reads_end(r, None)                             # (the counter is always ended: streams and pinned stages freed)
+                raise
+        msg = L.mfx_last_error().decode() if rc else ""
+        st = _ReadsStats()
+        rc_end = L.mfx_reads_end(r, C.byref(st))
+        if rc:
+            raise MfxError(rc, msg)
+        _check(rc_end)
+        return {f: getattr(st, f) for f, _ in _ReadsStats._fields_}
 
     def value(self, kmers):
         kmers = np.ascontiguousarray(kmers, dtype=np.uint64)

@@ -14,7 +14,11 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <mutex>
 #include <unistd.h>
 #include <future>
 #include <thread>
@@ -39,6 +43,8 @@ struct Globals {
   bool nosplit = false, debug = false, skipMissing = false, sharded = false;
   std::vector<uint32_t> copyKmerK;
   std::vector<double> copyKmerP;
+  std::vector<const char *> readsNames;  // -reads: the read counts from these FASTA / FASTQ files instead of -readmers
+  int kArg = 0;                          // -k (0: not given); with -reads: the run's k once the flags are checked
 };
 
 static void usage(const char *exe) {
@@ -54,6 +60,9 @@ static void usage(const char *exe) {
           "    -peak m           haploid k-mer coverage peak (required except -filter)\n"
           "    -prob file        readK,prob rows; row n overrides -peak for multiplicity n\n"
           "    -seqmers db       assembly k-mer database; default: counted from -sequence on the GPU\n"
+          "    -reads file       instead of -readmers: count the read k-mers of this FASTA / FASTQ file (plain, .gz, .bz2, .xz) on\n"
+          "                      the GPU into the k-mers the run asks for; repeatable.  -hist, -dump and the variant modes (k <= 31)\n"
+          "    -k k              k when no database gives it (-reads without -seqmers); must agree with -seqmers\n"
           "    -convert db       no report: rewrite the k-mer database <db> (any accepted form) as -output <file> in the flat form\n"
           "                      (sorted k-mers in delta-coded blocks; loads at the speed of the PCIe link)\n"
           "    -placed           with -convert: the records sorted by their PLACE in the table -hist / -dump build (13 <= k <= 31,\n"
@@ -156,6 +165,8 @@ static void fp_path(uint64_t &h, const char *path) {
 static uint64_t input_fingerprint(const Globals &G, bool seqOnly) {
   uint64_t h = 0xcbf29ce484222325ULL;
   fp_path(h, G.readDBname);
+  for (const char *r : G.readsNames) fp_path(h, r);
+  if (!G.readsNames.empty()) { const uint64_t kk = (uint64_t)G.kArg; fp_mix(h, &kk, sizeof(kk)); fp_mix(h, "reads", 6); }
   fp_path(h, G.seqDBname);
   if (!G.seqDBname || seqOnly) fp_path(h, G.seqName);   // the assembly side is counted from -sequence / the table holds ITS k-mers only
   if (seqOnly) fp_mix(h, "seq-only", 9);
@@ -570,6 +581,109 @@ static bool concat_parts(const std::string &out, const std::vector<std::string> 
   return fclose(o) == 0 && ok;
 }
 
+// -reads: the read counts of the run from its reads, counted on the device into the k-mers the index holds (mfx_reads_*).  One reader
+// thread per file (16 at most at a time) parses records into batches; this thread hands the batches to the counter, which copies them
+// and returns while the device counts, so parsing, transfer and counting overlap.  Returns false with the error printed.
+static bool count_reads_files(const Globals &G, mfx_index *ix) {
+  const auto t0 = std::chrono::steady_clock::now();
+  mfx_reads *rc = mfx_reads_begin(ix, 0);
+  if (!rc || mfx_reads_set_filter(rc, G.minV, G.maxV)) {
+    fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error());
+    if (rc) mfx_reads_end(rc, nullptr);
+    return false;
+  }
+  constexpr uint64_t BATCH_BASES = 16ull << 20;
+  std::mutex mu;
+  std::condition_variable cv_full, cv_room;
+  std::deque<std::vector<SeqRecord>> queue;
+  const size_t nfiles = G.readsNames.size(), nthreads = std::min<size_t>(16, nfiles), max_queued = 2 * nthreads + 2;
+  size_t running = nthreads;
+  std::atomic<size_t> next_file{0};
+  std::atomic<bool> failed{false};
+  std::string why;
+  auto push = [&](std::vector<SeqRecord> &b) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv_room.wait(lk, [&] { return queue.size() < max_queued || failed.load(); });
+    queue.push_back(std::move(b));
+    cv_full.notify_one();
+    b.clear();
+  };
+  std::vector<std::thread> readers;
+  for (size_t t = 0; t < nthreads; ++t)
+    readers.emplace_back([&]() {
+      for (size_t f; !failed.load() && (f = next_file++) < nfiles;) {
+        SeqFile sf(G.readsNames[f]);
+        if (!sf.ok()) {
+          std::lock_guard<std::mutex> lk(mu);
+          why = std::string("cannot open '") + G.readsNames[f] + "'";
+          failed = true;
+          break;
+        }
+        std::vector<SeqRecord> batch;
+        uint64_t held = 0;
+        for (SeqRecord r; sf.next(r); r = SeqRecord()) {
+          held += r.size();
+          batch.push_back(std::move(r));
+          if (held >= BATCH_BASES) { push(batch); held = 0; }
+          if (failed.load()) break;
+        }
+        if (!batch.empty()) push(batch);
+        if (sf.finish() != 0) {
+          std::lock_guard<std::mutex> lk(mu);
+          why = std::string("reading '") + G.readsNames[f] + "' failed (read error, or the decompressor exited with an error)";
+          failed = true;
+        }
+      }
+      std::lock_guard<std::mutex> lk(mu);
+      --running;
+      cv_full.notify_all();
+    });
+  double t_wait = 0, t_submit = 0;
+  std::vector<const char *> ptrs;
+  std::vector<uint64_t> lens;
+  while (true) {
+    std::vector<SeqRecord> b;
+    {
+      const auto tw = std::chrono::steady_clock::now();
+      std::unique_lock<std::mutex> lk(mu);
+      cv_full.wait(lk, [&] { return !queue.empty() || running == 0; });
+      t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
+      if (queue.empty()) break;
+      b = std::move(queue.front());
+      queue.pop_front();
+      cv_room.notify_one();
+    }
+    if (failed.load()) continue;                                   // (drain: the readers finish their pushes)
+    ptrs.resize(b.size());
+    lens.resize(b.size());
+    for (size_t i = 0; i < b.size(); ++i) { ptrs[i] = b[i].data(); lens[i] = b[i].size(); }
+    const auto ts = std::chrono::steady_clock::now();
+    const int arc = mfx_reads_add(rc, ptrs.data(), lens.data(), b.size());
+    t_submit += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    if (arc) {
+      std::lock_guard<std::mutex> lk(mu);
+      why = mfx_last_error();
+      failed = true;
+      cv_room.notify_all();
+    }
+  }
+  for (auto &t : readers) t.join();
+  mfx_reads_stats st;
+  const int erc = mfx_reads_end(rc, &st);
+  if (failed.load() || erc) {
+    fprintf(stderr, "ERROR: counting -reads: %s\n", failed.load() ? why.c_str() : mfx_last_error());
+    return false;
+  }
+  const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu counted, %lu dropped.\n", G.kArg, (unsigned long)st.reads,
+          (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)st.counted, (unsigned long)st.dropped);
+  if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
+    fprintf(stderr, "-- reads: %.3f s wall = %.3f s waiting for parsed records + %.3f s batching / encoding / waiting for a stage; device %.3f s kernel + "
+                    "%.3f s copy (idle %.0f %% of the wall)\n", wall, t_wait, t_submit, st.seconds_kernel, st.seconds_copy,
+            wall > 0 ? 100.0 * std::max(0.0, 1.0 - (st.seconds_kernel + st.seconds_copy) / wall) : 0.0);
+  return true;
+}
+
 #define DIE_MFX(what)                                                       \
   do {                                                                      \
     fprintf(stderr, "ERROR: %s: %s\n", what, mfx_last_error());             \
@@ -589,6 +703,14 @@ int main(int argc, char **argv) {
     if (is("-sequence")) G.seqName = val();
     else if (is("-seqmers")) G.seqDBname = val();
     else if (is("-readmers")) G.readDBname = val();
+    else if (is("-reads")) G.readsNames.push_back(val());
+    else if (is("-k")) {
+      const char *v = val();
+      char *e = nullptr;
+      const long kk = strtol(v, &e, 10);
+      G.kArg = (e != v && *e == 0 && kk >= 1 && kk <= 64) ? (int)kk : -1;
+      if (G.kArg < 0) err.push_back(std::string("Invalid -k '") + v + "': k is 1 to 64.\n");
+    }
     else if (is("-peak")) G.peak = strtod(val(), nullptr);
     else if (is("-prob")) G.pLookupTable = val();
     else if (is("-vcf")) G.vcfName = val();
@@ -637,6 +759,35 @@ int main(int argc, char **argv) {
     else err.push_back(std::string("Unknown option '") + argv[arg] + "'.\n");
   }
 
+  // -reads: every check before any device is touched
+  const bool fromReads = !G.readsNames.empty();
+  const bool variantFlag = G.reportType == OP_POLISH || G.reportType == OP_FILTER || G.reportType == OP_BETTER ||
+                           G.reportType == OP_STRICT || G.reportType == OP_LOOSE;
+  if (fromReads) {
+    if (G.convertName) err.push_back("-convert rewrites a k-mer database; it does not take -reads.\n");
+    if (G.readDBname) err.push_back("-reads and -readmers cannot be combined: the read counts come from one source.\n");
+    if (G.reportType == OP_COMPL) err.push_back("-completeness needs every read k-mer: it takes a read database (-readmers), not -reads.\n");
+    if (G.sharded) err.push_back("-sharded does not take -reads (give the read database with -readmers).\n");
+    if (G.kArg == 0 && !G.seqDBname) err.push_back("-reads needs -k (or -seqmers, whose k it then takes).\n");
+    for (const char *f : G.readsNames) {
+      struct stat rst;
+      if (stat(f, &rst) != 0 || !S_ISREG(rst.st_mode) || access(f, R_OK) != 0)
+        err.push_back(std::string("Cannot read the -reads file '") + f + "'.\n");
+    }
+    if (variantFlag && (G.indexName || G.devices.size() > 1))
+      err.push_back("The variant modes count -reads into the path-only index of the call set: one device, no -index.\n");
+    if (G.seqDBname && !G.convertName && !G.readDBname) {
+      mfx_db_info sdb;
+      if (mfx_db_probe(G.seqDBname, &sdb)) DIE_MFX("opening -seqmers");
+      if (G.kArg > 0 && sdb.k != G.kArg) err.push_back("-k " + std::to_string(G.kArg) + " disagrees with -seqmers, which holds " + std::to_string(sdb.k) + "-mers.\n");
+      else G.kArg = sdb.k;
+    }
+    if (variantFlag && G.kArg > 31)
+      err.push_back("The variant modes count -reads into the path-only index, which holds k <= 31 (here k = " + std::to_string(G.kArg) + ").\n");
+  }
+
+  if (G.kArg > 0 && G.readDBname && !fromReads) err.push_back("-k is taken from -readmers; give -k only with -reads.\n");
+
   if (G.convertName && err.empty()) {
     // merfin -convert <db> -output <file>: a database in any accepted form rewritten as this program's flat form (sorted
     // k-mers in delta-coded blocks), on the host -- no report, no device
@@ -666,7 +817,7 @@ int main(int argc, char **argv) {
   if (G.reportType == OP_COMPL && !G.seqName && !G.seqDBname)
     err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
   if (G.reportType == OP_NONE) err.push_back("No report type (-filter, -polish, -hist, -dump, -completeness) supplied.\n");
-  if (!G.readDBname) err.push_back("No read meryl database (-readmers) supplied.\n");
+  if (!G.readDBname && !fromReads) err.push_back("No read meryl database (-readmers) supplied.\n");
   if (!err.empty()) {
     usage(argv[0]);
     for (auto &e : err) fputs(e.c_str(), stderr);
@@ -706,8 +857,9 @@ int main(int argc, char **argv) {
 
   // load_Kmers, merfin-globals.C:114-163: the read DB defines k
   mfx_db_info rdb, adb;
-  if (mfx_db_probe(G.readDBname, &rdb)) DIE_MFX("opening -readmers");
-  const int k = rdb.k;
+  memset(&rdb, 0, sizeof(rdb));
+  if (!fromReads && mfx_db_probe(G.readDBname, &rdb)) DIE_MFX("opening -readmers");
+  const int k = fromReads ? G.kArg : rdb.k;                       // (-reads: -k, or the k of -seqmers, checked above)
   memset(&adb, 0, sizeof(adb));
   if (G.seqDBname) {
     if (mfx_db_probe(G.seqDBname, &adb)) DIE_MFX("opening -seqmers");
@@ -778,9 +930,13 @@ int main(int argc, char **argv) {
     const char *vs = getenv("MFX_VARIANT_SLOTS");
     const size_t slots = (vs && atoi(vs) > 0) ? (size_t)atoi(vs) : G.devices.size();
     const char *pe = getenv("MFX_CLI_PATH_INDEX"), *pa = getenv("MFX_CLI_VCF_AHEAD");
-    const bool can = variantMode && G.vcfName && G.seqName && slots == 1 && !G.sharded && k <= 31 && !G.indexName && !(pa && atoi(pa) == 0) &&
-                     !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")));
-    if (can && pe) pathOnly = atoi(pe) != 0;
+    const bool can = variantMode && G.vcfName && G.seqName && slots == 1 && !G.sharded && k <= 31 && !G.indexName &&
+                     (fromReads || (!(pa && atoi(pa) == 0) && !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")))));
+    if (fromReads && variantMode) {
+      // (the reads are counted into the k-mers the call set's paths ask for: there is no read database for the full tables)
+      if (!can) { fprintf(stderr, "ERROR: the variant modes count -reads into the path-only index of the call set, which this run cannot take.\n"); return 1; }
+      pathOnly = true;
+    } else if (can && pe) pathOnly = atoi(pe) != 0;
     else if (can) {
       const uint64_t capacity = rdb.n_kmers + (G.seqDBname ? adb.n_kmers : bases_upper_bound(G.seqName)) + 1024;
       const double fullGB = mfx_index_estimate_gb(k, capacity);
@@ -825,8 +981,9 @@ int main(int argc, char **argv) {
   // merfin-dump.C:44-61): they get a SEQUENCE-ONLY index -- the sequence's k-mers are claimed first, the databases only
   // update those (half of a 30x human read database, the error k-mers, never gets a slot; k <= 21: 8-byte slots).  The
   // other report types need the whole read database.  MFX_CLI_FULL_INDEX=1 builds the full tables for every type.
+  // (-reads: always -- the reads are counted into claimed k-mers; there is no read database for the full tables)
   bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP) && !G.sharded && k <= 31 &&
-                 !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")));
+                 (fromReads || !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX"))));
   const char *ov = getenv("MFX_CLI_OVERLAP");
   const bool compressed = G.seqName && mfx_suffix_tool(G.seqName) != nullptr;
   const bool wantOverlap = ov ? atoi(ov) != 0 : compressed;
@@ -924,7 +1081,7 @@ int main(int argc, char **argv) {
     if (!ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
     mfx_index_info info;
     if (mfx_index_get_info(ix, &info)) DIE_MFX("reading the index image");
-    if (info.k != k) { fprintf(stderr, "ERROR: the index image holds %d-mers but -readmers holds %d-mers.\n", info.k, k); return 1; }
+    if (info.k != k) { fprintf(stderr, "ERROR: the index image holds %d-mers but %s %d-mers.\n", info.k, fromReads ? "the run counts" : "-readmers holds", k); return 1; }
     uint64_t fp = 0, imin = 0, imax = 0;
     if (mfx_index_get_origin(ix, &fp, &imin, &imax)) DIE_MFX("reading the index image");
     if (seqOnly && info.seq_only == 0 && fp == fingerprintFull && imin == G.minV && imax == G.maxV) {
@@ -984,7 +1141,10 @@ int main(int argc, char **argv) {
         if (mfx_index_count_claimed(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
         step("count the sequence's k-mers");
       }
-      if (!lrc) {
+      if (!lrc && fromReads) {
+        if (!count_reads_files(G, ix)) return 1;
+        step("count -reads");
+      } else if (!lrc) {
         fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
         lrc = stage ? mfx_index_load_db_staged(ix, stage, 0, G.minV, G.maxV) : mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV);
         if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -readmers");
@@ -999,6 +1159,7 @@ int main(int argc, char **argv) {
     // (the staged bytes are not needed by the run; a fall-back to the full tables reads the files)
     if (stage) { mfx_db_stage_free(stage); stage = nullptr; }
     if (stageAsm) { mfx_db_stage_free(stageAsm); stageAsm = nullptr; }
+    if (!ix && fromReads) { fprintf(stderr, "ERROR: -reads needs the path-only index of the call set, which could not be built.\n"); return 1; }
     if (!ix) pathOnly = false;                                      // (the prepared call set runs on the full tables as well)
   }
   if (!ix && seqOnly) {
@@ -1030,6 +1191,10 @@ int main(int argc, char **argv) {
       lrc = mfx_index_load_db(ix, G.seqDBname, 1, 0, ~0ull);
       if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -seqmers");
       step("load -seqmers");
+    } else if (fromReads) {
+      fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
+      if (mfx_index_count_asm(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
+      step("count the sequence's k-mers");
     } else {
       // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186)
       fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
@@ -1041,7 +1206,11 @@ int main(int argc, char **argv) {
       step("count the sequence's k-mers + load -readmers");
       fused = true;
     }
-    if (!lrc && !fused) {
+    if (lrc == MFX_E_NONCANON && fromReads) { fprintf(stderr, "ERROR: -reads needs a canonical -seqmers database.\n"); return 1; }
+    if (!lrc && fromReads) {
+      if (!count_reads_files(G, ix)) return 1;
+      step("count -reads");
+    } else if (!lrc && !fused) {
       fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
       lrc = mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV);
       if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -readmers");
@@ -1080,8 +1249,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "\n%s\n\n", mfx_last_error());
         return 1;
       }
-      fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
-      if (mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV)) DIE_MFX("loading -readmers");
+      if (!fromReads) {
+        fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
+        if (mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV)) DIE_MFX("loading -readmers");
+      }
       if (G.seqDBname) {
         fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.seqDBname);
         if (mfx_index_load_db(ix, G.seqDBname, 1, 0, ~0ull)) DIE_MFX("loading -seqmers");
@@ -1102,6 +1273,8 @@ int main(int argc, char **argv) {
       fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
       if (mfx_index_count_asm(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
     }
+    // -reads (k > 31: this table holds the assembly's k-mers only; the reads update them)
+    if (fromReads && !count_reads_files(G, ix)) return 1;
     if (G.indexName) {
       fprintf(stderr, "-- Writing the index image '%s'.\n", G.indexName);
       if (mfx_index_set_fingerprint(ix, fingerprint) || mfx_index_save(ix, G.indexName)) DIE_MFX("writing the index image");

@@ -525,6 +525,15 @@ static int index_check(mfx_index *ix) {
   return MFX_OK;
 }
 
+int mfx_index_check(mfx_index *ix) { return index_check(ix); }
+
+// a table of 32 <= k <= 64 claims whatever it is given (mfx_wide.hip): once reads were counted into it, a k-mer it took now would lack
+// their counts -- its assembly side comes before mfx_reads_begin
+int mfx_reads_claim_error(const mfx_index *ix, const char *who) {
+  return mfx_fail(MFX_E_INVAL, "%s: reads were counted into this table of %d-mers (mfx_reads_begin); a table of k > %d claims every k-mer it is "
+                  "given, and one claimed now would lack the reads' counts -- give the assembly side before the reads", who, ix->k, MFX_MAX_K_NARROW);
+}
+
 // Host -> table pipeline.  LANES of pinned staging are filled by the host and emptied over PCIe into a RING of device
 // buffers; the insert kernel of a chunk runs on the device buffer.  The two are decoupled (round 4): a lane is free again
 // as soon as its chunk has crossed the link, a device buffer once its chunk is inserted -- so the transfers run ahead of
@@ -652,6 +661,8 @@ static int index_ingest_chunks(mfx_index *const *ixs, uint32_t nix, uint64_t n_h
   double t_wait = 0, t_fill = 0;
   uint64_t nchunks = 0, nbytes = 0;
   std::vector<mfx_ingest *> gs(nix, nullptr);
+  for (uint32_t i = 0; i < nix; ++i)
+    if (ixs[i]->reads_counted && ixs[i]->wide()) return mfx_reads_claim_error(ixs[i], "mfx_index_add / load");
   for (uint32_t i = 0; i < nix; ++i) {
     DevGuard dg(ixs[i]->device);
     ixs[i]->frozen = true;                                  // a sequence-only index takes no more claims once counts arrive
@@ -756,6 +767,9 @@ static int index_ingest(mfx_index *ix, uint64_t n, int side, Fill &&fill) {
 }
 
 static int set_read_filter(mfx_index *ix, uint64_t minV, uint64_t maxV) {
+  if (ix->reads_counted)
+    return mfx_fail(MFX_E_INVAL, "mfx_index_add_read / load: the read side of this index was counted from reads (mfx_reads_begin); an index takes its "
+                    "read counts from one source");
   if (ix->filter_set && (ix->minV != minV || ix->maxV != maxV))
     return mfx_fail(MFX_E_INVAL, "mfx_index_add_read: -min/-max must be the same for every batch of one index");
   ix->minV = minV; ix->maxV = maxV; ix->filter_set = true;
@@ -884,6 +898,7 @@ int mfx_index_add_delta_file(mfx_index *const *ixs, uint32_t nix, int fd, const 
 
 static int index_add(mfx_index *ix, const uint64_t *kmers, const uint32_t *values, uint64_t n, int side, int on_device) {
   if (!ix || (n && (!kmers || !values))) return mfx_fail(MFX_E_INVAL, "mfx_index_add: null argument");
+  if (ix->reads_counted && ix->wide()) return mfx_reads_claim_error(ix, "mfx_index_add");
   DevGuard g(ix->device);
   const size_t kw = ix->key_words();                      // uint64 words per k-mer (2 for k > 31)
   auto table_add = [&](const uint64_t *dk, const uint32_t *dv, uint64_t m, hipStream_t s) {
@@ -905,6 +920,9 @@ static int index_add(mfx_index *ix, const uint64_t *kmers, const uint32_t *value
 extern "C" int mfx_index_add_read(mfx_index *ix, const uint64_t *kmers, const uint32_t *values, uint64_t n,
                                   uint64_t minV, uint64_t maxV, int on_device) {
   if (!ix) return mfx_fail(MFX_E_INVAL, "mfx_index_add_read: null index");
+  if (ix->reads_counted)
+    return mfx_fail(MFX_E_INVAL, "mfx_index_add_read: the read side of this index was counted from reads (mfx_reads_begin); an index takes its "
+                    "read counts from one source");
   if (ix->filter_set && (ix->minV != minV || ix->maxV != maxV))
     return mfx_fail(MFX_E_INVAL, "mfx_index_add_read: -min/-max must be the same for every batch of one index");
   ix->minV = minV;
@@ -924,6 +942,7 @@ extern "C" int mfx_index_add_asm(mfx_index *ix, const uint64_t *kmers, const uin
 static int index_count(mfx_index *ix, const mfx_seq *seq, int count, void *stream, const char *who, bool defer = false, bool no_wait = false) {
   if (!ix || !seq) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
   if (ix->device != seq->device) return mfx_fail(MFX_E_INVAL, "index and sequence live on different devices");
+  if (ix->reads_counted && ix->wide()) return mfx_reads_claim_error(ix, who);
   if (ix->seq_only && ix->frozen && count != 2)
     return mfx_fail(MFX_E_INVAL, "%s: this sequence-only index already took counts; its k-mers must all be claimed before the first add / load "
                     "(a k-mer claimed now would have missed them)", who);

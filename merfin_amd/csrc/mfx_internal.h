@@ -55,6 +55,9 @@ int  mfx_index_add_delta_file(struct mfx_index *const *ixs, uint32_t nix, int fd
 int  mfx_index_add_multi(struct mfx_index *const *ixs, uint32_t nix, const uint64_t *kmers, const uint32_t *values, uint64_t n, int side,
                          uint64_t minV, uint64_t maxV);
 void mfx_index_ingest_release(struct mfx_index *ix);
+// the table's state after a load (probe-limit failures: MFX_E_FULL, damaged records, non-canonical k-mers); bumps ix->version
+int  mfx_index_check(struct mfx_index *ix);
+int  mfx_reads_claim_error(const struct mfx_index *ix, const char *who);     // MFX_E_INVAL: a claim into a k > 31 table after its read counter began
 // a delta-coded flat database opened for the staged load (mfx_db.cpp; mfx_api.cpp: mfx_db_stage)
 struct mfx_flat_delta_info { int k = 0, placed = 0; uint64_t n = 0, n_escape = 0, nblocks = 0, escapes_off = 0, fsize = 0; };
 void mfx_place_keys_host(int k, const uint64_t *kmers, uint64_t n, uint64_t *out, uint8_t *sbits_out = nullptr);      // mfx_db.cpp: P (mfx_place.h) of canonical k-mers, host threads; k = 31: P >> 1 and the strand bits
@@ -165,6 +168,7 @@ struct mfx_index {
   bool      compact = false;    // seq_only, k <= 31: 8-byte slots, 16 per line (mfx_table_view)
   bool      quot = false;       // compact, k > 21: quotient form of the key field
   bool      frozen = false;     // an add / load happened: no more claims
+  bool      reads_counted = false;   // a read counter (mfx_reads_begin) owns the read side: no database on it, and no more k-mers of any kind
   uint64_t  side_nlines = 0;    // compact: lines of the side table, which follows the nlines main lines in d_slots
   uint64_t  paths_token = 0;    // seq_only: the k-mers are those of a prepared VCF's PATHS (mfx_index_claim_paths), not a sequence's: the token of that call set
   uint32_t  seq_digest = 0;     // seq_only: content digest of the sequence the k-mers were claimed from (0: not recorded);

@@ -103,6 +103,18 @@ struct mfx_count_args {
   int             count = 1;          // 1: asmV += 1 per occurrence (`meryl count`); 0: claim the k-mers only (sequence-only index); 2: asmV += 1 for the k-mers claimed BEFORE, no claims
 };
 
+// one batch of reads for the read k-mer counter (mfx_reads_kernel / mfx_w_reads_kernel): the planes of mfx_pack_bases, reads back to
+// back with one invalid base between two; room for whole tiles + the halo ((npos + MFX_TILE - 1) / MFX_TILE * 128 + MFX_TILE_WORDS words,
+// invalid beyond npos)
+struct mfx_reads_args {
+  mfx_table_view  t;
+  const uint64_t *codes;
+  const uint32_t *valid;
+  uint64_t        npos;               // base positions of the batch (separators included)
+  uint64_t       *meta;               // the index's meta words (side-table claims that hit the probe limit: [2])
+  uint64_t       *stats;              // [4] += valid k-mers, k-mers added to a claimed k-mer, k-mers dropped, k-mers whose read count moved to the side table (or arrived in it)
+};
+
 // varMer::score of the paths of a batch (mfx_var_score_kernel): everything device memory
 struct mfx_var_score_args {
   const uint8_t  *text;               // the packed path text (every path followed by '\n')
@@ -176,5 +188,7 @@ hipError_t mfx_k_pack(const uint8_t *bases, uint64_t *codes, uint32_t *valid, ui
 hipError_t mfx_k_unpack(const uint64_t *codes, const uint32_t *valid, uint8_t *bases, uint64_t nwords, hipStream_t st);
 hipError_t mfx_k_valid_scatter(uint32_t *valid, const uint64_t *exc, uint32_t n, hipStream_t st);     // exc[i] = word index | word << 32
 hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st);
+hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st);        // k <= 31: sequence-only / path-only index (every layout)
+hipError_t mfx_kw_reads(const mfx_reads_args &a, hipStream_t st);       // 32 <= k <= 64 (mfx_wide.hip)
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);

@@ -3387,6 +3387,195 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_count_kernel(mfx_count_args a) 
 }
 
 // ===========================================================================
+// read k-mer counting (-reads, mfx_reads_*): the canonical k-mers of a batch of reads -- packed back to back into the planes
+// of mfx_pack_bases, one invalid base between two reads -- added to the READ counts of the k-mers the index holds.  Nothing
+// is claimed: a k-mer the index does not hold is dropped and counted as such.  The batch is cut into MFX_TILE tiles with
+// the k-1 halo whatever the read lengths, so every tile is full.
+//
+// Equal keys of one wave are summed before the add: homopolymer runs, (TTAGGG)n and satellite arrays send up to 64 equal
+// keys through one wave instruction, and the compact layout's add is a compare-and-swap loop on one word.  Each lane writes
+// its lane number into a 256-entry table of its wave at a hash of its key and reads back who holds that entry; a lane whose
+// holder has the same key folds its 1 into the holder's count (LDS atomic) and adds nothing itself.  Equal keys always meet
+// in one entry, so a wave issues one add per distinct key, except where another key took that entry (then both add alone).
+// Keys that repeat inside a wave are summed again per tile in a block table (mfx_reads_kernel).
+// ===========================================================================
+
+// counts[read] += v of a compact slot, as mfx_c_add(side 0); true when THIS add moved the field to the side table
+__device__ __forceinline__ bool mfx_c_add_read(const mfx_table_view &c, unsigned long long *w, unsigned long long cur, uint64_t key, uint32_t v,
+                                               uint64_t *meta) {
+  uint32_t amount;
+  bool moved = false;
+  while (true) {
+    const uint32_t f = (uint32_t)(cur >> 11) & MFX_CSAT;
+    if (f == MFX_CSAT) { amount = v; break; }
+    const uint64_t sum = (uint64_t)f + v;
+    const unsigned long long nw = sum >= MFX_CSAT ? (cur | ((unsigned long long)MFX_CSAT << 11)) : cur + ((unsigned long long)v << 11);
+    const unsigned long long old = atomicCAS(w, cur, nw);
+    if (old == cur) {
+      if (sum < MFX_CSAT) return false;
+      amount = (uint32_t)sum;
+      moved = true;
+      break;
+    }
+    cur = old;
+  }
+  uint32_t side_fresh = 0;
+  mfx_slot *sl = mfx_claim(mfx_side_view(c), key, meta, side_fresh);
+  if (sl) atomicAdd(&sl->readV, amount);
+  return moved;
+}
+
+// the slot of `key` in a 16-byte-slot sequence-only table, or nullptr (never claimed).  No claim runs beside the read counter
+// (the index is frozen), so the keys seen by plain loads are final.  One slot at a time (as the *_lean helpers): the whole-line
+// forms hold 32 registers of slots in flight, and a kernel's allocation is set by its hungriest path.
+__device__ __forceinline__ mfx_slot *mfx_reads_find16(const mfx_table_view &t, uint64_t key) {
+  const mfx_probe pr = mfx_home(t, key);
+  for (uint32_t d = 0; d < MFX_MAX_LINES; ++d) {
+    mfx_slot *ln = t.slots + mfx_probe_line(t, pr, d) * MFX_SLOTS_LINE;
+    bool any_empty = false;
+#pragma unroll 1
+    for (uint32_t q = 0; q < MFX_SLOTS_LINE; ++q) {
+      const uint4 s = *reinterpret_cast<const uint4 *>(ln + q);
+      const uint64_t sk = (uint64_t)s.x | ((uint64_t)s.y << 32);
+      if (sk == key) return ln + q;
+      any_empty |= sk == MFX_EMPTY;
+    }
+    if (any_empty) break;
+  }
+  return nullptr;
+}
+
+// the compact slot of a k-mer from candidate line 0 on (mfx_c_find, one mini-bucket at a time): its word in `word`, or nullptr
+__device__ __forceinline__ unsigned long long *mfx_reads_cfind(const mfx_table_view &c, const mfx_probe &pr, unsigned long long &word, bool &beyond) {
+  unsigned long long *cs = reinterpret_cast<unsigned long long *>(c.slots);
+  beyond = false;
+  const uint32_t dmax = mfx_c_maxlines(c);
+  for (uint32_t d = 0; d < dmax; ++d) {
+    unsigned long long *base = cs + mfx_probe_line(c, pr, d) * MFX_CSLOTS_LINE;
+    const uint64_t key = mfx_c_keyat(c, pr.fkey, d);
+    bool any_empty = false;
+#pragma unroll 1
+    for (uint32_t q = 0; q < MFX_CSLOTS_LINE; q += 2) {
+      const uint4 s = *reinterpret_cast<const uint4 *>(base + q);
+      const uint64_t x = (uint64_t)s.x | ((uint64_t)s.y << 32), y = (uint64_t)s.z | ((uint64_t)s.w << 32);
+      if (x != MFX_EMPTY && (x >> 22) == key) { word = x; return base + q; }
+      if (y != MFX_EMPTY && (y >> 22) == key) { word = y; return base + q + 1; }
+      any_empty |= (x == MFX_EMPTY) || (y == MFX_EMPTY);
+    }
+    if (any_empty) return nullptr;
+  }
+  beyond = c.quot != 0;
+  return nullptr;
+}
+
+// readV += v of the claimed k-mer `key`, or a counted drop; n_side: the k-mer's read count moved to (or lives in) the side table
+__device__ __forceinline__ void mfx_reads_add(const mfx_reads_args &a, uint64_t key, uint32_t v, uint64_t &n_counted, uint64_t &n_dropped,
+                                              uint64_t &n_side) {
+  bool hit = false;
+  if (a.t.compact) {
+    // the first mini-bucket of the k-mer's order answers for most (mfx_count_kernel, count == 2)
+    const mfx_probe pr = mfx_home(a.t, key);
+    unsigned long long *mb = reinterpret_cast<unsigned long long *>(a.t.slots) + mfx_probe_line(a.t, pr, 0) * MFX_CSLOTS_LINE + 2u * pr.b0;
+    const uint4 s4 = *reinterpret_cast<const uint4 *>(mb);
+    const uint64_t x = (uint64_t)s4.x | ((uint64_t)s4.y << 32), y = (uint64_t)s4.z | ((uint64_t)s4.w << 32);
+    unsigned long long *w = nullptr;
+    unsigned long long cur = 0;
+    bool beyond = false;
+    if (x == MFX_EMPTY) { }
+    else if ((x >> 22) == pr.fkey) { w = mb; cur = x; }
+    else if (y == MFX_EMPTY) { }
+    else if ((y >> 22) == pr.fkey) { w = mb + 1; cur = y; }
+    else w = mfx_reads_cfind(a.t, pr, cur, beyond);
+    if (w) {
+      hit = true;
+      if (mfx_c_add_read(a.t, w, cur, key, v, a.meta)) ++n_side;
+    } else if (beyond) {                                       // quotient form: beyond its candidate lines, under its full key in the side table
+      mfx_slot *ss = mfx_find_slot(mfx_side_view(a.t), key);
+      if (ss) {
+        hit = true;
+        if (atomicAdd(&ss->readV, v) == 0u) ++n_side;           // (its first read count)
+      }
+    }
+  } else {
+    mfx_slot *sl = mfx_reads_find16(a.t, key);
+    if (sl) { hit = true; atomicAdd(&sl->readV, v); }
+  }
+  if (hit) n_counted += v; else n_dropped += v;
+}
+
+// Keys that repeat inside a wave (the wave fold gave a lane v >= 2) are low-complexity sequence: the same few k-mers fill the
+// whole tile, and one add per wave and key still sends every wave of the device to the same words.  Those keys are summed
+// once more per tile in a block table (LDS) and added when the tile ends; i.i.d. reads almost never take this path.
+constexpr uint32_t MFX_READS_BT = 256;                         // entries of the block table (a power of two)
+
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ uint32_t s_own[MFX_BLOCK / 64][256];             // per wave: the lane that holds the entry of a key hash
+  __shared__ uint32_t s_fold[MFX_BLOCK];                       // per lane: equal keys of its wave folded into it
+  __shared__ unsigned long long s_bk[MFX_READS_BT];            // block table: keys (MFX_EMPTY: free) ...
+  __shared__ uint32_t s_bv[MFX_READS_BT];                      // ... and their occurrences in this tile
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const int k = a.t.k;
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  uint64_t n_kmers = 0, n_counted = 0, n_dropped = 0, n_side = 0;
+  for (uint32_t j = tid; j < MFX_READS_BT; j += MFX_BLOCK) { s_bk[j] = MFX_EMPTY; s_bv[j] = 0u; }
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t pos0 = tile * MFX_TILE;
+    const uint32_t n = a.npos - pos0 < MFX_TILE ? (uint32_t)(a.npos - pos0) : MFX_TILE;
+    __syncthreads();
+    mfx_tile_fill_packed(L, a.codes + (pos0 >> 5), a.valid + (pos0 >> 5));
+    __syncthreads();
+    for (uint32_t b = 0; b < MFX_TILE / MFX_BLOCK; ++b) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile (block-uniform)
+      const uint32_t p = b * MFX_BLOCK + tid;
+      uint64_t f;
+      const bool ok = mfx_tile_kmer(L, k, p, f) && p < n;
+      const uint64_t r = mfx_revcomp(f, k);
+      const uint64_t key = f < r ? f : r;
+      uint32_t v = ok ? 1u : 0u;
+      n_kmers += v;
+      // ---- fold the wave's equal keys into one lane each (every lane takes part: the shuffle reads any lane)
+      const uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 56);
+      s_fold[tid] = 0u;
+      if (ok) s_own[wv][h] = lane;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const uint32_t o = ok ? s_own[wv][h] : lane;
+      const uint64_t ko = __shfl(key, (int)o, 64);
+      if (ok && o != lane && ko == key) { atomicAdd(&s_fold[wv * 64u + o], 1u); v = 0u; }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (v) v += s_fold[tid];
+      __builtin_amdgcn_wave_barrier();                         // (s_fold / s_own are written again by the next step)
+      if (v >= 2u) {                                           // ---- a repeated key: into the block table (full: added now)
+        for (uint32_t q = 0, j = h; q < 8u; ++q, j = (j + 1u) & (MFX_READS_BT - 1u)) {
+          const unsigned long long prev = atomicCAS(&s_bk[j], (unsigned long long)MFX_EMPTY, (unsigned long long)key);
+          if (prev == MFX_EMPTY || prev == key) { atomicAdd(&s_bv[j], v); v = 0u; break; }
+        }
+      }
+      if (v) mfx_reads_add(a, key, v, n_counted, n_dropped, n_side);
+    }
+    __syncthreads();                                           // ---- the tile's block table goes to the index
+    for (uint32_t j = tid; j < MFX_READS_BT; j += MFX_BLOCK) {
+      const unsigned long long key = s_bk[j];
+      if (key == MFX_EMPTY) continue;
+      const uint32_t v = s_bv[j];
+      s_bk[j] = MFX_EMPTY;
+      s_bv[j] = 0u;
+      mfx_reads_add(a, key, v, n_counted, n_dropped, n_side);
+    }
+  }
+  n_kmers = mfx_wave_sum(n_kmers); n_counted = mfx_wave_sum(n_counted);
+  n_dropped = mfx_wave_sum(n_dropped); n_side = mfx_wave_sum(n_side);
+  if (lane == 0) {
+    if (n_kmers) atomicAdd((unsigned long long *)&a.stats[0], (unsigned long long)n_kmers);
+    if (n_counted) atomicAdd((unsigned long long *)&a.stats[1], (unsigned long long)n_counted);
+    if (n_dropped) atomicAdd((unsigned long long *)&a.stats[2], (unsigned long long)n_dropped);
+    if (n_side) atomicAdd((unsigned long long *)&a.stats[3], (unsigned long long)n_side);
+  }
+}
+
+// ===========================================================================
 // -completeness: one streaming pass over the joint table
 // (merfin-completeness.C:70-117; asm-only k-mers are skipped, :106-109; the
 // raw read value is used -- -min/-max do not apply there).
@@ -3683,5 +3872,11 @@ hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st) {
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st) {
   mfx_completeness_kernel<<<grid, MFX_BLOCK, 0, st>>>(t, peak, n_prob, probK, probP, partials);
+  return hipGetLastError();
+}
+hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st) {
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (ntiles == 0) return hipSuccess;
+  mfx_reads_kernel<<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }

@@ -371,6 +371,52 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_count_kernel(mfx_count_args a
   mfx_w_meta_flush(a.meta, fresh, 0u);
 }
 
+// read k-mer counting (mfx_reads_*; mfx_kernels.hip: mfx_reads_kernel): readV += 1 per occurrence of a k-mer the table holds,
+// nothing claimed.  Per lane, as the rest of this path; read counts are 32-bit here, nothing saturates.
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_reads_kernel(mfx_reads_args a) {
+  __shared__ mfx_tile_lds L;
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  uint64_t n_kmers = 0, n_counted = 0;
+  mfx_wslot *S = mfx_w_slots(a.t);
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t pos0 = tile * MFX_TILE;
+    const uint32_t n = a.npos - pos0 < MFX_TILE ? (uint32_t)(a.npos - pos0) : MFX_TILE;
+    __syncthreads();
+    mfx_tile_fill_packed(L, a.codes + (pos0 >> 5), a.valid + (pos0 >> 5));
+    __syncthreads();
+    for (uint32_t b = 0; b < MFX_TILE / MFX_BLOCK; ++b) {
+      const uint32_t p = b * MFX_BLOCK + tid;
+      mfx_u128 f;
+      if (!(p < n && mfx_w_tile_kmer(L, k, p, f))) continue;
+      ++n_kmers;
+      const mfx_u128 r = mfx_w_revcomp(f, k);
+      const mfx_u128 key = f < r ? f : r;
+      const uint64_t lo = (uint64_t)key, hi = (uint64_t)(key >> 64);
+      uint32_t q0;
+      uint64_t line = mfx_w_home(a.t, key, q0);
+      for (uint32_t d = 0; d < MFX_W_MAX_LINES; ++d) {       // the k-mer's slot order (mfx_w_lookup_from); the table is frozen: every state is 0 or 2
+        mfx_wslot *ln = S + line * MFX_WSLOTS_LINE;
+        bool end = false;
+        for (uint32_t qi = 0; qi < MFX_WSLOTS_LINE && !end; ++qi) {
+          mfx_wslot *sl = ln + ((q0 + qi) & (MFX_WSLOTS_LINE - 1u));
+          if (sl->state == 0) end = true;
+          else if (sl->lo == lo && sl->hi == hi) { atomicAdd(&sl->readV, 1u); ++n_counted; end = true; }
+        }
+        if (end) break;
+        if (++line >= a.t.nlines) line = 0;
+      }
+    }
+  }
+  const uint64_t nk = mfx_wave_sum(n_kmers), nc = mfx_wave_sum(n_counted);
+  if ((tid & 63u) == 0) {
+    if (nk) atomicAdd((unsigned long long *)&a.stats[0], (unsigned long long)nk);
+    if (nc) atomicAdd((unsigned long long *)&a.stats[1], (unsigned long long)nc);
+    if (nk > nc) atomicAdd((unsigned long long *)&a.stats[2], (unsigned long long)(nk - nc));
+  }
+}
+
 // -completeness (merfin-completeness.C:70-117): piece = top 6 bits of the 2k-bit k-mer
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_completeness_kernel(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK,
                                                                        const double *probP, double *pieces) {
@@ -442,6 +488,12 @@ hipError_t mfx_kw_count(const mfx_count_args &a, hipStream_t st) {
   if (a.ntiles == 0) return hipSuccess;
   const uint64_t blocks = a.ntiles < 8192 ? a.ntiles : 8192;
   mfx_w_count_kernel<<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_kw_reads(const mfx_reads_args &a, hipStream_t st) {
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (ntiles == 0) return hipSuccess;
+  mfx_w_reads_kernel<<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_kw_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP, double *partials,
