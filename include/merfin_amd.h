@@ -557,6 +557,45 @@ int mfx_dump_contig_sharded(mfx_eval *const *evs, const mfx_seq *const *seqs, ui
                             const char *name, const char *path, int append, uint64_t *kasm, uint64_t *kmissing);
 
 /* ------------------------------------------------------------------------ */
+/* -track: K* summarised per fixed window of every contig, on the device.    */
+/* The evaluation is -dump's (merfin-dump.C:44-67); what it replaces is the  */
+/* post-processing of the reference README, section "Assess collapses and    */
+/* duplications": -dump text -> awk -> wigToBigWig.  Per-base values never    */
+/* leave the device; one record per window comes back.                       */
+/* ------------------------------------------------------------------------ */
+/* Window w of contig c covers the k-mer start positions [w*W, min((w+1)*W, len_c)) -- column 2 of -dump, the index of
+ * mfx_dump_values.  A contig has ceil(len_c / W) windows (none when len_c == 0); the windows of contig c follow those
+ * of contig c-1.  Every field is an integer sum (or a min / max): the records do not depend on the order the device
+ * met the k-mers in.  Fixed layout, 72 bytes. */
+typedef struct mfx_track_window {
+  uint32_t n_kmers;        /* valid k-mers starting in the window (kasm, merfin-dump.C:48)                      */
+  uint32_t n_missing;      /* ... of those, readK == 0 (merfin-dump.C:56)                                      */
+  uint32_t n_scored;       /* ... of those, readK != 0 and K* finite: the sums, min and max are over these     */
+  uint32_t n_pos;          /* scored, K* > 0 (collapsed)                                                       */
+  uint32_t n_neg;          /* scored, K* < 0 (expanded)                                                        */
+  uint32_t n_nonfinite;    /* readK != 0 and asmK == 0 (a foreign -seqmers: getKmetric divides by 0); in no sum */
+  uint64_t sum_readK;      /* exact: readK and asmK are integer-valued for every k-mer                         */
+  uint64_t sum_asmK;
+  uint64_t sum_kstar_lo;   /* sum of K* as a signed 128-bit integer in units of 2^-52 (exact): low word ...     */
+  int64_t  sum_kstar_hi;   /* ... and high word                                                                */
+  double   min_kstar;      /* +inf when n_scored == 0                                                          */
+  double   max_kstar;      /* -inf when n_scored == 0                                                          */
+} mfx_track_window;
+/* windows of the whole sequence set for window length `window` (0 when window == 0) */
+uint64_t mfx_track_num_windows(const mfx_seq *seq, uint64_t window);
+/* The records of the whole sequence set (merfin-dump.C:44-67 per k-mer, reduced per window by the kernel) into the host
+ * array out[cap]; *n_out = their number, *kasm / *kmissing = the totals -hist and -dump count.  MFX_E_INVAL: window == 0,
+ * cap too small, a sharded index, a sequence object that holds a part only; MFX_E_NOMEM: the records do not fit the device. */
+int mfx_track_run(mfx_eval *ev, const mfx_seq *seq, uint64_t window, mfx_track_window *out, uint64_t cap, uint64_t *n_out,
+                  uint64_t *kasm, uint64_t *kmissing);
+/* Host only.  tsv_path: "#name start end n_kmers n_missing n_scored n_pos n_neg sum_readK sum_asmK mean_kstar min_kstar
+ * max_kstar" and one tab-separated line per window with n_kmers > 0; bedgraph_path: a bedGraph track of mean K* (windows
+ * with n_scored > 0) -- what the README's "Assess collapses and duplications" makes from the -dump text.  Either path may
+ * be NULL; .gz / .bz2 / .xz names go through the compressed writers.  names[c]: the contig names (up to the first blank). */
+int mfx_track_write(const mfx_track_window *w, uint64_t n, const mfx_seq *seq, const char *const *names, uint64_t window,
+                    const char *tsv_path, const char *bedgraph_path);
+
+/* ------------------------------------------------------------------------ */
 /* -filter / -polish / -better / -strict / -loose: replaces processVariants */
 /* + outputVariants (merfin-variants.C:131-345), vcfFile (vcf.C) and varMer  */
 /* (varMer.C).  The host enumerates the allele-combination paths of many     */

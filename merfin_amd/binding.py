@@ -87,7 +87,14 @@ SYMBOLS = [
     "mfx_pack_bases", "mfx_host_threads_share", "mfx_dump_values", "mfx_dump_contig", "mfx_dump_values_sharded", "mfx_dump_contig_sharded", "mfx_variants_run_sharded", "mfx_vcf_load", "mfx_vcf_free", "mfx_variants_run_vcf", "mfx_vcf_prepare", "mfx_vcf_path_bound", "mfx_index_claim_paths", "mfx_vcf_prepare_path_index", "mfx_completeness", "mfx_completeness_pieces", "mfx_variants_run",
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
+    "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
 ]
+
+# one window of Evaluator.track: the layout of mfx_track_window (include/merfin_amd.h), 72 bytes
+TRACK_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_missing", "<u4"), ("n_scored", "<u4"), ("n_pos", "<u4"), ("n_neg", "<u4"),
+                        ("n_nonfinite", "<u4"), ("sum_readK", "<u8"), ("sum_asmK", "<u8"), ("sum_kstar_lo", "<u8"),
+                        ("sum_kstar_hi", "<i8"), ("min_kstar", "<f8"), ("max_kstar", "<f8")])
+assert TRACK_DTYPE.itemsize == 72
 
 
 def _share_hip_runtime_with_torch():
@@ -274,6 +281,10 @@ def load_library():
     L.mfx_reads_set_filter.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.mfx_reads_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
     L.mfx_reads_end.argtypes = [vp, C.POINTER(_ReadsStats)]
+    L.mfx_track_num_windows.restype = C.c_uint64
+    L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
+    L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
+    L.mfx_track_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p]
     _lib = L
     return L
 
@@ -879,6 +890,15 @@ def hist_sharded(evaluators, routers, sequences):
     return r
 
 
+def track_write(windows, seqs, names, window, tsv_path=None, bedgraph_path=None):
+    """the records of Evaluator.track as text (mfx_track_write; host only): a table of every window with k-mers and / or a
+    bedGraph track of the mean K*; .gz / .bz2 / .xz names are compressed"""
+    w = np.ascontiguousarray(windows, dtype=TRACK_DTYPE)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    _check(load_library().mfx_track_write(C.c_void_p(w.ctypes.data), len(w), seqs.h, nm, int(window),
+                                          tsv_path.encode() if tsv_path else None, bedgraph_path.encode() if bedgraph_path else None))
+
+
 def pack_bases(seq):
     """host-side encoding of the packed sequence transport: bytes -> (codes uint64[ceil(n/32)], valid uint32[ceil(n/32)])"""
     src = np.frombuffer(bytes(seq), dtype=np.uint8)
@@ -1169,6 +1189,18 @@ class Evaluator:
         _check(load_library().mfx_dump_contig(self.h, seqs.h, contig, name.encode(), path.encode(), 1 if append else 0,
                                               C.byref(ka), C.byref(km)))
         return ka.value, km.value
+
+    def track(self, seqs, window):
+        """K* per window of `window` k-mer start positions of every contig, reduced on the device (mfx_track_run): a structured
+        array of dtype TRACK_DTYPE, one record per window (contig by contig), and the totals kasm, kmissing"""
+        L = load_library()
+        if int(window) < 0 or int(window) >= 2**64:
+            raise MfxError(-1, "track: the window must be an integer in [1, 2^64)")
+        n = L.mfx_track_num_windows(seqs.h, int(window))
+        w = np.zeros(max(n, 1), dtype=TRACK_DTYPE)
+        got, ka, km = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(L.mfx_track_run(self.h, seqs.h, int(window), C.c_void_p(w.ctypes.data), n, C.byref(got), C.byref(ka), C.byref(km)))
+        return w[:got.value], ka.value, km.value
 
     def variants(self, mode, vcf_path, names, contigs, out_path, comb=15, nosplit=False, debug_path=None, log_path=None):
         """-filter/-polish/-better/-strict/-loose over all contigs; returns clusters evaluated"""

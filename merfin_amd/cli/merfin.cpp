@@ -6,6 +6,8 @@
 // Report types: -hist, -dump, -completeness, and the variant modes -filter /
 // -polish / -better / -strict / -loose (paths enumerated on the host, every
 // path k-mer scored on the GPU).
+#include <ctype.h>
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,7 +31,7 @@
 #include "../../include/merfin_amd.h"
 #include "fasta.h"
 
-enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE };
+enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK };
 
 struct Globals {
   const char *seqName = nullptr, *seqDBname = nullptr, *readDBname = nullptr, *pLookupTable = nullptr;
@@ -45,6 +47,8 @@ struct Globals {
   std::vector<double> copyKmerP;
   std::vector<const char *> readsNames;  // -reads: the read counts from these FASTA / FASTQ files instead of -readmers
   int kArg = 0;                          // -k (0: not given); with -reads: the run's k once the flags are checked
+  uint64_t window = 1000;                // -window: k-mer start positions per window of -track
+  bool windowGiven = false;
 };
 
 static void usage(const char *exe) {
@@ -76,11 +80,15 @@ static void usage(const char *exe) {
           "                      for one GPU).  -hist routes every k-mer to the GPU that owns it; -dump and the variant modes\n"
           "                      look every k-mer up in all shards and add the answers; -completeness adds per-shard sums\n"
           "    -index file       cache of the built HBM index: loaded if it exists (the k-mer databases are then not\n"
-          "                      read), otherwise written after the build\n\n"
+          "                      read), otherwise written after the build\n"
+          "    -window W         with -track: k-mer start positions per window (default 1000)\n\n"
           "  Report types (exactly one):\n"
           "    -hist           0-centred K* histogram to <output>; QV and QV* on stderr\n"
           "    -dump           seqName, seqPos, readK, asmK, K* per k-mer to <output>  [-skipMissing]\n"
           "    -completeness   k-mer completeness from -seqmers (or -sequence) and -readmers\n"
+          "    -track          K* summarised per window of every contig on the GPU -> <output>.track.tsv, <output>.kstar.bedgraph\n"
+          "                    (mean K*) and <output>.missing.bedgraph (missing fraction)  [-window W]; an <output> ending in\n"
+          "                    .gz / .bz2 / .xz compresses the three files (out.gz -> out.track.tsv.gz ...)\n"
           "    -filter         keep variants (and combinations within k) that minimise missing k-mers -> <output>.filter.vcf\n"
           "    -polish         choose variant combinations by missing k-mers, ties by k* -> <output>.polish.vcf\n"
           "    -better -strict -loose   k*-free variants of -polish -> <output>.filter.vcf\n"
@@ -752,6 +760,16 @@ int main(int argc, char **argv) {
     else if (is("-polish")) G.reportType = OP_POLISH;
     else if (is("-hist")) G.reportType = OP_HIST;
     else if (is("-dump")) G.reportType = OP_DUMP;
+    else if (is("-track")) G.reportType = OP_TRACK;
+    else if (is("-window")) {
+      const char *v = val();
+      char *e = nullptr;
+      errno = 0;
+      const unsigned long long w = strtoull(v, &e, 10);
+      G.windowGiven = true;
+      if (e == v || *e != 0 || errno != 0 || w < 1 || !isdigit((unsigned char)v[0])) err.push_back(std::string("Invalid -window '") + v + "': a window is an integer of at least 1.\n");
+      else G.window = w;
+    }
     else if (is("-skipMissing")) G.skipMissing = true;
     else if (is("-completeness")) G.reportType = OP_COMPL;
     else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
@@ -787,6 +805,15 @@ int main(int argc, char **argv) {
   }
 
   if (G.kArg > 0 && G.readDBname && !fromReads) err.push_back("-k is taken from -readmers; give -k only with -reads.\n");
+
+  // -track: every check before any device is touched
+  if (G.windowGiven && G.reportType != OP_TRACK) err.push_back("-window sets the window of -track; it has no meaning without -track.\n");
+  if (G.reportType == OP_TRACK) {
+    if (G.sharded) err.push_back("-track does not take -sharded: a window's records need every k-mer's counts on one device.\n");
+    if (G.devices.size() > 1) err.push_back("-track runs on one device (-device d, or -devices naming one).\n");
+    if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -track always writes its windows.\n");
+    if (G.vcfName) err.push_back("-track does not take -vcf (the variant modes do).\n");
+  }
 
   if (G.convertName && err.empty()) {
     // merfin -convert <db> -output <file>: a database in any accepted form rewritten as this program's flat form (sorted
@@ -885,7 +912,7 @@ int main(int argc, char **argv) {
   // runs into the CPU quota of a 16-core box in some runs: 1.09-1.13 s or 1.27-1.29 s against 1.12-1.16 s this way)
   const bool stageFirst = !(getenv("MFX_CLI_STAGE_FIRST") && atoi(getenv("MFX_CLI_STAGE_FIRST")) == 0);
   auto begin_stage = [&]() {
-    const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP) && !G.sharded && k <= 31 && G.seqName && !G.seqDBname && !G.indexName &&
+    const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && k <= 31 && G.seqName && !G.seqDBname && !G.indexName &&
                           G.devices.size() == 1 && !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")));
     if (histLike && rdb.format == MFX_DB_FLAT) stage = mfx_db_stage_begin(G.readDBname, G.device);
   };
@@ -982,7 +1009,7 @@ int main(int argc, char **argv) {
   // update those (half of a 30x human read database, the error k-mers, never gets a slot; k <= 21: 8-byte slots).  The
   // other report types need the whole read database.  MFX_CLI_FULL_INDEX=1 builds the full tables for every type.
   // (-reads: always -- the reads are counted into claimed k-mers; there is no read database for the full tables)
-  bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP) && !G.sharded && k <= 31 &&
+  bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && k <= 31 &&
                  (fromReads || !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX"))));
   const char *ov = getenv("MFX_CLI_OVERLAP");
   const bool compressed = G.seqName && mfx_suffix_tool(G.seqName) != nullptr;
@@ -1373,6 +1400,48 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)km, (unsigned long)cumMissing, (unsigned long)cumAsm);
       }
       if (recs.empty()) { FILE *f = fopen(G.outName, "w"); if (f) fclose(f); }
+    }
+  } else if (G.reportType == OP_TRACK) {
+    // K* per window of every contig, reduced on the device (mfx_track_run): what the README's "Assess collapses and duplications"
+    // makes from the -dump text with awk and wigToBigWig.  The counts on stderr are those of -dump -skipMissing.
+    // (a compressed -output name -- out.gz / .bz2 / .xz -- keeps its suffix at the end of the three names: out.track.tsv.gz)
+    std::string stem = G.outName, zsuf;
+    if (mfx_suffix_tool(stem)) { const size_t dot = stem.rfind('.'); zsuf = stem.substr(dot); stem.resize(dot); }
+    const std::string tsvName = stem + ".track.tsv" + zsuf, bgName = stem + ".kstar.bedgraph" + zsuf, missName = stem + ".missing.bedgraph" + zsuf;
+    fprintf(stderr, "-- Summarise the k* metric per window of %lu positions to '%s', '%s' and '%s'.\n", (unsigned long)G.window, tsvName.c_str(),
+            bgName.c_str(), missName.c_str());
+    const uint64_t nw = mfx_track_num_windows(seq, G.window);
+    std::vector<mfx_track_window> win((size_t)nw);
+    uint64_t got = 0, kasm = 0, kmissing = 0;
+    if (mfx_track_run(ev, seq, G.window, win.data(), nw, &got, &kasm, &kmissing)) DIE_MFX("-track");
+    std::vector<const char *> names(recs.size());
+    for (size_t c = 0; c < recs.size(); ++c) names[c] = recs[c].name.c_str();
+    if (mfx_track_write(win.data(), got, seq, names.data(), G.window, tsvName.c_str(), bgName.c_str())) DIE_MFX("writing the windows");
+    mfx_file mf = mfx_open_writer(missName.c_str(), false);
+    if (!mf.f) { fprintf(stderr, "ERROR: cannot open '%s' for writing.\n", missName.c_str()); return 1; }
+    fprintf(mf.f, "track type=bedGraph name=\"missing\"\n");
+    uint64_t cumMissing = 0, cumAsm = 0;
+    std::vector<uint64_t> cmiss(recs.size(), 0), casm(recs.size(), 0);
+    size_t i = 0;
+    for (size_t c = 0; c < recs.size(); ++c)
+      for (uint64_t start = 0; start < lens[c]; start += G.window, ++i) {
+        const mfx_track_window &w = win[i];
+        cmiss[c] += w.n_missing;
+        casm[c] += w.n_kmers;
+        if (w.n_kmers)
+          fprintf(mf.f, "%s\t%lu\t%lu\t%.6f\n", names[c], (unsigned long)start, (unsigned long)std::min<uint64_t>(start + G.window, lens[c]),
+                  (double)w.n_missing / (double)w.n_kmers);
+      }
+    if (mfx_close(mf)) { fprintf(stderr, "ERROR: writing '%s' failed.\n", missName.c_str()); return 1; }
+    for (size_t c = 0; c < recs.size(); ++c) {
+      cumMissing += cmiss[c];
+      cumAsm += casm[c];
+      fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)cmiss[c], (unsigned long)cumMissing, (unsigned long)cumAsm);
+    }
+    if (cumAsm != kasm || cumMissing != kmissing) {
+      fprintf(stderr, "ERROR: -track: the windows hold %lu k-mers (%lu missing), the device counted %lu (%lu).\n", (unsigned long)cumAsm,
+              (unsigned long)cumMissing, (unsigned long)kasm, (unsigned long)kmissing);
+      return 1;
     }
   } else if (variantMode) {
     // open_Inputs + processVariants + outputVariants (merfin-globals.C:201-219, merfin-variants.C:131-345)

@@ -9,6 +9,7 @@
 
 #include <math.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -4024,6 +4025,136 @@ extern "C" int mfx_dump_values(mfx_eval *ev, const mfx_seq *seq, uint32_t contig
   MFX_HIP(hipMemcpy(st, ds.p, sizeof(st), hipMemcpyDeviceToHost));
   if (kasm) *kasm = st[0];
   if (kmissing) *kmissing = st[1];
+  return MFX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// -track: K* per fixed window of every contig, reduced on the device (mfx_track_kernel; csrc/mfx_track.h).  The evaluation is
+// -dump's (merfin-dump.C:44-67); the records replace the -dump text + awk + wigToBigWig route of the reference README,
+// "Assess collapses and duplications".
+// ---------------------------------------------------------------------------
+static_assert(sizeof(mfx_track_window) == 72 && offsetof(mfx_track_window, sum_readK) == 24 && offsetof(mfx_track_window, min_kstar) == 56,
+              "mfx_track_window: the kernels address the record as 9 words");
+
+extern "C" uint64_t mfx_track_num_windows(const mfx_seq *seq, uint64_t window) {
+  if (!seq || window == 0) return 0;
+  uint64_t n = 0;
+  for (uint32_t c = 0; c < seq->ncontigs; ++c) n += seq->len[c] / window + (seq->len[c] % window ? 1 : 0);
+  return n;
+}
+
+extern "C" int mfx_track_run(mfx_eval *ev, const mfx_seq *seq, uint64_t window, mfx_track_window *out, uint64_t cap, uint64_t *n_out,
+                             uint64_t *kasm, uint64_t *kmissing) {
+  if (!ev || !seq || !n_out) return mfx_fail(MFX_E_INVAL, "mfx_track_run: null argument");
+  if (window == 0) return mfx_fail(MFX_E_INVAL, "mfx_track_run: the window must hold at least one position");
+  if (ev->device != seq->device) return mfx_fail(MFX_E_INVAL, "evaluator and sequence live on different devices");
+  if (ev->ix->shard_n > 1)
+    return mfx_fail(MFX_E_INVAL, "mfx_track_run: the index is shard %u of %u: a window's records need every k-mer's counts; use a whole index",
+                    ev->ix->shard_rank, ev->ix->shard_n);
+  if (seq->partial) return mfx_seq_partial_error(seq, "-track");
+  const uint64_t nrec = mfx_track_num_windows(seq, window);
+  if (nrec > cap || (nrec && !out)) return mfx_fail(MFX_E_INVAL, "mfx_track_run: %lu windows, room for %lu", (unsigned long)nrec, (unsigned long)cap);
+  uint64_t longest = 0;
+  for (uint32_t c = 0; c < seq->ncontigs; ++c) longest = std::max(longest, seq->len[c]);
+  if (std::min(longest, window) > 0xffffffffull)
+    return mfx_fail(MFX_E_INVAL, "mfx_track_run: a window of more than 2^32 - 1 positions of one contig: its counters are 32 bits wide");
+  DevGuard g(ev->device);
+  int canon = 0;
+  int rc = index_canonical(ev->ix, &canon);
+  if (rc) return rc;
+  if ((rc = mfx_check_seq_of_index(ev->ix, seq, "-track")) != MFX_OK) return rc;
+  *n_out = nrec;
+  if (kasm) *kasm = 0;
+  if (kmissing) *kmissing = 0;
+  if (nrec == 0) return MFX_OK;
+  const bool planes = !ev->ix->wide() && (seq->planes_ok || seq->bases_stale);       // (the 128-bit kernel reads one byte per base)
+  if (!planes && (rc = mfx_seq_ensure_ascii(seq)) != MFX_OK) return rc;
+  const size_t bytes = (size_t)nrec * sizeof(mfx_track_window);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b)
+    return mfx_fail(MFX_E_NOMEM, "mfx_track_run: %lu windows of %lu positions take %.2f GB on the device, %.2f GB are free; use a longer window",
+                    (unsigned long)nrec, (unsigned long)window, (double)bytes / 1e9, (double)free_b / 1e9);
+  DevBuf<uint64_t> drec, dfirst, dst;
+  if (drec.alloc(nrec * 9) != hipSuccess) {
+    (void)hipGetLastError();
+    return mfx_fail(MFX_E_NOMEM, "mfx_track_run: no device memory for %lu windows (%.2f GB); use a longer window", (unsigned long)nrec, (double)bytes / 1e9);
+  }
+  std::vector<uint64_t> first(seq->ncontigs ? seq->ncontigs : 1, 0);
+  {
+    uint64_t r = 0;
+    for (uint32_t c = 0; c < seq->ncontigs; ++c) { first[c] = r; r += seq->len[c] / window + (seq->len[c] % window ? 1 : 0); }
+  }
+  MFX_HIP(dfirst.alloc(first.size()));
+  MFX_HIP(dst.alloc(2));
+  MFX_HIP(hipMemcpy(dfirst.p, first.data(), first.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  MFX_HIP(mfx_memset_now(dst.p, 0, 2 * sizeof(uint64_t)));
+  MFX_HIP(mfx_memset_now(drec.p, 0, bytes));
+  mfx_track_args a;
+  a.t = ev->ix->view();
+  a.canonical = canon;
+  a.bases = seq->d_bases;
+  if (planes) { a.codes = seq->d_codes; a.valid = seq->d_valid; }
+  a.contig_off = seq->d_contig_off;
+  a.contig_len = seq->d_contig_len;
+  a.tile_start = seq->d_tile_start;
+  a.tile_contig = seq->d_tile_contig;
+  a.contig_rec = dfirst.p;
+  a.ntiles = seq->ntiles;
+  a.window = window;
+  a.peak = ev->peak;
+  a.n_prob = ev->n_prob;
+  a.probK = ev->d_probK;
+  a.probP = ev->d_probP;
+  a.recs = drec.p;
+  a.stats = dst.p;
+  MFX_HIP(ev->ix->wide() ? mfx_kw_track(a, nullptr) : mfx_k_track(a, nullptr));
+  MFX_HIP(mfx_k_track_finish(drec.p, nrec, nullptr));
+  MFX_HIP(hipMemcpy(out, drec.p, bytes, hipMemcpyDeviceToHost));
+  uint64_t st[2];
+  MFX_HIP(hipMemcpy(st, dst.p, sizeof(st), hipMemcpyDeviceToHost));
+  if (kasm) *kasm = st[0];
+  if (kmissing) *kmissing = st[1];
+  return MFX_OK;
+}
+
+// mean K* of a window: the nearest double to the exact sum (an integer of 2^-52 units), over the number of scored k-mers
+static double track_mean(const mfx_track_window &w) {
+  const __int128 s = (__int128)(((unsigned __int128)(uint64_t)w.sum_kstar_hi << 64) | (unsigned __int128)w.sum_kstar_lo);
+  return ldexp((double)s, -52) / (double)w.n_scored;
+}
+
+extern "C" int mfx_track_write(const mfx_track_window *w, uint64_t n, const mfx_seq *seq, const char *const *names, uint64_t window,
+                               const char *tsv_path, const char *bedgraph_path) {
+  if (!seq || (!w && n) || !names || window == 0) return mfx_fail(MFX_E_INVAL, "mfx_track_write: null argument or no window length");
+  if (n != mfx_track_num_windows(seq, window))
+    return mfx_fail(MFX_E_INVAL, "mfx_track_write: %lu records, the sequences have %lu windows of %lu positions", (unsigned long)n,
+                    (unsigned long)mfx_track_num_windows(seq, window), (unsigned long)window);
+  for (int what = 0; what < 2; ++what) {
+    const char *path = what == 0 ? tsv_path : bedgraph_path;
+    if (!path) continue;
+    mfx_file fh = mfx_open_writer(path, false);             // compressedFileWriter: compressor chosen by suffix (mfx_pipe.h)
+    FILE *f = fh.f;
+    if (!f) return mfx_fail(MFX_E_IO, "cannot open '%s' for writing", path);
+    if (what == 0) fprintf(f, "#name\tstart\tend\tn_kmers\tn_missing\tn_scored\tn_pos\tn_neg\tsum_readK\tsum_asmK\tmean_kstar\tmin_kstar\tmax_kstar\n");
+    else fprintf(f, "track type=bedGraph name=\"K*\"\n");
+    uint64_t i = 0;
+    for (uint32_t c = 0; c < seq->ncontigs; ++c) {
+      const uint64_t len = seq->len[c];
+      for (uint64_t start = 0; start < len; start += window, ++i) {
+        const mfx_track_window &r = w[i];
+        const uint64_t end = std::min(start + window, len);
+        if (what == 0) {
+          if (r.n_kmers == 0) continue;
+          fprintf(f, "%s\t%lu\t%lu\t%u\t%u\t%u\t%u\t%u\t%lu\t%lu\t%.6f\t%.6f\t%.6f\n", names[c], (unsigned long)start, (unsigned long)end, r.n_kmers,
+                  r.n_missing, r.n_scored, r.n_pos, r.n_neg, (unsigned long)r.sum_readK, (unsigned long)r.sum_asmK,
+                  r.n_scored ? track_mean(r) : 0.0, r.min_kstar, r.max_kstar);
+        } else if (r.n_scored) {
+          fprintf(f, "%s\t%lu\t%lu\t%.6f\n", names[c], (unsigned long)start, (unsigned long)end, track_mean(r));
+        }
+      }
+    }
+    if (mfx_close(fh)) return mfx_fail(MFX_E_IO, "writing '%s' failed (stream error or the compressor exited with an error)", path);
+  }
   return MFX_OK;
 }
 

@@ -91,6 +91,26 @@ struct mfx_dump_args {
   int             recount = 0; // 1: readV holds final values; only the counters are taken again (sharded index)
 };
 
+// -track (mfx_track_kernel / mfx_w_track_kernel; csrc/mfx_track.h): the whole sequence set, tile by tile
+struct mfx_track_args {
+  mfx_table_view  t;
+  int             canonical;
+  const uint8_t  *bases;
+  const uint64_t *codes = nullptr;    // non-null (k <= 31): the tiles are read from the packed planes, as -hist does
+  const uint32_t *valid = nullptr;
+  const uint64_t *contig_off, *contig_len, *tile_start;
+  const uint32_t *tile_contig;
+  const uint64_t *contig_rec;         // [ncontigs] number of the first window record of each contig
+  uint64_t        ntiles;
+  uint64_t        window;             // start positions per window (>= 1)
+  double          peak;
+  uint32_t        n_prob;
+  const uint32_t *probK;
+  const double   *probP;
+  uint64_t       *recs;               // the records: 9 words each (mfx_track_window), zero at launch
+  uint64_t       *stats;              // [0] kasm [1] kmissing
+};
+
 struct mfx_count_args {
   mfx_table_view  t;
   const uint8_t  *bases;
@@ -181,6 +201,9 @@ hipError_t mfx_kw_count(const mfx_count_args &a, hipStream_t st);
 hipError_t mfx_kw_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP, double *partials,
                                int grid, hipStream_t st);
 hipError_t mfx_k_dump(const mfx_dump_args &a, hipStream_t st);
+hipError_t mfx_k_track(const mfx_track_args &a, hipStream_t st);          // k <= 31
+hipError_t mfx_kw_track(const mfx_track_args &a, hipStream_t st);         // 32 <= k <= 64 (mfx_wide.hip)
+hipError_t mfx_k_track_finish(uint64_t *recs, uint64_t nrec, hipStream_t st);   // the min / max keys of the records -> doubles (+inf / -inf where nothing was scored)
 // *out += the content digest of nwords 32-base words (codes != nullptr: from the packed planes, else from the bytes)
 hipError_t mfx_k_seq_digest(const uint8_t *bases, const uint64_t *codes, const uint32_t *valid, uint64_t nwords, uint64_t *out, hipStream_t st);
 hipError_t mfx_k_add_u32(uint32_t *dst, const uint32_t *src, uint64_t n, hipStream_t st);

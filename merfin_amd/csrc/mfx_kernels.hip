@@ -15,6 +15,7 @@
 #include "mfx_kernels.h"
 #include "mfx_device.h"
 #include "mfx_place.h"
+#include "mfx_track.h"
 
 #include <stdlib.h>
 #include <algorithm>
@@ -3097,6 +3098,93 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_dump_kernel(mfx_dump_args a) {
 }
 
 // ===========================================================================
+// -track: K* of every k-mer (merfin-dump.C:44-67) reduced per fixed window of its contig; no per-position array is
+// written.  The lookups are mfx_dump_kernel's; the tiles are the whole sequence set's (packed planes where the sequence
+// has them); the reduction is csrc/mfx_track.h.
+// ===========================================================================
+template <bool CANON, bool COMPACT>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_track_kernel(mfx_track_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_mailbox MB;
+  __shared__ mfx_trk_lds T;
+  __shared__ uint64_t s_red[MFX_BLOCK / 64][3];
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  mfx_trk_lds_clear(T);
+  uint64_t n_valid = 0, n_missing = 0, zz = 0;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    if (a.codes) {                                             // block-uniform
+      const uint64_t w0 = (a.contig_off[c] + pos0) >> 5;
+      mfx_tile_fill_packed(L, a.codes + w0, a.valid + w0);
+    } else {
+      mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    }
+    const mfx_trk_tile tt = mfx_trk_tile_begin(a.recs, a.contig_rec[c], a.window, pos0, n);
+    __syncthreads();                                           // the tile is in LDS; T is clear (kernel start / mfx_trk_tile_end)
+    mfx_trk_acc A;
+    mfx_trk_clear(A);
+    uint32_t cur = 0u;
+    for (uint32_t b = 0; b < MFX_TILE / MFX_BLOCK; b += MFX_BATCH) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      uint64_t key[MFX_BATCH], key2[MFX_BATCH];
+      uint32_t rv[MFX_BATCH], av[MFX_BATCH];
+      bool     ok[MFX_BATCH];
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;          // lane-consecutive positions
+        uint64_t f;
+        ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
+        const uint64_t r = mfx_revcomp(f, k);
+        if (CANON) { key[j] = f < r ? f : r; key2[j] = f < r ? r : f; }
+        else { key[j] = f; key2[j] = r; }
+      }
+      if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key, key2, ok, rv, av);
+      else mfx_group_lookup<MFX_BATCH>(a.t, MB, key, key2, ok, rv, av);
+      if (!CANON) {                                            // value(fmer) + value(rmer), uint32 arithmetic (merfin-globals.C:107-108)
+        uint32_t rv2[MFX_BATCH], av2[MFX_BATCH];
+        if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key2, key, ok, rv2, av2);
+        else mfx_group_lookup<MFX_BATCH>(a.t, MB, key2, key, ok, rv2, av2);
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) { rv[j] += rv2[j]; av[j] += av2[j]; }
+      } else if ((k & 1) == 0) {                               // even k: a palindromic k-mer is value(fmer) + value(rmer) of ONE slot
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) if (key[j] == key2[j]) { rv[j] += rv[j]; av[j] += av[j]; }
+      }
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        if (ok[j]) n_valid++;                                    // merfin-dump.C:48
+        if (mfx_trk_visit(tt, T, A, cur, (b + j) * MFX_BLOCK + tid, ok[j], a.peak, a.n_prob, a.probK, a.probP, rv[j], av[j])) n_missing++;   // :56-58
+      }
+    }
+    if (__any(A.cnt != 0ull)) mfx_trk_flush(tt, T, A, cur);
+    __syncthreads();                                           // every wave's shares of this tile are in T; the tile is consumed
+    mfx_trk_tile_end(tt, T);
+  }
+  mfx_block_sum3(n_valid, n_missing, zz, s_red);
+  if (tid == 0 && (n_valid | n_missing)) {
+    atomicAdd((unsigned long long *)&a.stats[0], n_valid);
+    atomicAdd((unsigned long long *)&a.stats[1], n_missing);
+  }
+}
+
+// the records after the last launch: words 7 / 8 (largest ~key, largest key; csrc/mfx_track.h) -> min_kstar / max_kstar
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_track_finish_kernel(uint64_t *recs, uint64_t nrec) {
+  const uint64_t stride = (uint64_t)gridDim.x * MFX_BLOCK;
+  for (uint64_t i = (uint64_t)blockIdx.x * MFX_BLOCK + threadIdx.x; i < nrec; i += stride) {
+    uint64_t *r = recs + 9ull * i;
+    const bool scored = (uint32_t)r[1] != 0u;
+    const double mn = scored ? mfx_trk_unkey(~r[7]) : __longlong_as_double(0x7ff0000000000000ll);
+    const double mx = scored ? mfx_trk_unkey(r[8]) : __longlong_as_double((long long)0xfff0000000000000ull);
+    r[7] = (uint64_t)__double_as_longlong(mn);
+    r[8] = (uint64_t)__double_as_longlong(mx);
+  }
+}
+
+// ===========================================================================
 // varMer::score on the device (varMer.C:66-144): one lane per alternative PATH of a batch of variant clusters.  The paths'
 // k-mers have been looked up by mfx_dump_kernel over the packed path text (readV / asmV per start position); this walks a
 // path's bases in order exactly as the reference does -- run length of valid bases, the k-mer ENDING at idx, readK / prob by
@@ -3858,6 +3946,21 @@ hipError_t mfx_k_dump(const mfx_dump_args &a, hipStream_t st) {
   else if (a.canonical)                mfx_dump_kernel<true, false, false><<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
   else if (a.t.compact)                mfx_dump_kernel<false, false, true><<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
   else                                 mfx_dump_kernel<false, false, false><<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_track(const mfx_track_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical && a.t.compact) mfx_track_kernel<true, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.canonical)           mfx_track_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.t.compact)           mfx_track_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else                            mfx_track_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_track_finish(uint64_t *recs, uint64_t nrec, hipStream_t st) {
+  if (nrec == 0) return hipSuccess;
+  const uint64_t blocks = (nrec + MFX_BLOCK - 1) / MFX_BLOCK;
+  mfx_track_finish_kernel<<<(unsigned)(blocks < 8192 ? blocks : 8192), MFX_BLOCK, 0, st>>>(recs, nrec);
   return hipGetLastError();
 }
 hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st) {

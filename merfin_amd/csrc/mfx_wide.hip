@@ -14,6 +14,7 @@
 // line around the line, then the next lines), a claim takes the first empty one, so a lookup stops at the first empty slot
 // of that order.
 #include "mfx_device.h"
+#include "mfx_track.h"
 
 typedef unsigned __int128 mfx_u128;
 
@@ -340,6 +341,48 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_dump_kernel(mfx_dump_args a) 
   }
 }
 
+// -track (csrc/mfx_track.h): the evaluation of mfx_w_dump_kernel over the tiles of the whole sequence set, reduced per window
+// by the same code as the k <= 31 kernel -- the records are the same whichever kernel made them
+template <bool CANON>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_track_kernel(mfx_track_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_trk_lds T;
+  __shared__ uint64_t s_red[MFX_BLOCK / 64][3];
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  mfx_trk_lds_clear(T);
+  uint64_t n_valid = 0, n_missing = 0, zz = 0;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    const mfx_trk_tile tt = mfx_trk_tile_begin(a.recs, a.contig_rec[c], a.window, pos0, n);
+    __syncthreads();
+    mfx_trk_acc A;
+    mfx_trk_clear(A);
+    uint32_t cur = 0u;
+    for (uint32_t b = 0; b < MFX_TILE / MFX_BLOCK; ++b) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      const uint32_t p = b * MFX_BLOCK + tid;
+      mfx_u128 f;
+      const bool ok = mfx_w_tile_kmer(L, k, p, f) && p < n;
+      uint2 v = make_uint2(0u, 0u);
+      if (ok) { v = mfx_w_getV<CANON>(a.t, f, k); n_valid++; }                                                 // merfin-dump.C:48
+      if (mfx_trk_visit(tt, T, A, cur, p, ok, a.peak, a.n_prob, a.probK, a.probP, v.x, v.y)) n_missing++;     // :56-58
+    }
+    if (__any(A.cnt != 0ull)) mfx_trk_flush(tt, T, A, cur);
+    __syncthreads();                                           // every wave's shares of this tile are in T; the tile is consumed
+    mfx_trk_tile_end(tt, T);
+  }
+  mfx_block_sum3(n_valid, n_missing, zz, s_red);
+  if (tid == 0 && (n_valid | n_missing)) {
+    atomicAdd((unsigned long long *)&a.stats[0], n_valid);
+    atomicAdd((unsigned long long *)&a.stats[1], n_missing);
+  }
+}
+
 // `meryl count` of the assembly (merfin-globals.C:182-186)
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_count_kernel(mfx_count_args a) {
   __shared__ mfx_tile_lds L;
@@ -482,6 +525,13 @@ hipError_t mfx_kw_dump(const mfx_dump_args &a, hipStream_t st) {
   if (blocks == 0) return hipSuccess;
   if (a.canonical) mfx_w_dump_kernel<true><<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
   else             mfx_w_dump_kernel<false><<<(unsigned)blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_kw_track(const mfx_track_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical) mfx_w_track_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_w_track_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_kw_count(const mfx_count_args &a, hipStream_t st) {
