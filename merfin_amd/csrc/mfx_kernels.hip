@@ -2246,6 +2246,10 @@ constexpr int MFX_BATCH = MFX_V_BATCH;          // queries per lane and cooperat
 #ifndef MFX_V_KFXLDS_K21
 #define MFX_V_KFXLDS_K21 1
 #endif
+// THE RULE the shared word rests on: a lane evaluates at most 16 k-mers of a tile (MFX_TILE / MFX_BLOCK positions, its own).  Sixteen
+// terms of at most 2^52 units stay below 2^56, sixteen bumps of the dominant-bin count fit the 8 bits above.  The deferred probe
+// (mfx_lane_flush) hands parked queries to OTHER lanes of the wave, which breaks the rule: an instance takes kfxlds or defer, never
+// both (static_assert in mfx_hist_kernel; tests/test_gpu_kstar_grid.py: test_saturation_tiles_of_the_packed_word fills both fields).
 constexpr uint32_t MFX_KFX_BASE = 32u;
 template <bool CANON, bool COMPACT, int KF> struct mfx_hist_tune { static constexpr int blocks = MFX_V_MINBLOCKS, batch = MFX_V_BATCH, defer = 0, kfxlds = 0; };
 template <> struct mfx_hist_tune<true, true, 21> { static constexpr int blocks = MFX_V_MINBLOCKS_K21, batch = MFX_V_BATCH_K21, defer = MFX_V_DEFER_K21, kfxlds = MFX_V_KFXLDS_K21; };
@@ -2323,6 +2327,9 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
     uint64_t kfx = 0;
     constexpr bool kfx_lds = mfx_hist_tune<CANON, COMPACT, KF>::kfxlds != 0 && COMPACT && CANON && KF != 0 && TF != 0;
     constexpr uint32_t mb_cap = kfx_lds ? MFX_KFX_BASE : 64u;      // mailbox entries the probe has
+    static_assert(!(mfx_hist_tune<CANON, COMPACT, KF>::kfxlds != 0 && mfx_hist_tune<CANON, COMPACT, KF>::defer != 0),
+                  "kfxlds packs 16 terms and a count of at most 16 into one LDS word per lane: the deferred probe lets a lane evaluate more than its own 16 k-mers of a tile");
+    static_assert(MFX_TILE / MFX_BLOCK <= 16, "the packed koverCpy word (56-bit sum, 8-bit count) holds 16 evaluations per lane and tile");
     unsigned long long *const kfxw = reinterpret_cast<unsigned long long *>(&MB.rec[(tid & ~63u) + MFX_KFX_BASE]) + (tid & 63u);   // (kfx_lds) this lane's word
     if (kfx_lds) *kfxw = 0ull;                                   // (the mailbox was handed back at the end of the tile before)
     // ... and so does the count of the dominant bin (`over` 0: nine k-mers in ten), in the same word above the 56 bits of the sum (a lane

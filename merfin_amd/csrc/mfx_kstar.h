@@ -87,6 +87,10 @@ MFX_HD double mfx_overcopy_term(double readK, double asmK, double prob) {
 // -- and is counted in units of 2^-52, rounded to nearest: term + 1.0 lies in [1, 2], where a double's last bit is 2^-52, so the
 // mantissa of the sum IS the rounded multiple (a term that rounds up to 1.0 gives 2.0, i.e. 2^52 units, by the same subtraction).
 // Order-free, therefore: which lane of a wave evaluated a k-mer, and when, does not change the sum.
+// DEFINED FOR term IN [0, 1] ONLY, i.e. for -prob rows in [0, 1] (probabilities; rows of exactly 0.0 and 1.0 are tested).  Outside:
+// a term above 1 (prob > 1) is under-counted -- term + 1.0 leaves [1, 2], and the mantissa bits then count units of 2^-51 and coarser
+// as if they were 2^-52; a negative term (prob < 0) yields a huge unsigned value.  Neither is detected: the tile-driven -hist
+// kernels give a wrong koverCpy for such a table, where the reference would add the out-of-range products as they are.
 MFX_HD uint64_t mfx_kfix(double term) {
   const double y = term + 1.0;
   uint64_t b;
