@@ -1117,11 +1117,13 @@ class Evaluator:
         """how the probe's queries that left the one-load path ended (cleared): first_pass / second_pass (cooperative passes over the home
         line / the next candidate line), side_table (a saturated count field), line_scans (further candidate lines: listed for
         mfx_hist_rest_kernel), side_not_in_two_slots (saturated, not in slot 0 / 1 of its side-table line: listed), ended_per_lane (no
-        list, or the list was full: scanned for by the lane itself)"""
+        list, or the list was full: scanned for by the lane itself).  first_pass counts every query that was not in its first mini-bucket;
+        second_bucket of them ended in the second mini-bucket of their order, per lane, and never reached a cooperative pass"""
         out = np.zeros(8, dtype=np.uint64)
         _check(load_library().mfx_eval_debug_counters(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return {"first_pass": int(out[0]), "second_pass": int(out[1]), "side_table": int(out[2]), "line_scans": int(out[3]),
-                "side_not_in_two_slots": int(out[4]), "ended_per_lane": int(out[5])}
+                "side_not_in_two_slots": int(out[4]), "ended_per_lane": int(out[5]),
+                "second_bucket": int(out[6])}
 
     def hist(self, seqs):
         r = HistResult()

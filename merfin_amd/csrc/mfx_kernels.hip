@@ -1601,6 +1601,77 @@ struct mfx_no_push {
 #ifndef MFX_V_TAIL_STEPS
 #define MFX_V_TAIL_STEPS 0            // cooperative steps of the probe's tail whose line loads are in flight together; 0: by the batch size (A/B: tools/ab_build.sh)
 #endif
+#ifndef MFX_V_BUCKET2
+#define MFX_V_BUCKET2 1               // a query that is not in its first mini-bucket reads the NEXT one of its order per lane before it goes to the cooperative passes -- in the instances that ask for it (MFX_V_BUCKET2_K21 / _K31 below); 0: in none (A/B, tools/ab_build.sh)
+#endif
+
+// The per-lane front of the probe (mfx_lane_lookup8, mfx_lane_probe_defer): the first mini-bucket of every query -- one 16-byte load
+// per lane and query, all B in flight -- and, for the queries that met neither their key nor an empty slot there, the SECOND mini-bucket
+// of their order, (b0 + 1) & 7 of the same line (mfx_c_claim walks a line in exactly this order, so a displaced k-mer is there unless
+// that mini-bucket was full as well -- which is common: neighbouring k-mers take CONSECUTIVE first mini-buckets (mfx_mod_place), so the
+// next one is the first of the next k-mer: 2.3 % of the queries of the 3 Gb i.i.d. world are displaced, 47 % of those are one on).  The line is the one the lane has
+// just fetched: an L1 / L2 hit, no new line from HBM -- and the query ends with no mailbox record, no ballot and no hand-off, so that
+// a batch whose displaced queries all end there never enters the cooperative tail.  B2 = false: no second load, every displaced query
+// goes to the passes (which instances take the step, and why not all: MFX_V_BUCKET2_K21 / _K31 at mfx_hist_tune).  The same rule in both mini-buckets: the key -> its fields (a saturated one: 0xfe, the
+// low word in rv); an empty slot before the key -> absent (value 0, merfin-globals.C:84); neither -> st 1, the passes.  The second
+// load lands in the registers of the first and ONE decode (fields, saturation, -min / -max) serves both.
+// dbg: [0] the queries that left the one-load path (counted before the second mini-bucket), [6] those the second mini-bucket ended.
+template <int B, bool B2>
+__device__ __forceinline__ void mfx_lane_front(const mfx_table_view &c, const uint64_t (&fkey)[B], const bool (&ok)[B], uint32_t (&rv)[B], uint32_t (&av)[B],
+                                               const uint32_t (&line)[B], const uint32_t (&b0)[B], uint32_t (&st)[B], unsigned long long *dbg) {
+  const uint4 *const slots0 = reinterpret_cast<const uint4 *>(c.slots);
+  constexpr uint32_t HIT = 3u;  // (here only) the key was met, its slot's low word is in rv: decoded below
+  uint4 v[B];
+#pragma unroll
+  for (int j = 0; j < B; ++j) v[j] = slots0[((uint64_t)line[j] << 3) | b0[j]];
+  // {key 42 | counts 22}: equal high words and low words that differ in the 22 count bits only (the empty word's key field is
+  // no k-mer's: poly-G is not canonical, and a quotient never has d = 3)
+  auto match = [&](int j) {
+    const uint4 s = v[j];
+    const uint64_t ks = fkey[j] << 22;
+    const uint32_t klo = (uint32_t)ks, khi = (uint32_t)(ks >> 32);
+    const bool ha = s.y == khi && ((s.x ^ klo) >> 22) == 0u, hb = s.w == khi && ((s.z ^ klo) >> 22) == 0u;
+    const bool room = s.y == 0xffffffffu || s.w == 0xffffffffu;
+    rv[j] = ha ? s.x : s.z;
+    st[j] = (ha || hb) ? HIT : (room ? 0xffu : 1u);
+  };
+#pragma unroll
+  for (int j = 0; j < B; ++j) {
+    match(j);
+    if (!ok[j]) st[j] = 0xffu;
+  }
+  bool left = false;
+#pragma unroll
+  for (int j = 0; j < B; ++j) left |= st[j] == 1u;
+  if ((B2 || dbg) && __any(left)) {                            // wave-uniform: ~95 % of the batches of 128 queries
+    if (dbg) {
+#pragma unroll
+      for (int j = 0; j < B; ++j) if (st[j] == 1u) atomicAdd(&dbg[0], 1ull);
+    }
+    if (B2) {
+#pragma unroll
+      for (int j = 0; j < B; ++j)
+        if (st[j] == 1u) v[j] = slots0[((uint64_t)line[j] << 3) | ((b0[j] + 1u) & 7u)];
+#pragma unroll
+      for (int j = 0; j < B; ++j)
+        if (st[j] == 1u) {
+          match(j);
+          if (dbg && st[j] != 1u) atomicAdd(&dbg[6], 1ull);
+        }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < B; ++j) {
+    const bool found = st[j] == HIT;
+    const uint32_t lo = rv[j];
+    const uint32_t r_rv = (lo >> 11) & MFX_CSAT, r_av = lo & MFX_CSAT;
+    const bool sat = r_rv == MFX_CSAT || r_av == MFX_CSAT;
+    const uint32_t f_rv = (r_rv < c.minV || r_rv > c.maxV) ? 0u : r_rv;      // -min / -max (merfin.C:199-200)
+    rv[j] = found ? (sat ? lo : f_rv) : 0u;
+    av[j] = (found && !sat) ? r_av : 0u;
+    if (found) st[j] = sat ? 0xfeu : 0xffu;
+  }
+}
 // fkey: what the key field of each query's slot holds in its home line (mfx_probe::fkey: the k-mer, or its quotient for k > 21);
 // line / b0: its home line and first mini-bucket (mfx_home, or mfx_wave_mod_line for a whole wave at once); a query that is not
 // ok must come with line 0 / b0 0 (a dummy load, ignored).  keyof(j): the canonical k-mer of query j -- asked for on the rare
@@ -1610,7 +1681,7 @@ struct mfx_no_push {
 // ended by mfx_hist_rest_kernel gets true when the query is on the list (the caller then must not evaluate it: bit j of the
 // result); mfx_no_push: there is no worklist, the rare endings are per-lane scans here and now.
 // CAP: the mailbox entries (of the wave's 64) the passes may use; the queries of a batch beyond them take the rare endings' way
-template <int B, class KeyOf, class Push = mfx_no_push, uint32_t CAP = 64u>
+template <int B, class KeyOf, class Push = mfx_no_push, uint32_t CAP = 64u, bool B2 = false>
 __device__ __forceinline__ uint32_t mfx_lane_lookup8(const mfx_table_view &c, mfx_mailbox &M, const uint64_t (&fkey)[B], const bool (&ok)[B],
                                                      uint32_t (&rv)[B], uint32_t (&av)[B], const uint32_t (&line)[B], const uint32_t (&b0)[B],
                                                      KeyOf keyof, unsigned long long *dbg = nullptr, Push push = Push()) {
@@ -1618,55 +1689,38 @@ __device__ __forceinline__ uint32_t mfx_lane_lookup8(const mfx_table_view &c, mf
   // [0] not in their first mini-bucket (first cooperative pass), [1] home line full of other k-mers (second cooperative pass),
   // [2] a saturated count (side table), [3] per-lane whole-line scans; tests assert that a world exercises every ending
   const uint32_t tid = threadIdx.x, sub16 = (tid & 7u) << 4, lane = tid & 63u, wbase = tid & ~63u;
-  const uint4 *const slots0 = reinterpret_cast<const uint4 *>(c.slots);
-  uint32_t st[B];               // 0xff done; 1 not in its first mini-bucket; 0xfe a count field is saturated (the slot's low word parked in rv);
+  uint32_t st[B];               // 0xff done; 1 in neither of its first two mini-buckets; 0xfe a count field is saturated (the slot's low word parked in rv);
                                 // 0xfd / 0xfc whole-line scans from candidate line 2 / 0 (set below)
-  uint4 v[B];
-  // ---- first mini-bucket of every query: one 16-byte load per lane and query, all B in flight
-#pragma unroll
-  for (int j = 0; j < B; ++j) v[j] = slots0[((uint64_t)line[j] << 3) | b0[j]];
-#pragma unroll
-  for (int j = 0; j < B; ++j) {
-    const uint4 s = v[j];
-    // {key 42 | counts 22}: equal high words and low words that differ in the 22 count bits only (the empty word's key field is
-    // no k-mer's: poly-G is not canonical, and a quotient never has d = 3)
-    const uint64_t ks = fkey[j] << 22;
-    const uint32_t klo = (uint32_t)ks, khi = (uint32_t)(ks >> 32);
-    const bool ha = s.y == khi && ((s.x ^ klo) >> 22) == 0u, hb = s.w == khi && ((s.z ^ klo) >> 22) == 0u;
-    const bool found = ha || hb, room = s.y == 0xffffffffu || s.w == 0xffffffffu;
-    const uint32_t lo = ha ? s.x : s.z;
-    const uint32_t r_rv = (lo >> 11) & MFX_CSAT, r_av = lo & MFX_CSAT;
-    const bool sat = r_rv == MFX_CSAT || r_av == MFX_CSAT;
-    const uint32_t f_rv = (r_rv < c.minV || r_rv > c.maxV) ? 0u : r_rv;      // -min / -max (merfin.C:199-200)
-    rv[j] = found ? (sat ? lo : f_rv) : 0u;
-    av[j] = (found && !sat) ? r_av : 0u;
-    st[j] = !ok[j] ? 0xffu : (found ? (sat ? 0xfeu : 0xffu) : (room ? 0xffu : 1u));  // an empty slot before the key: absent (value 0, merfin-globals.C:84)
-  }
+  // ---- first mini-bucket of every query, (B2) the second one for the displaced ones: per lane
+  mfx_lane_front<B, B2>(c, fkey, ok, rv, av, line, b0, st, dbg);
   // ---- (A/B form only: the side probe of saturated count fields in front of the passes; the shipped form runs it behind them, where
   // ONE test per batch guards it together with the listing -- and a saturated field met by a PASS is served by it as well)
 #if !MFX_V_SIDE_LATE
   mfx_side_direct<B>(c, st, rv, av, keyof, dbg);
 #endif
-  // ---- the queries that were not in their first mini-bucket (3 % at load factor 0.225): compacted into this wave's mailbox
-  // and served 8 per step by the cooperative whole-line probe -- the 8 lanes of a group fetch the query's HOME line with one
-  // coalesced request, so that whichever mini-bucket the k-mer went to, one more round trip finds it
-  uint32_t qpos[B];
-  uint32_t nq = 0;
+  // ---- the queries that were in neither of their first two mini-buckets (0.3 % at load factor 0.225: one batch of 128 in seven has
+  // one): compacted into this wave's mailbox and served 8 per step by the cooperative whole-line probe -- the 8 lanes of a group fetch
+  // the query's HOME line with one coalesced request, so that whichever mini-bucket the k-mer went to, one more round trip finds it.
+  // A batch with none skips the ballot prefix and the records with the passes.
+  bool left = false;
 #pragma unroll
-  for (int j = 0; j < B; ++j) {
-    const bool p = st[j] == 1u;
-    const uint64_t m = __ballot(p);
-    const uint32_t pos = nq + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL));
-    qpos[j] = 0xffffffffu;
-    if (p && pos < CAP) {
-      qpos[j] = pos;
-      const uint64_t ks = fkey[j] << 22;
-      M.rec[wbase + pos] = make_uint4((uint32_t)ks, (uint32_t)(ks >> 32), line[j], 0u);
+  for (int j = 0; j < B; ++j) left |= st[j] == 1u;
+  if (__any(left)) {                                           // wave-uniform
+    uint32_t qpos[B];
+    uint32_t nq = 0;
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const bool p = st[j] == 1u;
+      const uint64_t m = __ballot(p);
+      const uint32_t pos = nq + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL));
+      qpos[j] = 0xffffffffu;
+      if (p && pos < CAP) {
+        qpos[j] = pos;
+        const uint64_t ks = fkey[j] << 22;
+        M.rec[wbase + pos] = make_uint4((uint32_t)ks, (uint32_t)(ks >> 32), line[j], 0u);
+      }
+      nq += (uint32_t)__popcll(m);
     }
-    nq += (uint32_t)__popcll(m);
-  }
-  if (dbg && nq && lane == 0u) atomicAdd(&dbg[0], (unsigned long long)nq);
-  if (nq) {                                                    // wave-uniform
     mfx_wave_handoff();
     if (nq > CAP) nq = CAP;
     // One pass over the wave's entries: 8 lanes per entry read its line (rec.z) with one coalesced request and answer into the
@@ -1809,10 +1863,11 @@ __device__ __forceinline__ uint32_t mfx_lane_lookup8(const mfx_table_view &c, mf
 
 // ---------------------------------------------------------------------------
 // The same probe with its tail DEFERRED (the -hist kernel; MFX_V_DEFER).  mfx_lane_lookup8 ends every batch with the cooperative
-// pass over the few queries that were not in their first mini-bucket (~4 of a wave's 128 at load factor 0.18) -- two hand-offs, a
-// ballot prefix, the line loads, the answers, the collection: ~150 wave instructions that cost the same for 4 entries as for 64,
-// a quarter of what the wave issues per batch.  Here a batch only PARKS such a query in the wave's mailbox -- {key field << 22,
-// home line, tile position} -- and goes on; the mailbox is worked off when it holds MFX_DEFER_FLUSH entries or the tile ends
+// pass over the few queries that were not in their first mini-bucket (~3 of a wave's 128 at load factor 0.17) -- two hand-offs, a
+// ballot prefix, the line loads, the answers, the collection: 110-150 wave instructions that cost the same for 3 entries as for 64.
+// Here a batch first tries the displaced queries' SECOND mini-bucket per lane (mfx_lane_front: it ends about half of them) and only
+// PARKS what is left in the wave's mailbox -- {key field << 22, home line, tile position} -- and goes on; a parked query's home line is
+// fetched again at the flush, so every query the second mini-bucket ends is a line saved; the mailbox is worked off when it holds MFX_DEFER_FLUSH entries or the tile ends
 // (mfx_lane_flush): one cooperative pass over up to 64 entries (8 lanes read an entry's line with one request, four steps in
 // flight), then LANE e CONSUMES ENTRY e -- second candidate line, side table, further lines as before -- and evaluates it (K*, bin,
 // counters) itself, all lanes busy.  Whose lane a k-mer's result lands in does not matter: the counters are integers summed over
@@ -1829,31 +1884,13 @@ constexpr uint32_t MFX_DEFER_FLUSH = MFX_V_DEFER_FLUSH;
 constexpr uint32_t MFX_REC_FOUND = 0xffffffffu;                // rec.z of an answered entry (no line has this index)
 
 // phase A: the batch's loads and the one-load answers.  defer: bit j set = query j was parked (its rv / av come at the flush).
-template <int B, class KeyOf, class Push = mfx_no_push, uint32_t CAP = 64u>
+template <int B, class KeyOf, class Push = mfx_no_push, uint32_t CAP = 64u, bool B2 = false>
 __device__ __forceinline__ uint32_t mfx_lane_probe_defer(const mfx_table_view &c, mfx_mailbox &M, uint32_t &nq, const uint64_t (&fkey)[B], const bool (&ok)[B],
                                                          uint32_t (&rv)[B], uint32_t (&av)[B], const uint32_t (&line)[B], const uint32_t (&b0)[B],
                                                          const uint32_t (&pos)[B], KeyOf keyof, unsigned long long *dbg = nullptr, Push push = Push()) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wbase = tid & ~63u;
-  const uint4 *const slots0 = reinterpret_cast<const uint4 *>(c.slots);
   uint32_t st[B];               // 0xff done; 1 parked; 0xfe a count field is saturated (the slot's low word in rv); 0xfc whole-line scans from the home line
-  uint4 v[B];
-#pragma unroll
-  for (int j = 0; j < B; ++j) v[j] = slots0[((uint64_t)line[j] << 3) | b0[j]];
-#pragma unroll
-  for (int j = 0; j < B; ++j) {
-    const uint4 s = v[j];
-    const uint64_t ks = fkey[j] << 22;
-    const uint32_t klo = (uint32_t)ks, khi = (uint32_t)(ks >> 32);
-    const bool ha = s.y == khi && ((s.x ^ klo) >> 22) == 0u, hb = s.w == khi && ((s.z ^ klo) >> 22) == 0u;
-    const bool found = ha || hb, room = s.y == 0xffffffffu || s.w == 0xffffffffu;
-    const uint32_t lo = ha ? s.x : s.z;
-    const uint32_t r_rv = (lo >> 11) & MFX_CSAT, r_av = lo & MFX_CSAT;
-    const bool sat = r_rv == MFX_CSAT || r_av == MFX_CSAT;
-    const uint32_t f_rv = (r_rv < c.minV || r_rv > c.maxV) ? 0u : r_rv;      // -min / -max (merfin.C:199-200)
-    rv[j] = found ? (sat ? lo : f_rv) : 0u;
-    av[j] = (found && !sat) ? r_av : 0u;
-    st[j] = !ok[j] ? 0xffu : (found ? (sat ? 0xfeu : 0xffu) : (room ? 0xffu : 1u));  // an empty slot before the key: absent (value 0, merfin-globals.C:84)
-  }
+  mfx_lane_front<B, B2>(c, fkey, ok, rv, av, line, b0, st, dbg);    // the first mini-bucket, the second one for the displaced: only what is in neither is parked
   uint32_t defer = 0u;
 #pragma unroll
   for (int j = 0; j < B; ++j) {
@@ -1869,7 +1906,6 @@ __device__ __forceinline__ uint32_t mfx_lane_probe_defer(const mfx_table_view &c
         } else st[j] = 0xfcu;                                   // no room in the mailbox (more than 64 parked queries in this wave): scanned here and now
       }
       const uint32_t cnt = (uint32_t)__popcll(m);
-      if (dbg && lane == 0u) atomicAdd(&dbg[0], (unsigned long long)cnt);
       nq = nq + cnt < CAP ? nq + cnt : CAP;
     }
   }
@@ -2251,13 +2287,26 @@ constexpr int MFX_BATCH = MFX_V_BATCH;          // queries per lane and cooperat
 // (mfx_lane_flush) hands parked queries to OTHER lanes of the wave, which breaks the rule: an instance takes kfxlds or defer, never
 // both (static_assert in mfx_hist_kernel; tests/test_gpu_kstar_grid.py: test_saturation_tiles_of_the_packed_word fills both fields).
 constexpr uint32_t MFX_KFX_BASE = 32u;
-template <bool CANON, bool COMPACT, int KF> struct mfx_hist_tune { static constexpr int blocks = MFX_V_MINBLOCKS, batch = MFX_V_BATCH, defer = 0, kfxlds = 0; };
-template <> struct mfx_hist_tune<true, true, 21> { static constexpr int blocks = MFX_V_MINBLOCKS_K21, batch = MFX_V_BATCH_K21, defer = MFX_V_DEFER_K21, kfxlds = MFX_V_KFXLDS_K21; };
+// bucket2: the per-lane second mini-bucket step of the probe (mfx_lane_front).  It ends 47 % of the displaced queries of the 3 Gb i.i.d. world
+// (32.4 M of 69.7 M) with one more 16-byte load of a line the lane already has -- not the nine in ten it would take to keep most batches of
+// 128 out of the cooperative tail (eight in ten still enter it), because neighbouring k-mers take consecutive mini-buckets.  For the
+// DEFERRED probe every query it ends is one that is not parked, i.e. one home line that is not fetched again: k = 31 141.4 -> 144.2 G
+// k-mers/s.  For the undeferred k = 21 instances it is one more dependent round trip in 95 % of the batches that saves the tail in 15 %:
+// 151.5 -> 146.5 G (four windows), 138.9 -> 133.6 G (five); profiles/r07_second_bucket.txt.  The other callers of the probe (generic
+// instance, -dump, -track) have not been measured with it and stay without.
+#ifndef MFX_V_BUCKET2_K21
+#define MFX_V_BUCKET2_K21 0
+#endif
+#ifndef MFX_V_BUCKET2_K31
+#define MFX_V_BUCKET2_K31 1
+#endif
+template <bool CANON, bool COMPACT, int KF> struct mfx_hist_tune { static constexpr int blocks = MFX_V_MINBLOCKS, batch = MFX_V_BATCH, defer = 0, kfxlds = 0, bucket2 = 0; };
+template <> struct mfx_hist_tune<true, true, 21> { static constexpr int blocks = MFX_V_MINBLOCKS_K21, batch = MFX_V_BATCH_K21, defer = MFX_V_DEFER_K21, kfxlds = MFX_V_KFXLDS_K21, bucket2 = MFX_V_BUCKET2_K21; };
 #ifndef MFX_V_KFXLDS_K31
 #define MFX_V_KFXLDS_K31 0
 #endif
-template <> struct mfx_hist_tune<true, true, 31> { static constexpr int blocks = MFX_V_MINBLOCKS_K31, batch = MFX_V_BATCH_K31, defer = MFX_V_DEFER_K31, kfxlds = MFX_V_KFXLDS_K31; };
-template <> struct mfx_hist_tune<true, true, 0> { static constexpr int blocks = MFX_V_MINBLOCKS_GEN, batch = MFX_V_BATCH_GEN, defer = 0, kfxlds = 0; };
+template <> struct mfx_hist_tune<true, true, 31> { static constexpr int blocks = MFX_V_MINBLOCKS_K31, batch = MFX_V_BATCH_K31, defer = MFX_V_DEFER_K31, kfxlds = MFX_V_KFXLDS_K31, bucket2 = MFX_V_BUCKET2_K31; };
+template <> struct mfx_hist_tune<true, true, 0> { static constexpr int blocks = MFX_V_MINBLOCKS_GEN, batch = MFX_V_BATCH_GEN, defer = 0, kfxlds = 0, bucket2 = 0; };
 template <bool CANON, bool COMPACT, int KF, int WF, int TF, bool DBG = false>
 __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::blocks)) void mfx_hist_kernel(mfx_hist_args a) {
   constexpr int BT = mfx_hist_tune<CANON, COMPACT, KF>::batch;                  // queries per lane and probe sequence of this instance
@@ -2350,6 +2399,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
     // palindrome doubling below (an even k takes the undeferred probe)
     const bool defer_tail = MFX_V_DEFER != 0 && mfx_hist_tune<CANON, COMPACT, KF>::defer != 0 && COMPACT && CANON && KF != 0 && TF != 0 && (KF & 1) != 0;
     const bool quotf = KF ? KF > MFX_MAX_K_DIRECT : a.t.quot != 0;
+    constexpr bool bucket2 = MFX_V_BUCKET2 != 0 && mfx_hist_tune<CANON, COMPACT, KF>::bucket2 != 0;      // the probe's second mini-bucket step (mfx_lane_front)
     // The worklist of mfx_hist_rest_kernel: a query whose probe did not end in its two cooperative passes is LISTED -- {canonical
     // k-mer, aux, the (tile, wave) slot its koverCpy term belongs to, mode, "an even-k palindrome: both counts twice"} -- instead of
     // being scanned for by its lane while 63 others wait.  mode 0: aux = its home line; 1 (deep): ... and that line and the next are
@@ -2424,11 +2474,11 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
 #pragma unroll
           for (int j = 0; j < BT; ++j) posn[j] = (b + (uint32_t)j) * MFX_BLOCK + tid;
           auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { (void)jj; return push_wave(want, km, aux, mode, false); };     // (odd k: no palindromes)
-          parked = mfx_lane_probe_defer<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap>(
+          parked = mfx_lane_probe_defer<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap, bucket2>(
                        a.t, MB, nq, fkey, ok, rv, av, line, b0, posn, keyof, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr, mfx_push_fn<decltype(pj)>{pj});
         } else {
           auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { return push_wave(want, km, aux, mode, ((pal >> jj) & 1u) != 0u); };
-          parked = mfx_lane_lookup8<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap>(
+          parked = mfx_lane_lookup8<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap, bucket2>(
                        a.t, MB, fkey, ok, rv, av, line, b0, keyof, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr, mfx_push_fn<decltype(pj)>{pj});
         }
         if (even_k) {
@@ -3834,6 +3884,7 @@ hipError_t mfx_k_hist(const mfx_hist_args &a, int grid, hipStream_t st) {
   if (a.dbg && a.canonical && a.t.compact && a.t.k == 21 && a.t.mz_w == 4 && a.t.mz_t == 6 && !generic) mfx_hist_kernel<true, true, 21, 4, 6, true><<<grid, MFX_BLOCK, dyn, st>>>(a);
   else if (a.canonical && a.t.compact && a.t.k == 21 && a.t.mz_w == 4 && a.t.mz_t == 6 && !generic) mfx_hist_kernel<true, true, 21, 4, 6><<<grid, MFX_BLOCK, dyn, st>>>(a);
   else if (a.canonical && a.t.compact && a.t.k == 21 && a.t.mz_w == 5 && a.t.mz_t == 7 && !generic) mfx_hist_kernel<true, true, 21, 5, 7><<<grid, MFX_BLOCK, dyn, st>>>(a);
+  else if (a.dbg && a.canonical && a.t.compact && a.t.quot && a.t.k == 31 && a.t.mz_w == 4 && a.t.mz_t == 4 && !generic) mfx_hist_kernel<true, true, 31, 4, 4, true><<<grid, MFX_BLOCK, dyn, st>>>(a);
   else if (a.canonical && a.t.compact && a.t.quot && a.t.k == 31 && a.t.mz_w == 4 && a.t.mz_t == 4 && !generic) mfx_hist_kernel<true, true, 31, 4, 4><<<grid, MFX_BLOCK, dyn, st>>>(a);
   else if (a.canonical && a.t.compact) mfx_hist_kernel<true, true, 0, 0, 0><<<grid, MFX_BLOCK, dyn, st>>>(a);
   else if (a.canonical)                mfx_hist_kernel<true, false, 0, 0, 0><<<grid, MFX_BLOCK, dyn, st>>>(a);
