@@ -328,6 +328,44 @@ int       mfx_diag_gather_rate(int device, uint64_t table_bytes, double *lines_p
 int       mfx_eval_debug_enable(mfx_eval *ev, int on);
 int       mfx_eval_debug_counters(mfx_eval *ev, uint64_t *out8);
 
+/* Test hooks of the variant modes (no reference counterpart; csrc/mfx_debug.cpp): the per-path values of the traverse and score
+ * kernels, which a run only shows after bestFilter / bestVariant / ... have reduced them.  The cluster tables are raw arrays of
+ * csrc/mfx_traverse.h's structs, little endian, no padding beyond the named fields:
+ *   cluster 56 B  { u64 win_off; u32 win_len, nv, var0, path_cap; u64 text0, path0, row0; u32 text_cap, pad; }
+ *   variant 16 B  { u32 off, reflen, na, al0; }          allele 16 B  { u64 off; u32 len, pad; }
+ * A cluster's paths go to text[text0 ...] (each followed by '\n'; room text_cap), path slots path0 ... (room path_cap) and rows
+ * row0 + path * nv + variant.  status: 0 ok, 1 a replacement past the end of its string (std::string::replace throws there),
+ * 2 a limit or the reserved room exceeded.  Every offset is checked against its array first (MFX_E_INVAL).
+ *
+ * mfx_debug_traverse_host: the shared traverse (the code the device runs one wave per cluster) in its one-thread form, on the
+ * host; no device is opened.  text[text_end] is the caller's (filled with '\n' by the caller where it wants to see what stays
+ * untouched); the slots a cluster does not use are closed as the device closes them (length 0, cfirst = the slot itself). */
+int mfx_debug_traverse_host(const void *clusters, uint64_t ncl, const void *variants, uint64_t nvar, const void *alleles, uint64_t nal,
+                            const char *win_text, uint64_t win_bytes, const char *al_text, uint64_t al_bytes, uint64_t text_end,
+                            uint64_t path_cap, uint64_t row_cap, uint32_t *np, uint32_t *status, char *text, uint64_t *p_off,
+                            uint32_t *p_len, uint32_t *p_nv, uint64_t *p_voff, uint64_t *p_cfirst, int32_t *gt, uint32_t *vidx,
+                            uint32_t *vlen);
+/* varMer::score of host-enumerated paths on the device (what the variant modes run for clusters beyond the device traverse's
+ * limits): path p is text[off[p] .. + plen[p]), its nv[p] rows start at voff[p] in gt / vidx / vlen [nvals], cfirst[p] is the
+ * first path of its cluster.  Out: numM[npaths] and, need_dk, totdk[npaths]. */
+int mfx_debug_score_paths(mfx_eval *ev, const char *text, uint64_t len, uint64_t npaths, uint64_t nvals, const uint64_t *off,
+                          const uint32_t *plen, const uint32_t *nv, const uint64_t *voff, const uint64_t *cfirst, const int32_t *gt,
+                          const uint32_t *vidx, const uint32_t *vlen, int need_dk, uint32_t *numM, double *totdk);
+/* the same with clusters enumerated ON THE DEVICE behind a host part (text / path table as above, may be empty): the clusters'
+ * text0 is absolute in the batch text and lies in [len, text_end]; path0 / row0 count from 0 behind the host's paths / rows, and
+ * every one of the path_cap slots belongs to exactly one cluster.  Out: numM / totdk [npaths + path_cap] (device part behind the
+ * host's), np / status [ncl], and what a run leaves on the device: text_out[text_end] (the whole batch text, '\n' where nothing
+ * was written), the device part's path table p_off / p_len / p_nv / p_voff / p_cfirst [path_cap] (p_voff, p_cfirst absolute:
+ * + nvals / + npaths) and rows gt_out / vidx_out / vlen_out [row_cap]. */
+int mfx_debug_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, uint64_t npaths, uint64_t nvals, const uint64_t *off,
+                              const uint32_t *plen, const uint32_t *nv, const uint64_t *voff, const uint64_t *cfirst, const int32_t *gt,
+                              const uint32_t *vidx, const uint32_t *vlen, const void *clusters, uint64_t ncl, const void *variants,
+                              uint64_t nvar, const void *alleles, uint64_t nal, const char *win_text, uint64_t win_bytes,
+                              const char *al_text, uint64_t al_bytes, uint64_t text_end, uint64_t path_cap, uint64_t row_cap, int need_dk,
+                              uint32_t *numM, double *totdk, uint32_t *np, uint32_t *status, char *text_out, uint64_t *p_off,
+                              uint32_t *p_len, uint32_t *p_nv, uint64_t *p_voff, uint64_t *p_cfirst, int32_t *gt_out, uint32_t *vidx_out,
+                              uint32_t *vlen_out);
+
 /* merfinGlobal::getK(kmvalu,kmvalu,...) + getKmetric on the host, bit-exact
  * with the device code (merfin-globals.C:66-98, merfin-globals.H:248-261). */
 void mfx_getK(const mfx_kparams *kp, uint32_t readV, uint32_t asmV,

@@ -88,7 +88,17 @@ SYMBOLS = [
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
+    "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
+
+# the cluster tables of the variant modes' device traverse (csrc/mfx_traverse.h; static_asserted in csrc/mfx_debug.cpp)
+TRV_CLUSTER_DTYPE = np.dtype([("win_off", "<u8"), ("win_len", "<u4"), ("nv", "<u4"), ("var0", "<u4"), ("path_cap", "<u4"),
+                              ("text0", "<u8"), ("path0", "<u8"), ("row0", "<u8"), ("text_cap", "<u4"), ("pad", "<u4")])
+TRV_VARIANT_DTYPE = np.dtype([("off", "<u4"), ("reflen", "<u4"), ("na", "<u4"), ("al0", "<u4")])
+TRV_ALLELE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "<u4")])
+assert (TRV_CLUSTER_DTYPE.itemsize, TRV_VARIANT_DTYPE.itemsize, TRV_ALLELE_DTYPE.itemsize) == (56, 16, 16)
+TRV_OK, TRV_RANGE, TRV_ROOM = 0, 1, 2
+TRV_MAX_NV, TRV_MAX_PATHS, TRV_MAX_LEN = 8, 64, 640
 
 # one window of Evaluator.track: the layout of mfx_track_window (include/merfin_amd.h), 72 bytes
 TRACK_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_missing", "<u4"), ("n_scored", "<u4"), ("n_pos", "<u4"), ("n_neg", "<u4"),
@@ -285,6 +295,12 @@ def load_library():
     L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
     L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
     L.mfx_track_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p]
+    u64 = C.c_uint64
+    tables = [vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, u64, u64, u64]       # clusters .. al_bytes, text_end, path_cap, row_cap
+    paths = [vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]                # text, len, npaths, nvals, off .. vlen
+    L.mfx_debug_traverse_host.argtypes = tables + [vp] * 11
+    L.mfx_debug_score_paths.argtypes = [vp] + paths + [C.c_int, vp, vp]
+    L.mfx_debug_score_paths_trv.argtypes = [vp] + paths + tables + [C.c_int] + [vp] * 13
     _lib = L
     return L
 
@@ -1039,6 +1055,76 @@ def gather_rate(table_bytes, device=0):
     return out.value
 
 
+def _vp(a):
+    return C.c_void_p(a.ctypes.data if a.size else 0)
+
+
+class TraverseTables:
+    """A batch of variant clusters as the tables the device traverse reads (TRV_*_DTYPE arrays + window / allele text)."""
+
+    def __init__(self, clusters, variants, alleles, win_text, al_text, text_end, path_cap, row_cap):
+        self.cl = np.ascontiguousarray(clusters, dtype=TRV_CLUSTER_DTYPE)
+        self.var = np.ascontiguousarray(variants, dtype=TRV_VARIANT_DTYPE)
+        self.al = np.ascontiguousarray(alleles, dtype=TRV_ALLELE_DTYPE)
+        self.win = np.frombuffer(bytes(win_text), dtype=np.uint8)
+        self.alt = np.frombuffer(bytes(al_text), dtype=np.uint8)
+        self.text_end, self.path_cap, self.row_cap = int(text_end), int(path_cap), int(row_cap)
+
+    def args(self):
+        return [_vp(self.cl), len(self.cl), _vp(self.var), len(self.var), _vp(self.al), len(self.al), _vp(self.win), len(self.win),
+                _vp(self.alt), len(self.alt), self.text_end, self.path_cap, self.row_cap]
+
+
+class PathTable:
+    """host-enumerated paths inside their text (mfx_debug_score_paths): off / len / nv / voff / cfirst per path, gt / vidx / vlen rows"""
+
+    def __init__(self, text=b"", off=(), plen=(), nv=(), voff=(), cfirst=(), gt=(), vidx=(), vlen=()):
+        self.text = np.frombuffer(bytes(text), dtype=np.uint8)
+        self.off = np.ascontiguousarray(off, dtype=np.uint64)
+        self.len = np.ascontiguousarray(plen, dtype=np.uint32)
+        self.nv = np.ascontiguousarray(nv, dtype=np.uint32)
+        self.voff = np.ascontiguousarray(voff, dtype=np.uint64)
+        self.cfirst = np.ascontiguousarray(cfirst, dtype=np.uint64)
+        self.gt = np.ascontiguousarray(gt, dtype=np.int32)
+        self.vidx = np.ascontiguousarray(vidx, dtype=np.uint32)
+        self.vlen = np.ascontiguousarray(vlen, dtype=np.uint32)
+        assert len(self.off) == len(self.len) == len(self.nv) == len(self.voff) == len(self.cfirst)
+        assert len(self.gt) == len(self.vidx) == len(self.vlen)
+
+    def args(self):
+        return [_vp(self.text), len(self.text), len(self.off), len(self.gt), _vp(self.off), _vp(self.len), _vp(self.nv), _vp(self.voff),
+                _vp(self.cfirst), _vp(self.gt), _vp(self.vidx), _vp(self.vlen)]
+
+
+def _trv_outputs(t):
+    o = {"np": np.zeros(len(t.cl), dtype=np.uint32), "status": np.zeros(len(t.cl), dtype=np.uint32),
+         "text": np.full(max(t.text_end, 1), 10, dtype=np.uint8),
+         "p_off": np.zeros(max(t.path_cap, 1), dtype=np.uint64), "p_len": np.zeros(max(t.path_cap, 1), dtype=np.uint32),
+         "p_nv": np.zeros(max(t.path_cap, 1), dtype=np.uint32), "p_voff": np.zeros(max(t.path_cap, 1), dtype=np.uint64),
+         "p_cfirst": np.zeros(max(t.path_cap, 1), dtype=np.uint64), "gt": np.zeros(max(t.row_cap, 1), dtype=np.int32),
+         "vidx": np.zeros(max(t.row_cap, 1), dtype=np.uint32), "vlen": np.zeros(max(t.row_cap, 1), dtype=np.uint32)}
+    order = ["np", "status", "text", "p_off", "p_len", "p_nv", "p_voff", "p_cfirst", "gt", "vidx", "vlen"]
+    return o, [C.c_void_p(o[n].ctypes.data) for n in order]
+
+
+def _trv_trim(o, t):
+    o["text"] = o["text"][:t.text_end]
+    for n in ("p_off", "p_len", "p_nv", "p_voff", "p_cfirst"):
+        o[n] = o[n][:t.path_cap]
+    for n in ("gt", "vidx", "vlen"):
+        o[n] = o[n][:t.row_cap]
+    return o
+
+
+def debug_traverse_host(tables):
+    """test hook: the shared traverse, one thread, on the host (mfx_debug_traverse_host; needs no GPU).  Returns a dict of arrays:
+    np, status [ncl]; text [text_end] ('\\n' where nothing was written); p_off, p_len, p_nv, p_voff, p_cfirst [path_cap]; gt, vidx,
+    vlen [row_cap]"""
+    o, ptrs = _trv_outputs(tables)
+    _check(load_library().mfx_debug_traverse_host(*(tables.args() + ptrs)))
+    return _trv_trim(o, tables)
+
+
 class LoadedVcf:
     """a VCF read and parsed ahead of its run (mfx_vcf_load): no device involved"""
 
@@ -1175,6 +1261,28 @@ class Evaluator:
         p = lambda x: C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
         _check(load_library().mfx_hist_keys_launch(self.h, p(d_keys), p(d_contigs), n, ncontigs, p(d_counts), p(d_kover),
                                                    C.c_void_p(stream or 0)))
+
+    def debug_score_paths(self, paths, need_dk=True):
+        """test hook: varMer::score of host-enumerated paths on the device (mfx_debug_score_paths) -> (numM, totdk)"""
+        n = len(paths.off)
+        numM = np.zeros(max(n, 1), dtype=np.uint32)
+        totdk = np.zeros(max(n, 1), dtype=np.float64)
+        _check(load_library().mfx_debug_score_paths(self.h, *(paths.args() + [1 if need_dk else 0, C.c_void_p(numM.ctypes.data), C.c_void_p(totdk.ctypes.data)])))
+        return numM[:n], totdk[:n]
+
+    def debug_score_paths_trv(self, paths, tables, need_dk=True):
+        """test hook: the clusters of `tables` enumerated and scored on the device behind the host part `paths` (PathTable, may be
+        empty): mfx_debug_score_paths_trv.  Returns debug_traverse_host's dict (the device part; text = the whole batch text) plus
+        numM, totdk [host paths + path_cap]"""
+        n = len(paths.off) + tables.path_cap
+        numM = np.zeros(max(n, 1), dtype=np.uint32)
+        totdk = np.zeros(max(n, 1), dtype=np.float64)
+        o, ptrs = _trv_outputs(tables)
+        _check(load_library().mfx_debug_score_paths_trv(self.h, *(paths.args() + tables.args() + [1 if need_dk else 0, C.c_void_p(numM.ctypes.data),
+                                                                                                     C.c_void_p(totdk.ctypes.data)] + ptrs)))
+        o = _trv_trim(o, tables)
+        o["numM"], o["totdk"] = numM[:n], totdk[:n]
+        return o
 
     def dump_values(self, seqs, contig, pos_begin, pos_end):
         n = pos_end - pos_begin

@@ -4226,7 +4226,8 @@ int mfx_score_paths(mfx_eval *ev, const char *text, uint64_t len, const mfx_path
   return MFX_OK;
 }
 
-int mfx_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, const mfx_path_table *pt, const mfx_trv_batch *tb, int need_dk, uint32_t *numM, double *totdk) {
+int mfx_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, const mfx_path_table *pt, const mfx_trv_batch *tb, int need_dk, uint32_t *numM, double *totdk,
+                        const mfx_trv_readback *rb) {
   if (!ev || !pt || !tb || (len && !text) || !numM || (need_dk && !totdk) || (tb->ncl && (!tb->cl || !tb->var || !tb->al || !tb->np || !tb->status || !tb->p_len || !tb->gt)))
     return mfx_fail(MFX_E_INVAL, "mfx_score_paths_trv: null argument");
   if (ev->ix->seq_only && !ev->ix->paths_token) return mfx_fail(MFX_E_INVAL, "mfx_score_paths: a sequence-only index holds the k-mers of one sequence; alternative paths need the full index (or the path-only one: mfx_index_claim_paths)");
@@ -4329,6 +4330,19 @@ int mfx_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, const mfx_
     MFX_HIP(hipMemcpy(tb->status, dst.p, tb->ncl * 4, hipMemcpyDeviceToHost));
     if (tb->path_cap) MFX_HIP(hipMemcpy(tb->p_len, dlen.p + hp, tb->path_cap * 4, hipMemcpyDeviceToHost));
     if (tb->row_cap) MFX_HIP(hipMemcpy(tb->gt, dgt.p + hv, tb->row_cap * 4, hipMemcpyDeviceToHost));
+  }
+  if (rb) {
+    MFX_HIP(hipMemcpy(rb->text, dtext.p, total, hipMemcpyDeviceToHost));
+    if (tb->path_cap) {
+      MFX_HIP(hipMemcpy(rb->p_off, doff.p + hp, tb->path_cap * 8, hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(rb->p_voff, dvoff.p + hp, tb->path_cap * 8, hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(rb->p_cfirst, dcf.p + hp, tb->path_cap * 8, hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(rb->p_nv, dnv.p + hp, tb->path_cap * 4, hipMemcpyDeviceToHost));
+    }
+    if (tb->row_cap) {
+      MFX_HIP(hipMemcpy(rb->vidx, dvidx.p + hv, tb->row_cap * 4, hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(rb->vlen, dvlen.p + hv, tb->row_cap * 4, hipMemcpyDeviceToHost));
+    }
   }
   return MFX_OK;
 }

@@ -244,7 +244,15 @@ struct mfx_trv_batch {
   uint32_t *p_len = nullptr;                     // [path_cap] out: the length of every path slot
   int32_t *gt = nullptr;                         // [row_cap] out: the genotype rows
 };
-int mfx_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, const mfx_path_table *pt, const mfx_trv_batch *tb, int need_dk, uint32_t *numM, double *totdk);
+// rb (tests: mfx_debug_score_paths_trv; the product passes none): what the call otherwise leaves on the device comes back too -- the whole
+// batch text [max(text_end, len)] and, of the device part, the path table [path_cap] and the offset / length rows [row_cap]
+struct mfx_trv_readback {
+  char *text = nullptr;
+  uint64_t *p_off = nullptr, *p_voff = nullptr, *p_cfirst = nullptr;
+  uint32_t *p_nv = nullptr, *vidx = nullptr, *vlen = nullptr;
+};
+int mfx_score_paths_trv(mfx_eval *ev, const char *text, uint64_t len, const mfx_path_table *pt, const mfx_trv_batch *tb, int need_dk, uint32_t *numM, double *totdk,
+                        const mfx_trv_readback *rb = nullptr);
 
 // The PATH-ONLY index of the variant modes (mfx_index_claim_paths, mfx_variants.cpp): a batch's text is put together on the device exactly as
 // mfx_score_paths_trv does -- the host's paths copied in, the other clusters enumerated by the traverse kernel -- and the claim kernel of

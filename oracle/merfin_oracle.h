@@ -161,6 +161,16 @@ void orc_completeness_piece(const orc_params *p,
                             const uint64_t *ak, const uint32_t *av, uint64_t an,
                             double *total, double *undrc);
 
+/* ---- variant modes, ONE cluster (merfin_oracle_variants.cpp) ----------------
+ * traverse (merfin-variants.C:22-126) + varMer::score (varMer.C:48-145) of one cluster given as flat data; every path
+ * comes back in addSeqPath order.  Lookups: R / A, or cb != NULL (the k-mer's text; k > 31).  See the definition. */
+typedef void (*orc_getk_text_fn)(void *ctx, const char *kmer, int k, double *readK, double *asmK, double *prob);
+int orc_cluster_paths(const orc_params *p, const orc_lookup *R, const orc_lookup *A, orc_getk_text_fn cb, void *cb_ctx, int reportType,
+                      const char *win, uint32_t win_len, uint32_t nv, const uint32_t *v_off, const uint32_t *v_reflen,
+                      const uint32_t *v_na, const char *const *alleles, uint32_t path_cap, uint64_t text_cap, uint32_t *np,
+                      uint64_t *longest, int *status, char *text, uint64_t *text_len, uint32_t *p_len, int32_t *gt,
+                      uint32_t *vidx, uint32_t *vlen, uint32_t *numM, double *totdk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #include <functional>
 #include <list>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -221,8 +222,6 @@ struct vcfFile {                                         /* vcf.H:89-125 */
  * function of the k-mer's TEXT (k bases, all ACGT) -- the k-agnostic form used to pin the 32 <= k <= 64 path, whose k-mers
  * do not fit the 64-bit orc_kiter / orc_lookup (tests: a plain-Python getK over arbitrary-precision k-mers,
  * oracle/plain.py).  The validity rule is kmerIterator's: a k-mer ends at a base iff the k bases up to it are ACGT. */
-typedef void (*orc_getk_text_fn)(void *ctx, const char *kmer, int k, double *readK, double *asmK, double *prob);
-
 struct Globals {
   const orc_params *p;
   const orc_lookup *R, *A;
@@ -484,6 +483,11 @@ struct varMer {                                          /* varMer.H, varMer.C *
   }
 };
 
+/* longest `replaced` string a traverse built (orc_cluster_paths reports it: a candidate string has to fit the
+ * device's per-level buffer); bookkeeping only, nothing below reads it */
+size_t g_longest_replaced = 0;
+inline void note_replaced(const string &s) { if (s.size() > g_longest_replaced) g_longest_replaced = s.size(); }
+
 /* merfin-variants.C:22-126.  Parameter passing (by value / by reference) is
  * part of the algorithm and kept exactly. */
 string traverse(uint32_t idx, vector<uint32_t> &refIdxList, vector<uint32_t> refLenList,
@@ -495,6 +499,7 @@ string traverse(uint32_t idx, vector<uint32_t> &refIdxList, vector<uint32_t> ref
     path.push_back(j);
     char const *hap = haps[j];
     string replaced = candidate;
+    note_replaced(replaced);
     int skipped = 0;
     bool overlaps = false;
     int delta = 0;
@@ -502,6 +507,7 @@ string traverse(uint32_t idx, vector<uint32_t> &refIdxList, vector<uint32_t> ref
       refLenList[idx] = refLen;
       replaced = candidate;
       replaced.replace(refIdxList[idx], refLenList[idx], hap);
+      note_replaced(replaced);
       delta = (int)strlen(hap) - (int)refLenList[idx];
       uint32_t refAffected = refIdxList[idx] + refLenList[idx];
       refLenList[idx] = (uint32_t)strlen(hap);
@@ -532,6 +538,62 @@ string traverse(uint32_t idx, vector<uint32_t> &refIdxList, vector<uint32_t> ref
 }
 
 }  // namespace
+
+/* ONE cluster through traverse + varMer::score, every path out (tests of the device's traverse / score kernels, which the
+ * selectors above otherwise hide).  The cluster as flat data: its window text, per variant the offset in the window, the REF
+ * length and the number of alleles (REF first), the alleles as C strings in variant order.  Lookups: R / A, or cb (k > 31).
+ * reportType: OP_FILTER (4) scores numM only, anything else the delta-K terms too.
+ * Out, in addSeqPath order: text (every path followed by '\n'), p_len[path], rows of nv entries gt / vidx / vlen, numM, totdk
+ * (getTotdK); *np paths, *longest = the longest `replaced` string of the recursion, *status = 1 when std::string::replace threw
+ * out_of_range (what was added before it is still reported, unscored).  Returns 0, or -1 when path_cap / text_cap are too small. */
+extern "C" int orc_cluster_paths(const orc_params *p, const orc_lookup *R, const orc_lookup *A, orc_getk_text_fn cb, void *cb_ctx, int reportType,
+                                 const char *win, uint32_t win_len, uint32_t nv, const uint32_t *v_off, const uint32_t *v_reflen,
+                                 const uint32_t *v_na, const char *const *alleles, uint32_t path_cap, uint64_t text_cap, uint32_t *np,
+                                 uint64_t *longest, int *status, char *text, uint64_t *text_len, uint32_t *p_len, int32_t *gt,
+                                 uint32_t *vidx, uint32_t *vlen, uint32_t *numM, double *totdk) {
+  vector<uint32_t> refIdxList, refLenList;
+  vector<int> path;
+  map<int, vector<char const *>> mapPosHap;
+  uint32_t a0 = 0;
+  for (uint32_t i = 0; i < nv; i++) {
+    refIdxList.push_back(v_off[i]);
+    refLenList.push_back(v_reflen[i]);
+    mapPosHap[(int)i] = vector<char const *>(alleles + a0, alleles + a0 + v_na[i]);
+    a0 += v_na[i];
+  }
+  string refTemplate(win, win + win_len);
+  varMer seqMer(nullptr);                                  /* posGt: neither traverse nor score reads it */
+  g_longest_replaced = 0;
+  *status = 0;
+  try {
+    traverse(0, refIdxList, refLenList, mapPosHap, refTemplate, path, &seqMer);
+  } catch (const std::out_of_range &) {
+    *status = 1;
+  }
+  *longest = g_longest_replaced;
+  Globals G{p, R, A, reportType, 0, cb, cb_ctx};
+  if (*status == 0) seqMer.score(&G);
+  *np = (uint32_t)seqMer.seqs.size();
+  if (seqMer.seqs.size() > path_cap) return -1;
+  uint64_t at = 0;
+  for (size_t i = 0; i < seqMer.seqs.size(); i++) {
+    const string &s = seqMer.seqs[i];
+    if (at + s.size() + 1 > text_cap) return -1;
+    memcpy(text + at, s.data(), s.size());
+    at += s.size();
+    text[at++] = '\n';
+    p_len[i] = (uint32_t)s.size();
+    for (uint32_t j = 0; j < nv; j++) {
+      gt[i * nv + j] = seqMer.gtPaths[i].at(j);
+      vidx[i * nv + j] = seqMer.idxPaths[i].at(j);
+      vlen[i * nv + j] = seqMer.lenPaths[i].at(j);
+    }
+    numM[i] = *status == 0 ? seqMer.numMs[i] : 0;
+    totdk[i] = (*status == 0 && reportType != OP_FILTER) ? seqMer.getTotdK((int)i) : 0.0;
+  }
+  *text_len = at;
+  return 0;
+}
 
 /* processVariants + outputVariants over all contigs in input order.
  * mode: 4 filter, 5 polish, 6 better, 7 strict, 8 loose.  Writes the VCF text

@@ -106,6 +106,11 @@ def lib():
     L.orc_variants_run_cb.restype = C.c_long
     L.orc_variants_run_cb.argtypes = [C.POINTER(_Params), GETK_TEXT_FN, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_char_p,
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), u64p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
+    i32p = C.POINTER(C.c_int32)
+    L.orc_cluster_paths.restype = C.c_int
+    L.orc_cluster_paths.argtypes = [C.POINTER(_Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_char_p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, u32p,
+                                    u64p, C.POINTER(C.c_int), C.c_void_p, u64p, u32p, i32p, u32p, u32p, u32p, f64p]
     _lib = L
     return L
 
@@ -347,3 +352,54 @@ def variants_run_text(k, getk, mode, vcf_path, names, contigs, out_path, comb=15
     if rc < 0:
         raise RuntimeError("orc_variants_run_cb failed: %d" % rc)
     return rc
+
+
+def getk_text_fn(getk):
+    """a Python getk(kmer_text) -> (readK, asmK, prob) as the oracle's callback (keep the returned object alive while it is used)"""
+    def cb(_ctx, text, kk, rk, ak, pr):
+        a, b, c = getk(C.string_at(text, kk))
+        rk[0], ak[0], pr[0] = a, b, c
+    return GETK_TEXT_FN(cb)
+
+
+def cluster_paths(p, R, A, win, variants, need_dk=True, cb=None):
+    """traverse + varMer::score of ONE cluster (orc_cluster_paths).  win: the window's bytes; variants: [(offset in the window,
+    REF length, [allele bytes, REF first])]; R / A: Lookup objects, or cb = getk_text_fn(...) (k > 31).  Returns a dict: status
+    (1: std::string::replace threw out_of_range), longest (the longest candidate string built), paths = [bytes], gt / vidx / vlen
+    = int arrays [np, nv], numM [np], totdk [np] (float64) -- all in addSeqPath order."""
+    nv = len(variants)
+    off = np.array([v[0] for v in variants], dtype=np.uint32)
+    rl = np.array([v[1] for v in variants], dtype=np.uint32)
+    na = np.array([len(v[2]) for v in variants], dtype=np.uint32)
+    al = [a for v in variants for a in v[2]]
+    assert all(b"\0" not in a for a in al)
+    arr = (C.c_char_p * max(len(al), 1))(*al)
+    cap = 1
+    for v in variants:
+        cap *= len(v[2])
+    grow = sum(max(len(a) for a in v[2]) for v in variants)
+    tcap = cap * (len(win) + grow + 1)
+    text = np.zeros(tcap, dtype=np.uint8)
+    p_len = np.zeros(cap, dtype=np.uint32)
+    gt = np.zeros((cap, nv), dtype=np.int32)
+    vidx = np.zeros((cap, nv), dtype=np.uint32)
+    vlen = np.zeros((cap, nv), dtype=np.uint32)
+    numM = np.zeros(cap, dtype=np.uint32)
+    totdk = np.zeros(cap, dtype=np.float64)
+    n, tl, lg, st = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    rc = lib().orc_cluster_paths(p.ref(), R.h if R is not None else None, A.h if A is not None else None,
+                                 C.cast(cb, C.c_void_p) if cb is not None else None, None, 5 if need_dk else 4,
+                                 bytes(win), len(win), nv, _u32(off), _u32(rl), _u32(na), arr, cap, tcap, C.byref(n), C.byref(lg), C.byref(st),
+                                 C.c_void_p(text.ctypes.data), C.byref(tl), _u32(p_len), gt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 _u32(vidx), _u32(vlen), _u32(numM), _f64(totdk))
+    if rc:
+        raise RuntimeError("orc_cluster_paths: more paths or text than a cluster can have (%d)" % rc)
+    n = n.value
+    paths, at = [], 0
+    raw = text[:tl.value].tobytes()
+    for i in range(n):
+        paths.append(raw[at:at + int(p_len[i])])
+        assert raw[at + int(p_len[i])] == 10
+        at += int(p_len[i]) + 1
+    return {"status": st.value, "longest": lg.value, "paths": paths, "gt": gt[:n], "vidx": vidx[:n], "vlen": vlen[:n],
+            "numM": numM[:n], "totdk": totdk[:n]}
