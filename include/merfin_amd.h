@@ -712,6 +712,44 @@ int mfx_completeness(mfx_eval *ev, double *total, double *undrcpy);
  * merfin-completeness.C:56-66,119-120); arrays of 64 doubles each */
 int mfx_completeness_pieces(mfx_eval *ev, double *total64, double *undrcpy64);
 
+/* ------------------------------------------------------------------------ */
+/* -spectrum / -peak auto: the copy-number spectrum of an index.  No seam of  */
+/* the reference: merfin takes -peak from a k-mer multiplicity histogram of   */
+/* the read database made outside it (meryl histogram -> GenomeScope).  Here  */
+/* the 2-D histogram of the table's (read count, assembly count) pairs is one */
+/* streaming pass over the table, and its single-copy row gives the peak.     */
+/* ------------------------------------------------------------------------ */
+#define MFX_E_NODATA     -10  /* the data holds no answer (mfx_spectrum_peak: no peak in the row) */
+/* out: (copies + 2) x (max_mult + 1) cells, row-major.  Row r <= copies: entries whose assembly count is r; row copies + 1:
+ * assembly count > copies.  Column m < max_mult: read count m; column max_mult: read count >= max_mult.  An entry is counted
+ * once, with the counts mfx_index_value answers for its k-mer (the read count through the index's -min / -max filter, 0
+ * outside it); an entry whose two counts are both 0 is not counted.  *n_entries: the counted entries = the sum of the image.
+ * Every index form (a shard gives the spectrum of what it owns; a read-counted index that of its counted reads).
+ * MFX_E_INVAL: copies outside [1, 6], max_mult outside [4, 65536], or an index that took non-canonical inserts (such a
+ * database splits one k-mer over two entries: the spectrum of entries is not the spectrum of k-mers). */
+int mfx_spectrum_run(const mfx_index *ix, uint32_t copies, uint32_t max_mult, uint64_t *out, uint64_t *n_entries);
+/* Diagnostic (tools/spectrum_rate.py): the same pass `reps` times with the plain (aggregate 0) or the wave-aggregated (1) form of the
+ * kernel, the time of each between two HIP events into kernel_ms[reps]; the image is checked against its entry count and dropped. */
+int mfx_diag_spectrum_time(const mfx_index *ix, uint32_t copies, uint32_t max_mult, int aggregate, uint32_t reps, float *kernel_ms);
+typedef struct {
+  uint32_t valley;          /* first multiplicity at which the smoothed row stops falling                              */
+  uint32_t main_peak;       /* highest point of the smoothed row beyond the valley                                   */
+  uint32_t haploid_peak;    /* main_peak, or the peak at half of it where the 2-copy peak dominates: what -peak takes  */
+  uint64_t count_at_peak;   /* row[haploid_peak]                                                                     */
+} mfx_spectrum_peak_t;
+/* Host only, exact integer arithmetic on one row of max_mult + 1 cells (column 0 and the overflow column take no part).
+ * a[m], 1 <= m < max_mult: the mean of row[j] over j in [max(1, m-2), min(max_mult-1, m+2)], compared as rationals.
+ * valley v: the smallest m in [1, max_mult-2] with a[m] <= a[m+1]; main peak p: the m in (v, max_mult) with the largest a[m]
+ * (the smallest on ties); h: the m in [max(v+1, ceil(0.4 p)), floor(0.6 p)] with the largest a[m] (the smallest on ties);
+ * the haploid peak is h when that range is not empty, 10 a[h] >= a[p] and a[h] >= a[j] for every j within 2 of h, else p.
+ * MFX_E_NODATA: no v, or a[p] == 0 (an empty or falling row, a peak too low to tell from the error slope): ask for -peak. */
+int mfx_spectrum_peak(const uint64_t *row, uint32_t max_mult, mfx_spectrum_peak_t *out);
+/* Host only.  "Copies\tkmer_multiplicity\tCount", then one line per non-zero cell in row-major order: "read-only" (row 0), "1" ..
+ * "<copies>", ">copies" with the number filled in (the last row); m (the overflow column as max_mult); the count.
+ * with_read_only == 0 leaves row 0 out (a sequence-only index holds no such k-mers).  .gz / .bz2 / .xz names go through the
+ * compressed writers.  The layout is believed to be the one Merqury's spectra-cn plot reads; UNVALIDATED against Merqury. */
+int mfx_spectrum_write(const uint64_t *img, uint32_t copies, uint32_t max_mult, int with_read_only, const char *path);
+
 #ifdef __cplusplus
 }
 #endif

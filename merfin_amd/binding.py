@@ -54,6 +54,10 @@ class _ReadsStats(C.Structure):
                 ("dropped", C.c_uint64), ("saturated", C.c_uint64), ("seconds_kernel", C.c_double), ("seconds_copy", C.c_double)]
 
 
+class _SpectrumPeak(C.Structure):
+    _fields_ = [("valley", C.c_uint32), ("main_peak", C.c_uint32), ("haploid_peak", C.c_uint32), ("count_at_peak", C.c_uint64)]
+
+
 class _HistResult(C.Structure):
     _fields_ = [("kasm", C.c_uint64), ("kmissing", C.c_uint64), ("koverCpy", C.c_double),
                 ("undrMax", C.c_uint32), ("overMax", C.c_uint32),
@@ -88,6 +92,7 @@ SYMBOLS = [
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
+    "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
 
@@ -295,6 +300,10 @@ def load_library():
     L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
     L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
     L.mfx_track_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p]
+    L.mfx_spectrum_run.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p]
+    L.mfx_diag_spectrum_time.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
+    L.mfx_spectrum_peak.argtypes = [u64p, C.c_uint32, C.POINTER(_SpectrumPeak)]
+    L.mfx_spectrum_write.argtypes = [u64p, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p]
     u64 = C.c_uint64
     tables = [vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, u64, u64, u64]       # clusters .. al_bytes, text_end, path_cap, row_cap
     paths = [vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]                # text, len, npaths, nvals, off .. vlen
@@ -645,6 +654,21 @@ class Index:
         return {"k": i.k, "canonical": bool(i.canonical), "capacity": i.capacity, "distinct": i.distinct, "bytes": i.bytes,
                 "seq_only": bool(i.seq_only), "compact": bool(i.compact), "dropped": i.dropped}
 
+    def spectrum(self, copies=4, max_mult=10000, with_entries=False):
+        """the copy-number spectrum of the index's entries (mfx_spectrum_run): a (copies + 2, max_mult + 1) uint64 array -- row r:
+        assembly count r (the last row: > copies), column m: read count m after -min / -max (the last column: >= max_mult);
+        with_entries: also the number of counted entries"""
+        img = np.zeros((int(copies) + 2, int(max_mult) + 1), dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(load_library().mfx_spectrum_run(self.h, int(copies), int(max_mult), img.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        return (img, n.value) if with_entries else img
+
+    def spectrum_kernel_ms(self, copies=4, max_mult=10000, aggregate=False, reps=5):
+        """diagnostic (mfx_diag_spectrum_time): the spectrum kernels' time in ms, HIP events, of each of `reps` passes"""
+        ms = (C.c_float * reps)()
+        _check(load_library().mfx_diag_spectrum_time(self.h, int(copies), int(max_mult), 1 if aggregate else 0, reps, ms))
+        return list(ms)
+
     def export(self, sort=True):
         """every stored (k-mer, readV, asmV), sorted by k-mer (sort=False: table order).  k > 31: k-mers are rows
         [low 64 bits, high bits]"""
@@ -913,6 +937,29 @@ def track_write(windows, seqs, names, window, tsv_path=None, bedgraph_path=None)
     nm = (C.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else x for x in names])
     _check(load_library().mfx_track_write(C.c_void_p(w.ctypes.data), len(w), seqs.h, nm, int(window),
                                           tsv_path.encode() if tsv_path else None, bedgraph_path.encode() if bedgraph_path else None))
+
+
+E_NODATA = -10
+
+
+def spectrum_peak(row):
+    """the haploid peak of one spectrum row of max_mult + 1 cells (mfx_spectrum_peak; host only, exact): a dict of valley,
+    main_peak, haploid_peak and count_at_peak, or None when the rule finds no peak"""
+    row = np.ascontiguousarray(row, dtype=np.uint64)
+    out = _SpectrumPeak()
+    rc = load_library().mfx_spectrum_peak(row.ctypes.data_as(C.POINTER(C.c_uint64)), len(row) - 1, C.byref(out))
+    if rc == E_NODATA:
+        return None
+    _check(rc)
+    return {"valley": out.valley, "main_peak": out.main_peak, "haploid_peak": out.haploid_peak, "count_at_peak": out.count_at_peak}
+
+
+def spectrum_write(img, path, with_read_only=True):
+    """a spectrum image as text (mfx_spectrum_write; host only): Copies, kmer_multiplicity, Count per non-zero cell; .gz / .bz2 /
+    .xz names are compressed.  The layout is unvalidated against Merqury."""
+    img = np.ascontiguousarray(img, dtype=np.uint64)
+    _check(load_library().mfx_spectrum_write(img.ctypes.data_as(C.POINTER(C.c_uint64)), img.shape[0] - 2, img.shape[1] - 1,
+                                             1 if with_read_only else 0, path.encode() if isinstance(path, str) else path))
 
 
 def pack_bases(seq):

@@ -31,7 +31,7 @@
 #include "../../include/merfin_amd.h"
 #include "fasta.h"
 
-enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK };
+enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM };
 
 struct Globals {
   const char *seqName = nullptr, *seqDBname = nullptr, *readDBname = nullptr, *pLookupTable = nullptr;
@@ -49,6 +49,9 @@ struct Globals {
   int kArg = 0;                          // -k (0: not given); with -reads: the run's k once the flags are checked
   uint64_t window = 1000;                // -window: k-mer start positions per window of -track
   bool windowGiven = false;
+  bool peakAuto = false;                 // -peak auto: the haploid peak is read off the index's copy-number spectrum (mfx_spectrum_peak)
+  uint32_t copies = 4, maxMult = 10000;  // -copies / -maxmult of -spectrum
+  bool copiesGiven = false, maxMultGiven = false;
 };
 
 static void usage(const char *exe) {
@@ -61,7 +64,9 @@ static void usage(const char *exe) {
           "    -min m / -max m   ignore read k-mers with value below / above m\n"
           "    -memory m         do not use more than m GB (of HBM) for the k-mer tables\n"
           "    -threads t        accepted for compatibility (host threads)\n"
-          "    -peak m           haploid k-mer coverage peak (required except -filter)\n"
+          "    -peak m           haploid k-mer coverage peak (required except -filter and -spectrum)\n"
+          "    -peak auto        -hist, -dump, -track, -spectrum on one device: the peak is read off the single-copy row of the index's\n"
+          "                      copy-number spectrum (one more pass over the table on the GPU) and reported on stderr\n"
           "    -prob file        readK,prob rows; row n overrides -peak for multiplicity n\n"
           "    -seqmers db       assembly k-mer database; default: counted from -sequence on the GPU\n"
           "    -reads file       instead of -readmers: count the read k-mers of this FASTA / FASTQ file (plain, .gz, .bz2, .xz) on\n"
@@ -81,7 +86,9 @@ static void usage(const char *exe) {
           "                      look every k-mer up in all shards and add the answers; -completeness adds per-shard sums\n"
           "    -index file       cache of the built HBM index: loaded if it exists (the k-mer databases are then not\n"
           "                      read), otherwise written after the build\n"
-          "    -window W         with -track: k-mer start positions per window (default 1000)\n\n"
+          "    -window W         with -track: k-mer start positions per window (default 1000)\n"
+          "    -copies C         with -spectrum: rows for assembly counts 1 .. C, one more for > C (1 to 6, default 4)\n"
+          "    -maxmult M        with -spectrum: read counts of M and more share the last column (4 to 65536, default 10000)\n\n"
           "  Report types (exactly one):\n"
           "    -hist           0-centred K* histogram to <output>; QV and QV* on stderr\n"
           "    -dump           seqName, seqPos, readK, asmK, K* per k-mer to <output>  [-skipMissing]\n"
@@ -89,6 +96,8 @@ static void usage(const char *exe) {
           "    -track          K* summarised per window of every contig on the GPU -> <output>.track.tsv, <output>.kstar.bedgraph\n"
           "                    (mean K*) and <output>.missing.bedgraph (missing fraction)  [-window W]; an <output> ending in\n"
           "                    .gz / .bz2 / .xz compresses the three files (out.gz -> out.track.tsv.gz ...)\n"
+          "    -spectrum       copy-number spectrum (k-mers per read count and assembly count) -> <output>.spectra-cn.hist; the haploid\n"
+          "                    peak it shows on stderr.  No -peak needed.  [-copies C] [-maxmult M]\n"
           "    -filter         keep variants (and combinations within k) that minimise missing k-mers -> <output>.filter.vcf\n"
           "    -polish         choose variant combinations by missing k-mers, ties by k* -> <output>.polish.vcf\n"
           "    -better -strict -loose   k*-free variants of -polish -> <output>.filter.vcf\n"
@@ -719,7 +728,24 @@ int main(int argc, char **argv) {
       G.kArg = (e != v && *e == 0 && kk >= 1 && kk <= 64) ? (int)kk : -1;
       if (G.kArg < 0) err.push_back(std::string("Invalid -k '") + v + "': k is 1 to 64.\n");
     }
-    else if (is("-peak")) G.peak = strtod(val(), nullptr);
+    else if (is("-peak")) {
+      const char *v = val();
+      if (strcmp(v, "auto") == 0) G.peakAuto = true;
+      else G.peak = strtod(v, nullptr);
+    }
+    else if (is("-spectrum")) G.reportType = OP_SPECTRUM;
+    else if (is("-copies") || is("-maxmult")) {
+      const bool cp = is("-copies");
+      const char *v = val();
+      char *e = nullptr;
+      errno = 0;
+      const unsigned long long x = strtoull(v, &e, 10);
+      const unsigned long long lo = cp ? 1 : 4, hi = cp ? 6 : 65536;
+      (cp ? G.copiesGiven : G.maxMultGiven) = true;
+      if (e == v || *e != 0 || errno != 0 || !isdigit((unsigned char)v[0]) || x < lo || x > hi)
+        err.push_back(std::string("Invalid ") + (cp ? "-copies" : "-maxmult") + " '" + v + "': an integer from " + std::to_string(lo) + " to " + std::to_string(hi) + ".\n");
+      else (cp ? G.copies : G.maxMult) = (uint32_t)x;
+    }
     else if (is("-prob")) G.pLookupTable = val();
     else if (is("-vcf")) G.vcfName = val();
     else if (is("-output")) G.outName = val();
@@ -815,6 +841,25 @@ int main(int argc, char **argv) {
     if (G.vcfName) err.push_back("-track does not take -vcf (the variant modes do).\n");
   }
 
+  // -spectrum / -peak auto: every check before any device is touched
+  if ((G.copiesGiven || G.maxMultGiven) && G.reportType != OP_SPECTRUM)
+    err.push_back("-copies and -maxmult shape the image of -spectrum; they have no meaning without -spectrum.\n");
+  if (G.reportType == OP_SPECTRUM) {
+    if (G.vcfName) err.push_back("-spectrum does not take -vcf (the variant modes do).\n");
+    if (G.sharded) err.push_back("-spectrum does not take -sharded: this version counts the spectrum of one table on one device.\n");
+    if (G.devices.size() > 1) err.push_back("-spectrum runs on one device (-device d, or -devices naming one).\n");
+    if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -spectrum counts every entry of the table.\n");
+    if (!G.seqName && !G.seqDBname) err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
+    if (!G.seqName && !G.readsNames.empty()) err.push_back("-spectrum counts -reads into the k-mers of -sequence: give -sequence.\n");
+  }
+  if (G.peakAuto) {
+    if (G.peak != 0) err.push_back("-peak was given twice (a number and auto).\n");
+    if (G.reportType != OP_HIST && G.reportType != OP_DUMP && G.reportType != OP_TRACK && G.reportType != OP_SPECTRUM && G.reportType != OP_NONE)
+      err.push_back("-peak auto reads the peak off the table of -hist, -dump, -track or -spectrum; the variant modes and -completeness take -peak <number>.\n");
+    if (G.sharded) err.push_back("-peak auto does not take -sharded: no peak is defined on a sharded table.\n");
+    if (G.devices.size() > 1) err.push_back("-peak auto runs on one device (-device d, or -devices naming one).\n");
+  }
+
   if (G.convertName && err.empty()) {
     // merfin -convert <db> -output <file>: a database in any accepted form rewritten as this program's flat form (sorted
     // k-mers in delta-coded blocks), on the host -- no report, no device
@@ -835,12 +880,14 @@ int main(int argc, char **argv) {
   // merfin.C:159-181
   const bool variantMode = G.reportType == OP_POLISH || G.reportType == OP_FILTER || G.reportType == OP_BETTER ||
                            G.reportType == OP_STRICT || G.reportType == OP_LOOSE;
-  if (G.reportType != OP_COMPL) {
+  if (G.reportType == OP_SPECTRUM) {
+    if (!G.outName) err.push_back("No output (-output) supplied.\n");
+  } else if (G.reportType != OP_COMPL) {
     if (!G.seqName) err.push_back("No input sequences (-sequence) supplied.\n");
     if (!G.outName) err.push_back("No output (-output) supplied.\n");
   }
   if (variantMode && !G.vcfName) err.push_back("No variant call input (-vcf) supplied; mandatory for -filter or -polish.\n");
-  if (G.reportType != OP_FILTER && G.peak == 0) err.push_back("No haploid peak (-peak) supplied.\n");
+  if (G.reportType != OP_FILTER && G.reportType != OP_SPECTRUM && G.peak == 0 && !G.peakAuto) err.push_back("No haploid peak (-peak) supplied.\n");
   if (G.reportType == OP_COMPL && !G.seqName && !G.seqDBname)
     err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
   if (G.reportType == OP_NONE) err.push_back("No report type (-filter, -polish, -hist, -dump, -completeness) supplied.\n");
@@ -1009,7 +1056,8 @@ int main(int argc, char **argv) {
   // update those (half of a 30x human read database, the error k-mers, never gets a slot; k <= 21: 8-byte slots).  The
   // other report types need the whole read database.  MFX_CLI_FULL_INDEX=1 builds the full tables for every type.
   // (-reads: always -- the reads are counted into claimed k-mers; there is no read database for the full tables)
-  bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && k <= 31 &&
+  // (-spectrum: the full tables from -readmers -- its read-only row needs every read k-mer; with -reads the index -hist would build)
+  bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || (G.reportType == OP_SPECTRUM && fromReads)) && !G.sharded && k <= 31 &&
                  (fromReads || !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX"))));
   const char *ov = getenv("MFX_CLI_OVERLAP");
   const bool compressed = G.seqName && mfx_suffix_tool(G.seqName) != nullptr;
@@ -1313,9 +1361,42 @@ int main(int argc, char **argv) {
     finish_seq();
     if (seqOnDevice && !make_seq()) DIE_MFX("uploading sequences");
   }
+  // -spectrum / -peak auto: one streaming pass over the table (mfx_spectrum_run), the haploid peak off its single-copy row
+  if (G.reportType == OP_SPECTRUM || G.peakAuto) {
+    const bool report = G.reportType == OP_SPECTRUM;
+    const uint32_t copies = report ? G.copies : 4u, maxMult = report ? G.maxMult : 10000u;
+    std::vector<uint64_t> img((size_t)(copies + 2) * (maxMult + 1));
+    uint64_t entries = 0;
+    if (mfx_spectrum_run(ix, copies, maxMult, img.data(), &entries)) DIE_MFX(report ? "-spectrum" : "-peak auto");
+    if (report) {
+      // a table that holds the k-mers of -sequence only (-reads) has no read-only k-mers: the row is left out, not written as zeros
+      const bool withReadOnly = !fromReads;
+      const std::string name = std::string(G.outName) + ".spectra-cn.hist";
+      fprintf(stderr, "-- Copy-number spectrum of the %d-mers to '%s'.\n", k, name.c_str());
+      if (mfx_spectrum_write(img.data(), copies, maxMult, withReadOnly ? 1 : 0, name.c_str())) DIE_MFX("writing the spectrum");
+      uint64_t asmOnly = 0, readOnly = 0;
+      for (uint32_t r = 1; r < copies + 2; ++r) asmOnly += img[(size_t)r * (maxMult + 1)];
+      for (uint32_t m = 0; m <= maxMult; ++m) readOnly += img[m];
+      fprintf(stderr, "Entries counted: %lu\nAssembly-only k-mers: %lu\n", (unsigned long)entries, (unsigned long)asmOnly);
+      if (withReadOnly) fprintf(stderr, "Read-only k-mers: %lu\n", (unsigned long)readOnly);
+      else fprintf(stderr, "The table holds the k-mers of -sequence only (-reads): the read-only row is left out.\n");
+    }
+    mfx_spectrum_peak_t pk;
+    if (mfx_spectrum_peak(img.data() + (size_t)(maxMult + 1), maxMult, &pk) == MFX_OK) {
+      fprintf(stderr, "Haploid peak (auto): %u  (main peak %u, valley %u, single-copy k-mers at the peak %lu)\n", pk.haploid_peak, pk.main_peak, pk.valley,
+              (unsigned long)pk.count_at_peak);
+      if (G.peakAuto) G.peak = (double)pk.haploid_peak;
+    } else if (report) {
+      fprintf(stderr, "No haploid peak found in the single-copy row (%s); the other report types need -peak <number>.\n", mfx_last_error());
+    } else {
+      fprintf(stderr, "ERROR: -peak auto found no haploid peak in the single-copy row of the spectrum (%s). Give -peak <number>.\n", mfx_last_error());
+      return 1;
+    }
+    lap("spectrum");
+  }
   mfx_kparams kp{G.peak, (uint32_t)G.copyKmerK.size(), G.copyKmerK.data(), G.copyKmerP.data()};
-  mfx_eval *ev = mfx_eval_create(ix, &kp, 0);
-  if (!ev) DIE_MFX("creating evaluator");
+  mfx_eval *ev = G.reportType == OP_SPECTRUM ? nullptr : mfx_eval_create(ix, &kp, 0);
+  if (!ev && G.reportType != OP_SPECTRUM) DIE_MFX("creating evaluator");
 
   int rc = 0;
   if (G.reportType == OP_HIST) {
@@ -1596,7 +1677,7 @@ int main(int argc, char **argv) {
   }
 
   lap("evaluate + write");
-  mfx_eval_free(ev);
+  if (ev) mfx_eval_free(ev);
   if (seq) mfx_seq_free(seq);
   mfx_index_free(ix);
   lap("release");

@@ -16,6 +16,7 @@
 #include "mfx_device.h"
 #include "mfx_place.h"
 #include "mfx_track.h"
+#include "mfx_spectrum.h"
 
 #include <stdlib.h>
 #include <algorithm>
@@ -3767,6 +3768,89 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_completeness_kernel(mfx_table_v
 }
 
 // ===========================================================================
+// -spectrum / -peak auto: the copy-number spectrum of the table's entries, one streaming pass (mfx_spectrum.h; no reference
+// counterpart).  Every form is walked as mfx_table_export_kernel walks it; an entry's pair is what a lookup answers for it
+// (the read count through -min / -max, mfx_c_fields / mfx_lookup; the assembly count as stored).  Integer counts only: the
+// image is exact and does not depend on the order the entries were met in.
+// Persistent blocks; four 16-byte loads per lane are in flight before the first is looked at.  The loops run the same
+// number of turns for every lane of a block (mfx_spec_count votes across the wave).
+// ===========================================================================
+template <bool AGG>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_spectrum_kernel(mfx_spectrum_args a) {
+  __shared__ uint32_t s_bins[MFX_SPEC_LDS_WORDS];
+  mfx_spec_begin(a, s_bins);
+  const mfx_table_view &t = a.t;
+  constexpr int U = 4;
+  uint64_t counted = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = blockIdx.x * (uint64_t)blockDim.x;
+  const uint4 *S = reinterpret_cast<const uint4 *>(t.slots);
+  const uint4 none = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+  if (!t.compact) {                                              // 16-byte slots: one load per slot
+    const uint64_t n = t.nlines * MFX_SLOTS_LINE;
+    for (uint64_t b = first; b < n; b += U * stride) {
+      uint4 s[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) { const uint64_t i = b + j * stride + threadIdx.x; s[j] = i < n ? S[i] : none; }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const bool have = (s[j].x & s[j].y) != 0xffffffffu;
+        const uint32_t rv = (s[j].z < t.minV || s[j].z > t.maxV) ? 0u : s[j].z;          // -min / -max (merfin.C:199-200)
+        counted += mfx_spec_count<AGG>(a, s_bins, have, rv, s[j].w);
+      }
+    }
+  } else {                                                       // 8-byte slots: one load gives two
+    const uint64_t n = t.nlines * (MFX_CSLOTS_LINE / 2);
+    for (uint64_t b = first; b < n; b += U * stride) {
+      uint4 s[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) { const uint64_t i = b + j * stride + threadIdx.x; s[j] = i < n ? S[i] : none; }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const uint64_t i = b + j * stride + threadIdx.x;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const uint64_t x = h ? (uint64_t)s[j].z | ((uint64_t)s[j].w << 32) : (uint64_t)s[j].x | ((uint64_t)s[j].y << 32);
+          const bool have = x != MFX_EMPTY;
+          uint32_t rv = ((uint32_t)x >> 11) & MFX_CSAT, av = (uint32_t)x & MFX_CSAT;
+          if (have && (rv == MFX_CSAT || av == MFX_CSAT)) {      // rare: the exact count is in the side table under the k-mer
+            uint64_t km = x >> 22;
+            if (t.quot) {                                        // (line, key field) -> k-mer, as the export does
+              const uint32_t d = (uint32_t)(km >> MFX_Q_DSHIFT), line = (uint32_t)(i / (MFX_CSLOTS_LINE / 2));
+              const uint32_t home = line >= d ? line - d : line + (uint32_t)t.nlines - d;
+              km = mfx_q_invert(t, home, km & ((1ull << MFX_Q_DSHIFT) - 1ull));
+            }
+            const uint2 v = mfx_c_fields(t, km, (uint32_t)x);
+            rv = v.x; av = v.y;
+          } else if (rv < t.minV || rv > t.maxV) rv = 0u;
+          counted += mfx_spec_count<AGG>(a, s_bins, have, rv, av);
+        }
+      }
+    }
+    if (t.quot) {
+      // quotient form: the k-mers beyond their candidate lines live in the side table only; its other entries are the exact
+      // counts of saturated fields, whose k-mers were counted above
+      const mfx_table_view sv = mfx_side_view(t);
+      const uint64_t ns = sv.nlines * MFX_SLOTS_LINE;
+      const uint4 *SS = reinterpret_cast<const uint4 *>(sv.slots);
+      for (uint64_t b = first; b < ns; b += stride) {
+        const uint64_t i = b + threadIdx.x;
+        const uint4 s = i < ns ? SS[i] : none;
+        const uint64_t key = (uint64_t)s.x | ((uint64_t)s.y << 32);
+        bool have = key != MFX_EMPTY;
+        if (have) {
+          unsigned long long word = 0;
+          bool beyond;
+          have = !mfx_c_find(t, mfx_home(t, key), 0, word, beyond) && beyond;
+        }
+        const uint32_t rv = (s.z < t.minV || s.z > t.maxV) ? 0u : s.z;
+        counted += mfx_spec_count<AGG>(a, s_bins, have, rv, s.w);
+      }
+    }
+  }
+  mfx_spec_end(a, s_bins, counted);
+}
+
+// ===========================================================================
 // Diagnostic: the random-access LINE rate of this device's HBM -- independent 16-byte loads at uniformly random 128-byte
 // lines of a table far beyond the caches, four in flight per lane (tools/ubench_gather.hip found the rate the same for
 // 8 .. 16 bytes per lane, 1 .. 8 loads in flight and 4 .. 16 blocks per CU, for tables of 8 .. 160 GiB).  It is the roof
@@ -4033,6 +4117,13 @@ hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st) {
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st) {
   mfx_completeness_kernel<<<grid, MFX_BLOCK, 0, st>>>(t, peak, n_prob, probK, probP, partials);
+  return hipGetLastError();
+}
+hipError_t mfx_k_spectrum(const mfx_spectrum_args &a, int grid, hipStream_t st) {
+  const unsigned g = mfx_spec_grid(a.t.compact ? a.t.nlines * MFX_CSLOTS_LINE + a.t.side_nlines * MFX_SLOTS_LINE : a.t.nlines * MFX_SLOTS_LINE,
+                                   a.t.compact ? 3u : 1u, grid);      // compact: two slots per lane and turn, and one of the side pass
+  if (a.aggregate) mfx_spectrum_kernel<true><<<g, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_spectrum_kernel<false><<<g, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st) {

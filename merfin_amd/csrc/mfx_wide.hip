@@ -15,6 +15,7 @@
 // of that order.
 #include "mfx_device.h"
 #include "mfx_track.h"
+#include "mfx_spectrum.h"
 
 typedef unsigned __int128 mfx_u128;
 
@@ -496,7 +497,38 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_completeness_kernel(mfx_table
   }
 }
 
+// -spectrum / -peak auto (mfx_spectrum.h; mfx_spectrum_kernel is the k <= 31 form): a slot's second 16 bytes
+// {readV, asmV, state} say everything, the key is not loaded
+template <bool AGG>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_spectrum_kernel(mfx_spectrum_args a) {
+  __shared__ uint32_t s_bins[MFX_SPEC_LDS_WORDS];
+  mfx_spec_begin(a, s_bins);
+  constexpr int U = 4;
+  uint64_t counted = 0;
+  const uint64_t n = a.t.nlines * MFX_WSLOTS_LINE;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint4 *S = reinterpret_cast<const uint4 *>(a.t.slots);
+  for (uint64_t b = blockIdx.x * (uint64_t)blockDim.x; b < n; b += U * stride) {      // the same turns for every lane of the block
+    uint4 s[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) { const uint64_t i = b + j * stride + threadIdx.x; s[j] = i < n ? S[2 * i + 1] : make_uint4(0u, 0u, 0u, 0u); }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const bool have = s[j].z == 2u && s[j].w == 0u;            // state 2: ready
+      const uint32_t rv = (s[j].x < a.t.minV || s[j].x > a.t.maxV) ? 0u : s[j].x;      // merfin.C:199-200
+      counted += mfx_spec_count<AGG>(a, s_bins, have, rv, s[j].y);
+    }
+  }
+  mfx_spec_end(a, s_bins, counted);
+}
+
 // ---- launch wrappers --------------------------------------------------------------------------------------
+hipError_t mfx_kw_spectrum(const mfx_spectrum_args &a, int grid, hipStream_t st) {
+  const unsigned g = mfx_spec_grid(a.t.nlines * MFX_WSLOTS_LINE, 1u, grid);
+  if (a.aggregate) mfx_w_spectrum_kernel<true><<<g, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_w_spectrum_kernel<false><<<g, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
 hipError_t mfx_kw_table_add(mfx_table_view t, const uint64_t *kmers, const uint32_t *values, uint64_t n, int side, uint64_t *meta, hipStream_t st) {
   if (n == 0) return hipSuccess;
   uint64_t blocks = (n + 255) / 256;
