@@ -317,16 +317,29 @@ typedef struct mfx_eval mfx_eval;
 mfx_eval *mfx_eval_create(const mfx_index *ix, const mfx_kparams *kp, uint32_t nbins);
 void      mfx_eval_free(mfx_eval *ev);
 uint32_t  mfx_eval_nbins(const mfx_eval *ev);
-/* Test hook (no reference counterpart): -hist launches of this evaluator run the DEBUG instance of the kernel where one
- * exists (compact layout, k = 21) and count how its probe's queries ended: out8[0] not in the first mini-bucket (first
- * cooperative pass), [1] home line full (second cooperative pass), [2] saturated count (side table), [3] per-lane
- * whole-line scans.  mfx_eval_debug_counters reads and clears them.  Never the measured configuration. */
 /* Diagnostic (no reference counterpart): random 128-byte lines per second this device's HBM delivers to independent
  * 16-byte loads over a table of table_bytes (allocated and released by the call): the roof of the index probe on this
  * box; bench.py reports the -hist kernel's line rate against it (roofline.gather_ceiling). */
 int       mfx_diag_gather_rate(int device, uint64_t table_bytes, double *lines_per_s);
+/* Test hook (no reference counterpart): -hist launches of this evaluator run the DEBUG instance of the kernel where one
+ * exists (compact layout, k = 21) and count how its probe's queries ended: out8[0] not in the first mini-bucket (first
+ * cooperative pass), [1] home line full (second cooperative pass), [2] saturated count (side table), [3] per-lane
+ * whole-line scans.  mfx_eval_debug_counters reads and clears them.  Never the measured configuration. */
 int       mfx_eval_debug_enable(mfx_eval *ev, int on);
 int       mfx_eval_debug_counters(mfx_eval *ev, uint64_t *out8);
+/* Test hooks of the -hist worklist (no reference counterpart; csrc/mfx_debug.cpp).  Over a compact, canonical table the -hist
+ * kernel lists the rare endings of its probe in one segment per block and a second kernel ends them; the result must not depend
+ * on what was listed.  mfx_eval_debug_worklist: how every later -hist launch of this evaluator (all launch forms) gets its list --
+ * mode 0 none, 1 the default sizing, 2 a segment holds at most min(default, segcap) entries (segcap >= 1; the allocation is the
+ * default's).  mfx_eval_debug_worklist_read: the list of the last launch of launch slot 0 / 1 (a plain launch uses slot 0, a
+ * streamed run's chunks alternate), after synchronising the device: *segs segments of at most *segcap entries (0, 0: that launch
+ * had no list), counts[*segs] entries per segment, *n_entries their sum, and the entries themselves, segment after segment, as
+ * 16-byte records { u64 canonical k-mer; u32 aux; u32 slot | mode << 29 | dbl << 31 } with slot = (tile of the launch) * 4 +
+ * wave.  counts / entries may be NULL (sizes first); *_cap: what the caller's buffers hold (words / records).  Everything is
+ * checked against the list's allocation before it is copied. */
+int       mfx_eval_debug_worklist(mfx_eval *ev, int mode, uint32_t segcap);
+int       mfx_eval_debug_worklist_read(mfx_eval *ev, int slot, uint32_t *segs, uint32_t *segcap, uint64_t *counts, uint64_t counts_cap,
+                                       void *entries, uint64_t entries_cap, uint64_t *n_entries);
 
 /* Test hooks of the variant modes (no reference counterpart; csrc/mfx_debug.cpp): the per-path values of the traverse and score
  * kernels, which a run only shows after bestFilter / bestVariant / ... have reduced them.  The cluster tables are raw arrays of

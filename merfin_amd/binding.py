@@ -85,7 +85,7 @@ SYMBOLS = [
     "mfx_seq_upload", "mfx_seq_from_device", "mfx_seq_free", "mfx_seq_num_contigs", "mfx_seq_num_bases",
     "mfx_seq_num_tiles",
     "mfx_diag_gather_rate",
-    "mfx_eval_create", "mfx_eval_free", "mfx_eval_nbins", "mfx_eval_debug_enable", "mfx_eval_debug_counters", "mfx_getK", "mfx_getKmetric", "mfx_histoQV",
+    "mfx_eval_create", "mfx_eval_free", "mfx_eval_nbins", "mfx_eval_debug_enable", "mfx_eval_debug_counters", "mfx_eval_debug_worklist", "mfx_eval_debug_worklist_read", "mfx_getK", "mfx_getKmetric", "mfx_histoQV",
     "mfx_hist_run", "mfx_hist_result_free", "mfx_hist_launch", "mfx_hist_launch_cyclic", "mfx_hist_result_from_counts",
     "mfx_hist_take_overflow", "mfx_hist_report", "mfx_diag_stream_rates",
     "mfx_pack_bases", "mfx_host_threads_share", "mfx_dump_values", "mfx_dump_contig", "mfx_dump_values_sharded", "mfx_dump_contig_sharded", "mfx_variants_run_sharded", "mfx_vcf_load", "mfx_vcf_free", "mfx_variants_run_vcf", "mfx_vcf_prepare", "mfx_vcf_path_bound", "mfx_index_claim_paths", "mfx_vcf_prepare_path_index", "mfx_completeness", "mfx_completeness_pieces", "mfx_variants_run",
@@ -104,6 +104,10 @@ TRV_ALLELE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "<u4")])
 assert (TRV_CLUSTER_DTYPE.itemsize, TRV_VARIANT_DTYPE.itemsize, TRV_ALLELE_DTYPE.itemsize) == (56, 16, 16)
 TRV_OK, TRV_RANGE, TRV_ROOM = 0, 1, 2
 TRV_MAX_NV, TRV_MAX_PATHS, TRV_MAX_LEN = 8, 64, 640
+
+# one entry of the -hist worklist as Evaluator.debug_worklist_read returns it (include/merfin_amd.h): w = slot | mode << 29 | dbl << 31
+WORKLIST_DTYPE = np.dtype([("kmer", "<u8"), ("aux", "<u4"), ("w", "<u4")])
+assert WORKLIST_DTYPE.itemsize == 16
 
 # one window of Evaluator.track: the layout of mfx_track_window (include/merfin_amd.h), 72 bytes
 TRACK_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_missing", "<u4"), ("n_scored", "<u4"), ("n_pos", "<u4"), ("n_neg", "<u4"),
@@ -213,6 +217,8 @@ def load_library():
     L.mfx_diag_gather_rate.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_double)]
     L.mfx_eval_debug_enable.argtypes = [vp, C.c_int]
     L.mfx_eval_debug_counters.argtypes = [vp, u64p]
+    L.mfx_eval_debug_worklist.argtypes = [vp, C.c_int, C.c_uint32]
+    L.mfx_eval_debug_worklist_read.argtypes = [vp, C.c_int, u32p, u32p, u64p, C.c_uint64, vp, C.c_uint64, u64p]
     L.mfx_getK.argtypes = [C.POINTER(_KP), C.c_uint32, C.c_uint32, f64p, f64p, f64p]
     L.mfx_getKmetric.restype = C.c_double
     L.mfx_getKmetric.argtypes = [C.c_double, C.c_double]
@@ -1257,6 +1263,25 @@ class Evaluator:
         return {"first_pass": int(out[0]), "second_pass": int(out[1]), "side_table": int(out[2]), "line_scans": int(out[3]),
                 "side_not_in_two_slots": int(out[4]), "ended_per_lane": int(out[5]),
                 "second_bucket": int(out[6])}
+
+    def debug_worklist(self, mode=1, segcap=0):
+        """test hook: the worklist of this evaluator's later -hist launches -- mode 0 none, 1 the default sizing, 2 segments of at most
+        `segcap` entries in the default's allocation (mfx_eval_debug_worklist)"""
+        _check(load_library().mfx_eval_debug_worklist(self.h, mode, segcap))
+
+    def debug_worklist_read(self, slot=0):
+        """the list of the last launch of launch slot `slot`, read back after a device synchronise: (segs, segcap, counts[segs],
+        entries) with entries a WORKLIST_DTYPE array, segment after segment (segment g: entries[counts[:g].sum():][:counts[g]]);
+        (0, 0, empty, empty) when that launch had no list"""
+        L = load_library()
+        segs, segcap, n = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        _check(L.mfx_eval_debug_worklist_read(self.h, slot, C.byref(segs), C.byref(segcap), None, 0, None, 0, C.byref(n)))
+        counts = np.zeros(segs.value, dtype=np.uint64)
+        ent = np.zeros(n.value, dtype=WORKLIST_DTYPE)
+        _check(L.mfx_eval_debug_worklist_read(self.h, slot, C.byref(segs), C.byref(segcap), counts.ctypes.data_as(C.POINTER(C.c_uint64)), len(counts),
+                                              C.c_void_p(ent.ctypes.data), len(ent), C.byref(n)))
+        assert n.value == len(ent) and segs.value == len(counts)
+        return segs.value, segcap.value, counts, ent
 
     def hist(self, seqs):
         r = HistResult()

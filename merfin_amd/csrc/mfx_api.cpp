@@ -1844,10 +1844,8 @@ static int ensure_tile_partials(mfx_eval *ev, uint64_t ntiles) {
 
 // The worklist of a launch over ntl tiles (mfx_hist_rest_kernel): room for one position in 32 -- a genome with human-like repeat
 // families lists 1-2 % of its positions (profiles/r06_repeats_ab.txt); a launch that lists more ends the rest per lane, as every
-// launch did before round 6.  0.5 bytes per position of the largest launch so far; MFX_HIST_WORKLIST=0: no lists.
+// launch did before round 6.  0.5 bytes per position of the largest launch so far.
 static int ensure_worklist(mfx_eval *ev, int slot, uint64_t ntl) {
-  static const bool off = [] { const char *e = getenv("MFX_HIST_WORKLIST"); return e && atoi(e) == 0; }();
-  if (off) return MFX_OK;
   const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(1u << 16, ntl * MFX_TILE / 32), 0xffffffffull);
   if (ev->d_wl[slot] && ev->wl_cap[slot] >= want) return MFX_OK;
   if (ev->d_wl[slot]) { MFX_HIP(hipDeviceSynchronize()); (void)hipFree(ev->d_wl[slot]); ev->d_wl[slot] = nullptr; ev->wl_cap[slot] = 0; }
@@ -1928,7 +1926,11 @@ static int hist_launch(mfx_eval *ev, const mfx_seq *seq, uint64_t tile_begin, ui
   a.ks.partials = ev->d_partials;
   a.ks.ovf = ev->d_ovf;
   a.dbg = ev->d_dbg;
-  if (a.t.compact && canon && ntl < (1ull << 27)) {          // the probe's rare endings are listed and ended by mfx_hist_rest_kernel (mfx_kernels.hip)
+  // MFX_HIST_WORKLIST=0 (read per launch, as MFX_FORCE_TWO_STRAND above) or the test hook's mode 0: no list, every wave ends its own rare endings
+  const char *wl_env = getenv("MFX_HIST_WORKLIST");
+  const bool wl_off = (wl_env && atoi(wl_env) == 0) || ev->dbg_wl_mode == 0;
+  ev->wl_used_segs[ctr_slot] = ev->wl_used_segcap[ctr_slot] = 0;
+  if (a.t.compact && canon && ntl < (1ull << 27) && !wl_off) {   // the probe's rare endings are listed and ended by mfx_hist_rest_kernel (mfx_kernels.hip)
     // (a streamed run's chunks grow to 128 MB of bases: its lists are made for that size at its first chunk, not re-made as they grow)
     rc = ensure_worklist(ev, ctr_slot, chunk_of_total ? std::max<uint64_t>(ntl, std::min<uint64_t>(chunk_of_total, (128ull << 20) / MFX_TILE)) : ntl);
     if (rc) return rc;
@@ -1937,6 +1939,9 @@ static int hist_launch(mfx_eval *ev, const mfx_seq *seq, uint64_t tile_begin, ui
       a.wl = ev->d_wl[ctr_slot];
       a.wl_segs = (uint32_t)segs;
       a.wl_segcap = (uint32_t)(ev->wl_cap[ctr_slot] / segs);
+      if (ev->dbg_wl_mode == 2) a.wl_segcap = std::min(a.wl_segcap, ev->dbg_wl_segcap);       // (test hook: fuller segments of the same allocation)
+      ev->wl_used_segs[ctr_slot] = a.wl_segs;
+      ev->wl_used_segcap[ctr_slot] = a.wl_segcap;
     }
   }
   MFX_HIP(ev->ix->wide() ? mfx_kw_hist(a, (int)std::min<uint64_t>((uint64_t)ev->grid, ntl), (hipStream_t)stream)

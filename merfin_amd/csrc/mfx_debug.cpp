@@ -1,12 +1,15 @@
-// mfx_debug.cpp -- test-facing entries over the variant modes' production functions (include/merfin_amd.h: mfx_debug_*).  The suite
+// mfx_debug.cpp -- test-facing entries (include/merfin_amd.h: mfx_debug_*, mfx_eval_debug_worklist*; the -hist worklist's are at the end of
+// the file).  Those over the variant modes' production functions: the suite
 // otherwise sees the traverse and score kernels only through the selectors (bestFilter, bestVariant, ...), which reduce numM to a minimum
 // and totdk to a truncated tie-break; these hand a caller the per-path values, the path text and the path table themselves.  Nothing here
 // computes: the host entry runs mfx_traverse_cluster (the scalar instantiation of what the device's kernel runs per wave), the other two
 // call mfx_score_paths / mfx_score_paths_trv.  What they add is the CHECK of the caller's tables: every offset a kernel would follow is
 // inside its array before anything is launched.
 #include "mfx_internal.h"
+#include "mfx_kernels.h"
 
 #include <stddef.h>
+#include <string.h>
 
 // the tables cross the C ABI as raw arrays (numpy structured dtypes in merfin_amd/binding.py): their layout is part of the ABI
 static_assert(sizeof(mfx_trv_variant) == 16 && offsetof(mfx_trv_variant, off) == 0 && offsetof(mfx_trv_variant, reflen) == 4 &&
@@ -134,4 +137,57 @@ extern "C" int mfx_debug_score_paths_trv(mfx_eval *ev, const char *text, uint64_
   rb.p_off = p_off; rb.p_voff = p_voff; rb.p_cfirst = p_cfirst; rb.p_nv = p_nv;
   rb.vidx = vidx_out; rb.vlen = vlen_out;
   return mfx_score_paths_trv(ev, text, len, &pt, &tb, need_dk, numM, totdk, &rb);
+}
+
+// ---------------------------------------------------------------------------
+// The -hist worklist (mfx_hist_kernel's push_wave, mfx_hist_rest_kernel): how this evaluator's launches are given their list, and the
+// list of the last launch read back.  hist_launch (mfx_api.cpp) applies the mode to every launch form; production never calls these.
+// ---------------------------------------------------------------------------
+extern "C" int mfx_eval_debug_worklist(mfx_eval *ev, int mode, uint32_t segcap) {
+  if (!ev) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist: null argument");
+  if (mode < 0 || mode > 2) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist: mode %d (0 no list, 1 default, 2 segments of at most segcap entries)", mode);
+  if (mode == 2 && segcap == 0) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist: mode 2 with segments of 0 entries (mode 0 turns the list off)");
+  ev->dbg_wl_mode = mode;
+  ev->dbg_wl_segcap = mode == 2 ? segcap : 0u;
+  return MFX_OK;
+}
+
+extern "C" int mfx_eval_debug_worklist_read(mfx_eval *ev, int slot, uint32_t *segs, uint32_t *segcap, uint64_t *counts, uint64_t counts_cap, void *entries,
+                                            uint64_t entries_cap, uint64_t *n_entries) {
+  if (!ev || !segs || !segcap || !n_entries) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: null argument");
+  if (slot < 0 || slot > 1) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: slot %d (0 or 1)", slot);
+  *segs = ev->wl_used_segs[slot];
+  *segcap = ev->wl_used_segcap[slot];
+  *n_entries = 0;
+  if (!*segs) return MFX_OK;                                   // the last launch of this slot had no list
+  const uint64_t S = *segs, SC = *segcap;
+  if (!ev->d_wl[slot] || S > MFX_WL_HEADER - 2 || S * SC > ev->wl_cap[slot])
+    return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: %lu segments of %lu entries do not lie in the list of %lu entries", (unsigned long)S,
+                    (unsigned long)SC, (unsigned long)ev->wl_cap[slot]);
+  int prev = 0;
+  MFX_HIP(hipGetDevice(&prev));
+  MFX_HIP(hipSetDevice(ev->device));
+  struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{prev};
+  MFX_HIP(hipDeviceSynchronize());
+  std::vector<uint64_t> n(S);
+  MFX_HIP(hipMemcpy(n.data(), ev->d_wl[slot] + 2, S * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  uint64_t total = 0;
+  for (uint64_t g = 0; g < S; ++g) {
+    if (n[g] > SC) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: segment %lu counts %lu entries, beyond its %lu", (unsigned long)g, (unsigned long)n[g], (unsigned long)SC);
+    total += n[g];
+  }
+  *n_entries = total;
+  if (counts) {
+    if (counts_cap < S) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: %lu segments, the caller's counts hold %lu", (unsigned long)S, (unsigned long)counts_cap);
+    memcpy(counts, n.data(), S * sizeof(uint64_t));
+  }
+  if (entries) {                                               // segment after segment, each with its own count of 16-byte records
+    if (entries_cap < total) return mfx_fail(MFX_E_INVAL, "mfx_eval_debug_worklist_read: %lu entries, the caller's buffer holds %lu", (unsigned long)total, (unsigned long)entries_cap);
+    uint8_t *dst = static_cast<uint8_t *>(entries);
+    for (uint64_t g = 0; g < S; ++g) {
+      if (n[g]) MFX_HIP(hipMemcpy(dst, ev->d_wl[slot] + MFX_WL_HEADER + 2 * g * SC, n[g] * 16, hipMemcpyDeviceToHost));
+      dst += n[g] * 16;
+    }
+  }
+  return MFX_OK;
 }

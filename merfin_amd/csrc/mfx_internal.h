@@ -285,6 +285,11 @@ struct mfx_eval {
   uint64_t  tile_partials_cap = 0;   // doubles allocated
   uint64_t *d_wl[2] = {nullptr, nullptr};   // the worklists of mfx_hist_rest_kernel (mfx_kernels.h: mfx_hist_args::wl), one per launch slot (a streamed run's launches alternate between two streams)
   uint64_t  wl_cap[2] = {0, 0};      // entries each holds
+  // test hook (mfx_eval_debug_worklist, mfx_debug.cpp): 0 this evaluator's launches get no list, 1 the default sizing, 2 a segment holds at most
+  // dbg_wl_segcap entries (the allocation stays); wl_used_*: what the last launch of each slot ran with (0, 0: no list), for mfx_eval_debug_worklist_read
+  int       dbg_wl_mode = 1;
+  uint32_t  dbg_wl_segcap = 0;
+  uint32_t  wl_used_segs[2] = {0, 0}, wl_used_segcap[2] = {0, 0};
   uint64_t *d_ovf = nullptr;         // the table of far K* bins: [0] distinct keys, [1] lost occurrences, [2, 2+S) occurrences, [2+S, 2+2S) keys (mfx_device.h)
   uint64_t *d_dbg = nullptr;         // [8] probe path counters of the DEBUG instance of the -hist kernel (mfx_eval_debug_enable); null: the measured instance runs
   uint8_t  *h_stage[2] = {nullptr, nullptr};   // pinned staging of the streamed upload (pageable sources), kept between calls

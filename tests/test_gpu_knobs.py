@@ -35,6 +35,7 @@ LIB_KNOBS = [
     ("MFX_BLOCKS_PER_CU", "1"), ("MFX_HOST_THREADS", "1"), ("MFX_HIST_GENERIC", "1"), ("MFX_FORCE_TWO_STRAND", "1"),
     ("MFX_FLAT_DELTA", "0"), ("MFX_FLAT_PACKED", "0"),
     ("MFX_LOAD_FACTOR", "0.6"),
+    ("MFX_HIST_WORKLIST", "0"),          # no worklist: every wave of the -hist kernel ends its own rare endings (read per launch)
 ]
 
 _worlds = {}
