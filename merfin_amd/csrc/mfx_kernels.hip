@@ -910,12 +910,15 @@ __global__ __launch_bounds__(256) void mfx_table_update_kernel(mfx_table_view t,
 // and puts them into the table itself -- the decoded k-mers never exist in memory.
 // dir[b] = {first k-mer, payload byte offset (48 bits) | kbits << 48 | vbits << 56}; dir[nblocks] closes the last block.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mfx_bits_at(const uint64_t *w, uint64_t bit, uint32_t nbits) {     // nbits <= 63
+// (a field is at most 64 bits wide -- the differences of a placed 31-mer file, whose stored numbers have 64 bits: mfx_place.h -- and its
+// mask is the same for every field of a block: made once per block, not per entry)
+__device__ __forceinline__ uint64_t mfx_field_mask(uint32_t nbits) { return nbits >= 64u ? ~0ull : (1ull << nbits) - 1ull; }
+__device__ __forceinline__ uint64_t mfx_bits_at(const uint64_t *w, uint64_t bit, uint32_t nbits, uint64_t mask) {     // nbits <= 64, mask = mfx_field_mask(nbits)
   const uint64_t i = bit >> 6;
   const uint32_t sh = (uint32_t)bit & 63u;
   uint64_t x = w[i] >> sh;
   if (sh + nbits > 64u) x |= w[i + 1] << (64u - sh);
-  return x & ((1ull << nbits) - 1ull);
+  return x & mask;
 }
 
 __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view t, const uint64_t *payload, const uint64_t *dir,
@@ -929,6 +932,7 @@ __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view
   for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
     const uint64_t first = dir[2 * (uint64_t)b], info = dir[2 * (uint64_t)b + 1];
     const uint32_t kb = (uint32_t)(info >> 48) & 0xffu, vb = (uint32_t)(info >> 56) & 0xffu;
+    const uint64_t kmask = mfx_field_mask(kb), vmask = mfx_field_mask(vb);
     const uint64_t left = n - (uint64_t)b * MFX_DELTA_BLOCK;
     const uint32_t cnt = left < MFX_DELTA_BLOCK ? (uint32_t)left : (uint32_t)MFX_DELTA_BLOCK;
     const uint64_t *pw = payload + (((info & 0xffffffffffffull) - payload_base) >> 3);
@@ -939,7 +943,7 @@ __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view
 #pragma unroll 4
     for (uint32_t i = 0; i < PER; ++i) {
       const uint32_t e = e0 + i;
-      if (e > 0u && e < cnt && kb) mine += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb);
+      if (e > 0u && e < cnt && kb) mine += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb, kmask);
     }
     uint64_t inc = mine;                                       // inclusive scan over the workgroup
 #pragma unroll
@@ -959,9 +963,9 @@ __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view
         const uint32_t e = e0 + g + i;
         key[i] = 0; v[i] = 0u;
         if (e < cnt) {
-          if (e > 0u && kb) run += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb);
+          if (e > 0u && kb) run += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb, kmask);
           key[i] = run;
-          v[i] = (uint32_t)mfx_bits_at(pw, vbit0 + (uint64_t)e * vb, vb);
+          v[i] = (uint32_t)mfx_bits_at(pw, vbit0 + (uint64_t)e * vb, vb, vmask);
           if (v[i] == (1u << vb) - 1u) v[i] = 0u;              // escape: added separately (the file's escape list)
         }
       }
@@ -1031,6 +1035,7 @@ __global__ __launch_bounds__(256) void mfx_table_add_placed_kernel(mfx_table_vie
   for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
     const uint64_t first = dir[2 * (uint64_t)b], info = dir[2 * (uint64_t)b + 1];
     const uint32_t kb = (uint32_t)(info >> 48) & 0xffu, vb = (uint32_t)(info >> 56) & 0xffu;
+    const uint64_t kmask = mfx_field_mask(kb), vmask = mfx_field_mask(vb);
     const uint64_t left = n - (uint64_t)b * MFX_DELTA_BLOCK;
     const uint32_t cnt = left < MFX_DELTA_BLOCK ? (uint32_t)left : (uint32_t)MFX_DELTA_BLOCK;
     const uint64_t *pw = payload + (((info & 0xffffffffffffull) - payload_base) >> 3);
@@ -1043,7 +1048,7 @@ __global__ __launch_bounds__(256) void mfx_table_add_placed_kernel(mfx_table_vie
 #pragma unroll
       for (uint32_t i = 0; i < 4; ++i) {
         const uint32_t e = e0 + i;
-        d[i] = (e > 0u && e < cnt && kb) ? mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb) : 0ull;     // entry e > 0 has difference e - 1
+        d[i] = (e > 0u && e < cnt && kb) ? mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb, kmask) : 0ull;     // entry e > 0 has difference e - 1
         mine += d[i];
       }
       uint64_t inc = mine;                                     // inclusive scan over the workgroup
@@ -1067,7 +1072,7 @@ __global__ __launch_bounds__(256) void mfx_table_add_placed_kernel(mfx_table_vie
         run += d[i];
         if (e < cnt) {
           uint32_t top, hi, pm;
-          v[i] = (uint32_t)mfx_bits_at(pw, vbit0 + (uint64_t)e * vb, vb);
+          v[i] = (uint32_t)mfx_bits_at(pw, vbit0 + (uint64_t)e * vb, vb, vmask);
           if (v[i] == (1u << vb) - 1u) v[i] = 0u;              // escape: added separately (the file's escape list)
           uint32_t sb = 0u;
           if (split) { sb = v[i] & 1u; v[i] >>= 1; }           // k = 31: the strand bit of P travels in the count field (mfx_place.h)
@@ -3921,10 +3926,17 @@ hipError_t mfx_k_table_add(mfx_table_view t, const uint64_t *kmers, const uint32
   else                mfx_table_add_kernel<1><<<(unsigned)blocks, 256, 0, st>>>(t, kmers, values, n, side, meta);
   return hipGetLastError();
 }
+// workgroups of the two decode launches: one per block, 8192 at most.  MFX_INGEST_GRID (read per launch: tests switch it) caps them
+// lower, so that a workgroup takes several blocks in turn -- what a launch of more than 8192 blocks does
+static uint32_t mfx_ingest_grid(uint32_t nblocks) {
+  uint32_t cap = 8192u;
+  if (const char *e = getenv("MFX_INGEST_GRID")) { const long v = atol(e); if (v >= 1 && v <= 8192) cap = (uint32_t)v; }
+  return nblocks < cap ? nblocks : cap;
+}
 hipError_t mfx_k_table_add_delta(mfx_table_view t, const uint64_t *payload, const uint64_t *dir, uint32_t nblocks, uint64_t n,
                                  uint64_t payload_base, int side, uint64_t *meta, hipStream_t st) {
   if (nblocks == 0) return hipSuccess;
-  mfx_table_add_delta_kernel<<<nblocks < 8192u ? nblocks : 8192u, 256, 0, st>>>(t, payload, dir, nblocks, n, payload_base, side, meta);
+  mfx_table_add_delta_kernel<<<mfx_ingest_grid(nblocks), 256, 0, st>>>(t, payload, dir, nblocks, n, payload_base, side, meta);
   return hipGetLastError();
 }
 // does this table take a placed database's records by their own placement?  (the compact layout under its default placement)
@@ -3937,7 +3949,7 @@ int mfx_k_table_takes_placed(const mfx_table_view &t) {
 hipError_t mfx_k_table_add_placed(mfx_table_view t, const uint64_t *payload, const uint64_t *dir, uint32_t nblocks, uint64_t n,
                                   uint64_t payload_base, int side, uint64_t *meta, hipStream_t st) {
   if (nblocks == 0) return hipSuccess;
-  mfx_table_add_placed_kernel<<<nblocks < 8192u ? nblocks : 8192u, 256, 0, st>>>(t, payload, dir, nblocks, n, payload_base, side, meta, mfx_k_table_takes_placed(t));
+  mfx_table_add_placed_kernel<<<mfx_ingest_grid(nblocks), 256, 0, st>>>(t, payload, dir, nblocks, n, payload_base, side, meta, mfx_k_table_takes_placed(t));
   return hipGetLastError();
 }
 hipError_t mfx_k_place_keys(int k, const uint64_t *kmers, uint64_t n, uint64_t *out, hipStream_t st) {

@@ -2,58 +2,10 @@
 k-mers is decoded here by an independent reader (numpy / Python ints, from the format's description in the header of
 mfx_db.cpp) and must give back the arrays.  The GPU side of the format -- the kernel that decodes and inserts the blocks --
 is pinned by tests/test_gpu_db.py against the other forms of the same database."""
-import struct
-
 import numpy as np
 import pytest
 
-BLOCK = 4096
-
-
-def read_flat(path):
-    raw = open(path, "rb").read()
-    magic, k, flags, n, n_esc = struct.unpack_from("<8sIIQQ", raw, 0)
-    assert magic == b"MFXKMER1"
-    return raw, k, flags, n, n_esc
-
-
-def bits_at(words, bit, nbits):
-    i, sh = bit >> 6, bit & 63
-    x = int(words[i]) >> sh
-    if sh + nbits > 64:
-        x |= int(words[i + 1]) << (64 - sh)
-    return x & ((1 << nbits) - 1)
-
-
-def decode_delta(path):
-    raw, k, flags, n, n_esc = read_flat(path)
-    assert flags & 4
-    (nblocks,) = struct.unpack_from("<Q", raw, 32)
-    assert nblocks == (n + BLOCK - 1) // BLOCK
-    d = np.frombuffer(raw, dtype="<u8", count=2 * (nblocks + 1), offset=40)
-    keys, vals = [], []
-    for b in range(nblocks):
-        first, info = int(d[2 * b]), int(d[2 * b + 1])
-        off, kb, vb = info & ((1 << 48) - 1), (info >> 48) & 0xff, (info >> 56) & 0xff
-        nxt = int(d[2 * b + 3]) & ((1 << 48) - 1)
-        cnt = min(BLOCK, n - b * BLOCK)
-        assert off % 8 == 0 and nxt - off == (((cnt - 1) * kb + 63) // 64 + (cnt * vb + 63) // 64) * 8
-        w = np.frombuffer(raw, dtype="<u8", count=(nxt - off) // 8, offset=off)
-        vw = w[((cnt - 1) * kb + 63) // 64:]
-        cur = first
-        for e in range(cnt):
-            if e:
-                cur += bits_at(w, (e - 1) * kb, kb) if kb else 0
-            keys.append(cur)
-            v = bits_at(vw, e * vb, vb)
-            vals.append(None if v == (1 << vb) - 1 else v)
-    end = int(d[2 * nblocks + 1]) & ((1 << 48) - 1)
-    assert len(raw) == end + 12 * n_esc
-    ek = np.frombuffer(raw, dtype="<u8", count=n_esc, offset=end).tolist()
-    ev = np.frombuffer(raw, dtype="<u4", count=n_esc, offset=end + 8 * n_esc).tolist()
-    esc = dict(zip(ek, ev))
-    assert len(esc) == n_esc and sum(v is None for v in vals) == n_esc
-    return k, keys, [esc[kk] if v is None else v for kk, v in zip(keys, vals)]
+from tests.delta_blocks import decode_delta, read_flat   # (the decoder lives with its inverse now)
 
 
 @pytest.mark.parametrize("k,n,seed", [(21, 1, 1), (21, 4096, 2), (21, 4097, 3), (15, 20000, 4), (31, 3 * 4096 + 77, 5), (4, 200, 6)])
