@@ -1,0 +1,43 @@
+// mfx_host.h -- what the host files of the library share besides mfx_internal.h: the scoped device helpers and the pieces of
+// mfx_api.cpp that the several-slot drivers (mfx_multi.cpp) are built from.  Host only; no kernel file includes it.
+#pragma once
+#include "mfx_internal.h"
+
+struct DevGuard {   // makes `dev` the current device for a scope
+  int prev = -1;
+  bool ok = false;
+  explicit DevGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    ok = (hipSetDevice(dev) == hipSuccess);
+  }
+  ~DevGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+template <class T>
+struct DevBuf {   // scoped device scratch
+  T *p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) { return hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)); }
+};
+
+// ---- defined in mfx_api.cpp ---------------------------------------------------
+int index_canonical(const mfx_index *ix, int *canon);
+int eval_run_enqueue(mfx_eval *ev, const mfx_seq *seq, uint32_t part_rank, uint32_t part_n);
+int result_take_overflow(mfx_eval *ev, uint64_t novf, mfx_hist_result *out);
+unsigned t_sharers_get();                // what the calling thread last passed to mfx_host_threads_share
+
+// a sequence's packed planes: the words each holds (a tile reads 130 words from its first one), and their allocation
+inline uint64_t seq_plane_words(const mfx_seq *s) { return s->buf_bytes / 32 + (MFX_TILE + 64) / 32 + 1; }
+int seq_alloc_planes(mfx_seq *s);
+
+// the streamed run over the tiles [tl, th) of an assembly in host memory (no part: all of them, and the result in `out`)
+struct StreamPart {
+  uint64_t tl = 0, th = 0;
+  uint64_t *d_counts = nullptr;          // caller's device image / koverCpy to accumulate into (cleared by the caller); null: the evaluator's own, returned on the host
+  double   *d_kover = nullptr;
+  std::vector<double> *chunk_sums = nullptr;   // the first-level koverCpy sums of the part (4096 (tile, wave) values each), for a bit-stable sum over the parts
+  bool      want_result = true;          // false: the image stays in ev->sr.h_img (or on the device), no mfx_hist_result is made
+};
+int hist_run_streamed_packed(mfx_eval *ev, mfx_seq *seq, const char *const *bases, mfx_hist_result *out, const StreamPart *part = nullptr);

@@ -131,8 +131,8 @@ def test_two_rank_launcher_keeps_bins_beyond_the_dense_image(tmp_path):
     from oracle import pyoracle as po
     from tests.test_cli import _write_fasta
     from tests.test_gpu_parity import oracle_hist
-    from tests.test_gpu_streamed_multi import _overflow_world
-    k, peak, contigs, read, asm = _overflow_world(m)
+    from tests.overflow_world import overflow_world
+    k, peak, contigs, read, asm = overflow_world(300)
     p, g, ka, km = oracle_hist(k, peak, contigs, read, asm)
     assert g.c.undrMax > 65536 and g.c.overMax > 65536
     po.report_histogram(p, g, str(tmp_path / "o.hist"), str(tmp_path / "o.sum"))

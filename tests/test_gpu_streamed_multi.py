@@ -11,6 +11,7 @@ import pytest
 
 from oracle import pyoracle as po
 from tests import synth
+from tests.overflow_world import overflow_world
 from tests.test_gpu_parity import assert_hist_equal, build_index, oracle_hist
 
 pytestmark = pytest.mark.gpu
@@ -261,24 +262,9 @@ def test_one_process_several_slots_matches_oracle(nslots, five_mb_world):
         m.hist_multi([evs[0], evs[0]], [seqs, seqs])
 
 
-def _overflow_world(m):
-    """asmK/readK ratios > 13107 (K* bin >= 65536: beyond the default dense image) on both halves of the tile range"""
-    k = 21
-    r = synth.rng(331)
-    contigs = [synth.random_contig(r, 300 * 4096).tobytes(), synth.random_contig(r, 300 * 4096 + 11).tobytes()]
-    ak, av = po.count_kmers(k, contigs)
-    av = av.copy()
-    rv = np.full(len(ak), 5, dtype=np.uint32)
-    first = po.count_kmers(k, [contigs[0][:60], contigs[0][-60:], contigs[1][:60], contigs[1][-60:]])[0]
-    hot = np.isin(ak, first)
-    av[hot] = 70000 + (np.arange(hot.sum()) % 7) * 100000     # undr bins 349 995 ... 3.3 M
-    rv[np.isin(ak, po.count_kmers(k, [contigs[1][5000:5040]])[0])] = 900000   # over bins ~ 900 000
-    return k, 5.0, contigs, (ak, rv), (ak, av)
-
-
 def test_overflow_bins_survive_the_multi_slot_reduction():
     import merfin_amd as m
-    k, peak, contigs, read, asm = _overflow_world(m)
+    k, peak, contigs, read, asm = overflow_world(300)
     p, g, ka, km = oracle_hist(k, peak, contigs, read, asm)
     assert g.c.undrMax > 65536 and g.c.overMax > 65536
     ix = build_index(m, k, read, asm)
@@ -296,7 +282,7 @@ def test_rccl_communicator_world_of_one():
     device; one rank's image is already the global one, so every word must come back unchanged"""
     torch = pytest.importorskip("torch")
     import merfin_amd as m
-    k, peak, contigs, read, asm = _overflow_world(m)
+    k, peak, contigs, read, asm = overflow_world(300)
     p, g, ka, km = oracle_hist(k, peak, contigs, read, asm)
     ix = build_index(m, k, read, asm)
     seqs = m.Sequences(contigs)

@@ -8,6 +8,7 @@ OUT=../../tools/_build/ab
 mkdir -p $OUT/$NAME
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-unused-function"
 for f in mfx_kernels mfx_wide; do /opt/rocm/bin/hipcc $FLAGS "$@" -c $f.hip -o $OUT/$NAME/$f.o; done
-/opt/rocm/bin/hipcc $FLAGS -shared -o $OUT/lib_$NAME.so $OUT/$NAME/mfx_kernels.o $OUT/$NAME/mfx_wide.o ../_build/mfx_sort.o ../_build/mfx_api.o ../_build/mfx_db.o \
-  ../_build/mfx_variants.o ../_build/mfx_comm.o ../_build/mfx_reads.o ../_build/mfx_pack.o -L/opt/rocm/lib -lrccl
+# every other object of the library's own build (make -C merfin_amd/csrc first), whatever files it has
+REST=$(ls ../_build/*.o | grep -v -e /mfx_kernels.o -e /mfx_wide.o)
+/opt/rocm/bin/hipcc $FLAGS -shared -o $OUT/lib_$NAME.so $OUT/$NAME/mfx_kernels.o $OUT/$NAME/mfx_wide.o $REST -L/opt/rocm/lib -lrccl
 echo built $OUT/lib_$NAME.so
