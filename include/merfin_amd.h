@@ -249,6 +249,15 @@ int mfx_index_get_info(const mfx_index *ix, mfx_index_info *out);
 int mfx_index_export(const mfx_index *ix, uint64_t *kmers, uint32_t *readV, uint32_t *asmV,
                      uint64_t *n_out);
 
+/* One side of a full index (not sharded, k <= 31) as a k-mer database: the k-mers whose count on `side` (0: read counts, 1: assembly
+ * counts) is non-zero, with those counts -- byte for byte the file mfx_db_write_flat(path, k, kmers, values, n) writes for them in
+ * ascending order, i.e. what `merfin -convert` makes of a database of them (its -placed form: convert the result).  With
+ * mfx_reads_begin_all this is `meryl count` of the reads: count once, run every mode from the file.  The k-mers are sorted on the
+ * device, one key range of at most 2^28 entries at a time (MFX_WRITE_DB_RANGE, read per call, lowers that: docs/KNOBS.md), and
+ * collected on the host: peak host memory is 12 bytes per k-mer written, as for mfx_db_convert.  Nothing else may use the index during
+ * the call.  n_kmers (may be NULL): the k-mers written. */
+int mfx_index_write_db(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers);
+
 /* ------------------------------------------------------------------------ */
 /* Read k-mer counting: the read counts of a run straight from its reads     */
 /* (FASTA / FASTQ records), no k-mer database in between.                   */
@@ -281,6 +290,26 @@ int        mfx_reads_set_filter(mfx_reads *r, uint64_t minV, uint64_t maxV);
 int        mfx_reads_add(mfx_reads *r, const char *const *bases, const uint64_t *lens, uint64_t n);
 /* out may be NULL; r is freed whatever the result */
 int        mfx_reads_end(mfx_reads *r, mfx_reads_stats *out);
+
+/* The CLAIMING counter -- `meryl count` of the reads: every canonical k-mer of the reads is claimed if the index does not hold it, and its
+ * read count grows by its occurrences.  Nothing is dropped: stats.dropped == 0 and counted == kmers.  The same object as mfx_reads_begin
+ * gives, used with the same mfx_reads_add / mfx_reads_set_filter / mfx_reads_end.  The index: a full one (mfx_index_create*), 1 <= k <= 31,
+ * not sharded, its read side untouched; its assembly side may be filled before or after (those adds claim as always; the index is not
+ * frozen).  Refused with MFX_E_INVAL: a sequence-only or path-only index, k > 31, a sharded index, a read side that already took counts.
+ * The TABLE GROWS, because nobody knows the reads' distinct k-mers beforehand; create the index small.  No launch may overfill the table:
+ * a batch of B positions is enqueued only while  distinct + pending + B <= 0.7 x slots  (distinct: the table's count as last read;
+ * pending: the positions enqueued since, each of which may claim a k-mer).  Otherwise the batches in flight are waited for and the count
+ * is read again; if the bound still fails, every entry moves into a table of the smallest power-of-two multiple of the lines (at least
+ * twice) with  distinct + B <= 0.35 x slots, and the old table is freed.  mfx_index_get_info shows the new capacity and bytes.  Both tables
+ * are alive while the entries move: that sum honours the index's max_gb, the new table the free device memory.  A table that cannot grow
+ * fails the mfx_reads_add (or _end) that needed it with MFX_E_NOMEM, naming both sizes; the counter is then failed, mfx_reads_end reports
+ * MFX_E_NOMEM too, and the index can only be freed.  A claiming counter does not end in MFX_E_FULL.
+ * As for every call that changes an index: NO evaluator, replica or image of the index may exist while a claiming counter is open -- they
+ * hold the table's address and geometry, and a growth replaces both. */
+mfx_reads *mfx_reads_begin_all(mfx_index *ix, uint64_t batch_bases);
+/* what claiming counters did to the index's table so far: growths, their wall time, of that the kernels that moved the entries, and the
+ * bytes those read and wrote (any pointer may be NULL) */
+int        mfx_index_growths(const mfx_index *ix, uint64_t *n, double *seconds, double *rehash_seconds, uint64_t *rehash_bytes);
 
 /* ------------------------------------------------------------------------ */
 /* Sequences: replaces the loader callback loadSequence (merfin.C:30-53) +  */

@@ -91,6 +91,7 @@ SYMBOLS = [
     "mfx_pack_bases", "mfx_host_threads_share", "mfx_dump_values", "mfx_dump_contig", "mfx_dump_values_sharded", "mfx_dump_contig_sharded", "mfx_variants_run_sharded", "mfx_vcf_load", "mfx_vcf_free", "mfx_variants_run_vcf", "mfx_vcf_prepare", "mfx_vcf_path_bound", "mfx_index_claim_paths", "mfx_vcf_prepare_path_index", "mfx_completeness", "mfx_completeness_pieces", "mfx_variants_run",
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
+    "mfx_reads_begin_all", "mfx_index_growths", "mfx_index_write_db",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
@@ -302,6 +303,10 @@ def load_library():
     L.mfx_reads_set_filter.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.mfx_reads_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
     L.mfx_reads_end.argtypes = [vp, C.POINTER(_ReadsStats)]
+    L.mfx_reads_begin_all.restype = vp
+    L.mfx_reads_begin_all.argtypes = [vp, C.c_uint64]
+    L.mfx_index_growths.argtypes = [vp, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double), u64p]
+    L.mfx_index_write_db.argtypes = [vp, C.c_int, C.c_char_p, u64p]
     L.mfx_track_num_windows.restype = C.c_uint64
     L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
     L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
@@ -623,9 +628,33 @@ class Index:
         records, any case, N breaks a k-mer) are added to the read counts of the k-mers this index holds, the others are
         dropped.  A sequence-only / path-only index (k > 31: a table of the assembly's k-mers) whose read side has no counts
         yet.  Returns the counter's statistics as a dict."""
+        return self._count_reads(load_library().mfx_reads_begin, reads, batch_bases, minV, maxV, chunk)
+
+    def count_reads_all(self, reads, batch_bases=0, chunk=4096, minV=0, maxV=2**64 - 1):
+        """`meryl count` of the reads on the device (mfx_reads_begin_all): every canonical k-mer of `reads` is claimed if this index
+        does not hold it, and its read count grows by its occurrences; the table grows as it fills (info() shows the new capacity,
+        growths() how often).  A full index, k <= 31, not sharded, whose read side has no counts yet; no Evaluator or replica of it
+        may exist meanwhile.  Returns the counter's statistics as a dict (dropped == 0)."""
+        return self._count_reads(load_library().mfx_reads_begin_all, reads, batch_bases, minV, maxV, chunk)
+
+    def growths(self):
+        """what claiming counters did to the table (mfx_index_growths)"""
+        n, b = C.c_uint64(0), C.c_uint64(0)
+        s, rs = C.c_double(0), C.c_double(0)
+        _check(load_library().mfx_index_growths(self.h, C.byref(n), C.byref(s), C.byref(rs), C.byref(b)))
+        return {"growths": n.value, "seconds": s.value, "rehash_seconds": rs.value, "rehash_bytes": b.value}
+
+    def write_db(self, path, side=0):
+        """the k-mers with a non-zero count on `side` (0: reads, 1: assembly) as the sorted flat database db_write_flat makes of them
+        (mfx_index_write_db); returns their number"""
+        n = C.c_uint64(0)
+        _check(load_library().mfx_index_write_db(self.h, int(side), path.encode(), C.byref(n)))
+        return n.value
+
+    def _count_reads(self, begin, reads, batch_bases, minV, maxV, chunk):
         L = load_library()
         recs = [x.encode() if isinstance(x, str) else bytes(x) for x in reads]      # (before begin: a bad record leaves the index as it was)
-        r = _need(L.mfx_reads_begin(self.h, int(batch_bases)))
+        r = _need(begin(self.h, int(batch_bases)))
         rc = L.mfx_reads_set_filter(r, int(minV), int(maxV))
         for o in range(0, len(recs), chunk):
             if rc:

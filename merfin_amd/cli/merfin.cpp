@@ -52,6 +52,8 @@ struct Globals {
   bool peakAuto = false;                 // -peak auto: the haploid peak is read off the index's copy-number spectrum (mfx_spectrum_peak)
   uint32_t copies = 4, maxMult = 10000;  // -copies / -maxmult of -spectrum
   bool copiesGiven = false, maxMultGiven = false;
+  bool count = false;                    // -count: no report; the k-mers of -reads counted on the GPU and written as a database
+  bool peakGiven = false, devicesGiven = false;
 };
 
 static void usage(const char *exe) {
@@ -74,6 +76,9 @@ static void usage(const char *exe) {
           "    -k k              k when no database gives it (-reads without -seqmers); must agree with -seqmers\n"
           "    -convert db       no report: rewrite the k-mer database <db> (any accepted form) as -output <file> in the flat form\n"
           "                      (sorted k-mers in delta-coded blocks; loads at the speed of the PCIe link)\n"
+          "    -count            no report: count every k-mer of the -reads files on the GPU (`meryl count`; -k K, K <= 31) and write\n"
+          "                      the sorted flat database -output <file>, which every mode takes as -readmers.  -min / -max are not\n"
+          "                      applied: a database holds every count, the filter acts when it is loaded.  One device.\n"
           "    -placed           with -convert: the records sorted by their PLACE in the table -hist / -dump build (13 <= k <= 31,\n"
           "                      canonical databases): such a database is applied to the table line after line\n"
           "    -device d         HIP device (default 0)\n"
@@ -601,10 +606,11 @@ static bool concat_parts(const std::string &out, const std::vector<std::string> 
 // -reads: the read counts of the run from its reads, counted on the device into the k-mers the index holds (mfx_reads_*).  One reader
 // thread per file (16 at most at a time) parses records into batches; this thread hands the batches to the counter, which copies them
 // and returns while the device counts, so parsing, transfer and counting overlap.  Returns false with the error printed.
-static bool count_reads_files(const Globals &G, mfx_index *ix) {
+// all (-count): the claiming counter -- every k-mer of the reads, no filter; *all_stats gets its statistics and the caller reports.
+static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false, mfx_reads_stats *all_stats = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
-  mfx_reads *rc = mfx_reads_begin(ix, 0);
-  if (!rc || mfx_reads_set_filter(rc, G.minV, G.maxV)) {
+  mfx_reads *rc = all ? mfx_reads_begin_all(ix, 0) : mfx_reads_begin(ix, 0);
+  if (!rc || mfx_reads_set_filter(rc, all ? 0 : G.minV, all ? ~0ull : G.maxV)) {
     fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error());
     if (rc) mfx_reads_end(rc, nullptr);
     return false;
@@ -692,8 +698,10 @@ static bool count_reads_files(const Globals &G, mfx_index *ix) {
     return false;
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu counted, %lu dropped.\n", G.kArg, (unsigned long)st.reads,
-          (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)st.counted, (unsigned long)st.dropped);
+  if (all_stats) *all_stats = st;
+  if (!all)
+    fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu counted, %lu dropped.\n", G.kArg, (unsigned long)st.reads,
+            (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)st.counted, (unsigned long)st.dropped);
   if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
     fprintf(stderr, "-- reads: %.3f s wall = %.3f s waiting for parsed records + %.3f s batching / encoding / waiting for a stage; device %.3f s kernel + "
                     "%.3f s copy (idle %.0f %% of the wall)\n", wall, t_wait, t_submit, st.seconds_kernel, st.seconds_copy,
@@ -732,6 +740,7 @@ int main(int argc, char **argv) {
       const char *v = val();
       if (strcmp(v, "auto") == 0) G.peakAuto = true;
       else G.peak = strtod(v, nullptr);
+      G.peakGiven = true;
     }
     else if (is("-spectrum")) G.reportType = OP_SPECTRUM;
     else if (is("-copies") || is("-maxmult")) {
@@ -777,6 +786,7 @@ int main(int argc, char **argv) {
     else if (is("-index")) G.indexName = val();
     else if (is("-sharded")) G.sharded = true;
     else if (is("-convert")) G.convertName = val();
+    else if (is("-count")) G.count = true;
     else if (is("-placed")) G.placed = true;
     else if (is("-nosplit")) G.nosplit = true;
     else if (is("-filter")) G.reportType = OP_FILTER;
@@ -801,6 +811,66 @@ int main(int argc, char **argv) {
     else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
     else if (is("-debug")) G.debug = true;
     else err.push_back(std::string("Unknown option '") + argv[arg] + "'.\n");
+  }
+
+  // -count: every check before any device is touched (the checks of a report from -reads below do not apply to it)
+  if (G.count) {
+    if (G.convertName) err.push_back("-count and -convert are two operations: give one of them.\n");
+    if (G.reportType != OP_NONE) err.push_back("-count is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
+    if (G.readsNames.empty()) err.push_back("-count needs the reads it counts: give -reads <file> (repeatable).\n");
+    if (G.kArg == 0) err.push_back("-count needs -k: no database gives it.\n");
+    if (!G.outName) err.push_back("-count writes a k-mer database: give -output <file>.\n");
+    if (G.kArg > 31)
+      err.push_back("-count holds k <= 31 (here k = " + std::to_string(G.kArg) + "): count larger k-mers with `meryl count` and give the database as -readmers.\n");
+    if (G.readDBname) err.push_back("-count makes the read database: it does not take -readmers.\n");
+    if (G.seqDBname) err.push_back("-count counts reads: it does not take -seqmers.\n");
+    if (G.seqName) err.push_back("-count counts reads: it does not take -sequence.\n");
+    if (G.vcfName) err.push_back("-count does not take -vcf (the variant modes do).\n");
+    if (G.peakGiven) err.push_back("-count evaluates nothing: it does not take -peak.\n");
+    if (G.sharded) err.push_back("-count does not take -sharded: the table it counts into lives on one device.\n");
+    if (G.indexName) err.push_back("-count does not take -index: it writes a database, not a table image.\n");
+    if (G.devices.size() > 1) err.push_back("-count runs on one device (-device d, or -devices naming one).\n");
+    for (const char *f : G.readsNames) {
+      struct stat rst;
+      if (stat(f, &rst) != 0 || !S_ISREG(rst.st_mode) || access(f, R_OK) != 0)
+        err.push_back(std::string("Cannot read the -reads file '") + f + "'.\n");
+    }
+    if (!err.empty()) {
+      usage(argv[0]);
+      for (auto &e : err) fputs(e.c_str(), stderr);
+      return 1;
+    }
+    if (!G.devices.empty()) G.device = G.devices[0];
+    if (mfx_device_count() <= G.device) {
+      fprintf(stderr, "ERROR: HIP device %d not available (%d visible). This program has no CPU path.\n", G.device, mfx_device_count());
+      return 1;
+    }
+    // the table is created small and grows with what the reads hold (mfx_reads_begin_all)
+    const auto tc0 = std::chrono::steady_clock::now();
+    mfx_index *ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
+    if (!ix) DIE_MFX("creating the k-mer table");
+    struct IxGuard { mfx_index *ix; ~IxGuard() { mfx_index_free(ix); } } ixGuard{ix};
+    fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s.\n", G.kArg, (unsigned long)G.readsNames.size(), G.readsNames.size() == 1 ? "" : "s");
+    mfx_reads_stats st;
+    if (!count_reads_files(G, ix, true, &st)) return 1;
+    mfx_index_info info;
+    uint64_t growths = 0;
+    if (mfx_index_get_info(ix, &info) || mfx_index_growths(ix, &growths, nullptr, nullptr, nullptr)) DIE_MFX("-count");
+    fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu distinct; the table grew %lu time%s to %.3f GB.\n", G.kArg,
+            (unsigned long)st.reads, (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)info.distinct, (unsigned long)growths,
+            growths == 1 ? "" : "s", (double)info.bytes / 1e9);
+    const auto tc1 = std::chrono::steady_clock::now();
+    uint64_t n = 0;
+    if (mfx_index_write_db(ix, 0, G.outName, &n)) DIE_MFX("-count: writing the database");
+    struct stat ost;
+    fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
+    if (stat(G.outName, &ost) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", ost.st_size / 1e9, (double)ost.st_size / (double)n);
+    fprintf(stderr, ".\n");
+    if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
+      fprintf(stderr, "-- count: %.3f s counting, %.3f s sorting and writing\n", std::chrono::duration<double>(tc1 - tc0).count(),
+              std::chrono::duration<double>(std::chrono::steady_clock::now() - tc1).count());
+    fprintf(stderr, "Bye!\n");
+    return 0;
   }
 
   // -reads: every check before any device is touched

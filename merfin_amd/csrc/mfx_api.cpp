@@ -413,6 +413,7 @@ static mfx_index *index_create(int k, uint64_t capacity_kmers, double max_gb, in
   ix->device = device;
   ix->k = k;
   ix->capacity_kmers = capacity_kmers;
+  ix->max_gb = max_gb > 0 ? max_gb : 0;
   ix->seq_only = seq_only;
   ix->compact = compact;
   ix->quot = compact && k > MFX_MAX_K_DIRECT;

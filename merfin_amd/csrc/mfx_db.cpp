@@ -15,6 +15,8 @@
 //                 refuses anything whose magic numbers / sizes do not match
 //                 rather than guessing.
 #include "mfx_internal.h"
+#include "mfx_kernels.h"
+#include "mfx_grow.h"
 #include "mfx_pipe.h"
 #include "mfx_place.h"
 
@@ -1438,6 +1440,99 @@ extern "C" int mfx_db_convert(const char *in_path, const char *out_path, uint64_
   try { return mfx_db_convert_impl(in_path, out_path, n_out); }                       // (nothing leaves the C ABI as an exception)
   catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_convert: out of memory"); }
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_convert: %s", e.what()); }
+}
+
+
+// ---------------------------------------------------------------------------
+// mfx_index_write_db: one side of a full table as the sorted flat database `merfin -convert` makes -- what turns the claiming read
+// counter's table (mfx_reads_begin_all) into a -readmers file.  On the device (mfx_sort.hip): one streaming pass counts the entries
+// with a non-zero count on `side` per bin of their top MFX_DB_BIN_BITS key bits; the bins are grouped into key ranges of at most R
+// entries (mfx_grow.h: mfx_group_bins); per range the entries are compacted out of the table, radix-sorted and copied behind the ranges
+// before them.  Ranges ascend and are sorted, so the host arrays are the whole side in ascending order: the existing writer gets them.
+// ---------------------------------------------------------------------------
+constexpr int MFX_DB_BIN_BITS = 12;
+constexpr uint64_t MFX_DB_RANGE_DEFAULT = 1ull << 28;        // entries per range: 2 x 12 bytes x 2^28 = 6 GB of device buffers + the sort's
+
+namespace {
+struct DbDev {                                                 // device buffers of one call, freed on every way out
+  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~DbDev() { for (void *x : p) if (x) (void)hipFree(x); }
+};
+}  // namespace
+
+static int mfx_index_write_db_impl(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {
+  if (!ix || !path) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: null argument");
+  if (side != 0 && side != 1) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: side %d (0: the read counts, 1: the assembly counts)", side);
+  if (ix->seq_only) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: a sequence-only or path-only index holds part of a database only; write a full index (mfx_index_create)");
+  if (ix->wide()) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: the sorted form holds k <= %d; this index holds %d-mers", MFX_MAX_K_NARROW, ix->k);
+  if (ix->shard_n > 1) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: a sharded index holds part of a database only");
+  uint64_t R = MFX_DB_RANGE_DEFAULT;
+  if (const char *e = getenv("MFX_WRITE_DB_RANGE")) {          // read per call: tests reach several ranges on small tables
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  struct Back { int d; ~Back() { if (d >= 0) (void)hipSetDevice(d); } } back{prev};
+  MFX_HIP(hipSetDevice(ix->device));
+  const int key_bits = 2 * ix->k, bin_bits = std::min(key_bits, MFX_DB_BIN_BITS), shift = key_bits - bin_bits;
+  const uint32_t nbins = 1u << bin_bits;
+  mfx_table_view t = ix->view();
+  DbDev D;
+  uint64_t *d_bins = nullptr;
+  MFX_HIP(hipMalloc(&D.p[0], (nbins + 1) * sizeof(uint64_t)));     // the bins, then the export's counter
+  d_bins = (uint64_t *)D.p[0];
+  unsigned long long *d_count = (unsigned long long *)(d_bins + nbins);
+  MFX_HIP(mfx_memset_now(d_bins, 0, (nbins + 1) * sizeof(uint64_t)));
+  MFX_HIP(mfx_k_db_bins(t, side, shift, nbins, d_bins, nullptr));
+  std::vector<uint64_t> bins(nbins);
+  MFX_HIP(hipMemcpy(bins.data(), d_bins, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::vector<mfx_bin_range> ranges;
+  mfx_group_bins(bins.data(), nbins, R, ranges);
+  uint64_t n = 0, maxn = 0;
+  for (const auto &r : ranges) { n += r.n; maxn = std::max(maxn, r.n); }
+  std::vector<uint64_t> keys(n);
+  std::vector<uint32_t> vals(n);
+  if (n) {
+    size_t tmp_bytes = 0;
+    if (int rc = mfx_sort_db_pairs(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, maxn, key_bits, nullptr)) return rc;
+    hipError_t e = hipMalloc(&D.p[1], maxn * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[2], maxn * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[3], maxn * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[4], maxn * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[5], tmp_bytes ? tmp_bytes : 1);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return mfx_fail(MFX_E_NOMEM, "mfx_index_write_db: the buffers of a key range of %lu k-mers (%.3f GB) do not fit the device: %s; lower MFX_WRITE_DB_RANGE",
+                      (unsigned long)maxn, ((double)maxn * 24 + (double)tmp_bytes) / 1e9, hipGetErrorString(e));
+    }
+    uint64_t at = 0;
+    for (const auto &r : ranges) {
+      MFX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), nullptr));
+      MFX_HIP(mfx_k_db_export(t, side, shift, r.bin_lo, r.bin_hi, (uint64_t *)D.p[1], (uint32_t *)D.p[3], maxn, d_count, nullptr));
+      unsigned long long got = 0;
+      MFX_HIP(hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipStreamSynchronize(nullptr));
+      if (got != r.n)
+        return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: the table changed while it was written (a key range held %lu k-mers, then %lu); nothing else may "
+                        "use the index during the call", (unsigned long)r.n, (unsigned long)got);
+      if (int rc = mfx_sort_db_pairs(D.p[5], tmp_bytes, (const uint64_t *)D.p[1], (uint64_t *)D.p[2], (const uint32_t *)D.p[3], (uint32_t *)D.p[4], r.n,
+                                     key_bits, nullptr))
+        return rc;
+      MFX_HIP(hipMemcpyAsync(keys.data() + at, D.p[2], r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipMemcpyAsync(vals.data() + at, D.p[4], r.n * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipStreamSynchronize(nullptr));
+      at += r.n;
+    }
+  }
+  if (n_kmers) *n_kmers = n;
+  return mfx_db_write_flat_impl(path, ix->k, keys.data(), vals.data(), n);
+}
+
+extern "C" int mfx_index_write_db(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {
+  try { return mfx_index_write_db_impl(ix, side, path, n_kmers); }                     // (nothing leaves the C ABI as an exception)
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_index_write_db: out of memory (12 bytes of host memory per k-mer written)"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_index_write_db: %s", e.what()); }
 }
 
 

@@ -1,0 +1,54 @@
+// mfx_grow.h -- the plain host arithmetic of the claiming read counter's table (mfx_reads.cpp) and of mfx_index_write_db's key ranges
+// (mfx_db.cpp).  No HIP, no library state: tools/native/grow_sanitize.cpp drives it under the sanitizers.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+// ---- a table that grows ----------------------------------------------------------------------------------------------------------
+// A launch never overfills the table: a batch of B positions is enqueued only while
+//   distinct + pending + B <= 0.7 x slots          (0.7: the smallest load factor of a full table, MFX_LF_MAX)
+// holds, where `distinct` is the table's meta[0] as last read and `pending` the positions enqueued since that read (each of them may
+// claim one k-mer).  All in integers: 10 (d + p + B) <= 7 slots.
+inline bool mfx_grow_fits(uint64_t distinct, uint64_t pending, uint64_t B, uint64_t slots) {
+  const unsigned __int128 need = (unsigned __int128)distinct + pending + B;
+  return need * 10u <= (unsigned __int128)slots * 7u;
+}
+
+// The table a counter grows into: the smallest power-of-two multiple (>= 2) of the current lines for which
+//   distinct + B <= 0.35 x slots                   (20 (d + B) <= 7 slots)
+// so that a grown table takes at least as many claims again as it holds before it has to grow once more.  0: no such table below
+// max_lines (the device numbers its lines in 32 bits).
+inline uint64_t mfx_grow_lines(uint64_t distinct, uint64_t B, uint64_t nlines, uint32_t slots_line, uint64_t max_lines) {
+  if (nlines == 0 || slots_line == 0) return 0;
+  const unsigned __int128 need = ((unsigned __int128)distinct + B) * 20u;
+  for (uint64_t mult = 2; mult != 0 && nlines <= max_lines / mult; mult <<= 1) {
+    const uint64_t nl = nlines * mult;
+    if (need <= (unsigned __int128)nl * slots_line * 7u) return nl;
+  }
+  return 0;
+}
+
+// ---- key ranges of a sorted export ---------------------------------------------------------------------------------------------------
+// bins[b]: entries whose top key bits are b.  Consecutive bins are grouped into ranges [bin_lo, bin_hi) of at most R entries each; a
+// bin that alone holds more than R is a range of its own (the caller sizes its buffers by the largest range).  Empty bins join the range
+// before them or are skipped: no range is empty, the ranges are ascending and together hold every non-empty bin.
+struct mfx_bin_range { uint32_t bin_lo, bin_hi; uint64_t n; };
+
+inline void mfx_group_bins(const uint64_t *bins, uint32_t nbins, uint64_t R, std::vector<mfx_bin_range> &out) {
+  out.clear();
+  if (R == 0) R = 1;
+  mfx_bin_range cur{0, 0, 0};
+  for (uint32_t b = 0; b < nbins; ++b) {
+    const uint64_t c = bins[b];
+    if (c == 0) continue;
+    if (cur.n != 0 && (c > R || cur.n > R - c)) {             // (cur.n + c > R without the overflow)
+      out.push_back(cur);
+      cur.n = 0;
+    }
+    if (cur.n == 0) cur.bin_lo = b;
+    cur.bin_hi = b + 1;
+    cur.n += c;
+  }
+  if (cur.n != 0) out.push_back(cur);
+}

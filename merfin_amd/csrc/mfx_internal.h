@@ -173,6 +173,10 @@ struct mfx_index {
   uint64_t  paths_token = 0;    // seq_only: the k-mers are those of a prepared VCF's PATHS (mfx_index_claim_paths), not a sequence's: the token of that call set
   uint32_t  seq_digest = 0;     // seq_only: content digest of the sequence the k-mers were claimed from (0: not recorded);
                                 // evaluating another sequence on it is refused (mfx_seq_digest32, mfx_api.cpp)
+  double    max_gb = 0;         // the -memory cap the table was created under (0: none): a table that grows honours it (mfx_reads_begin_all)
+  // what a claiming read counter did to the table (mfx_index_growths): growths, their wall time, the rehash kernels' time and the bytes they read + wrote
+  uint64_t  grow_count = 0, rehash_bytes = 0;
+  double    grow_seconds = 0, rehash_seconds = 0;
   uint64_t  total_lines() const { return nlines + side_nlines; }
   bool      wide() const { return k > MFX_MAX_K_NARROW; }
   uint32_t  slots_per_line() const { return wide() ? MFX_WSLOTS_LINE : compact ? MFX_CSLOTS_LINE : MFX_SLOTS_LINE; }

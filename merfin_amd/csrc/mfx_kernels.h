@@ -213,5 +213,16 @@ hipError_t mfx_k_valid_scatter(uint32_t *valid, const uint64_t *exc, uint32_t n,
 hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st);
 hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st);        // k <= 31: sequence-only / path-only index (every layout)
 hipError_t mfx_kw_reads(const mfx_reads_args &a, hipStream_t st);       // 32 <= k <= 64 (mfx_wide.hip)
+hipError_t mfx_k_reads_claim(const mfx_reads_args &a, hipStream_t st);  // k <= 31, a full table of 16-byte slots: every k-mer is claimed if absent (mfx_reads_begin_all)
+// every entry of a full table of 16-byte slots into the (empty) table nt; meta: nt's words, zero at launch ([0]: entries moved, [2]: probe-limit failures)
+hipError_t mfx_k_table_rehash(const mfx_slot *old_slots, uint64_t old_nslots, mfx_table_view nt, uint64_t *meta, hipStream_t st);
+// mfx_index_write_db (mfx_sort.hip): bins[key >> shift] += 1 for every entry whose count on `side` is non-zero
+hipError_t mfx_k_db_bins(mfx_table_view t, int side, int shift, uint32_t nbins, uint64_t *bins, hipStream_t st);
+// ... those of them with bin_lo <= key >> shift < bin_hi, compacted into keys / vals (at most cap; *count ends as their number, also beyond cap)
+hipError_t mfx_k_db_export(mfx_table_view t, int side, int shift, uint32_t bin_lo, uint32_t bin_hi, uint64_t *keys, uint32_t *vals, uint64_t cap,
+                           unsigned long long *count, hipStream_t st);
+// ascending keys (bits [0, key_bits)) with their values; tmp == nullptr: only tmp_bytes is set
+int mfx_sort_db_pairs(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, uint64_t n, int key_bits,
+                      hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);

@@ -782,6 +782,29 @@ __global__ __launch_bounds__(256) void mfx_table_add_kernel(mfx_table_view t, co
   mfx_meta_flush(meta, fresh, noncanon);
 }
 
+// A table that grows (mfx_reads.cpp: the claiming read counter): every entry of the old table moves to the new one.  Persistent blocks
+// stream the old slots, one 16-byte load per lane (a wave reads 1 KB in a row); an occupied slot's key is claimed in the new table and both
+// counts are written with ONE plain 8-byte store: the keys of a table are distinct, so every new slot has exactly one writer.  meta: the
+// words of the NEW table (zero at launch): [0] ends as the number of entries moved, [2] as the claims that hit the probe limit.
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_table_rehash_kernel(const mfx_slot *old_slots, uint64_t old_nslots, mfx_table_view nt, uint64_t *meta) {
+  const uint64_t stride = (uint64_t)gridDim.x * MFX_BLOCK;
+  uint32_t fresh = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * MFX_BLOCK; base < old_nslots; base += stride) {      // wave-uniform trip count
+    const uint64_t i = base + threadIdx.x;
+    if (i >= old_nslots) continue;
+    const uint4 s = *reinterpret_cast<const uint4 *>(old_slots + i);
+    const uint64_t key = (uint64_t)s.x | ((uint64_t)s.y << 32);
+    if (key == MFX_EMPTY) continue;
+    mfx_slot *sl = mfx_claim(nt, key, meta, fresh);
+#ifdef MFX_V_REHASH_NO_ASM                                   // A/B build only: the assembly count is left behind (tests/test_gpu_count.py must FAIL on it)
+    if (sl) *reinterpret_cast<uint2 *>(&sl->readV) = make_uint2(s.z, 0u);
+#else
+    if (sl) *reinterpret_cast<uint2 *>(&sl->readV) = make_uint2(s.z, s.w);
+#endif
+  }
+  mfx_meta_flush(meta, fresh, 0u);
+}
+
 // UB k-mers of every lane go into the table (v == 0: none), all lanes of the wave together.
 //  * SEQUENCE-ONLY index: the key set is frozen (the k-mers claimed from the sequence), an add finds its k-mer's slot and
 //    updates the count, or drops the k-mer (T.dropped -> meta[3]).  Only canonical k-mers were claimed: a non-canonical
@@ -3619,11 +3642,35 @@ __device__ __forceinline__ unsigned long long *mfx_reads_cfind(const mfx_table_v
   return nullptr;
 }
 
+// the slot of `key` if it sits in the k-mer's HOME line (the claiming counter's first step: in a 30x read set 29 of 30 occurrences meet a
+// k-mer that is already there, and most k-mers live in their home line), else nullptr.  Claims run beside this: a key once written never
+// changes and slots fill in order (mfx_claim), so a key seen by a plain load is final and the first empty slot ends the line; a stale
+// "empty" only sends the lane to mfx_claim, which decides with atomics.
+__device__ __forceinline__ mfx_slot *mfx_reads_find_home(const mfx_table_view &t, uint64_t key) {
+  const mfx_probe pr = mfx_home(t, key);
+  mfx_slot *ln = t.slots + mfx_probe_line(t, pr, 0) * MFX_SLOTS_LINE;
+#pragma unroll 1
+  for (uint32_t q = 0; q < MFX_SLOTS_LINE; ++q) {
+    const uint4 s = *reinterpret_cast<const uint4 *>(ln + q);
+    const uint64_t sk = (uint64_t)s.x | ((uint64_t)s.y << 32);
+    if (sk == key) return ln + q;
+    if (sk == MFX_EMPTY) break;
+  }
+  return nullptr;
+}
+
 // readV += v of the claimed k-mer `key`, or a counted drop; n_side: the k-mer's read count moved to (or lives in) the side table
+// CLAIM (mfx_reads_begin_all; a full table of 16-byte slots): a k-mer the table does not hold is claimed -- per lane: find in the home
+// line, mfx_claim on a miss -- and `fresh` counts the claims (mfx_meta_flush); a drop is a claim that hit the probe limit
+template <bool CLAIM>
 __device__ __forceinline__ void mfx_reads_add(const mfx_reads_args &a, uint64_t key, uint32_t v, uint64_t &n_counted, uint64_t &n_dropped,
-                                              uint64_t &n_side) {
+                                              uint64_t &n_side, uint32_t &fresh) {
   bool hit = false;
-  if (a.t.compact) {
+  if (CLAIM) {
+    mfx_slot *sl = mfx_reads_find_home(a.t, key);
+    if (!sl) sl = mfx_claim(a.t, key, a.meta, fresh);
+    if (sl) { hit = true; atomicAdd(&sl->readV, v); }
+  } else if (a.t.compact) {
     // the first mini-bucket of the k-mer's order answers for most (mfx_count_kernel, count == 2)
     const mfx_probe pr = mfx_home(a.t, key);
     unsigned long long *mb = reinterpret_cast<unsigned long long *>(a.t.slots) + mfx_probe_line(a.t, pr, 0) * MFX_CSLOTS_LINE + 2u * pr.b0;
@@ -3659,6 +3706,7 @@ __device__ __forceinline__ void mfx_reads_add(const mfx_reads_args &a, uint64_t 
 // once more per tile in a block table (LDS) and added when the tile ends; i.i.d. reads almost never take this path.
 constexpr uint32_t MFX_READS_BT = 256;                         // entries of the block table (a power of two)
 
+template <bool CLAIM>
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) {
   __shared__ mfx_tile_lds L;
   __shared__ uint32_t s_own[MFX_BLOCK / 64][256];             // per wave: the lane that holds the entry of a key hash
@@ -3669,6 +3717,7 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) 
   const int k = a.t.k;
   const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
   uint64_t n_kmers = 0, n_counted = 0, n_dropped = 0, n_side = 0;
+  uint32_t fresh = 0;                                          // CLAIM: k-mers this lane claimed
   for (uint32_t j = tid; j < MFX_READS_BT; j += MFX_BLOCK) { s_bk[j] = MFX_EMPTY; s_bv[j] = 0u; }
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const uint64_t pos0 = tile * MFX_TILE;
@@ -3704,18 +3753,32 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) 
           if (prev == MFX_EMPTY || prev == key) { atomicAdd(&s_bv[j], v); v = 0u; break; }
         }
       }
-      if (v) mfx_reads_add(a, key, v, n_counted, n_dropped, n_side);
+#ifdef MFX_V_READS_CLAIM_COOP                                // A/B build only: the claiming instance adds with the cooperative insert (every lane takes part, v == 0: none)
+      if (CLAIM) { mfx_group_insert(a.t, key, v, 0, a.meta, fresh); n_counted += v; continue; }
+#endif
+      if (v) mfx_reads_add<CLAIM>(a, key, v, n_counted, n_dropped, n_side, fresh);
     }
     __syncthreads();                                           // ---- the tile's block table goes to the index
     for (uint32_t j = tid; j < MFX_READS_BT; j += MFX_BLOCK) {
       const unsigned long long key = s_bk[j];
+#ifdef MFX_V_READS_CLAIM_COOP
+      if (CLAIM) {
+        const uint32_t cv = key == MFX_EMPTY ? 0u : s_bv[j];
+        s_bk[j] = MFX_EMPTY;
+        s_bv[j] = 0u;
+        mfx_group_insert(a.t, key == MFX_EMPTY ? 0ull : (uint64_t)key, cv, 0, a.meta, fresh);
+        n_counted += cv;
+        continue;
+      }
+#endif
       if (key == MFX_EMPTY) continue;
       const uint32_t v = s_bv[j];
       s_bk[j] = MFX_EMPTY;
       s_bv[j] = 0u;
-      mfx_reads_add(a, key, v, n_counted, n_dropped, n_side);
+      mfx_reads_add<CLAIM>(a, key, v, n_counted, n_dropped, n_side, fresh);
     }
   }
+  if (CLAIM) mfx_meta_flush(a.meta, fresh, 0u);
   n_kmers = mfx_wave_sum(n_kmers); n_counted = mfx_wave_sum(n_counted);
   n_dropped = mfx_wave_sum(n_dropped); n_side = mfx_wave_sum(n_side);
   if (lane == 0) {
@@ -4141,6 +4204,18 @@ hipError_t mfx_k_spectrum(const mfx_spectrum_args &a, int grid, hipStream_t st) 
 hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st) {
   const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
   if (ntiles == 0) return hipSuccess;
-  mfx_reads_kernel<<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
+  mfx_reads_kernel<false><<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_reads_claim(const mfx_reads_args &a, hipStream_t st) {
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (ntiles == 0) return hipSuccess;
+  mfx_reads_kernel<true><<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_table_rehash(const mfx_slot *old_slots, uint64_t old_nslots, mfx_table_view nt, uint64_t *meta, hipStream_t st) {
+  if (old_nslots == 0) return hipSuccess;
+  const uint64_t blocks = (old_nslots + MFX_BLOCK - 1) / MFX_BLOCK;
+  mfx_table_rehash_kernel<<<(unsigned)(blocks < 4096 ? blocks : 4096), MFX_BLOCK, 0, st>>>(old_slots, old_nslots, nt, meta);
   return hipGetLastError();
 }

@@ -5,8 +5,16 @@
 // a record longer than the room left is cut, and its rest starts the next batch k-1 bases before the cut, so every k-mer
 // is in exactly one batch.  A full batch is packed into 2-bit codes + validity bits (mfx_pack_bases) in one of two pinned
 // stages, copied and counted on that stage's stream: the caller parses the next records while the device counts.
+//
+// The CLAIMING counter (mfx_reads_begin_all; a full table of 16-byte slots) claims every k-mer it meets, in a table that GROWS: nobody
+// knows the reads' distinct k-mers beforehand.  No launch may overfill the table, so before a batch is enqueued the bound of mfx_grow.h
+// is checked against the table's distinct count as last read and the positions enqueued since; when it fails the stages are settled and
+// the count is read again, and when it still fails every entry moves into a larger table (mfx_table_rehash_kernel).
 #include "mfx_internal.h"
 #include "mfx_kernels.h"
+#include "mfx_grow.h"
+
+#include <chrono>
 
 #include <string.h>
 
@@ -48,6 +56,12 @@ struct mfx_reads {
   uint64_t *d_stats = nullptr;       // [4] kmers, counted, dropped, saturated
   mfx_reads_stats stats{};
   bool failed = false;
+  int  fail_code = MFX_OK;           // claiming counter: why it failed (MFX_E_NOMEM: the table could not grow)
+  std::string fail_text;
+  // claiming counter (mfx_reads_begin_all)
+  bool claim = false;
+  uint64_t distinct_known = 0;       // the table's meta[0] as last read
+  uint64_t pending = 0;              // positions enqueued since that read: each may claim a k-mer
 };
 
 static void reads_free(mfx_reads *r) {
@@ -81,12 +95,113 @@ static int stage_settle(mfx_reads *r, mfx_reads::Stage &s) {
   return MFX_OK;
 }
 
+// every entry of the table into one of new_lines lines; the index then holds the new table
+static int table_grow(mfx_index *ix, uint64_t new_lines, uint64_t distinct) {
+  const uint64_t old_bytes = ix->nlines * MFX_ALIGN;
+  mfx_slot *ns = nullptr;
+  uint64_t *nmeta = nullptr;
+  MFX_HIP(hipMalloc((void **)&nmeta, MFX_META_WORDS * sizeof(uint64_t)));
+  while (true) {
+    const uint64_t new_bytes = new_lines * MFX_ALIGN;
+    size_t free_b = 0, total_b = 0;
+    const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    if (!known) (void)hipGetLastError();
+    // the old and the new table are alive together until every entry has moved
+    if ((ix->max_gb > 0 && (double)old_bytes + (double)new_bytes > ix->max_gb * 1e9) || (known && new_bytes > free_b) ||
+        hipMalloc((void **)&ns, new_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(nmeta);
+      return mfx_fail(MFX_E_NOMEM, "the k-mer table cannot grow from %.6f GB to %.6f GB (%lu k-mers stored): both tables are held while the entries move, "
+                      "under a limit of %.6f GB (-memory; 0: none) with %.6f GB of device memory free", (double)old_bytes / 1e9, (double)new_bytes / 1e9,
+                      (unsigned long)distinct, ix->max_gb, known ? (double)free_b / 1e9 : 0.0);
+    }
+    mfx_table_view nt = ix->view();
+    nt.slots = ns;
+    nt.nlines = new_lines;
+    nt.qshift = 0;
+    for (uint64_t x = new_lines; x > 1; x >>= 1) ++nt.qshift;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint64_t meta[MFX_META_WORDS] = {0};
+    float ms = 0;
+    const bool ok = mfx_memset_now(nmeta, 0, MFX_META_WORDS * sizeof(uint64_t)) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
+                    hipEventCreate(&e1) == hipSuccess && mfx_k_table_init(ns, new_lines * MFX_SLOTS_LINE, nullptr) == hipSuccess &&
+                    hipEventRecord(e0, nullptr) == hipSuccess &&
+                    mfx_k_table_rehash(ix->d_slots, ix->nlines * MFX_SLOTS_LINE, nt, nmeta, nullptr) == hipSuccess &&
+                    hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+                    hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+                    hipMemcpy(meta, nmeta, sizeof(meta), hipMemcpyDeviceToHost) == hipSuccess;
+    const hipError_t err = ok ? hipSuccess : hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (!ok) {
+      (void)hipFree(ns);
+      (void)hipFree(nmeta);
+      return mfx_fail(MFX_E_HIP, "moving the k-mer table into a larger one failed: %s", hipGetErrorString(err));
+    }
+    ix->rehash_seconds += ms * 1e-3;
+    ix->rehash_bytes += old_bytes + meta[0] * 2 * MFX_ALIGN;          // the old lines read, a line read and written per entry claimed
+    if (meta[2] == 0 && meta[0] == distinct) break;
+    (void)hipFree(ns);
+    ns = nullptr;
+    if (meta[2] == 0) {                                                // (never seen: the keys of a table are distinct)
+      (void)hipFree(nmeta);
+      return mfx_fail(MFX_E_HIP, "moving the k-mer table into a larger one lost entries: %lu of %lu arrived", (unsigned long)meta[0], (unsigned long)distinct);
+    }
+    // entries hit the probe limit in the larger table (one minimizer's k-mers beyond its lines): a table twice as large again
+    if (new_lines > ((1ull << 32) - 16) / 2) { (void)hipFree(nmeta); return mfx_fail(MFX_E_NOMEM, "the k-mer table cannot grow beyond 2^32 lines (%.6f GB now, %.6f GB tried)", (double)old_bytes / 1e9, (double)new_bytes / 1e9); }
+    new_lines *= 2;
+  }
+  (void)hipFree(nmeta);
+  (void)hipFree(ix->d_slots);
+  ix->d_slots = ns;
+  ix->nlines = new_lines;
+  ix->capacity_kmers = (uint64_t)((double)new_lines * MFX_SLOTS_LINE * 0.7);
+  ix->version++;
+  return MFX_OK;
+}
+
+// claiming counter: room for a batch of B positions, whatever they hold (mfx_grow.h)
+static int claim_reserve(mfx_reads *r, uint64_t B) {
+  mfx_index *ix = r->ix;
+#ifdef MFX_V_GROW_NO_PENDING                                  // A/B build only: the bound without the positions in flight (tests/test_gpu_count.py must FAIL on it)
+  const uint64_t pending = 0;
+#else
+  const uint64_t pending = r->pending;
+#endif
+  if (mfx_grow_fits(r->distinct_known, pending, B, ix->nlines * MFX_SLOTS_LINE)) return MFX_OK;
+  for (auto &s : r->S) if (int rc = stage_settle(r, s)) return rc;
+  uint64_t meta[3] = {0, 0, 0};
+  MFX_HIP(hipMemcpy(meta, ix->d_meta, sizeof(meta), hipMemcpyDeviceToHost));
+  r->distinct_known = meta[0];
+  r->pending = 0;
+  if (mfx_grow_fits(r->distinct_known, 0, B, ix->nlines * MFX_SLOTS_LINE)) return MFX_OK;
+  const uint64_t nl = mfx_grow_lines(r->distinct_known, B, ix->nlines, MFX_SLOTS_LINE, (1ull << 32) - 16);
+  if (nl == 0)
+    return mfx_fail(MFX_E_NOMEM, "the k-mer table cannot grow from %.6f GB to one that holds %lu k-mers and a batch of %lu positions: beyond 2^32 lines "
+                    "(%.6f GB)", (double)ix->nlines * MFX_ALIGN / 1e9, (unsigned long)r->distinct_known, (unsigned long)B, (double)(1ull << 32) * MFX_ALIGN / 1e9);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = table_grow(ix, nl, r->distinct_known);
+  if (rc == MFX_OK) {
+    ix->grow_count += 1;
+    ix->grow_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return rc;
+}
+
 // the batch in r->bytes goes to the device on the next stage
 static int reads_flush(mfx_reads *r) {
   if (r->used == 0) return MFX_OK;
   mfx_reads::Stage &s = r->S[r->cur];
   if (int rc = stage_settle(r, s)) return rc;
   const uint64_t npos = r->used;
+  if (r->claim) {
+    if (int rc = claim_reserve(r, npos)) {
+      r->fail_code = rc;
+      r->fail_text = mfx_last_error();
+      return rc;
+    }
+    r->pending += npos;
+  }
   const uint64_t ntiles = (npos + MFX_TILE - 1) / MFX_TILE;
   const uint64_t nw = std::min(r->words, ntiles * (MFX_TILE / 32) + MFX_TILE_WORDS_HOST);
   const uint64_t packed = (npos + 31) / 32;
@@ -106,7 +221,7 @@ static int reads_flush(mfx_reads *r) {
   MFX_HIP(hipMemcpyAsync(s.dc, s.hc, nw * sizeof(uint64_t), hipMemcpyHostToDevice, s.st));
   MFX_HIP(hipMemcpyAsync(s.dv, s.hv, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
   MFX_HIP(hipEventRecord(s.e1, s.st));
-  MFX_HIP(r->ix->wide() ? mfx_kw_reads(a, s.st) : mfx_k_reads(a, s.st));
+  MFX_HIP(r->claim ? mfx_k_reads_claim(a, s.st) : r->ix->wide() ? mfx_kw_reads(a, s.st) : mfx_k_reads(a, s.st));
   MFX_HIP(hipEventRecord(s.e2, s.st));
   s.busy = true;
   r->cur = (r->cur + 1) % MFX_READS_STAGES;
@@ -114,31 +229,27 @@ static int reads_flush(mfx_reads *r) {
   return MFX_OK;
 }
 
-extern "C" mfx_reads *mfx_reads_begin(mfx_index *ix, uint64_t batch_bases) {
-  if (!ix) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin: null index"); return nullptr; }
-  if (!ix->seq_only && !ix->wide()) {
-    mfx_fail(MFX_E_INVAL, "mfx_reads_begin: the index is neither sequence-only nor path-only -- reads are counted only into k-mers claimed "
-             "before (mfx_index_create_for_seq + mfx_index_count_asm / mfx_index_claim_seq, or mfx_index_claim_paths)");
-    return nullptr;
-  }
-  if (ix->shard_n > 1) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin: a sharded index does not take read counts from reads"); return nullptr; }
+// what both counters ask of the index's read side and of the batch, then the stages; `who`: the entry point, for the texts
+static mfx_reads *reads_open(mfx_index *ix, uint64_t batch_bases, const char *who, bool claim) {
+  if (ix->shard_n > 1) { mfx_fail(MFX_E_INVAL, "%s: a sharded index does not take read counts from reads", who); return nullptr; }
   if (ix->filter_set || ix->reads_counted) {
-    mfx_fail(MFX_E_INVAL, "mfx_reads_begin: the read side of this index already took counts (a database load or an earlier read counter); "
-             "an index takes its read counts from one source");
+    mfx_fail(MFX_E_INVAL, "%s: the read side of this index already took counts (a database load or an earlier read counter); "
+             "an index takes its read counts from one source", who);
     return nullptr;
   }
   const uint64_t min_batch = 2ull * (uint64_t)ix->k + 2;
   if (batch_bases == 0) batch_bases = MFX_READS_BATCH_DEFAULT;
   if (batch_bases < min_batch) {
-    mfx_fail(MFX_E_INVAL, "mfx_reads_begin: a batch of %llu bases is too small for %d-mers (at least %llu)", (unsigned long long)batch_bases,
+    mfx_fail(MFX_E_INVAL, "%s: a batch of %llu bases is too small for %d-mers (at least %llu)", who, (unsigned long long)batch_bases,
              ix->k, (unsigned long long)min_batch);
     return nullptr;
   }
-  if (batch_bases > (1ull << 34)) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin: batch of %llu bases is beyond 2^34", (unsigned long long)batch_bases); return nullptr; }
+  if (batch_bases > (1ull << 34)) { mfx_fail(MFX_E_INVAL, "%s: batch of %llu bases is beyond 2^34", who, (unsigned long long)batch_bases); return nullptr; }
   DeviceScope g(ix->device);
   if (!g.ok) { mfx_fail(MFX_E_HIP, "hipSetDevice(%d) failed", ix->device); return nullptr; }
   mfx_reads *r = new mfx_reads;
   r->ix = ix;
+  r->claim = claim;
   r->cap = batch_bases;
   r->words = (batch_bases + MFX_TILE - 1) / MFX_TILE * (MFX_TILE / 32) + MFX_TILE_WORDS_HOST;
   r->bytes.resize(batch_bases + 32);
@@ -152,18 +263,60 @@ extern "C" mfx_reads *mfx_reads_begin(mfx_index *ix, uint64_t batch_bases) {
          hipEventCreate(&s.e0) == hipSuccess && hipEventCreate(&s.e1) == hipSuccess && hipEventCreate(&s.e2) == hipSuccess;
   }
   if (!ok) {
-    mfx_fail(MFX_E_NOMEM, "mfx_reads_begin: staging of %llu bases per batch could not be allocated: %s", (unsigned long long)batch_bases,
+    mfx_fail(MFX_E_NOMEM, "%s: staging of %llu bases per batch could not be allocated: %s", who, (unsigned long long)batch_bases,
              hipGetErrorString(hipGetLastError()));
     reads_free(r);
     return nullptr;
   }
-  // from here on the read side belongs to this counter: no claim (the frozen rule), no second source of read counts
-  ix->frozen = true;
+  if (claim) {                                                 // what the assembly side claimed before
+    uint64_t d = 0;
+    if (hipMemcpy(&d, ix->d_meta, sizeof(d), hipMemcpyDeviceToHost) != hipSuccess) {
+      mfx_fail(MFX_E_HIP, "%s: reading the table's state failed: %s", who, hipGetErrorString(hipGetLastError()));
+      reads_free(r);
+      return nullptr;
+    }
+    r->distinct_known = d;
+  }
+  // from here on the read side belongs to this counter: no second source of read counts, and -- the update-only counter -- no claim (the frozen rule)
+  if (!claim) ix->frozen = true;
   ix->reads_counted = true;
   ix->filter_set = true;
   ix->minV = 0;
   ix->maxV = ~0ull;
   return r;
+}
+
+extern "C" mfx_reads *mfx_reads_begin(mfx_index *ix, uint64_t batch_bases) {
+  if (!ix) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin: null index"); return nullptr; }
+  if (!ix->seq_only && !ix->wide()) {
+    mfx_fail(MFX_E_INVAL, "mfx_reads_begin: the index is neither sequence-only nor path-only -- reads are counted only into k-mers claimed "
+             "before (mfx_index_create_for_seq + mfx_index_count_asm / mfx_index_claim_seq, or mfx_index_claim_paths)");
+    return nullptr;
+  }
+  return reads_open(ix, batch_bases, "mfx_reads_begin", false);
+}
+
+extern "C" mfx_reads *mfx_reads_begin_all(mfx_index *ix, uint64_t batch_bases) {
+  if (!ix) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: null index"); return nullptr; }
+  if (ix->seq_only) {
+    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: a sequence-only or path-only index holds the k-mers claimed for it and takes no others -- count every "
+             "k-mer of the reads into a full index (mfx_index_create), or only the claimed ones with mfx_reads_begin");
+    return nullptr;
+  }
+  if (ix->wide()) {
+    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: the table that grows holds k <= %d; this index holds %d-mers", MFX_MAX_K_NARROW, ix->k);
+    return nullptr;
+  }
+  return reads_open(ix, batch_bases, "mfx_reads_begin_all", true);
+}
+
+extern "C" int mfx_index_growths(const mfx_index *ix, uint64_t *n, double *seconds, double *rehash_seconds, uint64_t *rehash_bytes) {
+  if (!ix) return mfx_fail(MFX_E_INVAL, "mfx_index_growths: null index");
+  if (n) *n = ix->grow_count;
+  if (seconds) *seconds = ix->grow_seconds;
+  if (rehash_seconds) *rehash_seconds = ix->rehash_seconds;
+  if (rehash_bytes) *rehash_bytes = ix->rehash_bytes;
+  return MFX_OK;
 }
 
 extern "C" int mfx_reads_set_filter(mfx_reads *r, uint64_t minV, uint64_t maxV) {
@@ -222,6 +375,7 @@ extern "C" int mfx_reads_end(mfx_reads *r, mfx_reads_stats *out) {
     r->stats.dropped = st[2];
     r->stats.saturated = st[3];
     if (rc == MFX_OK) rc = mfx_index_check(r->ix);               // a side table that filled up: MFX_E_FULL, as a database load
+    if (rc == MFX_OK && r->failed && r->fail_code != MFX_OK) rc = mfx_fail(r->fail_code, "mfx_reads_end: %s", r->fail_text.c_str());
     if (rc == MFX_OK && r->failed) rc = mfx_fail(MFX_E_INVAL, "mfx_reads_end: a batch of this counter failed");
   }
   if (out) *out = r->stats;
