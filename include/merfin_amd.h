@@ -258,6 +258,27 @@ int mfx_index_export(const mfx_index *ix, uint64_t *kmers, uint32_t *readV, uint
  * the call.  n_kmers (may be NULL): the k-mers written. */
 int mfx_index_write_db(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers);
 
+/* The entries with a non-zero count on `side` per top min(2k, 12) bits of their k-mer: bins[b] for b < *nbins = 2^min(2k, 12), the rest of
+ * the 4096 words zero (nbins may be NULL).  The histogram mfx_index_write_db groups its key ranges by, behind the same refusals; what a
+ * count in several passes cuts its key ranges with. */
+int mfx_index_key_bins(const mfx_index *ix, int side, uint64_t *bins /* [4096] */, uint32_t *nbins);
+
+/* A database written from SEVERAL tables -- the passes of a count over ascending key ranges (mfx_reads_begin_range).  append_index is the
+ * device part of mfx_index_write_db (bins, key ranges, export, sort, copy) and adds the side's k-mers behind those the writer holds; the
+ * smallest of them must exceed the writer's last k-mer, otherwise MFX_E_INVAL: the append adds nothing and the writer stays usable.  An
+ * append of zero k-mers is fine.  n_added (may be NULL): the k-mers this append added.  close writes the file mfx_db_write_flat makes of
+ * everything appended -- nothing exists at `path` before -- and frees w whatever the result; abort frees w and writes nothing.
+ * mfx_index_write_db is open + append + close.  Host memory: 12 bytes per k-mer held until close (the file's directory precedes its blocks,
+ * so a writer that streams to disk is a change of the format) -- at rest.  The k-mers are kept in two contiguous arrays, allocated to the
+ * exact size; an append that adds n to h held allocates arrays of h + n and moves the h into them, so WHILE IT RUNS the old and the new
+ * arrays are alive together: a transient peak of 12 x (2 h + n) bytes, i.e. up to 24 bytes per k-mer at the last of many appends.  Size
+ * the host for that (a read store beside it takes its share too).  A single append -- mfx_index_write_db -- allocates once. */
+typedef struct mfx_db_writer mfx_db_writer;
+mfx_db_writer *mfx_db_writer_open(const char *path, int k);
+int  mfx_db_writer_append_index(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added);
+int  mfx_db_writer_close(mfx_db_writer *w, uint64_t *n_kmers);
+void mfx_db_writer_abort(mfx_db_writer *w);
+
 /* ------------------------------------------------------------------------ */
 /* Read k-mer counting: the read counts of a run straight from its reads     */
 /* (FASTA / FASTQ records), no k-mer database in between.                   */
@@ -303,10 +324,38 @@ int        mfx_reads_end(mfx_reads *r, mfx_reads_stats *out);
  * twice) with  distinct + B <= 0.35 x slots, and the old table is freed.  mfx_index_get_info shows the new capacity and bytes.  Both tables
  * are alive while the entries move: that sum honours the index's max_gb, the new table the free device memory.  A table that cannot grow
  * fails the mfx_reads_add (or _end) that needed it with MFX_E_NOMEM, naming both sizes; the counter is then failed, mfx_reads_end reports
- * MFX_E_NOMEM too, and the index can only be freed.  A claiming counter does not end in MFX_E_FULL.
+ * MFX_E_NOMEM too.  Nothing was launched for the batch that needed the larger table, and the batches before it are complete: the table is
+ * intact and holds their counts.  The index may still be READ -- mfx_index_get_info, mfx_index_key_bins, mfx_index_export -- and freed; it
+ * takes no other counter.  A claiming counter does not end in MFX_E_FULL.
  * As for every call that changes an index: NO evaluator, replica or image of the index may exist while a claiming counter is open -- they
  * hold the table's address and geometry, and a growth replaces both. */
 mfx_reads *mfx_reads_begin_all(mfx_index *ix, uint64_t batch_bases);
+/* The RANGED claiming counter: as mfx_reads_begin_all, for the canonical k-mers with key_lo <= kmer < key_hi only (a k-mer as the number its
+ * 2k bits are, A C G T = 0 1 2 3).  One pass of a count whose table does not fit the device: ascending ranges give ascending tables, which
+ * mfx_db_writer_append_index joins into the database of one pass, byte for byte.  The conditions and refusals of mfx_reads_begin_all, and
+ * MFX_E_INVAL for key_lo > key_hi and for key_hi > 4^k; key_lo == key_hi counts nothing; [0, 4^k) is mfx_reads_begin_all.
+ * Statistics: `kmers` is every valid k-mer of the reads, `counted` the occurrences in the range, `dropped` 0 -- the k-mers left to other
+ * passes are kmers - counted.  The growth bound counts every position of a batch as a possible claim, in range or not: pessimistic for a
+ * narrow range, by one batch. */
+mfx_reads *mfx_reads_begin_range(mfx_index *ix, uint64_t batch_bases, uint64_t key_lo, uint64_t key_hi);
+
+/* The read store: the batches of a read set as the counters send them to the device (2-bit codes and validity bits, 3 bits per base), kept
+ * on the host, so that the second and later passes of a count parse and decompress nothing.  It needs no device.
+ *   create: k and batch_bases as for a counter (0: 64 Mi); max_bytes: the planes the store may hold (0: no limit).
+ *   add: records as for mfx_reads_add (the same batching code).  MFX_OK, or 1: full -- the store is incomplete from now on and every
+ *        later add returns 1; or an error (< 0).
+ *   info: batches held (the one being filled included), their bytes, the records and bases passed in, complete or not (any may be NULL).
+ *   mfx_reads_replay: the store's batches [first_batch, first_batch + n_batches) go through counter r -- update-only, claiming or ranged --
+ *        as its own batches do (its stages, its growth bound); the records and bases those batches brought are added to r's statistics,
+ *        so replaying every batch once gives the statistics of mfx_reads_add of the same records.  Refused with MFX_E_INVAL: an incomplete
+ *        store, a store of another k, a counter whose batch is smaller than the store's.  Records r holds from mfx_reads_add go first.
+ * A store is not changed by a replay; do not add to it from another thread meanwhile. */
+typedef struct mfx_reads_store mfx_reads_store;
+mfx_reads_store *mfx_reads_store_create(int k, uint64_t batch_bases, uint64_t max_bytes);
+int  mfx_reads_store_add(mfx_reads_store *s, const char *const *bases, const uint64_t *lens, uint64_t n);
+int  mfx_reads_store_info(const mfx_reads_store *s, uint64_t *batches, uint64_t *bytes, uint64_t *reads, uint64_t *n_bases, int *complete);
+int  mfx_reads_replay(mfx_reads *r, const mfx_reads_store *s, uint64_t first_batch, uint64_t n_batches);
+void mfx_reads_store_free(mfx_reads_store *s);
 /* what claiming counters did to the index's table so far: growths, their wall time, of that the kernels that moved the entries, and the
  * bytes those read and wrote (any pointer may be NULL) */
 int        mfx_index_growths(const mfx_index *ix, uint64_t *n, double *seconds, double *rehash_seconds, uint64_t *rehash_bytes);

@@ -92,6 +92,8 @@ SYMBOLS = [
     "mfx_index_set_shard", "mfx_router_create", "mfx_router_free", "mfx_route_tiles", "mfx_hist_keys_launch",
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
     "mfx_reads_begin_all", "mfx_index_growths", "mfx_index_write_db",
+    "mfx_reads_begin_range", "mfx_index_key_bins", "mfx_db_writer_open", "mfx_db_writer_append_index", "mfx_db_writer_close", "mfx_db_writer_abort",
+    "mfx_reads_store_create", "mfx_reads_store_add", "mfx_reads_store_info", "mfx_reads_replay", "mfx_reads_store_free",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
@@ -307,6 +309,22 @@ def load_library():
     L.mfx_reads_begin_all.argtypes = [vp, C.c_uint64]
     L.mfx_index_growths.argtypes = [vp, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double), u64p]
     L.mfx_index_write_db.argtypes = [vp, C.c_int, C.c_char_p, u64p]
+    L.mfx_reads_begin_range.restype = vp
+    L.mfx_reads_begin_range.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mfx_index_key_bins.argtypes = [vp, C.c_int, u64p, C.POINTER(C.c_uint32)]
+    L.mfx_db_writer_open.restype = vp
+    L.mfx_db_writer_open.argtypes = [C.c_char_p, C.c_int]
+    L.mfx_db_writer_append_index.argtypes = [vp, vp, C.c_int, u64p]
+    L.mfx_db_writer_close.argtypes = [vp, u64p]
+    L.mfx_db_writer_abort.restype = None
+    L.mfx_db_writer_abort.argtypes = [vp]
+    L.mfx_reads_store_create.restype = vp
+    L.mfx_reads_store_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
+    L.mfx_reads_store_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
+    L.mfx_reads_store_info.argtypes = [vp, u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]
+    L.mfx_reads_replay.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.mfx_reads_store_free.restype = None
+    L.mfx_reads_store_free.argtypes = [vp]
     L.mfx_track_num_windows.restype = C.c_uint64
     L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
     L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
@@ -637,6 +655,20 @@ class Index:
         may exist meanwhile.  Returns the counter's statistics as a dict (dropped == 0)."""
         return self._count_reads(load_library().mfx_reads_begin_all, reads, batch_bases, minV, maxV, chunk)
 
+    def count_reads_range(self, reads, key_lo, key_hi, batch_bases=0, chunk=4096):
+        """one pass of a count in several (mfx_reads_begin_range): as count_reads_all, for the canonical k-mers with key_lo <= k-mer < key_hi
+        only.  In the statistics `kmers` is every valid k-mer of the reads and `counted` the occurrences in the range."""
+        L = load_library()
+        return self._count_reads(lambda h, bb: L.mfx_reads_begin_range(h, bb, int(key_lo), int(key_hi)), reads, batch_bases, 0, 2**64 - 1, chunk)
+
+    def key_bins(self, side=0):
+        """the entries with a non-zero count on `side` per top min(2k, 12) bits of their k-mer (mfx_index_key_bins): a uint64 array of
+        2^min(2k, 12) bins"""
+        bins = np.zeros(4096, dtype=np.uint64)
+        n = C.c_uint32(0)
+        _check(load_library().mfx_index_key_bins(self.h, int(side), bins.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        return bins[:n.value].copy()
+
     def growths(self):
         """what claiming counters did to the table (mfx_index_growths)"""
         n, b = C.c_uint64(0), C.c_uint64(0)
@@ -735,6 +767,93 @@ class Index:
     def close(self):
         if getattr(self, "h", None):
             load_library().mfx_index_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class DbWriter:
+    """a k-mer database written from several tables in ascending key order (mfx_db_writer_*): append(index) per table, then close() writes
+    the file db_write_flat makes of everything appended; nothing exists at `path` before.  abort() (or dropping the object) writes nothing."""
+
+    def __init__(self, path, k):
+        self.h = _need(load_library().mfx_db_writer_open(str(path).encode(), int(k)))
+
+    def append(self, index, side=0):
+        """the k-mers of `index` with a non-zero count on `side` behind those held; they must start above the last one held (else MfxError,
+        nothing added).  Returns their number."""
+        n = C.c_uint64(0)
+        _check(load_library().mfx_db_writer_append_index(self.h, index.h, int(side), C.byref(n)))
+        return n.value
+
+    def close(self):
+        n = C.c_uint64(0)
+        h, self.h = self.h, None
+        _check(load_library().mfx_db_writer_close(h, C.byref(n)))
+        return n.value
+
+    def abort(self):
+        if getattr(self, "h", None):
+            load_library().mfx_db_writer_abort(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.abort()
+
+
+class ReadsStore:
+    """the packed batches of a read set on the host (mfx_reads_store_*), 3 bits per base: parse once, count in several passes.  No device."""
+
+    def __init__(self, k, batch_bases=0, max_bytes=0):
+        self.k = int(k)
+        self.h = _need(load_library().mfx_reads_store_create(self.k, int(batch_bases), int(max_bytes)))
+
+    def add(self, reads, chunk=4096):
+        """records (bytes or str) into the store; False: the store is full and incomplete from now on"""
+        L = load_library()
+        recs = [x.encode() if isinstance(x, str) else bytes(x) for x in reads]
+        for o in range(0, len(recs), chunk):
+            part = recs[o:o + chunk]
+            ptrs = (C.c_char_p * len(part))(*part)
+            lens = (C.c_uint64 * len(part))(*[len(x) for x in part])
+            rc = L.mfx_reads_store_add(self.h, ptrs, lens, len(part))
+            if rc == 1:
+                return False
+            _check(rc)
+        return True
+
+    def info(self):
+        b, y, r, n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        c = C.c_int(0)
+        _check(load_library().mfx_reads_store_info(self.h, C.byref(b), C.byref(y), C.byref(r), C.byref(n), C.byref(c)))
+        return {"batches": b.value, "bytes": y.value, "reads": r.value, "bases": n.value, "complete": bool(c.value)}
+
+    def replay(self, index, key_range=None, update_only=False, batch_bases=0, first_batch=0, n_batches=None):
+        """the store's batches through a counter of `index` (mfx_reads_replay): the claiming counter, the ranged one over key_range =
+        (key_lo, key_hi), or with update_only the counter of count_reads.  Returns the counter's statistics."""
+        L = load_library()
+        if update_only:
+            r = L.mfx_reads_begin(index.h, int(batch_bases))
+        elif key_range is None:
+            r = L.mfx_reads_begin_all(index.h, int(batch_bases))
+        else:
+            r = L.mfx_reads_begin_range(index.h, int(batch_bases), int(key_range[0]), int(key_range[1]))
+        r = _need(r)
+        if n_batches is None:
+            n_batches = self.info()["batches"] - first_batch
+        rc = L.mfx_reads_replay(r, self.h, int(first_batch), int(n_batches))
+        msg = L.mfx_last_error().decode() if rc else ""
+        st = _ReadsStats()
+        rc_end = L.mfx_reads_end(r, C.byref(st))
+        if rc:
+            raise MfxError(rc, msg)
+        _check(rc_end)
+        return {f: getattr(st, f) for f, _ in _ReadsStats._fields_}
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().mfx_reads_store_free(self.h)
             self.h = None
 
     def __del__(self):

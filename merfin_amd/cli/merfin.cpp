@@ -30,6 +30,7 @@
 
 #include "../../include/merfin_amd.h"
 #include "fasta.h"
+#include "../csrc/mfx_grow.h"     // mfx_cut_bins: the key ranges of -count -passes
 
 enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM };
 
@@ -54,6 +55,8 @@ struct Globals {
   bool copiesGiven = false, maxMultGiven = false;
   bool count = false;                    // -count: no report; the k-mers of -reads counted on the GPU and written as a database
   bool peakGiven = false, devicesGiven = false;
+  bool passesGiven = false, passesAuto = false;   // -count -passes P|auto: the k-mers counted in passes over key ranges
+  uint32_t passes = 1;
 };
 
 static void usage(const char *exe) {
@@ -79,6 +82,9 @@ static void usage(const char *exe) {
           "    -count            no report: count every k-mer of the -reads files on the GPU (`meryl count`; -k K, K <= 31) and write\n"
           "                      the sorted flat database -output <file>, which every mode takes as -readmers.  -min / -max are not\n"
           "                      applied: a database holds every count, the filter acts when it is loaded.  One device.\n"
+          "    -passes P|auto    with -count: the k-mers are counted in P passes (1 to 4096) over ascending key ranges, each in a table\n"
+          "                      of its own, for read sets whose table does not fit the device (-memory); auto: one pass, and a range\n"
+          "                      whose table cannot grow is cut in two.  The reads are parsed once and kept packed in host memory.\n"
           "    -placed           with -convert: the records sorted by their PLACE in the table -hist / -dump build (13 <= k <= 31,\n"
           "                      canonical databases): such a database is applied to the table line after line\n"
           "    -device d         HIP device (default 0)\n"
@@ -603,18 +609,13 @@ static bool concat_parts(const std::string &out, const std::vector<std::string> 
   return fclose(o) == 0 && ok;
 }
 
-// -reads: the read counts of the run from its reads, counted on the device into the k-mers the index holds (mfx_reads_*).  One reader
-// thread per file (16 at most at a time) parses records into batches; this thread hands the batches to the counter, which copies them
-// and returns while the device counts, so parsing, transfer and counting overlap.  Returns false with the error printed.
-// all (-count): the claiming counter -- every k-mer of the reads, no filter; *all_stats gets its statistics and the caller reports.
-static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false, mfx_reads_stats *all_stats = nullptr) {
-  const auto t0 = std::chrono::steady_clock::now();
-  mfx_reads *rc = all ? mfx_reads_begin_all(ix, 0) : mfx_reads_begin(ix, 0);
-  if (!rc || mfx_reads_set_filter(rc, all ? 0 : G.minV, all ? ~0ull : G.maxV)) {
-    fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error());
-    if (rc) mfx_reads_end(rc, nullptr);
-    return false;
-  }
+// The records of the -reads files to `sink`, batch after batch: one reader thread per file (16 at most at a time) parses records into
+// batches of about 16 M bases; this thread hands them to sink(bases, lens, n), which returns 0 to go on.  Anything else stops the readers
+// and ends the call with that value (the sink keeps its own error text).  FEED_FILE_FAILED, no value of a sink or of the library: a file failed,
+// and `file_why`, which only the readers write, under the lock, says how.  t_wait: seconds this thread waited for parsed records.
+constexpr int FEED_FILE_FAILED = 1 << 20;
+template <class Sink>
+static int feed_reads_files(const Globals &G, Sink &&sink, std::string &file_why, double *t_wait_out = nullptr) {
   constexpr uint64_t BATCH_BASES = 16ull << 20;
   std::mutex mu;
   std::condition_variable cv_full, cv_room;
@@ -623,7 +624,7 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
   size_t running = nthreads;
   std::atomic<size_t> next_file{0};
   std::atomic<bool> failed{false};
-  std::string why;
+  int result = 0;
   auto push = [&](std::vector<SeqRecord> &b) {
     std::unique_lock<std::mutex> lk(mu);
     cv_room.wait(lk, [&] { return queue.size() < max_queued || failed.load(); });
@@ -638,8 +639,9 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
         SeqFile sf(G.readsNames[f]);
         if (!sf.ok()) {
           std::lock_guard<std::mutex> lk(mu);
-          why = std::string("cannot open '") + G.readsNames[f] + "'";
+          file_why = std::string("cannot open '") + G.readsNames[f] + "'";
           failed = true;
+          result = FEED_FILE_FAILED;
           break;
         }
         std::vector<SeqRecord> batch;
@@ -653,15 +655,18 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
         if (!batch.empty()) push(batch);
         if (sf.finish() != 0) {
           std::lock_guard<std::mutex> lk(mu);
-          why = std::string("reading '") + G.readsNames[f] + "' failed (read error, or the decompressor exited with an error)";
-          failed = true;
+          if (!failed.load()) {                                          // (a reader stopped on purpose ends its decompressor early: no finding)
+            file_why = std::string("reading '") + G.readsNames[f] + "' failed (read error, or the decompressor exited with an error)";
+            failed = true;
+            result = FEED_FILE_FAILED;
+          }
         }
       }
       std::lock_guard<std::mutex> lk(mu);
       --running;
       cv_full.notify_all();
     });
-  double t_wait = 0, t_submit = 0;
+  double t_wait = 0;
   std::vector<const char *> ptrs;
   std::vector<uint64_t> lens;
   while (true) {
@@ -680,21 +685,56 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
     ptrs.resize(b.size());
     lens.resize(b.size());
     for (size_t i = 0; i < b.size(); ++i) { ptrs[i] = b[i].data(); lens[i] = b[i].size(); }
-    const auto ts = std::chrono::steady_clock::now();
-    const int arc = mfx_reads_add(rc, ptrs.data(), lens.data(), b.size());
-    t_submit += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
-    if (arc) {
+    const int src = sink(ptrs.data(), lens.data(), (uint64_t)b.size());
+    if (src) {
       std::lock_guard<std::mutex> lk(mu);
-      why = mfx_last_error();
+      if (!failed.load()) result = src;
       failed = true;
       cv_room.notify_all();
     }
   }
   for (auto &t : readers) t.join();
+  if (t_wait_out) *t_wait_out = t_wait;
+  return result;
+}
+
+// -reads: the read counts of the run from its reads, counted on the device into the k-mers the index holds (mfx_reads_*).  The reader
+// threads parse (feed_reads_files); this thread hands the batches to the counter, which copies them and returns while the device counts,
+// so parsing, transfer and counting overlap.  Returns false with the error printed.
+// all (-count): the claiming counter -- every k-mer of the reads, no filter; *all_stats gets its statistics and the caller reports.
+// range (-count -passes): the claiming counter over the k-mers of [range[0], range[1]); batch: its bases per device batch (0: the library's).
+// fail_code: where to put the code of a failing counter INSTEAD of printing the error (the text stays in `fail_text`).
+static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false, mfx_reads_stats *all_stats = nullptr, uint64_t batch = 0,
+                              const uint64_t *range = nullptr, int *fail_code = nullptr, std::string *fail_text = nullptr) {
+  const auto t0 = std::chrono::steady_clock::now();
+  mfx_reads *rc = range ? mfx_reads_begin_range(ix, batch, range[0], range[1]) : all ? mfx_reads_begin_all(ix, batch) : mfx_reads_begin(ix, 0);
+  if (!rc || mfx_reads_set_filter(rc, all ? 0 : G.minV, all ? ~0ull : G.maxV)) {
+    fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error());
+    if (rc) mfx_reads_end(rc, nullptr);
+    return false;
+  }
+  double t_wait = 0, t_submit = 0;
+  std::string file_why, add_why;                                 // (the readers write the first, this thread the second)
+  const int frc = feed_reads_files(G, [&](const char *const *bases, const uint64_t *lens, uint64_t n) {
+    const auto ts = std::chrono::steady_clock::now();
+    const int arc = mfx_reads_add(rc, bases, lens, n);
+    t_submit += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    if (arc) add_why = mfx_last_error();
+    return arc;
+  }, file_why, &t_wait);
   mfx_reads_stats st;
   const int erc = mfx_reads_end(rc, &st);
-  if (failed.load() || erc) {
-    fprintf(stderr, "ERROR: counting -reads: %s\n", failed.load() ? why.c_str() : mfx_last_error());
+  if (frc || erc) {
+    const bool file_failed = frc == FEED_FILE_FAILED;
+    const int code = file_failed ? MFX_E_IO : frc ? frc : erc;   // (frc otherwise: the code of the mfx_reads_add that failed)
+    const std::string text = file_failed ? file_why : frc ? add_why : std::string(mfx_last_error());
+    if (fail_code && !file_failed) {
+      *fail_code = code;
+      if (fail_text) *fail_text = text;
+      return false;
+    }
+    fprintf(stderr, "ERROR: counting -reads: %s\n", text.c_str());
+    if (fail_code) *fail_code = MFX_OK;
     return false;
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -714,6 +754,273 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
     fprintf(stderr, "ERROR: %s: %s\n", what, mfx_last_error());             \
     return 1;                                                               \
   } while (0)
+
+// ---- -count -passes: the k-mers of the reads counted in passes over ascending key ranges ------------------------------------------------
+// A range is [bin_lo, bin_hi) of the 2^min(2k, 12) bins of the top key bits (mfx_index_key_bins).  Every pass counts its range into an index
+// of its own, created at 1024 lines under -memory (mfx_reads_begin_range), and appends the table to one writer (mfx_db_writer_*): ascending
+// ranges append into the file of one pass, byte for byte.  A range whose table cannot grow (MFX_E_NOMEM) is cut in two at the bins of the
+// table it reached (mfx_cut_bins) and both halves are queued.  The reads are parsed once into a read store (mfx_reads_store_*) beside
+// pass 1 and replayed from it afterwards; without a store (MFX_COUNT_STORE_GB=0, or one that filled up) every pass reads the files.
+namespace {
+struct CountPasses {
+  const Globals &G;
+  uint64_t batch = 0;                                            // MFX_COUNT_BATCH
+  uint32_t nbins = 0;
+  int shift = 0;
+  std::deque<std::pair<uint32_t, uint32_t>> todo;                // the ranges to count, ascending
+  mfx_db_writer *w = nullptr;
+  uint64_t n_pass = 0, n_refused = 0, distinct = 0, counted = 0, growths = 0;
+  double max_gb = 0;
+  mfx_reads_stats first{};                                       // the statistics of the first pass that ended: reads, bases, k-mers
+  bool have_first = false;
+  // the pass that runs
+  mfx_index *ix = nullptr;
+  mfx_reads *r = nullptr;
+  std::pair<uint32_t, uint32_t> cur{0, 0};
+  std::chrono::steady_clock::time_point t0;
+
+  explicit CountPasses(const Globals &g) : G(g) {}
+  ~CountPasses() {
+    if (r) mfx_reads_end(r, nullptr);
+    if (ix) mfx_index_free(ix);
+    if (w) mfx_db_writer_abort(w);
+  }
+  uint64_t key_of(uint32_t bin) const { return (uint64_t)bin << shift; }     // (bin == nbins: 4^k)
+
+  // the next range of the queue gets its index and its counter; false: the error is printed
+  bool begin() {
+    cur = todo.front();
+    todo.pop_front();
+    t0 = std::chrono::steady_clock::now();
+    ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
+    if (!ix) { fprintf(stderr, "ERROR: creating the k-mer table: %s\n", mfx_last_error()); return false; }
+    r = mfx_reads_begin_range(ix, batch, key_of(cur.first), key_of(cur.second));
+    if (!r) { fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error()); return false; }
+    return true;
+  }
+  // the pass's table could not grow: its range is cut in two at the bins of what it holds.  false: a range of one bin -- the library's text ends the run
+  bool refuse(const std::string &text) {
+    if (cur.second - cur.first < 2) {
+      fprintf(stderr, "ERROR: counting -reads: %s\n", text.c_str());
+      fprintf(stderr, "-- The key range that does not fit is one bin of %u (bin %u): no pass can be smaller.  Increase -memory.\n", nbins, cur.first);
+      return false;
+    }
+    std::vector<uint64_t> bins(4096);
+    std::vector<mfx_bin_range> halves;
+    if (mfx_index_key_bins(ix, 0, bins.data(), nullptr) == MFX_OK) mfx_cut_bins(bins.data(), cur.first, cur.second, 2, halves);
+    const uint32_t cut = halves.size() == 2 ? halves[0].bin_hi : cur.first + (cur.second - cur.first) / 2;   // (entries in one bin only so far: the middle)
+    fprintf(stderr, "-- Bins [%u, %u) of %u: refused, the table could not grow beyond %.6f GB; cut in two at bin %u.\n", cur.first, cur.second, nbins,
+            table_gb(), cut);
+    mfx_index_free(ix);
+    ix = nullptr;
+    todo.push_front({cut, cur.second});
+    todo.push_front({cur.first, cut});
+    ++n_refused;
+    return true;
+  }
+  double table_gb() const {
+    mfx_index_info info;
+    return ix && mfx_index_get_info(ix, &info) == MFX_OK ? (double)info.bytes / 1e9 : 0.0;
+  }
+  // the counter of the running pass ends.  1: done, its table appended; 0: refused and cut in two; -1: failed, the error is printed
+  int finish(const char *source) {
+    mfx_reads_stats st;
+    const int erc = mfx_reads_end(r, &st);
+    r = nullptr;
+    if (erc == MFX_E_NOMEM) return refuse(mfx_last_error()) ? 0 : -1;
+    if (erc) { fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error()); return -1; }
+    return append(st, source) ? 1 : -1;
+  }
+  bool append(const mfx_reads_stats &st, const char *source) {
+    mfx_index_info info;
+    uint64_t g = 0, added = 0;
+    if (mfx_index_get_info(ix, &info) || mfx_index_growths(ix, &g, nullptr, nullptr, nullptr)) { fprintf(stderr, "ERROR: -count: %s\n", mfx_last_error()); return false; }
+    if (mfx_db_writer_append_index(w, ix, 0, &added)) { fprintf(stderr, "ERROR: -count: collecting the k-mers of a pass: %s\n", mfx_last_error()); return false; }
+    mfx_index_free(ix);
+    ix = nullptr;
+    if (!have_first) { first = st; have_first = true; }
+    ++n_pass;
+    distinct += added;
+    counted += st.counted;
+    growths += g;
+    max_gb = std::max(max_gb, (double)info.bytes / 1e9);
+    fprintf(stderr, "-- Pass %lu: bins [%u, %u) of %u: %lu k-mers counted, %lu distinct, table %.3f GB, %.2f s, %s.\n", (unsigned long)n_pass, cur.first,
+            cur.second, nbins, (unsigned long)st.counted, (unsigned long)added, (double)info.bytes / 1e9,
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), source);
+    return true;
+  }
+};
+
+// half of MemAvailable, in bytes (0: unknown)
+static uint64_t half_of_available_memory() {
+  FILE *f = fopen("/proc/meminfo", "r");
+  if (!f) return 0;
+  char line[256];
+  unsigned long long kb = 0;
+  while (fgets(line, sizeof(line), f))
+    if (sscanf(line, "MemAvailable: %llu kB", &kb) == 1) break;
+  fclose(f);
+  return (uint64_t)kb * 1024 / 2;
+}
+}  // namespace
+
+static int count_in_passes(const Globals &G) {
+  CountPasses C(G);
+  if (const char *e = getenv("MFX_COUNT_BATCH")) C.batch = strtoull(e, nullptr, 10);
+  const int bits = std::min(2 * G.kArg, 12);
+  C.nbins = 1u << bits;
+  C.shift = 2 * G.kArg - bits;
+  uint64_t store_bytes = half_of_available_memory();
+  if (const char *e = getenv("MFX_COUNT_STORE_GB")) store_bytes = (uint64_t)(std::max(0.0, strtod(e, nullptr)) * 1e9);
+  const uint32_t P = G.passesAuto ? 1 : G.passes;
+  C.w = mfx_db_writer_open(G.outName, G.kArg);
+  if (!C.w) DIE_MFX("-count");
+  struct StoreGuard { mfx_reads_store *s; ~StoreGuard() { if (s) mfx_reads_store_free(s); } } SG{nullptr};
+  if (store_bytes) {
+    SG.s = mfx_reads_store_create(G.kArg, C.batch, store_bytes);
+    if (!SG.s) DIE_MFX("-count: the read store");
+  }
+  std::vector<uint64_t> bins(4096);
+  std::vector<mfx_bin_range> cuts;
+  // the P ranges from the k-mers of the pilot: `replay` sends them through a claiming counter of a throw-away index
+  auto ranges_from_pilot = [&](auto &&count_pilot) {
+    C.todo.clear();
+    mfx_index *pix = P > 1 ? mfx_index_create(G.kArg, 1024, G.maxMemory, G.device) : nullptr;
+    if (pix && count_pilot(pix) && mfx_index_key_bins(pix, 0, bins.data(), nullptr) == MFX_OK) {
+      mfx_cut_bins(bins.data(), 0, C.nbins, P, cuts);
+      for (const auto &c : cuts) C.todo.push_back({c.bin_lo, c.bin_hi});
+    }
+    if (pix) mfx_index_free(pix);
+    if (C.todo.empty()) C.todo.push_back({0u, C.nbins});           // one pass, or a pilot that showed nothing: the refusals cut from here
+  };
+  bool from_store = SG.s != nullptr;
+  if (from_store) {
+    // ---- the files are parsed once: the store fills, pass 1 counts every batch as it is complete
+    uint64_t sent = 0;                                             // batches of the store pass 1 has taken
+    bool started = false, pass1 = false;
+    int fatal = 0;
+    auto pilot = [&](mfx_index *pix) {
+      mfx_reads *pr = mfx_reads_begin_all(pix, C.batch);
+      if (!pr) return false;
+      const int rrc = mfx_reads_replay(pr, SG.s, 0, 1);
+      return mfx_reads_end(pr, nullptr) == MFX_OK && rrc == MFX_OK;
+    };
+    // batches [sent, upto) through pass 1; a refusal ends pass 1 (its halves are queued) and the store goes on filling
+    auto advance = [&](uint64_t upto) {
+      if (!started && upto > 0) {
+        started = true;
+        ranges_from_pilot(pilot);
+        pass1 = C.begin();
+        if (!pass1) { fatal = 1; return; }
+      }
+      if (!pass1 || upto <= sent) return;
+      const int rrc = mfx_reads_replay(C.r, SG.s, sent, upto - sent);
+      sent = upto;
+      if (rrc == MFX_OK) return;
+      pass1 = false;
+      if (C.finish("from memory") < 0) fatal = 1;                  // (MFX_E_NOMEM: refused and cut; anything else is printed)
+    };
+    std::string file_why, store_why;
+    const int frc = feed_reads_files(G, [&](const char *const *bases, const uint64_t *lens, uint64_t n) {
+      const int arc = mfx_reads_store_add(SG.s, bases, lens, n);
+      if (arc) { if (arc < 0) store_why = mfx_last_error(); return arc; }
+      uint64_t held = 0;
+      mfx_reads_store_info(SG.s, &held, nullptr, nullptr, nullptr, nullptr);
+      if (held > 1) advance(held - 1);                             // (the last batch is still being filled)
+      return fatal ? 2 : 0;
+    }, file_why);
+    if (frc == 2 || fatal) return 1;
+    if (frc == FEED_FILE_FAILED || frc < 0) { fprintf(stderr, "ERROR: counting -reads: %s\n", (frc < 0 ? store_why : file_why).c_str()); return 1; }
+    if (frc == 1) {                                                // the store is full: every pass reads the files
+      fprintf(stderr, "-- The read store is full at %.3f GB (MFX_COUNT_STORE_GB): every pass reads the files.\n", (double)store_bytes / 1e9);
+      if (C.r) { mfx_reads_end(C.r, nullptr); C.r = nullptr; }
+      if (C.ix) { mfx_index_free(C.ix); C.ix = nullptr; }
+      mfx_reads_store_free(SG.s);
+      SG.s = nullptr;
+      from_store = false;
+      C.n_refused = 0;
+    } else {
+      uint64_t held = 0;
+      mfx_reads_store_info(SG.s, &held, nullptr, nullptr, nullptr, nullptr);
+      if (!started && held == 0) ranges_from_pilot([](mfx_index *) { return false; });      // no k-mer in the files: one pass over nothing
+      advance(held);
+      if (fatal) return 1;
+      if (pass1 && C.finish("from memory") < 0) return 1;
+      while (!C.todo.empty()) {
+        if (!C.begin()) return 1;
+        const int rrc = mfx_reads_replay(C.r, SG.s, 0, held);
+        if (rrc != MFX_OK && rrc != MFX_E_NOMEM) { fprintf(stderr, "ERROR: counting -reads: %s\n", mfx_last_error()); return 1; }
+        if (C.finish("from memory") < 0) return 1;
+      }
+    }
+  }
+  if (!from_store) {
+    // ---- no store: the pilot is the first batch of the first file's records, every pass reads the files
+    if (C.n_pass == 0) {
+      auto pilot = [&](mfx_index *pix) {
+        mfx_reads *pr = mfx_reads_begin_all(pix, C.batch);
+        if (!pr) return false;
+        mfx_reads_store *one = mfx_reads_store_create(G.kArg, C.batch, 0);
+        std::string why;
+        bool ok = one != nullptr;
+        if (ok) {
+          feed_reads_files(G, [&](const char *const *bases, const uint64_t *lens, uint64_t n) {
+            uint64_t held = 0;
+            if (mfx_reads_store_add(one, bases, lens, n)) return 3;
+            mfx_reads_store_info(one, &held, nullptr, nullptr, nullptr, nullptr);
+            return held > 1 ? 3 : 0;                               // the first batch is complete: enough
+          }, why);
+          uint64_t held = 0;
+          mfx_reads_store_info(one, &held, nullptr, nullptr, nullptr, nullptr);
+          ok = held > 0 && mfx_reads_replay(pr, one, 0, 1) == MFX_OK;
+        }
+        if (one) mfx_reads_store_free(one);
+        return mfx_reads_end(pr, nullptr) == MFX_OK && ok;
+      };
+      ranges_from_pilot(pilot);
+    }
+    while (!C.todo.empty()) {
+      C.cur = C.todo.front();
+      C.todo.pop_front();
+      C.t0 = std::chrono::steady_clock::now();
+      C.ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
+      if (!C.ix) DIE_MFX("creating the k-mer table");
+      const uint64_t range[2] = {C.key_of(C.cur.first), C.key_of(C.cur.second)};
+      mfx_reads_stats st;
+      int code = MFX_OK;
+      std::string text;
+      if (!count_reads_files(G, C.ix, true, &st, C.batch, range, &code, &text)) {
+        if (code != MFX_E_NOMEM) {
+          if (code != MFX_OK) fprintf(stderr, "ERROR: counting -reads: %s\n", text.c_str());
+          return 1;
+        }
+        if (!C.refuse(text)) return 1;
+        continue;
+      }
+      if (!C.append(st, "from the files")) return 1;
+    }
+  }
+  if (C.have_first && C.counted != C.first.kmers) {
+    fprintf(stderr, "ERROR: -count: the passes counted %lu of the reads' %lu k-mers\n", (unsigned long)C.counted, (unsigned long)C.first.kmers);
+    return 1;
+  }
+  fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu distinct; the table grew %lu time%s to %.3f GB in %lu pass%s (%lu refused and split).\n",
+          G.kArg, (unsigned long)C.first.reads, (unsigned long)C.first.bases, (unsigned long)C.first.kmers, (unsigned long)C.distinct, (unsigned long)C.growths,
+          C.growths == 1 ? "" : "s", C.max_gb, (unsigned long)C.n_pass, C.n_pass == 1 ? "" : "es", (unsigned long)C.n_refused);
+  const auto tw0 = std::chrono::steady_clock::now();
+  uint64_t n = 0;
+  mfx_db_writer *w = C.w;
+  C.w = nullptr;
+  if (mfx_db_writer_close(w, &n)) DIE_MFX("-count: writing the database");
+  struct stat ost;
+  fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
+  if (stat(G.outName, &ost) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", ost.st_size / 1e9, (double)ost.st_size / (double)n);
+  fprintf(stderr, ".\n");
+  if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
+    fprintf(stderr, "-- count: %.3f s writing\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count());
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
 
 int main(int argc, char **argv) {
   // MFX_CLI_TIMING=3: wall-clock stamps (seconds since the epoch) at main / after the device check / at the end, so that a
@@ -787,6 +1094,18 @@ int main(int argc, char **argv) {
     else if (is("-sharded")) G.sharded = true;
     else if (is("-convert")) G.convertName = val();
     else if (is("-count")) G.count = true;
+    else if (is("-passes")) {
+      const char *v = val();
+      char *e = nullptr;
+      errno = 0;
+      const long long x = strtoll(v, &e, 10);
+      G.passesGiven = true;
+      if (strcmp(v, "auto") == 0) G.passesAuto = true;
+      else if (e == v || *e != 0 || errno != 0) err.push_back(std::string("Invalid -passes '") + v + "': the passes of -count are a number from 1 to 4096, or auto.\n");
+      else if (x < 1) err.push_back(std::string("Invalid -passes '") + v + "': -count takes at least one pass (1 to 4096, or auto).\n");
+      else if (x > 4096) err.push_back(std::string("Invalid -passes '") + v + "': a pass takes at least one of the 4096 key bins, so there are 4096 at most (or auto).\n");
+      else G.passes = (uint32_t)x;
+    }
     else if (is("-placed")) G.placed = true;
     else if (is("-nosplit")) G.nosplit = true;
     else if (is("-filter")) G.reportType = OP_FILTER;
@@ -845,14 +1164,28 @@ int main(int argc, char **argv) {
       fprintf(stderr, "ERROR: HIP device %d not available (%d visible). This program has no CPU path.\n", G.device, mfx_device_count());
       return 1;
     }
+    if (G.passesGiven) {
+      fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s in passes over key ranges.\n", G.kArg, (unsigned long)G.readsNames.size(),
+              G.readsNames.size() == 1 ? "" : "s");
+      return count_in_passes(G);
+    }
     // the table is created small and grows with what the reads hold (mfx_reads_begin_all)
     const auto tc0 = std::chrono::steady_clock::now();
+    uint64_t count_batch = 0;                                      // MFX_COUNT_BATCH (docs/KNOBS.md): bases per device batch; unset: the library's
+    if (const char *e = getenv("MFX_COUNT_BATCH")) count_batch = strtoull(e, nullptr, 10);
     mfx_index *ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
     if (!ix) DIE_MFX("creating the k-mer table");
     struct IxGuard { mfx_index *ix; ~IxGuard() { mfx_index_free(ix); } } ixGuard{ix};
     fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s.\n", G.kArg, (unsigned long)G.readsNames.size(), G.readsNames.size() == 1 ? "" : "s");
     mfx_reads_stats st;
-    if (!count_reads_files(G, ix, true, &st)) return 1;
+    int count_code = MFX_OK;
+    std::string count_text;
+    if (!count_reads_files(G, ix, true, &st, count_batch, nullptr, &count_code, &count_text)) {
+      if (count_code != MFX_OK) fprintf(stderr, "ERROR: counting -reads: %s\n", count_text.c_str());
+      if (count_code == MFX_E_NOMEM)
+        fprintf(stderr, "-- Hint: -passes auto counts the k-mers in passes over key ranges, each in a table of its own that fits -memory and the device.\n");
+      return 1;
+    }
     mfx_index_info info;
     uint64_t growths = 0;
     if (mfx_index_get_info(ix, &info) || mfx_index_growths(ix, &growths, nullptr, nullptr, nullptr)) DIE_MFX("-count");
@@ -872,6 +1205,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Bye!\n");
     return 0;
   }
+
+  if (G.passesGiven && !G.count) err.push_back("-passes divides the work of -count: it has no meaning without -count.\n");
 
   // -reads: every check before any device is touched
   const bool fromReads = !G.readsNames.empty();

@@ -1460,73 +1460,177 @@ struct DbDev {                                                 // device buffers
 };
 }  // namespace
 
-static int mfx_index_write_db_impl(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {
-  if (!ix || !path) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: null argument");
-  if (side != 0 && side != 1) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: side %d (0: the read counts, 1: the assembly counts)", side);
-  if (ix->seq_only) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: a sequence-only or path-only index holds part of a database only; write a full index (mfx_index_create)");
-  if (ix->wide()) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: the sorted form holds k <= %d; this index holds %d-mers", MFX_MAX_K_NARROW, ix->k);
-  if (ix->shard_n > 1) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: a sharded index holds part of a database only");
+// the refusals of mfx_index_write_db, for everything that reads a side of a full table by key bins; `who`: the entry point, for the texts
+static int db_side_checks(const mfx_index *ix, int side, const char *who) {
+  if (side != 0 && side != 1) return mfx_fail(MFX_E_INVAL, "%s: side %d (0: the read counts, 1: the assembly counts)", who, side);
+  if (ix->seq_only) return mfx_fail(MFX_E_INVAL, "%s: a sequence-only or path-only index holds part of a database only; write a full index (mfx_index_create)", who);
+  if (ix->wide()) return mfx_fail(MFX_E_INVAL, "%s: the sorted form holds k <= %d; this index holds %d-mers", who, MFX_MAX_K_NARROW, ix->k);
+  if (ix->shard_n > 1) return mfx_fail(MFX_E_INVAL, "%s: a sharded index holds part of a database only", who);
+  return MFX_OK;
+}
+
+namespace {
+struct DeviceBack {                                            // the caller's device again on every way out
+  int d = -1;
+  DeviceBack() { if (hipGetDevice(&d) != hipSuccess) d = -1; }
+  ~DeviceBack() { if (d >= 0) (void)hipSetDevice(d); }
+};
+}  // namespace
+
+// bins[key >> shift] of the side's entries, on the host (nbins = 2^min(2k, 12)); d_bins: nbins + 1 device words, the last left zero
+static int db_side_bins(const mfx_index *ix, int side, uint64_t *d_bins, std::vector<uint64_t> &bins) {
+  const int key_bits = 2 * ix->k, bin_bits = std::min(key_bits, MFX_DB_BIN_BITS), shift = key_bits - bin_bits;
+  const uint32_t nbins = 1u << bin_bits;
+  MFX_HIP(mfx_memset_now(d_bins, 0, (nbins + 1) * sizeof(uint64_t)));
+  MFX_HIP(mfx_k_db_bins(ix->view(), side, shift, nbins, d_bins, nullptr));
+  bins.resize(nbins);
+  MFX_HIP(hipMemcpy(bins.data(), d_bins, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return MFX_OK;
+}
+
+static int mfx_index_key_bins_impl(const mfx_index *ix, int side, uint64_t *out, uint32_t *nbins_out) {
+  if (!ix || !out) return mfx_fail(MFX_E_INVAL, "mfx_index_key_bins: null argument");
+  if (int rc = db_side_checks(ix, side, "mfx_index_key_bins")) return rc;
+  DeviceBack back;
+  MFX_HIP(hipSetDevice(ix->device));
+  const uint32_t nbins = 1u << std::min(2 * ix->k, MFX_DB_BIN_BITS);
+  DbDev D;
+  MFX_HIP(hipMalloc(&D.p[0], (nbins + 1) * sizeof(uint64_t)));
+  std::vector<uint64_t> bins;
+  if (int rc = db_side_bins(ix, side, (uint64_t *)D.p[0], bins)) return rc;
+  memset(out, 0, (1u << MFX_DB_BIN_BITS) * sizeof(uint64_t));
+  memcpy(out, bins.data(), nbins * sizeof(uint64_t));
+  if (nbins_out) *nbins_out = nbins;
+  return MFX_OK;
+}
+
+extern "C" int mfx_index_key_bins(const mfx_index *ix, int side, uint64_t *bins, uint32_t *nbins) {
+  try { return mfx_index_key_bins_impl(ix, side, bins, nbins); }
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_index_key_bins: out of memory"); }
+}
+
+// the writer that takes several tables (mfx_db_writer_*): the host arrays of the database so far, ascending
+struct mfx_db_writer {
+  std::string path;
+  int k = 0;
+  std::vector<uint64_t> keys;
+  std::vector<uint32_t> vals;
+};
+
+// the device part: the side's entries, by key ranges compacted out of the table, sorted and copied behind what the writer holds
+static int db_append_index(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added, const char *who) {
+  if (n_added) *n_added = 0;
+  if (int rc = db_side_checks(ix, side, who)) return rc;
+  if (ix->k != w->k) return mfx_fail(MFX_E_INVAL, "%s: the writer holds %d-mers, the index %d-mers", who, w->k, ix->k);
   uint64_t R = MFX_DB_RANGE_DEFAULT;
   if (const char *e = getenv("MFX_WRITE_DB_RANGE")) {          // read per call: tests reach several ranges on small tables
     const long long v = atoll(e);
     if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
   }
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  struct Back { int d; ~Back() { if (d >= 0) (void)hipSetDevice(d); } } back{prev};
+  DeviceBack back;
   MFX_HIP(hipSetDevice(ix->device));
   const int key_bits = 2 * ix->k, bin_bits = std::min(key_bits, MFX_DB_BIN_BITS), shift = key_bits - bin_bits;
   const uint32_t nbins = 1u << bin_bits;
   mfx_table_view t = ix->view();
   DbDev D;
-  uint64_t *d_bins = nullptr;
   MFX_HIP(hipMalloc(&D.p[0], (nbins + 1) * sizeof(uint64_t)));     // the bins, then the export's counter
-  d_bins = (uint64_t *)D.p[0];
+  uint64_t *d_bins = (uint64_t *)D.p[0];
   unsigned long long *d_count = (unsigned long long *)(d_bins + nbins);
-  MFX_HIP(mfx_memset_now(d_bins, 0, (nbins + 1) * sizeof(uint64_t)));
-  MFX_HIP(mfx_k_db_bins(t, side, shift, nbins, d_bins, nullptr));
-  std::vector<uint64_t> bins(nbins);
-  MFX_HIP(hipMemcpy(bins.data(), d_bins, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> bins;
+  if (int rc = db_side_bins(ix, side, d_bins, bins)) return rc;
   std::vector<mfx_bin_range> ranges;
   mfx_group_bins(bins.data(), nbins, R, ranges);
   uint64_t n = 0, maxn = 0;
   for (const auto &r : ranges) { n += r.n; maxn = std::max(maxn, r.n); }
-  std::vector<uint64_t> keys(n);
-  std::vector<uint32_t> vals(n);
-  if (n) {
-    size_t tmp_bytes = 0;
-    if (int rc = mfx_sort_db_pairs(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, maxn, key_bits, nullptr)) return rc;
-    hipError_t e = hipMalloc(&D.p[1], maxn * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[2], maxn * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[3], maxn * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[4], maxn * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[5], tmp_bytes ? tmp_bytes : 1);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return mfx_fail(MFX_E_NOMEM, "mfx_index_write_db: the buffers of a key range of %lu k-mers (%.3f GB) do not fit the device: %s; lower MFX_WRITE_DB_RANGE",
-                      (unsigned long)maxn, ((double)maxn * 24 + (double)tmp_bytes) / 1e9, hipGetErrorString(e));
-    }
-    uint64_t at = 0;
-    for (const auto &r : ranges) {
-      MFX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), nullptr));
-      MFX_HIP(mfx_k_db_export(t, side, shift, r.bin_lo, r.bin_hi, (uint64_t *)D.p[1], (uint32_t *)D.p[3], maxn, d_count, nullptr));
-      unsigned long long got = 0;
-      MFX_HIP(hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipStreamSynchronize(nullptr));
-      if (got != r.n)
-        return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: the table changed while it was written (a key range held %lu k-mers, then %lu); nothing else may "
-                        "use the index during the call", (unsigned long)r.n, (unsigned long)got);
-      if (int rc = mfx_sort_db_pairs(D.p[5], tmp_bytes, (const uint64_t *)D.p[1], (uint64_t *)D.p[2], (const uint32_t *)D.p[3], (uint32_t *)D.p[4], r.n,
-                                     key_bits, nullptr))
-        return rc;
-      MFX_HIP(hipMemcpyAsync(keys.data() + at, D.p[2], r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipMemcpyAsync(vals.data() + at, D.p[4], r.n * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipStreamSynchronize(nullptr));
-      at += r.n;
-    }
+  if (n == 0) return MFX_OK;
+  const uint64_t held = w->keys.size();
+  struct Undo {                                                // an append that fails adds nothing
+    mfx_db_writer *w; uint64_t held; bool keep = false;
+    ~Undo() { if (!keep) { w->keys.resize(held); w->vals.resize(held); } }
+  } undo{w, held};
+  w->keys.reserve(held + n);                                     // exactly: resize alone would double the capacity.  The k-mers held move into the new
+  w->vals.reserve(held + n);                                     // arrays, so both are alive for the move: see the header on the writer's host memory
+  w->keys.resize(held + n);
+  w->vals.resize(held + n);
+  size_t tmp_bytes = 0;
+  if (int rc = mfx_sort_db_pairs(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, maxn, key_bits, nullptr)) return rc;
+  hipError_t e = hipMalloc(&D.p[1], maxn * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[2], maxn * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[3], maxn * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[4], maxn * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[5], tmp_bytes ? tmp_bytes : 1);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a key range of %lu k-mers (%.3f GB) do not fit the device: %s; lower MFX_WRITE_DB_RANGE", who,
+                    (unsigned long)maxn, ((double)maxn * 24 + (double)tmp_bytes) / 1e9, hipGetErrorString(e));
   }
-  if (n_kmers) *n_kmers = n;
-  return mfx_db_write_flat_impl(path, ix->k, keys.data(), vals.data(), n);
+  uint64_t at = held;
+  for (const auto &r : ranges) {
+    MFX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), nullptr));
+    MFX_HIP(mfx_k_db_export(t, side, shift, r.bin_lo, r.bin_hi, (uint64_t *)D.p[1], (uint32_t *)D.p[3], maxn, d_count, nullptr));
+    unsigned long long got = 0;
+    MFX_HIP(hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipStreamSynchronize(nullptr));
+    if (got != r.n)
+      return mfx_fail(MFX_E_INVAL, "%s: the table changed while it was written (a key range held %lu k-mers, then %lu); nothing else may "
+                      "use the index during the call", who, (unsigned long)r.n, (unsigned long)got);
+    if (int rc = mfx_sort_db_pairs(D.p[5], tmp_bytes, (const uint64_t *)D.p[1], (uint64_t *)D.p[2], (const uint32_t *)D.p[3], (uint32_t *)D.p[4], r.n,
+                                   key_bits, nullptr))
+      return rc;
+    MFX_HIP(hipMemcpyAsync(w->keys.data() + at, D.p[2], r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipMemcpyAsync(w->vals.data() + at, D.p[4], r.n * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipStreamSynchronize(nullptr));
+    if (at == held && held != 0 && w->keys[held] <= w->keys[held - 1])
+      return mfx_fail(MFX_E_INVAL, "%s: the appended k-mers start at %llu, not above the writer's last k-mer %llu: tables are appended in ascending key order, "
+                      "their key ranges apart", who, (unsigned long long)w->keys[held], (unsigned long long)w->keys[held - 1]);
+    at += r.n;
+  }
+  undo.keep = true;
+  if (n_added) *n_added = n;
+  return MFX_OK;
+}
+
+extern "C" mfx_db_writer *mfx_db_writer_open(const char *path, int k) {
+  if (!path) { mfx_fail(MFX_E_INVAL, "mfx_db_writer_open: null argument"); return nullptr; }
+  if (k < 1 || k > MFX_MAX_K_NARROW) { mfx_fail(MFX_E_INVAL, "mfx_db_writer_open: the sorted form holds 1 <= k <= %d; k = %d", MFX_MAX_K_NARROW, k); return nullptr; }
+  try {
+    mfx_db_writer *w = new mfx_db_writer;
+    w->path = path;
+    w->k = k;
+    return w;
+  } catch (const std::bad_alloc &) { mfx_fail(MFX_E_NOMEM, "mfx_db_writer_open: out of memory"); return nullptr; }
+}
+
+extern "C" int mfx_db_writer_append_index(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added) {
+  if (!w || !ix) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_append_index: null argument");
+  try { return db_append_index(w, ix, side, n_added, "mfx_db_writer_append_index"); }     // (nothing leaves the C ABI as an exception)
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_writer_append_index: out of memory (12 bytes of host memory per k-mer held)"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_writer_append_index: %s", e.what()); }
+}
+
+extern "C" int mfx_db_writer_close(mfx_db_writer *w, uint64_t *n_kmers) {
+  if (!w) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_close: null argument");
+  int rc;
+  try {
+    if (n_kmers) *n_kmers = w->keys.size();
+    rc = mfx_db_write_flat_impl(w->path.c_str(), w->k, w->keys.data(), w->vals.data(), w->keys.size());
+  }
+  catch (const std::bad_alloc &) { rc = mfx_fail(MFX_E_NOMEM, "mfx_db_writer_close: out of memory"); }
+  catch (const std::exception &e) { rc = mfx_fail(MFX_E_IO, "mfx_db_writer_close: %s", e.what()); }
+  delete w;
+  return rc;
+}
+
+extern "C" void mfx_db_writer_abort(mfx_db_writer *w) { delete w; }
+
+static int mfx_index_write_db_impl(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {
+  if (!ix || !path) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db: null argument");
+  mfx_db_writer w;
+  w.path = path;
+  w.k = ix->k;
+  if (int rc = db_append_index(&w, ix, side, nullptr, "mfx_index_write_db")) return rc;
+  if (n_kmers) *n_kmers = w.keys.size();
+  return mfx_db_write_flat_impl(path, ix->k, w.keys.data(), w.vals.data(), w.keys.size());
 }
 
 extern "C" int mfx_index_write_db(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {

@@ -1,5 +1,6 @@
 // mfx_grow.h -- the plain host arithmetic of the claiming read counter's table (mfx_reads.cpp) and of mfx_index_write_db's key ranges
-// (mfx_db.cpp).  No HIP, no library state: tools/native/grow_sanitize.cpp drives it under the sanitizers.
+// (mfx_db.cpp), and the key ranges of the passes of `merfin -count -passes` (mfx_cut_bins).  No HIP, no library state:
+// tools/native/grow_sanitize.cpp and tools/native/cuts_sanitize.cpp drive it under the sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -51,4 +52,69 @@ inline void mfx_group_bins(const uint64_t *bins, uint32_t nbins, uint64_t R, std
     cur.n += c;
   }
   if (cur.n != 0) out.push_back(cur);
+}
+
+// ---- key ranges of the passes of a count ---------------------------------------------------------------------------------------------
+// The bins [bin_lo, bin_hi) cut at bin boundaries into consecutive ranges that together are [bin_lo, bin_hi) -- a bin without entries here
+// may hold some in a later pass, so it belongs to a range too.  No range lacks entries, so there are min(parts, non-empty bins) ranges
+// (none when no bin holds an entry).  The cuts are chosen so that the largest range's mass is minimal; of the cuttings that reach it the
+// first in ascending order of the cuts wins (every cut as early as the others still allow).  Masses are summed in 128 bits; a range's n
+// saturates at 2^64 - 1.
+inline void mfx_cut_bins(const uint64_t *bins, uint32_t bin_lo, uint32_t bin_hi, uint32_t parts, std::vector<mfx_bin_range> &out) {
+  typedef unsigned __int128 u128;
+  out.clear();
+  if (bin_hi <= bin_lo || parts == 0) return;
+  const uint32_t nb = bin_hi - bin_lo;
+  const uint64_t *b = bins + bin_lo;
+  u128 total = 0;
+  uint64_t largest = 0;
+  uint32_t nonempty = 0;
+  for (uint32_t i = 0; i < nb; ++i) {
+    total += b[i];
+    if (b[i] > largest) largest = b[i];
+    if (b[i]) ++nonempty;
+  }
+  if (nonempty == 0) return;
+  const uint32_t m = parts < nonempty ? parts : nonempty;
+  // need[c]: the fewest ranges of mass <= T that hold the bins from c on (0 at the end); nxt: where the longest such range from c ends
+  std::vector<uint32_t> need(nb + 1), ne(nb + 1);
+  auto fewest = [&](u128 T) {
+    need[nb] = 0;
+    u128 sum = 0;
+    uint32_t e = nb;                                           // the range from c ends at e: [c, e) has mass `sum` <= T, and is as long as T allows
+    for (uint32_t c = nb; c-- > 0;) {
+      sum += b[c];
+      while (sum > T) sum -= b[--e];
+      need[c] = 1 + need[e];
+    }
+    return need[0];
+  };
+  u128 lo = largest, hi = total;                               // the smallest T with fewest(T) <= m
+  while (lo < hi) {
+    const u128 mid = lo + (hi - lo) / 2;
+    if (fewest(mid) <= m) hi = mid; else lo = mid + 1;
+  }
+  const u128 T = lo;
+  fewest(T);
+  ne[nb] = 0;
+  for (uint32_t c = nb; c-- > 0;) ne[c] = ne[c + 1] + (b[c] ? 1u : 0u);
+  uint32_t at = 0;
+  for (uint32_t left = m; left > 0; --left) {
+    mfx_bin_range r{bin_lo + at, bin_hi, 0};
+    u128 sum = 0;
+    uint32_t c = at;
+    if (left == 1) {
+      for (; c < nb; ++c) sum += b[c];
+    } else {
+      // the earliest end c: the range holds entries, and the bins from c on make exactly left - 1 ranges
+      while (true) {
+        sum += b[c++];
+        if (sum != 0 && need[c] <= left - 1 && left - 1 <= ne[c]) break;
+      }
+    }
+    r.bin_hi = bin_lo + c;
+    r.n = sum > (u128)~0ull ? ~0ull : (uint64_t)sum;
+    out.push_back(r);
+    at = c;
+  }
 }

@@ -133,6 +133,7 @@ struct mfx_reads_args {
   uint64_t        npos;               // base positions of the batch (separators included)
   uint64_t       *meta;               // the index's meta words (side-table claims that hit the probe limit: [2])
   uint64_t       *stats;              // [4] += valid k-mers, k-mers added to a claimed k-mer, k-mers dropped, k-mers whose read count moved to the side table (or arrived in it)
+  uint64_t        key_lo = 0, key_hi = 0;   // mfx_k_reads_claim_range only: the k-mers with key_lo <= key < key_hi are counted
 };
 
 // varMer::score of the paths of a batch (mfx_var_score_kernel): everything device memory
@@ -214,6 +215,7 @@ hipError_t mfx_k_count(const mfx_count_args &a, hipStream_t st);
 hipError_t mfx_k_reads(const mfx_reads_args &a, hipStream_t st);        // k <= 31: sequence-only / path-only index (every layout)
 hipError_t mfx_kw_reads(const mfx_reads_args &a, hipStream_t st);       // 32 <= k <= 64 (mfx_wide.hip)
 hipError_t mfx_k_reads_claim(const mfx_reads_args &a, hipStream_t st);  // k <= 31, a full table of 16-byte slots: every k-mer is claimed if absent (mfx_reads_begin_all)
+hipError_t mfx_k_reads_claim_range(const mfx_reads_args &a, hipStream_t st);   // ... only the k-mers of [a.key_lo, a.key_hi); the others add to stats[0] alone (mfx_reads_begin_range)
 // every entry of a full table of 16-byte slots into the (empty) table nt; meta: nt's words, zero at launch ([0]: entries moved, [2]: probe-limit failures)
 hipError_t mfx_k_table_rehash(const mfx_slot *old_slots, uint64_t old_nslots, mfx_table_view nt, uint64_t *meta, hipStream_t st);
 // mfx_index_write_db (mfx_sort.hip): bins[key >> shift] += 1 for every entry whose count on `side` is non-zero

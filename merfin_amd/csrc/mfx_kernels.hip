@@ -3706,7 +3706,10 @@ __device__ __forceinline__ void mfx_reads_add(const mfx_reads_args &a, uint64_t 
 // once more per tile in a block table (LDS) and added when the tile ends; i.i.d. reads almost never take this path.
 constexpr uint32_t MFX_READS_BT = 256;                         // entries of the block table (a power of two)
 
-template <bool CLAIM>
+// RANGED (mfx_reads_begin_range; with CLAIM): only the k-mers with key_lo <= key < key_hi are counted.  A valid k-mer out of the range adds
+// to n_kmers and does nothing else: it takes no s_own entry (an in-range lane with the same hash would then add alone, or lose its fold),
+// folds into nobody, and reaches neither the block table nor mfx_reads_add.
+template <bool CLAIM, bool RANGED = false>
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) {
   __shared__ mfx_tile_lds L;
   __shared__ uint32_t s_own[MFX_BLOCK / 64][256];             // per wave: the lane that holds the entry of a key hash
@@ -3729,11 +3732,12 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_reads_kernel(mfx_reads_args a) 
       if (b * MFX_BLOCK >= n) break;                           // short last tile (block-uniform)
       const uint32_t p = b * MFX_BLOCK + tid;
       uint64_t f;
-      const bool ok = mfx_tile_kmer(L, k, p, f) && p < n;
+      const bool valid = mfx_tile_kmer(L, k, p, f) && p < n;
       const uint64_t r = mfx_revcomp(f, k);
       const uint64_t key = f < r ? f : r;
+      n_kmers += valid ? 1u : 0u;
+      const bool ok = RANGED ? (valid && key >= a.key_lo && key < a.key_hi) : valid;     // (the lanes of a wave differ here; nothing below asks for a uniform ok)
       uint32_t v = ok ? 1u : 0u;
-      n_kmers += v;
       // ---- fold the wave's equal keys into one lane each (every lane takes part: the shuffle reads any lane)
       const uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 56);
       s_fold[tid] = 0u;
@@ -4211,6 +4215,12 @@ hipError_t mfx_k_reads_claim(const mfx_reads_args &a, hipStream_t st) {
   const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
   if (ntiles == 0) return hipSuccess;
   mfx_reads_kernel<true><<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_reads_claim_range(const mfx_reads_args &a, hipStream_t st) {
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (ntiles == 0) return hipSuccess;
+  mfx_reads_kernel<true, true><<<(unsigned)(ntiles < 8192 ? ntiles : 8192), MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_k_table_rehash(const mfx_slot *old_slots, uint64_t old_nslots, mfx_table_view nt, uint64_t *meta, hipStream_t st) {

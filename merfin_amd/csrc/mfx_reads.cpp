@@ -10,6 +10,11 @@
 // knows the reads' distinct k-mers beforehand.  No launch may overfill the table, so before a batch is enqueued the bound of mfx_grow.h
 // is checked against the table's distinct count as last read and the positions enqueued since; when it fails the stages are settled and
 // the count is read again, and when it still fails every entry moves into a larger table (mfx_table_rehash_kernel).
+//
+// The RANGED claiming counter (mfx_reads_begin_range) is the claiming counter for the k-mers of one key range: one pass of a count whose
+// table does not fit the device.  The READ STORE (mfx_reads_store_*) keeps the packed batches of a read set on the host and mfx_reads_replay
+// sends them through any counter, so that the passes after the first parse nothing; store and counter cut records into batches with the
+// same code (batch_records, batch_pack).
 #include "mfx_internal.h"
 #include "mfx_kernels.h"
 #include "mfx_grow.h"
@@ -37,14 +42,91 @@ struct DeviceScope {
   }
   ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// ---- records into batches: what mfx_reads_add and mfx_reads_store_add share ----------------------------------------------------
+// The bytes of the batch being filled.  batch_records copies records in, one 'N' between two; a record longer than the room left is cut and
+// its rest starts the next batch k-1 bases before the cut.  Whenever a batch is complete `flush` is called (it sends or keeps b.bytes[0, b.used)
+// and sets b.used = 0; non-zero: its error, passed on).  batch_pack turns such a batch into the planes a launch reads.
+struct Batch {
+  uint64_t cap = 0;                  // bases per batch
+  std::vector<uint8_t> bytes;
+  uint64_t used = 0;
+};
+
+// planes of npos bases in nw words each (nw >= (npos + 31) / 32): the words beyond the bases are invalid (the halo of the last tile)
+void batch_pack(const uint8_t *bytes, uint64_t npos, uint64_t nw, uint64_t *codes, uint32_t *valid) {
+  const uint64_t packed = (npos + 31) / 32;
+  mfx_pack_bases(bytes, npos, codes, valid);
+  if (nw > packed) {
+    memset(codes + packed, 0, (nw - packed) * sizeof(uint64_t));
+    memset(valid + packed, 0, (nw - packed) * sizeof(uint32_t));
+  }
+}
+
+template <class Flush>
+int batch_records(Batch &b, uint64_t k, const char *const *bases, const uint64_t *lens, uint64_t n, uint64_t &n_reads, uint64_t &n_bases, const char *who,
+                  Flush &&flush) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t len = lens[i];
+    n_reads += 1;
+    n_bases += len;
+    if (len < k) continue;                                     // no k-mer
+    if (!bases[i]) return mfx_fail(MFX_E_INVAL, "%s: record %llu has no bases", who, (unsigned long long)i);
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(bases[i]);
+    uint64_t at = 0;
+    while (true) {
+      if (b.cap - b.used < k) {                                // no whole k-mer fits: the batch goes
+        if (int rc = flush()) return rc;
+      }
+      const uint64_t take = std::min(len - at, b.cap - b.used);
+      memcpy(b.bytes.data() + b.used, src + at, take);
+      b.used += take;
+      if (at + take == len) {
+        if (b.used < b.cap) b.bytes[b.used++] = 'N';           // (a read that ends the batch needs no separator)
+        break;
+      }
+      at += take - (k - 1);                                    // the rest, from the first k-mer this batch does not hold
+      if (int rc = flush()) return rc;
+    }
+  }
+  return MFX_OK;
+}
+
+// the batch size both the counters and the store take; 0: refused (the text is set)
+uint64_t batch_size_checked(uint64_t batch_bases, int k, const char *who) {
+  const uint64_t min_batch = 2ull * (uint64_t)k + 2;
+  if (batch_bases == 0) batch_bases = MFX_READS_BATCH_DEFAULT;
+  if (batch_bases < min_batch) {
+    mfx_fail(MFX_E_INVAL, "%s: a batch of %llu bases is too small for %d-mers (at least %llu)", who, (unsigned long long)batch_bases, k,
+             (unsigned long long)min_batch);
+    return 0;
+  }
+  if (batch_bases > (1ull << 34)) { mfx_fail(MFX_E_INVAL, "%s: batch of %llu bases is beyond 2^34", who, (unsigned long long)batch_bases); return 0; }
+  return batch_bases;
+}
 }  // namespace
+
+// the read store (mfx_reads_store_*): the packed batches of a read set, kept on the host so that a second pass parses nothing
+struct mfx_reads_store {
+  int k = 0;
+  Batch b;                           // the batch being filled: the store's last batch while it holds bases
+  uint64_t max_bytes = 0;            // 0: no limit
+  struct Packed {
+    std::vector<uint64_t> codes;     // (npos + 31) / 32 words of each plane: 3 bits per base
+    std::vector<uint32_t> valid;
+    uint64_t npos = 0, reads = 0, bases = 0;      // reads / bases: the records added since the batch before was complete
+  };
+  std::vector<Packed> batches;
+  uint64_t bytes = 0;                // of the complete batches' planes
+  uint64_t reads = 0, bases = 0;     // records and bases passed in
+  uint64_t reads_kept = 0, bases_kept = 0;        // of those: in the statistics of a complete batch
+  bool complete = true;
+};
 
 struct mfx_reads {
   mfx_index *ix = nullptr;
-  uint64_t cap = 0;                  // bases per batch
+  Batch b;                           // the batch being filled
   uint64_t words = 0;                // plane words per stage (whole tiles + the halo)
-  std::vector<uint8_t> bytes;        // the batch being filled
-  uint64_t used = 0;
   struct Stage {
     uint64_t *hc = nullptr, *dc = nullptr;
     uint32_t *hv = nullptr, *dv = nullptr;
@@ -62,6 +144,9 @@ struct mfx_reads {
   bool claim = false;
   uint64_t distinct_known = 0;       // the table's meta[0] as last read
   uint64_t pending = 0;              // positions enqueued since that read: each may claim a k-mer
+  // ranged claiming counter (mfx_reads_begin_range over less than [0, 4^k))
+  bool ranged = false;
+  uint64_t key_lo = 0, key_hi = 0;
 };
 
 static void reads_free(mfx_reads *r) {
@@ -188,12 +273,12 @@ static int claim_reserve(mfx_reads *r, uint64_t B) {
   return rc;
 }
 
-// the batch in r->bytes goes to the device on the next stage
-static int reads_flush(mfx_reads *r) {
-  if (r->used == 0) return MFX_OK;
+// a batch of npos positions goes to the device on the next stage; fill(codes, valid, nw) writes its planes of nw words into the stage
+template <class Fill>
+static int reads_send(mfx_reads *r, uint64_t npos, Fill &&fill) {
+  if (npos == 0) return MFX_OK;
   mfx_reads::Stage &s = r->S[r->cur];
   if (int rc = stage_settle(r, s)) return rc;
-  const uint64_t npos = r->used;
   if (r->claim) {
     if (int rc = claim_reserve(r, npos)) {
       r->fail_code = rc;
@@ -204,12 +289,7 @@ static int reads_flush(mfx_reads *r) {
   }
   const uint64_t ntiles = (npos + MFX_TILE - 1) / MFX_TILE;
   const uint64_t nw = std::min(r->words, ntiles * (MFX_TILE / 32) + MFX_TILE_WORDS_HOST);
-  const uint64_t packed = (npos + 31) / 32;
-  mfx_pack_bases(r->bytes.data(), npos, s.hc, s.hv);
-  if (nw > packed) {                                           // the halo of the last tile: invalid bases
-    memset(s.hc + packed, 0, (nw - packed) * sizeof(uint64_t));
-    memset(s.hv + packed, 0, (nw - packed) * sizeof(uint32_t));
-  }
+  fill(s.hc, s.hv, nw);
   mfx_reads_args a;
   a.t = r->ix->view();
   a.codes = s.dc;
@@ -217,15 +297,24 @@ static int reads_flush(mfx_reads *r) {
   a.npos = npos;
   a.meta = r->ix->d_meta;
   a.stats = r->d_stats;
+  a.key_lo = r->key_lo;
+  a.key_hi = r->key_hi;
   MFX_HIP(hipEventRecord(s.e0, s.st));
   MFX_HIP(hipMemcpyAsync(s.dc, s.hc, nw * sizeof(uint64_t), hipMemcpyHostToDevice, s.st));
   MFX_HIP(hipMemcpyAsync(s.dv, s.hv, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
   MFX_HIP(hipEventRecord(s.e1, s.st));
-  MFX_HIP(r->claim ? mfx_k_reads_claim(a, s.st) : r->ix->wide() ? mfx_kw_reads(a, s.st) : mfx_k_reads(a, s.st));
+  MFX_HIP(r->ranged ? mfx_k_reads_claim_range(a, s.st) : r->claim ? mfx_k_reads_claim(a, s.st) : r->ix->wide() ? mfx_kw_reads(a, s.st) : mfx_k_reads(a, s.st));
   MFX_HIP(hipEventRecord(s.e2, s.st));
   s.busy = true;
   r->cur = (r->cur + 1) % MFX_READS_STAGES;
-  r->used = 0;
+  return MFX_OK;
+}
+
+// the batch being filled goes to the device
+static int reads_flush(mfx_reads *r) {
+  const uint64_t npos = r->b.used;
+  if (int rc = reads_send(r, npos, [&](uint64_t *hc, uint32_t *hv, uint64_t nw) { batch_pack(r->b.bytes.data(), npos, nw, hc, hv); })) return rc;
+  r->b.used = 0;
   return MFX_OK;
 }
 
@@ -237,22 +326,16 @@ static mfx_reads *reads_open(mfx_index *ix, uint64_t batch_bases, const char *wh
              "an index takes its read counts from one source", who);
     return nullptr;
   }
-  const uint64_t min_batch = 2ull * (uint64_t)ix->k + 2;
-  if (batch_bases == 0) batch_bases = MFX_READS_BATCH_DEFAULT;
-  if (batch_bases < min_batch) {
-    mfx_fail(MFX_E_INVAL, "%s: a batch of %llu bases is too small for %d-mers (at least %llu)", who, (unsigned long long)batch_bases,
-             ix->k, (unsigned long long)min_batch);
-    return nullptr;
-  }
-  if (batch_bases > (1ull << 34)) { mfx_fail(MFX_E_INVAL, "%s: batch of %llu bases is beyond 2^34", who, (unsigned long long)batch_bases); return nullptr; }
+  batch_bases = batch_size_checked(batch_bases, ix->k, who);
+  if (batch_bases == 0) return nullptr;
   DeviceScope g(ix->device);
   if (!g.ok) { mfx_fail(MFX_E_HIP, "hipSetDevice(%d) failed", ix->device); return nullptr; }
   mfx_reads *r = new mfx_reads;
   r->ix = ix;
   r->claim = claim;
-  r->cap = batch_bases;
+  r->b.cap = batch_bases;
   r->words = (batch_bases + MFX_TILE - 1) / MFX_TILE * (MFX_TILE / 32) + MFX_TILE_WORDS_HOST;
-  r->bytes.resize(batch_bases + 32);
+  r->b.bytes.resize(batch_bases + 32);
   bool ok = hipMalloc((void **)&r->d_stats, 4 * sizeof(uint64_t)) == hipSuccess && mfx_memset_now(r->d_stats, 0, 4 * sizeof(uint64_t)) == hipSuccess;
   for (auto &s : r->S) {
     if (!ok) break;
@@ -296,18 +379,46 @@ extern "C" mfx_reads *mfx_reads_begin(mfx_index *ix, uint64_t batch_bases) {
   return reads_open(ix, batch_bases, "mfx_reads_begin", false);
 }
 
-extern "C" mfx_reads *mfx_reads_begin_all(mfx_index *ix, uint64_t batch_bases) {
-  if (!ix) { mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: null index"); return nullptr; }
+// what a claiming counter asks of the index; `who`: the entry point, for the texts
+static bool claim_index_ok(const mfx_index *ix, const char *who) {
+  if (!ix) { mfx_fail(MFX_E_INVAL, "%s: null index", who); return false; }
   if (ix->seq_only) {
-    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: a sequence-only or path-only index holds the k-mers claimed for it and takes no others -- count every "
-             "k-mer of the reads into a full index (mfx_index_create), or only the claimed ones with mfx_reads_begin");
-    return nullptr;
+    mfx_fail(MFX_E_INVAL, "%s: a sequence-only or path-only index holds the k-mers claimed for it and takes no others -- count every "
+             "k-mer of the reads into a full index (mfx_index_create), or only the claimed ones with mfx_reads_begin", who);
+    return false;
   }
   if (ix->wide()) {
-    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_all: the table that grows holds k <= %d; this index holds %d-mers", MFX_MAX_K_NARROW, ix->k);
+    mfx_fail(MFX_E_INVAL, "%s: the table that grows holds k <= %d; this index holds %d-mers", who, MFX_MAX_K_NARROW, ix->k);
+    return false;
+  }
+  return true;
+}
+
+extern "C" mfx_reads *mfx_reads_begin_all(mfx_index *ix, uint64_t batch_bases) {
+  if (!claim_index_ok(ix, "mfx_reads_begin_all")) return nullptr;
+  return reads_open(ix, batch_bases, "mfx_reads_begin_all", true);
+}
+
+extern "C" mfx_reads *mfx_reads_begin_range(mfx_index *ix, uint64_t batch_bases, uint64_t key_lo, uint64_t key_hi) {
+  if (!claim_index_ok(ix, "mfx_reads_begin_range")) return nullptr;
+  const uint64_t top = 1ull << (2 * ix->k);                    // 4^k (k <= 31)
+  if (key_lo > key_hi) {
+    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_range: the range starts above its end (key_lo %llu > key_hi %llu)", (unsigned long long)key_lo,
+             (unsigned long long)key_hi);
     return nullptr;
   }
-  return reads_open(ix, batch_bases, "mfx_reads_begin_all", true);
+  if (key_hi > top) {
+    mfx_fail(MFX_E_INVAL, "mfx_reads_begin_range: the range ends beyond the %d-mers (key_hi %llu > 4^%d = %llu)", ix->k, (unsigned long long)key_hi, ix->k,
+             (unsigned long long)top);
+    return nullptr;
+  }
+  mfx_reads *r = reads_open(ix, batch_bases, "mfx_reads_begin_range", true);
+  if (r && !(key_lo == 0 && key_hi == top)) {                  // every k-mer: the launches of mfx_reads_begin_all
+    r->ranged = true;
+    r->key_lo = key_lo;
+    r->key_hi = key_hi;
+  }
+  return r;
 }
 
 extern "C" int mfx_index_growths(const mfx_index *ix, uint64_t *n, double *seconds, double *rehash_seconds, uint64_t *rehash_bytes) {
@@ -330,30 +441,114 @@ extern "C" int mfx_reads_add(mfx_reads *r, const char *const *bases, const uint6
   if (!r || (n && (!bases || !lens))) return mfx_fail(MFX_E_INVAL, "mfx_reads_add: null argument");
   if (r->failed) return mfx_fail(MFX_E_INVAL, "mfx_reads_add: an earlier batch failed; end the counter");
   DeviceScope g(r->ix->device);
-  const uint64_t k = (uint64_t)r->ix->k;
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t len = lens[i];
-    r->stats.reads += 1;
-    r->stats.bases += len;
-    if (len < k) continue;                                     // no k-mer
-    if (!bases[i]) return mfx_fail(MFX_E_INVAL, "mfx_reads_add: record %llu has no bases", (unsigned long long)i);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(bases[i]);
-    uint64_t at = 0;
-    while (true) {
-      if (r->cap - r->used < k) {                              // no whole k-mer fits: the batch goes
-        if (int rc = reads_flush(r)) { r->failed = true; return rc; }
-      }
-      const uint64_t take = std::min(len - at, r->cap - r->used);
-      memcpy(r->bytes.data() + r->used, src + at, take);
-      r->used += take;
-      if (at + take == len) {
-        if (r->used < r->cap) r->bytes[r->used++] = 'N';       // (a read that ends the batch needs no separator)
-        break;
-      }
-      at += take - (k - 1);                                    // the rest, from the first k-mer this batch does not hold
-      if (int rc = reads_flush(r)) { r->failed = true; return rc; }
-    }
+  return batch_records(r->b, (uint64_t)r->ix->k, bases, lens, n, r->stats.reads, r->stats.bases, "mfx_reads_add", [&]() {
+    const int rc = reads_flush(r);
+    if (rc) r->failed = true;
+    return rc;
+  });
+}
+
+// ---- the read store ---------------------------------------------------------------------------------------------------------------
+static uint64_t store_batch_bytes(uint64_t npos) { return (npos + 31) / 32 * (sizeof(uint64_t) + sizeof(uint32_t)); }
+
+// the batch being filled is complete: its planes are kept
+static int store_keep(mfx_reads_store *s) {
+  const uint64_t npos = s->b.used;
+  if (npos == 0) return MFX_OK;
+  if (s->max_bytes && s->bytes + store_batch_bytes(npos) > s->max_bytes) { s->complete = false; return 1; }
+  mfx_reads_store::Packed p;
+  const uint64_t nw = (npos + 31) / 32;
+  p.codes.resize(nw);
+  p.valid.resize(nw);
+  batch_pack(s->b.bytes.data(), npos, nw, p.codes.data(), p.valid.data());
+  p.npos = npos;
+  p.reads = s->reads - s->reads_kept;
+  p.bases = s->bases - s->bases_kept;
+  s->reads_kept = s->reads;
+  s->bases_kept = s->bases;
+  s->bytes += store_batch_bytes(npos);
+  s->batches.push_back(std::move(p));
+  s->b.used = 0;
+  return MFX_OK;
+}
+
+extern "C" mfx_reads_store *mfx_reads_store_create(int k, uint64_t batch_bases, uint64_t max_bytes) {
+  if (k < 1 || k > MFX_MAX_K) { mfx_fail(MFX_E_INVAL, "mfx_reads_store_create: k = %d (1 <= k <= %d)", k, MFX_MAX_K); return nullptr; }
+  batch_bases = batch_size_checked(batch_bases, k, "mfx_reads_store_create");
+  if (batch_bases == 0) return nullptr;
+  try {
+    mfx_reads_store *s = new mfx_reads_store;
+    s->k = k;
+    s->max_bytes = max_bytes;
+    s->b.cap = batch_bases;
+    s->b.bytes.resize(batch_bases + 32);
+    return s;
+  } catch (const std::bad_alloc &) { mfx_fail(MFX_E_NOMEM, "mfx_reads_store_create: out of memory"); return nullptr; }
+}
+
+extern "C" int mfx_reads_store_add(mfx_reads_store *s, const char *const *bases, const uint64_t *lens, uint64_t n) {
+  if (!s || (n && (!bases || !lens))) return mfx_fail(MFX_E_INVAL, "mfx_reads_store_add: null argument");
+  if (!s->complete) return 1;
+  try {
+    const int rc = batch_records(s->b, (uint64_t)s->k, bases, lens, n, s->reads, s->bases, "mfx_reads_store_add", [&]() { return store_keep(s); });
+    if (rc < 0) s->complete = false;                           // (a record without bases: what came before it is kept, the store is not the read set)
+    if (rc) return rc;
+    if (s->max_bytes && s->bytes + store_batch_bytes(s->b.used) > s->max_bytes) { s->complete = false; return 1; }
+    return MFX_OK;
+  } catch (const std::bad_alloc &) {
+    s->complete = false;
+    return mfx_fail(MFX_E_NOMEM, "mfx_reads_store_add: out of memory (%llu bytes of batches held)", (unsigned long long)s->bytes);
   }
+}
+
+extern "C" int mfx_reads_store_info(const mfx_reads_store *s, uint64_t *batches, uint64_t *bytes, uint64_t *reads, uint64_t *n_bases, int *complete) {
+  if (!s) return mfx_fail(MFX_E_INVAL, "mfx_reads_store_info: null argument");
+  if (batches) *batches = s->batches.size() + (s->b.used ? 1 : 0);
+  if (bytes) *bytes = s->bytes + store_batch_bytes(s->b.used);
+  if (reads) *reads = s->reads;
+  if (n_bases) *n_bases = s->bases;
+  if (complete) *complete = s->complete ? 1 : 0;
+  return MFX_OK;
+}
+
+extern "C" void mfx_reads_store_free(mfx_reads_store *s) { delete s; }
+
+extern "C" int mfx_reads_replay(mfx_reads *r, const mfx_reads_store *s, uint64_t first_batch, uint64_t n_batches) {
+  if (!r || !s) return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: null argument");
+  if (r->failed) return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: an earlier batch failed; end the counter");
+  if (!s->complete) return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: the store is incomplete (it was full before the reads ended): it is not the read set");
+  if (s->k != r->ix->k) return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: the store holds batches cut for %d-mers, the counter counts %d-mers", s->k, r->ix->k);
+  if (r->b.cap < s->b.cap)
+    return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: the counter's batch of %llu bases is smaller than the store's of %llu", (unsigned long long)r->b.cap,
+                    (unsigned long long)s->b.cap);
+  const uint64_t held = s->batches.size() + (s->b.used ? 1 : 0);
+  if (first_batch > held || n_batches > held - first_batch)
+    return mfx_fail(MFX_E_INVAL, "mfx_reads_replay: batches [%llu, %llu + %llu) of a store of %llu", (unsigned long long)first_batch,
+                    (unsigned long long)first_batch, (unsigned long long)n_batches, (unsigned long long)held);
+  DeviceScope g(r->ix->device);
+  if (int rc = reads_flush(r)) { r->failed = true; return rc; }               // records of mfx_reads_add before: their batch goes first
+  for (uint64_t i = first_batch; i < first_batch + n_batches; ++i) {
+    int rc;
+    if (i < s->batches.size()) {
+      const mfx_reads_store::Packed &p = s->batches[i];
+      rc = reads_send(r, p.npos, [&](uint64_t *hc, uint32_t *hv, uint64_t nw) {
+        const uint64_t packed = p.codes.size();
+        memcpy(hc, p.codes.data(), packed * sizeof(uint64_t));
+        memcpy(hv, p.valid.data(), packed * sizeof(uint32_t));
+        memset(hc + packed, 0, (nw - packed) * sizeof(uint64_t));
+        memset(hv + packed, 0, (nw - packed) * sizeof(uint32_t));
+      });
+      if (rc == MFX_OK) { r->stats.reads += p.reads; r->stats.bases += p.bases; }
+    } else {                                                   // the store's last batch, still as bytes
+      const uint64_t npos = s->b.used;
+      rc = reads_send(r, npos, [&](uint64_t *hc, uint32_t *hv, uint64_t nw) { batch_pack(s->b.bytes.data(), npos, nw, hc, hv); });
+      if (rc == MFX_OK) { r->stats.reads += s->reads - s->reads_kept; r->stats.bases += s->bases - s->bases_kept; }
+    }
+    if (rc) { r->failed = true; return rc; }
+  }
+  // records after the last complete batch that brought no bases (shorter than k): counted by the replay that reaches the store's end (also one of no
+  // batches: a store whose every record is shorter than k)
+  if (first_batch + n_batches == held && s->b.used == 0) { r->stats.reads += s->reads - s->reads_kept; r->stats.bases += s->bases - s->bases_kept; }
   return MFX_OK;
 }
 

@@ -8,6 +8,14 @@ straight from host arrays.  Kernel rates are the reads' k-mers over the counter'
 include the host's batching, packing, the copies, and -- the claiming counter -- the growths.
 
     python tools/count_rate.py [--mb 256] [--cov 30] [--len 150] [--err 0.005] [--k 21] [--reps 2] [--out DIR] [--claim-only]
+
+--passes 1,2,4 [--max-gb G] adds the legs of a count in passes (mfx_reads_begin_range): the same reads are packed once into a read store
+(mfx_reads_store_*), then counted from it in P passes over P equal key ranges (NOT equal shares: a canonical k-mer is the smaller of two, so
+the quarters of the key space hold 7/16, 5/16, 3/16 and 1/16 of an i.i.d. genome's k-mers -- the CLI cuts by the key histogram instead), each
+into an index created small; per pass the kernel seconds, per P the whole call with the writer that joins the tables (DbWriter).
+--passes-files adds, at the largest P, passes that take the reads from mfx_reads_add again (generated anew: what a pass from the files pays on
+the host).
+--max-gb G runs the driver of `-passes auto` under that limit: one range, a refused range cut in two at the median of its table's bins.
 """
 import argparse
 import ctypes as C
@@ -56,6 +64,108 @@ def _feed(torch, L, r, world, a, nreads):
     return t_gen, t_add
 
 
+def _fill_store(torch, m, world, a, nreads):
+    """all reads into a read store; (store, seconds generating, seconds in mfx_reads_store_add)"""
+    L = m.load_library()
+    s = m.ReadsStore(a.k, 0, 0)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    chunk = 1 << 20
+    t_gen = t_add = 0.0
+    done = 0
+    while done < nreads:
+        c = min(chunk, nreads - done)
+        tg = time.time()
+        host = _read_chunk(torch, world, c, a.len, a.err, g).cpu().numpy()
+        t_gen += time.time() - tg
+        ta = time.time()
+        ptrs = (C.c_char_p * c).from_buffer_copy(np.arange(c, dtype=np.uint64) * a.len + host.ctypes.data)
+        lens = np.full(c, a.len, dtype=np.uint64)
+        assert L.mfx_reads_store_add(s.h, ptrs, lens.ctypes.data_as(C.POINTER(C.c_uint64)), c) == 0, L.mfx_last_error()
+        t_add += time.time() - ta
+        done += c
+    return s, t_gen, t_add
+
+
+def _pass_legs(torch, m, world, a, nreads, db):
+    """the legs of --passes / --passes-files / --max-gb"""
+    from merfin_amd.binding import _ReadsStats
+    L = m.load_library()
+    top = 4 ** a.k
+    store, t_gen, t_add = _fill_store(torch, m, world, a, nreads)
+    si = store.info()
+    print("store       %d batches, %.2f GB (%.3f bytes per base), filled in %.2f s of mfx_reads_store_add (generating the reads %.2f s)"
+          % (si["batches"], si["bytes"] / 1e9, si["bytes"] / max(si["bases"], 1), t_add, t_gen), flush=True)
+    for rep in range(a.reps):
+        plist = [int(x) for x in a.passes.split(",") if x]
+        for P in plist:
+            for source in (["store"] + (["add"] if a.passes_files and P > 1 and P == max(plist) else [])):
+                w = m.DbWriter(db, a.k)
+                t0 = time.time()
+                kern, gen_all, n_all = [], 0.0, 0
+                for i in range(P):
+                    lo, hi = top * i // P, top * (i + 1) // P
+                    ix = m.Index(a.k, 1024)
+                    tp = time.time()
+                    if source == "store":
+                        st = store.replay(ix, key_range=(lo, hi))
+                        st_k, st_c = st["seconds_kernel"], st["counted"]
+                    else:
+                        r = L.mfx_reads_begin_range(ix.h, 0, lo, hi)
+                        assert r, L.mfx_last_error()
+                        tg, _ = _feed(torch, L, r, world, a, nreads)
+                        gen_all += tg
+                        rs = _ReadsStats()
+                        assert L.mfx_reads_end(r, C.byref(rs)) == 0, L.mfx_last_error()
+                        st_k, st_c = rs.seconds_kernel, rs.counted
+                    tp = time.time() - tp
+                    kern.append(st_k)
+                    n_all += st_c
+                    gr = ix.growths()
+                    print("rep %d  P=%d %-5s pass %d  counted %.3f G  distinct %.3f G  kernel %.4f s  pass %.2f s  growths %d (%.3f s)  table %.2f GB"
+                          % (rep, P, source, i + 1, st_c / 1e9, ix.info()["distinct"] / 1e9, st_k, tp, gr["growths"], gr["seconds"], ix.info()["bytes"] / 1e9), flush=True)
+                    w.append(ix)
+                    ix.close()
+                t_count = time.time() - t0 - gen_all
+                tw = time.time()
+                nk = w.close()
+                tw = time.time() - tw
+                print("rep %d  P=%d %-5s kernels %.4f s in all (%s); counting and collecting %.2f s (the reads' generation taken out), writing %.2f s; %.3f G k-mers counted, "
+                      "%.3f G written" % (rep, P, source, sum(kern), " + ".join("%.4f" % x for x in kern), t_count, tw, n_all / 1e9, nk / 1e9), flush=True)
+                os.remove(db)
+    if a.max_gb > 0:
+        # the driver of `-passes auto`: one range; a range whose table cannot grow is cut in two at the median of the bins it reached
+        todo, npass, nref = [(0, 4096)], 0, 0
+        shift = 2 * a.k - 12
+        w = m.DbWriter(db, a.k)
+        t0 = time.time()
+        while todo:
+            blo, bhi = todo.pop(0)
+            ix = m.Index(a.k, 1024, max_gb=a.max_gb)
+            tp = time.time()
+            try:
+                st = store.replay(ix, key_range=(blo << shift, bhi << shift))
+            except m.MfxError as e:
+                assert e.code == -2 and bhi - blo > 1, str(e)
+                c = np.cumsum(ix.key_bins(0)[blo:bhi].astype(np.float64))
+                cut = blo + 1 + int(np.searchsorted(c[:-1], c[-1] / 2))
+                cut = min(max(cut, blo + 1), bhi - 1)
+                print("forced      bins [%d, %d) refused after %.2f s at %.2f GB: %s; cut at %d" % (blo, bhi, time.time() - tp, ix.info()["bytes"] / 1e9, str(e)[:110], cut),
+                      flush=True)
+                ix.close()
+                todo[:0] = [(blo, cut), (cut, bhi)]
+                nref += 1
+                continue
+            npass += 1
+            print("forced      pass %d bins [%d, %d)  counted %.3f G  distinct %.3f G  kernel %.4f s  pass %.2f s  table %.2f GB"
+                  % (npass, blo, bhi, st["counted"] / 1e9, ix.info()["distinct"] / 1e9, st["seconds_kernel"], time.time() - tp, ix.info()["bytes"] / 1e9), flush=True)
+            w.append(ix)
+            ix.close()
+        nk = w.close()
+        print("forced      max_gb %.3f: %d passes, %d refused and split, %.3f G k-mers written, %.2f s in all" % (a.max_gb, npass, nref, nk / 1e9, time.time() - t0), flush=True)
+        os.remove(db)
+    store.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=int, default=256)
@@ -66,6 +176,10 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--claim-only", action="store_true", help="only the claiming counter's leg (A/B of two builds through MFX_LIB)")
     ap.add_argument("--out", default=None, help="directory of the database written (default: tmpfs)")
+    ap.add_argument("--passes", default="", help="e.g. 1,2,4: also count from a read store in that many passes over equal key ranges")
+    ap.add_argument("--passes-files", action="store_true", help="with --passes: at the largest P also passes fed through mfx_reads_add again")
+    ap.add_argument("--passes-only", action="store_true", help="only the legs of --passes / --max-gb")
+    ap.add_argument("--max-gb", type=float, default=0.0, help="with --passes: also the driver of -passes auto under this table limit")
     a = ap.parse_args()
     import torch
     import merfin_amd as m
@@ -84,7 +198,9 @@ def main():
     out_dir = a.out or tempfile.mkdtemp(prefix="mfx_count_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     db = os.path.join(out_dir, "reads.mfxk")
     try:
-        for rep in range(a.reps):
+        if a.passes or a.max_gb > 0:
+            _pass_legs(torch, m, world, a, nreads, db)
+        for rep in range(0 if a.passes_only else a.reps):
             # ---- the claiming counter into a table created small
             ix = m.Index(a.k, 1024)
             r = L.mfx_reads_begin_all(ix.h, 0)
