@@ -93,6 +93,7 @@ SYMBOLS = [
     "mfx_reads_begin", "mfx_reads_set_filter", "mfx_reads_add", "mfx_reads_end",
     "mfx_reads_begin_all", "mfx_index_growths", "mfx_index_write_db",
     "mfx_reads_begin_range", "mfx_index_key_bins", "mfx_db_writer_open", "mfx_db_writer_append_index", "mfx_db_writer_close", "mfx_db_writer_abort",
+    "mfx_db_writer_open_streamed", "mfx_db_writer_append_sorted", "mfx_db_writer_info", "mfx_index_write_db_streamed",
     "mfx_reads_store_create", "mfx_reads_store_add", "mfx_reads_store_info", "mfx_reads_replay", "mfx_reads_store_free",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
@@ -318,6 +319,11 @@ def load_library():
     L.mfx_db_writer_close.argtypes = [vp, u64p]
     L.mfx_db_writer_abort.restype = None
     L.mfx_db_writer_abort.argtypes = [vp]
+    L.mfx_db_writer_open_streamed.restype = vp
+    L.mfx_db_writer_open_streamed.argtypes = [C.c_char_p, C.c_int]
+    L.mfx_db_writer_append_sorted.argtypes = [vp, u64p, C.POINTER(C.c_uint32), C.c_uint64]
+    L.mfx_db_writer_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p]
+    L.mfx_index_write_db_streamed.argtypes = [vp, C.c_int, C.c_char_p, u64p]
     L.mfx_reads_store_create.restype = vp
     L.mfx_reads_store_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
     L.mfx_reads_store_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
@@ -676,11 +682,13 @@ class Index:
         _check(load_library().mfx_index_growths(self.h, C.byref(n), C.byref(s), C.byref(rs), C.byref(b)))
         return {"growths": n.value, "seconds": s.value, "rehash_seconds": rs.value, "rehash_bytes": b.value}
 
-    def write_db(self, path, side=0):
+    def write_db(self, path, side=0, streamed=False):
         """the k-mers with a non-zero count on `side` (0: reads, 1: assembly) as the sorted flat database db_write_flat makes of them
-        (mfx_index_write_db); returns their number"""
+        (mfx_index_write_db); returns their number.  streamed: the blocks are coded on the device and go to disk as they are made
+        (mfx_index_write_db_streamed) -- the same bytes"""
         n = C.c_uint64(0)
-        _check(load_library().mfx_index_write_db(self.h, int(side), path.encode(), C.byref(n)))
+        L = load_library()
+        _check((L.mfx_index_write_db_streamed if streamed else L.mfx_index_write_db)(self.h, int(side), str(path).encode(), C.byref(n)))
         return n.value
 
     def _count_reads(self, begin, reads, batch_bases, minV, maxV, chunk):
@@ -775,10 +783,13 @@ class Index:
 
 class DbWriter:
     """a k-mer database written from several tables in ascending key order (mfx_db_writer_*): append(index) per table, then close() writes
-    the file db_write_flat makes of everything appended; nothing exists at `path` before.  abort() (or dropping the object) writes nothing."""
+    the file db_write_flat makes of everything appended; nothing exists at `path` before.  abort() (or dropping the object) writes nothing.
+    streamed: the blocks go to the spool `path`.blocks as they are made (mfx_db_writer_open_streamed) and the host keeps the directory, the
+    escapes and less than one block of k-mers; close() puts header, directory, spool and escapes together -- the same bytes."""
 
-    def __init__(self, path, k):
-        self.h = _need(load_library().mfx_db_writer_open(str(path).encode(), int(k)))
+    def __init__(self, path, k, streamed=False):
+        L = load_library()
+        self.h = _need((L.mfx_db_writer_open_streamed if streamed else L.mfx_db_writer_open)(str(path).encode(), int(k)))
 
     def append(self, index, side=0):
         """the k-mers of `index` with a non-zero count on `side` behind those held; they must start above the last one held (else MfxError,
@@ -786,6 +797,22 @@ class DbWriter:
         n = C.c_uint64(0)
         _check(load_library().mfx_db_writer_append_index(self.h, index.h, int(side), C.byref(n)))
         return n.value
+
+    def append_sorted(self, kmers, values):
+        """host arrays, strictly ascending and above the last k-mer held (else MfxError, nothing added); returns their number"""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        if len(kmers) != len(values):
+            raise ValueError("append_sorted: %d k-mers, %d values" % (len(kmers), len(values)))
+        _check(load_library().mfx_db_writer_append_sorted(self.h, kmers.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                          values.ctypes.data_as(C.POINTER(C.c_uint32)), len(kmers)))
+        return len(kmers)
+
+    def info(self):
+        """{kmers, blocks, escapes, spool_bytes, held_bytes} (mfx_db_writer_info); held_bytes: the host memory that grows with the database"""
+        v = [C.c_uint64(0) for _ in range(5)]
+        _check(load_library().mfx_db_writer_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("kmers", "blocks", "escapes", "spool_bytes", "held_bytes"), (x.value for x in v)))
 
     def close(self):
         n = C.c_uint64(0)

@@ -864,7 +864,22 @@ static uint64_t half_of_available_memory() {
 }
 }  // namespace
 
+// the writer of -count: the streamed one (the blocks are coded on the device and go to disk as they are made) unless MFX_COUNT_WRITER=host
+// asks for the one that collects the k-mers on the host (docs/KNOBS.md); both write the same bytes.  -1: the knob holds something else
+static int count_writer_streamed() {
+  if (const char *e = getenv("MFX_COUNT_WRITER")) {
+    if (!strcmp(e, "host")) return 0;
+    if (!strcmp(e, "stream")) return 1;
+    fprintf(stderr, "ERROR: -count: MFX_COUNT_WRITER is 'stream' or 'host', not '%s'.\n", e);
+    return -1;
+  }
+  const char *de = getenv("MFX_FLAT_DELTA");                      // (another form than delta-coded blocks: only the host writer makes it)
+  return !(de && atoi(de) == 0);
+}
+
 static int count_in_passes(const Globals &G) {
+  const int streamed = count_writer_streamed();
+  if (streamed < 0) return 1;
   CountPasses C(G);
   if (const char *e = getenv("MFX_COUNT_BATCH")) C.batch = strtoull(e, nullptr, 10);
   const int bits = std::min(2 * G.kArg, 12);
@@ -873,7 +888,7 @@ static int count_in_passes(const Globals &G) {
   uint64_t store_bytes = half_of_available_memory();
   if (const char *e = getenv("MFX_COUNT_STORE_GB")) store_bytes = (uint64_t)(std::max(0.0, strtod(e, nullptr)) * 1e9);
   const uint32_t P = G.passesAuto ? 1 : G.passes;
-  C.w = mfx_db_writer_open(G.outName, G.kArg);
+  C.w = streamed ? mfx_db_writer_open_streamed(G.outName, G.kArg) : mfx_db_writer_open(G.outName, G.kArg);
   if (!C.w) DIE_MFX("-count");
   struct StoreGuard { mfx_reads_store *s; ~StoreGuard() { if (s) mfx_reads_store_free(s); } } SG{nullptr};
   if (store_bytes) {
@@ -1169,6 +1184,8 @@ int main(int argc, char **argv) {
               G.readsNames.size() == 1 ? "" : "s");
       return count_in_passes(G);
     }
+    const int streamed = count_writer_streamed();
+    if (streamed < 0) return 1;
     // the table is created small and grows with what the reads hold (mfx_reads_begin_all)
     const auto tc0 = std::chrono::steady_clock::now();
     uint64_t count_batch = 0;                                      // MFX_COUNT_BATCH (docs/KNOBS.md): bases per device batch; unset: the library's
@@ -1194,7 +1211,7 @@ int main(int argc, char **argv) {
             growths == 1 ? "" : "s", (double)info.bytes / 1e9);
     const auto tc1 = std::chrono::steady_clock::now();
     uint64_t n = 0;
-    if (mfx_index_write_db(ix, 0, G.outName, &n)) DIE_MFX("-count: writing the database");
+    if (streamed ? mfx_index_write_db_streamed(ix, 0, G.outName, &n) : mfx_index_write_db(ix, 0, G.outName, &n)) DIE_MFX("-count: writing the database");
     struct stat ost;
     fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
     if (stat(G.outName, &ost) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", ost.st_size / 1e9, (double)ost.st_size / (double)n);

@@ -21,6 +21,7 @@
 #include "mfx_place.h"
 
 #include <dirent.h>
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,6 +34,7 @@
 #include <atomic>
 #include <chrono>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -618,27 +620,19 @@ inline bool text_is_plain(const std::string &path) { return mfx_suffix_tool(path
 // ---- delta-coded flat form ---------------------------------------------------
 struct DeltaBlockPlan { uint8_t kb = 0, vb = 2; uint32_t nesc = 0; uint64_t bytes = 0; };
 
-inline uint32_t bit_length(uint64_t x) { return x ? 64u - (uint32_t)__builtin_clzll(x) : 0u; }
-
-// widths and size of block [b, b + cnt) of a strictly ascending database
+// widths and size of block [b, b + cnt) of a strictly ascending database: the rule itself is mfx_delta.h, shared with the encoder kernels
 DeltaBlockPlan plan_delta_block(const uint64_t *kmers, const uint32_t *values, uint32_t cnt) {
   DeltaBlockPlan p;
   uint64_t maxd = 0;
   for (uint32_t i = 1; i < cnt; ++i) maxd = std::max(maxd, kmers[i] - kmers[i - 1]);
-  p.kb = (uint8_t)bit_length(maxd);
-  uint32_t hist[34] = {0};                                    // bit length of value + 1: a value fits vb bits iff that is <= vb
-  for (uint32_t i = 0; i < cnt; ++i) ++hist[bit_length((uint64_t)values[i] + 1)];
-  uint64_t best = ~0ull;
-  uint32_t above = 0;                                         // values that need more than vb bits
-  for (int vb = 33; vb >= 2; --vb) {
-    if (vb <= MFX_DELTA_MAX_VBITS) {
-      const uint64_t cost = (uint64_t)cnt * vb + 96ull * above;
-      if (cost <= best) { best = cost; p.vb = (uint8_t)vb; p.nesc = above; }
-    }
-    above += hist[vb];
-  }
-  const uint64_t kwords = ((uint64_t)(cnt - 1) * p.kb + 63) / 64, vwords = ((uint64_t)cnt * p.vb + 63) / 64;
-  p.bytes = (kwords + vwords) * 8;
+  p.kb = (uint8_t)mfx_bit_length(maxd);
+  uint32_t hist[MFX_DELTA_VBINS] = {0};                       // bit length of value + 1: a value fits vb bits iff that is <= vb
+  for (uint32_t i = 0; i < cnt; ++i) ++hist[mfx_delta_vbin(values[i])];
+  uint32_t vb, nesc;
+  mfx_delta_vbits(hist, cnt, vb, nesc);
+  p.vb = (uint8_t)vb;
+  p.nesc = nesc;
+  p.bytes = mfx_delta_bytes(cnt, p.kb, p.vb);
   return p;
 }
 
@@ -1455,7 +1449,7 @@ constexpr uint64_t MFX_DB_RANGE_DEFAULT = 1ull << 28;        // entries per rang
 
 namespace {
 struct DbDev {                                                 // device buffers of one call, freed on every way out
-  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~DbDev() { for (void *x : p) if (x) (void)hipFree(x); }
 };
 }  // namespace
@@ -1515,10 +1509,302 @@ struct mfx_db_writer {
   int k = 0;
   std::vector<uint64_t> keys;
   std::vector<uint32_t> vals;
+  // the streamed kind (mfx_db_writer_open_streamed): the blocks go to the spool <path>.blocks as they are made.  What stays on the host is
+  // the directory (16 bytes per MFX_DELTA_BLOCK k-mers), the escapes and the carry: the fewer than MFX_DELTA_BLOCK pairs behind the last
+  // full block.  close writes header and directory, puts the spool behind them, then the escapes: the bytes of write_flat_delta.
+  bool streamed = false;
+  std::string spool;
+  int fd = -1;
+  uint64_t n = 0, spool_bytes = 0;                             // k-mers appended (those of the carry too); bytes of the spool
+  std::vector<uint64_t> dir;                                   // per block written: its first k-mer, its spool offset | kb << 48 | vb << 56
+  std::vector<uint64_t> ek;                                    // the escapes, in the file's order
+  std::vector<uint32_t> ev;
+  std::vector<uint64_t> ck;                                    // the carry
+  std::vector<uint32_t> cv;
+  uint64_t last = 0;                                           // the last k-mer appended (n > 0)
+  size_t bounce = 16u << 20;                                   // bytes of one pinned bounce buffer (MFX_DB_BOUNCE, read at open)
+  double t_export = 0, t_sort = 0, t_plan = 0, t_pack = 0, t_copy = 0, t_spool = 0;      // MFX_DB_TIMING
+  ~mfx_db_writer() {
+    if (fd >= 0) close(fd);
+    if (streamed && !spool.empty()) unlink(spool.c_str());
+  }
 };
 
+static double db_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+static int spool_write(mfx_db_writer *w, const void *p, uint64_t bytes) {         // behind the spool's end
+  const char *c = (const char *)p;
+  for (uint64_t done = 0; done < bytes;) {
+    const ssize_t r = pwrite(w->fd, c + done, bytes - done, (off_t)(w->spool_bytes + done));
+    if (r <= 0) return mfx_fail(MFX_E_IO, "writing '%s' failed: %s", w->spool.c_str(), strerror(errno));
+    done += (uint64_t)r;
+  }
+  w->spool_bytes += bytes;
+  return MFX_OK;
+}
+
+namespace {
+// an append to a streamed writer that fails adds nothing: spool, directory, escapes and carry as they were
+struct StreamUndo {
+  mfx_db_writer *w;
+  uint64_t n, spool_bytes, last;
+  size_t ndir, nesc;
+  std::vector<uint64_t> ck;
+  std::vector<uint32_t> cv;
+  bool keep = false;
+  explicit StreamUndo(mfx_db_writer *w_) : w(w_), n(w_->n), spool_bytes(w_->spool_bytes), last(w_->last), ndir(w_->dir.size()), nesc(w_->ek.size()),
+                                           ck(w_->ck), cv(w_->cv) {}
+  ~StreamUndo() {
+    if (keep) return;
+    w->n = n; w->last = last;
+    w->dir.resize(ndir); w->ek.resize(nesc); w->ev.resize(nesc);
+    w->ck.swap(ck); w->cv.swap(cv);
+    if (w->spool_bytes != spool_bytes) { w->spool_bytes = spool_bytes; (void)!ftruncate(w->fd, (off_t)spool_bytes); }
+  }
+};
+
+// full blocks packed on the host (pack_delta_block) and written to the spool a few MB at a time
+struct StreamHostOut {
+  mfx_db_writer *w;
+  std::vector<uint64_t> buf;
+  uint64_t pending = 0;                                        // bytes of buf not yet in the spool
+  int add(const uint64_t *k, const uint32_t *v, uint32_t cnt) {
+    const DeltaBlockPlan p = plan_delta_block(k, v, cnt);
+    if (buf.size() < (pending + p.bytes) / 8) buf.resize((pending + p.bytes) / 8);
+    pack_delta_block(k, v, cnt, p, buf.data() + pending / 8);
+    w->dir.push_back(k[0]);
+    w->dir.push_back((w->spool_bytes + pending) | ((uint64_t)p.kb << 48) | ((uint64_t)p.vb << 56));
+    pending += p.bytes;
+    if (p.nesc) {
+      const uint32_t esc = (1u << p.vb) - 1u;
+      for (uint32_t i = 0; i < cnt; ++i) if (v[i] >= esc) { w->ek.push_back(k[i]); w->ev.push_back(v[i]); }
+    }
+    return pending >= (8u << 20) ? flush() : MFX_OK;
+  }
+  int flush() {
+    const uint64_t b = pending;
+    pending = 0;
+    return b ? spool_write(w, buf.data(), b) : MFX_OK;
+  }
+};
+}  // namespace
+
+// strictly ascending host arrays behind what a streamed writer holds (the caller checked the order)
+static int stream_append_host(mfx_db_writer *w, const uint64_t *kmers, const uint32_t *values, uint64_t n) {
+  if (n == 0) return MFX_OK;
+  StreamUndo undo(w);
+  StreamHostOut out{w};
+  uint64_t pos = 0;
+  if (!w->ck.empty()) {                                        // the carry first: filled up to a block, if the append reaches that far
+    pos = std::min<uint64_t>(MFX_DELTA_BLOCK - w->ck.size(), n);
+    w->ck.insert(w->ck.end(), kmers, kmers + pos);
+    w->cv.insert(w->cv.end(), values, values + pos);
+    if (w->ck.size() == MFX_DELTA_BLOCK) {
+      if (int rc = out.add(w->ck.data(), w->cv.data(), MFX_DELTA_BLOCK)) return rc;
+      w->ck.clear();
+      w->cv.clear();
+    }
+  }
+  for (; n - pos >= MFX_DELTA_BLOCK; pos += MFX_DELTA_BLOCK)
+    if (int rc = out.add(kmers + pos, values + pos, MFX_DELTA_BLOCK)) return rc;
+  if (pos < n) {                                               // (the carry is empty here)
+    w->ck.assign(kmers + pos, kmers + n);
+    w->cv.assign(values + pos, values + n);
+  }
+  if (int rc = out.flush()) return rc;
+  w->n += n;
+  w->last = kmers[n - 1];
+  undo.keep = true;
+  return MFX_OK;
+}
+
 // the device part: the side's entries, by key ranges compacted out of the table, sorted and copied behind what the writer holds
+namespace {
+struct DbBounce {                                              // two pinned buffers and their events: the packed bytes' way to the spool
+  void *pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~DbBounce() {
+    for (void *x : pin) if (x) (void)hipHostFree(x);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+}  // namespace
+
+// `bytes` of device memory behind the spool's end: the copy of piece i + 1 runs while piece i is written
+static int spool_from_device(mfx_db_writer *w, DbBounce &B, const char *src, uint64_t bytes, double &t_copy, double &t_write) {
+  const uint64_t piece = w->bounce;
+  const uint64_t np = (bytes + piece - 1) / piece;
+  auto len = [&](uint64_t i) { return std::min<uint64_t>(piece, bytes - i * piece); };
+  for (uint64_t i = 0; i <= np; ++i) {
+    if (i < np) {
+      MFX_HIP(hipMemcpyAsync(B.pin[i & 1], src + i * piece, len(i), hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipEventRecord(B.ev[i & 1], nullptr));
+    }
+    if (i > 0) {
+      const double t0 = db_now();
+      MFX_HIP(hipEventSynchronize(B.ev[(i - 1) & 1]));
+      const double t1 = db_now();
+      if (int rc = spool_write(w, B.pin[(i - 1) & 1], len(i - 1))) return rc;
+      t_copy += t1 - t0;
+      t_write += db_now() - t1;
+    }
+  }
+  return MFX_OK;
+}
+
+// the device part of the streamed kind: per key range export and sort as below, the sort's output behind the carry; the full blocks are
+// planned and packed on the device (mfx_sort.hip) and reach the spool through the bounce buffers; what is left is the next carry
+static int db_append_index_streamed(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added, const char *who) {
+  if (n_added) *n_added = 0;
+  if (int rc = db_side_checks(ix, side, who)) return rc;
+  if (ix->k != w->k) return mfx_fail(MFX_E_INVAL, "%s: the writer holds %d-mers, the index %d-mers", who, w->k, ix->k);
+  uint64_t R = MFX_DB_RANGE_DEFAULT;
+  if (const char *e = getenv("MFX_WRITE_DB_RANGE")) {
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
+  }
+  DeviceBack back;
+  MFX_HIP(hipSetDevice(ix->device));
+  const int key_bits = 2 * ix->k, bin_bits = std::min(key_bits, MFX_DB_BIN_BITS), shift = key_bits - bin_bits;
+  const uint32_t nbins = 1u << bin_bits;
+  mfx_table_view t = ix->view();
+  DbDev D;
+  MFX_HIP(hipMalloc(&D.p[0], (nbins + 1) * sizeof(uint64_t)));     // the bins, then the export's counter
+  uint64_t *d_bins = (uint64_t *)D.p[0];
+  unsigned long long *d_count = (unsigned long long *)(d_bins + nbins);
+  std::vector<uint64_t> bins;
+  if (int rc = db_side_bins(ix, side, d_bins, bins)) return rc;
+  std::vector<mfx_bin_range> ranges;
+  mfx_group_bins(bins.data(), nbins, R, ranges);
+  uint64_t n = 0, maxn = 0;
+  for (const auto &r : ranges) { n += r.n; maxn = std::max(maxn, r.n); }
+  if (n == 0) return MFX_OK;
+  StreamUndo undo(w);
+  // cap pairs: a range behind a carry.  p[1]: the export's k-mers, then its counts -- 12 bytes a pair, free again after the sort: a block
+  // takes at most (62 + 22) bits a pair, so the packed words go there.  p[2], p[4]: the sorted pairs.  p[3]: plan and offsets of the blocks.
+  const uint64_t cap = maxn + MFX_DELTA_BLOCK - 1, maxb = cap / MFX_DELTA_BLOCK;
+  size_t tmp_bytes = 0;
+  if (int rc = mfx_sort_db_pairs(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, maxn, key_bits, nullptr)) return rc;
+  hipError_t e = hipMalloc(&D.p[1], cap * 12);
+  if (e == hipSuccess) e = hipMalloc(&D.p[2], cap * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[4], cap * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&D.p[5], tmp_bytes ? tmp_bytes : 1);
+  if (e == hipSuccess) e = hipMalloc(&D.p[3], (maxb ? maxb : 1) * (sizeof(mfx_delta_plan) + 8 + 4));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a key range of %lu k-mers (%.3f GB) do not fit the device: %s; lower MFX_WRITE_DB_RANGE", who,
+                    (unsigned long)maxn, ((double)cap * 24 + (double)tmp_bytes) / 1e9, hipGetErrorString(e));
+  }
+  uint64_t *x_keys = (uint64_t *)D.p[1], *s_keys = (uint64_t *)D.p[2], *d_out = (uint64_t *)D.p[1];
+  uint32_t *x_vals = (uint32_t *)((char *)D.p[1] + cap * 8), *s_vals = (uint32_t *)D.p[4];
+  mfx_delta_plan *d_plan = (mfx_delta_plan *)D.p[3];
+  uint64_t *d_woff = (uint64_t *)(d_plan + maxb);
+  uint32_t *d_eoff = (uint32_t *)(d_woff + maxb);
+  uint64_t esc_cap = 0;                                        // pairs p[6] (k-mers) and p[7] (counts) hold: grown to what a range escapes
+  DbBounce B;
+  for (int i = 0; i < 2; ++i) {
+    MFX_HIP(hipHostMalloc(&B.pin[i], w->bounce, hipHostMallocDefault));
+    MFX_HIP(hipEventCreateWithFlags(&B.ev[i], hipEventDisableTiming));
+  }
+  std::vector<mfx_delta_plan> plan;
+  std::vector<uint64_t> woff;
+  std::vector<uint32_t> eoff;
+  const bool had = w->n != 0;
+  const uint64_t before = w->last;
+  bool first = true;
+  for (const auto &r : ranges) {
+    double t0 = db_now();
+    MFX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), nullptr));
+    MFX_HIP(mfx_k_db_export(t, side, shift, r.bin_lo, r.bin_hi, x_keys, x_vals, maxn, d_count, nullptr));
+    unsigned long long got = 0;
+    MFX_HIP(hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipStreamSynchronize(nullptr));
+    if (got != r.n)
+      return mfx_fail(MFX_E_INVAL, "%s: the table changed while it was written (a key range held %lu k-mers, then %lu); nothing else may "
+                      "use the index during the call", who, (unsigned long)r.n, (unsigned long)got);
+    double t1 = db_now();
+    w->t_export += t1 - t0;
+    if (r.n == 0) continue;
+    const uint64_t c = w->ck.size(), m = c + r.n, nb = m / MFX_DELTA_BLOCK, rem = m % MFX_DELTA_BLOCK;      // m <= cap: c < MFX_DELTA_BLOCK, r.n <= maxn
+    if (c) {
+      MFX_HIP(hipMemcpyAsync(s_keys, w->ck.data(), c * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
+      MFX_HIP(hipMemcpyAsync(s_vals, w->cv.data(), c * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+    }
+    if (int rc = mfx_sort_db_pairs(D.p[5], tmp_bytes, x_keys, s_keys + c, x_vals, s_vals + c, r.n, key_bits, nullptr)) return rc;
+    uint64_t ends[2] = {0, 0};                                   // the range's first and last k-mer
+    MFX_HIP(hipMemcpyAsync(&ends[0], s_keys + c, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipMemcpyAsync(&ends[1], s_keys + m - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+    MFX_HIP(hipStreamSynchronize(nullptr));
+    t0 = db_now();
+    w->t_sort += t0 - t1;
+    if (first && had && ends[0] <= before)
+      return mfx_fail(MFX_E_INVAL, "%s: the appended k-mers start at %llu, not above the writer's last k-mer %llu: tables are appended in ascending key order, "
+                      "their key ranges apart", who, (unsigned long long)ends[0], (unsigned long long)before);
+    first = false;
+    if (nb) {
+      MFX_HIP(mfx_k_delta_plan(s_keys, s_vals, (uint32_t)nb, d_plan, nullptr));
+      plan.resize(nb);
+      MFX_HIP(hipMemcpy(plan.data(), d_plan, nb * sizeof(mfx_delta_plan), hipMemcpyDeviceToHost));
+      woff.resize(nb);
+      eoff.resize(nb);
+      uint64_t words = 0, escapes = 0;
+      for (uint64_t b = 0; b < nb; ++b) {                      // the plain scan: where every block's words and escapes start
+        const uint32_t kb = plan[b].widths & 0xffu, vb = plan[b].widths >> 8;
+        woff[b] = words;
+        eoff[b] = (uint32_t)escapes;
+        w->dir.push_back(plan[b].first);
+        w->dir.push_back((w->spool_bytes + words * 8) | ((uint64_t)kb << 48) | ((uint64_t)vb << 56));
+        words += mfx_delta_bytes(MFX_DELTA_BLOCK, kb, vb) / 8;
+        escapes += plan[b].nesc;
+      }
+      if (words * 8 > cap * 12 || escapes > m) return mfx_fail(MFX_E_HIP, "%s: the block plan of a key range is damaged", who);      // (nothing is packed beyond the buffers)
+      if (escapes > esc_cap) {
+        for (int i = 6; i < 8; ++i) if (D.p[i]) { (void)hipFree(D.p[i]); D.p[i] = nullptr; }
+        hipError_t ee = hipMalloc(&D.p[6], escapes * sizeof(uint64_t));
+        if (ee == hipSuccess) ee = hipMalloc(&D.p[7], escapes * sizeof(uint32_t));
+        if (ee != hipSuccess) {
+          (void)hipGetLastError();
+          return mfx_fail(MFX_E_NOMEM, "%s: the %lu escapes of a key range do not fit the device: %s; lower MFX_WRITE_DB_RANGE", who, (unsigned long)escapes,
+                          hipGetErrorString(ee));
+        }
+        esc_cap = escapes;
+      }
+      MFX_HIP(hipMemcpyAsync(d_woff, woff.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
+      MFX_HIP(hipMemcpyAsync(d_eoff, eoff.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+      t1 = db_now();
+      w->t_plan += t1 - t0;
+      MFX_HIP(mfx_k_delta_pack(s_keys, s_vals, (uint32_t)nb, d_plan, d_woff, d_eoff, d_out, (uint64_t *)D.p[6], (uint32_t *)D.p[7], nullptr));
+      MFX_HIP(hipStreamSynchronize(nullptr));                  // (woff / eoff are pageable: their copies are done before the next range changes them)
+      t0 = db_now();
+      w->t_pack += t0 - t1;
+      if (int rc = spool_from_device(w, B, (const char *)d_out, words * 8, w->t_copy, w->t_spool)) return rc;
+      if (escapes) {
+        const size_t held = w->ek.size();
+        w->ek.resize(held + escapes);
+        w->ev.resize(held + escapes);
+        MFX_HIP(hipMemcpy(w->ek.data() + held, D.p[6], escapes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        MFX_HIP(hipMemcpy(w->ev.data() + held, D.p[7], escapes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      }
+    }
+    w->ck.resize(rem);
+    w->cv.resize(rem);
+    if (rem && nb) {                                           // (no block made: the carry only grew, by what the sort put behind it)
+      MFX_HIP(hipMemcpy(w->ck.data(), s_keys + nb * MFX_DELTA_BLOCK, rem * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(w->cv.data(), s_vals + nb * MFX_DELTA_BLOCK, rem * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } else if (rem) {
+      MFX_HIP(hipMemcpy(w->ck.data() + c, s_keys + c, r.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(w->cv.data() + c, s_vals + c, r.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    w->n += r.n;
+    w->last = ends[1];
+  }
+  undo.keep = true;
+  if (n_added) *n_added = n;
+  return MFX_OK;
+}
+
 static int db_append_index(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added, const char *who) {
+  if (w->streamed) return db_append_index_streamed(w, ix, side, n_added, who);
   if (n_added) *n_added = 0;
   if (int rc = db_side_checks(ix, side, who)) return rc;
   if (ix->k != w->k) return mfx_fail(MFX_E_INVAL, "%s: the writer holds %d-mers, the index %d-mers", who, w->k, ix->k);
@@ -1608,12 +1894,141 @@ extern "C" int mfx_db_writer_append_index(mfx_db_writer *w, const mfx_index *ix,
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_writer_append_index: %s", e.what()); }
 }
 
+static int db_open_streamed(const char *path, int k, mfx_db_writer **out) {
+  *out = nullptr;
+  if (!path) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_open_streamed: null argument");
+  if (k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_open_streamed: the sorted form holds 1 <= k <= %d; k = %d", MFX_MAX_K_NARROW, k);
+  if (const char *de = getenv("MFX_FLAT_DELTA"))
+    if (atoi(de) == 0) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_open_streamed: the streamed writer makes delta-coded blocks; MFX_FLAT_DELTA=0 asks for another form");
+  try {
+    std::unique_ptr<mfx_db_writer> w(new mfx_db_writer);
+    w->path = path;
+    w->k = k;
+    w->streamed = true;
+    if (const char *e = getenv("MFX_DB_BOUNCE")) {               // bytes of a bounce buffer: tests reach several pieces on small tables
+      const long long v = atoll(e);
+      if (v >= 8 && (uint64_t)v < w->bounce) w->bounce = (size_t)v & ~(size_t)7;
+    }
+    const std::string spool = w->path + ".blocks";
+    w->fd = open(spool.c_str(), O_RDWR | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (w->fd < 0) return mfx_fail(MFX_E_IO, "mfx_db_writer_open_streamed: cannot create the spool '%s': %s", spool.c_str(), strerror(errno));
+    w->spool = spool;                                            // (set once the file is this writer's: only then is it removed with it)
+    *out = w.release();
+    return MFX_OK;
+  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_writer_open_streamed: out of memory"); }
+}
+
+extern "C" mfx_db_writer *mfx_db_writer_open_streamed(const char *path, int k) {
+  mfx_db_writer *w = nullptr;
+  (void)db_open_streamed(path, k, &w);
+  return w;
+}
+
+static int db_append_sorted(mfx_db_writer *w, const uint64_t *kmers, const uint32_t *values, uint64_t n) {
+  if (n == 0) return MFX_OK;
+  const bool had = w->streamed ? w->n != 0 : !w->keys.empty();
+  const uint64_t before = w->streamed ? w->last : (had ? w->keys.back() : 0);
+  if (had && kmers[0] <= before)
+    return mfx_fail(MFX_E_INVAL, "mfx_db_writer_append_sorted: the appended k-mers start at %llu, not above the writer's last k-mer %llu", (unsigned long long)kmers[0],
+                    (unsigned long long)before);
+  for (uint64_t i = 1; i < n; ++i)
+    if (kmers[i] <= kmers[i - 1])
+      return mfx_fail(MFX_E_INVAL, "mfx_db_writer_append_sorted: the k-mers are not strictly ascending (k-mer %lu is %llu, the one before it %llu)", (unsigned long)i,
+                      (unsigned long long)kmers[i], (unsigned long long)kmers[i - 1]);
+  if (w->streamed) return stream_append_host(w, kmers, values, n);
+  const size_t held = w->keys.size();
+  try {
+    w->keys.insert(w->keys.end(), kmers, kmers + n);
+    w->vals.insert(w->vals.end(), values, values + n);
+  } catch (...) { w->keys.resize(held); w->vals.resize(held); throw; }
+  return MFX_OK;
+}
+
+extern "C" int mfx_db_writer_append_sorted(mfx_db_writer *w, const uint64_t *kmers, const uint32_t *values, uint64_t n) {
+  if (!w || (n && (!kmers || !values))) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_append_sorted: null argument");
+  try { return db_append_sorted(w, kmers, values, n); }
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_writer_append_sorted: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_writer_append_sorted: %s", e.what()); }
+}
+
+extern "C" int mfx_db_writer_info(const mfx_db_writer *w, uint64_t *kmers, uint64_t *blocks, uint64_t *escapes, uint64_t *spool_bytes, uint64_t *held_bytes) {
+  if (!w) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_info: null argument");
+  if (kmers) *kmers = w->streamed ? w->n : w->keys.size();
+  if (blocks) *blocks = w->dir.size() / 2;
+  if (escapes) *escapes = w->ek.size();
+  if (spool_bytes) *spool_bytes = w->spool_bytes;
+  if (held_bytes)
+    *held_bytes = w->streamed ? w->dir.size() * 8 + w->ek.size() * 8 + w->ev.size() * 4 + w->ck.size() * 8 + w->cv.size() * 4 : w->keys.size() * 8 + w->vals.size() * 4;
+  return MFX_OK;
+}
+
+// the spool's bytes behind what `out` holds: copy_file_range where the file systems take it, else read and write
+static int spool_to_file(mfx_db_writer *w, int out, const char *path) {
+  uint64_t done = 0;
+  off_t in_off = 0;
+  while (done < w->spool_bytes) {
+    const ssize_t r = copy_file_range(w->fd, &in_off, out, nullptr, (size_t)std::min<uint64_t>(w->spool_bytes - done, 1u << 30), 0);
+    if (r <= 0) break;                                           // (not supported here, or the spool is short: the loop below says which)
+    done += (uint64_t)r;
+  }
+  std::vector<char> buf(done < w->spool_bytes ? (8u << 20) : 0);
+  while (done < w->spool_bytes) {
+    const ssize_t r = pread(w->fd, buf.data(), (size_t)std::min<uint64_t>(buf.size(), w->spool_bytes - done), (off_t)done);
+    if (r <= 0) return mfx_fail(MFX_E_IO, "reading '%s' failed", w->spool.c_str());
+    for (ssize_t o = 0; o < r;) {
+      const ssize_t x = write(out, buf.data() + o, (size_t)(r - o));
+      if (x <= 0) return mfx_fail(MFX_E_IO, "short write to '%s'", path);
+      o += x;
+    }
+    done += (uint64_t)r;
+  }
+  return MFX_OK;
+}
+
+static int db_close_streamed(mfx_db_writer *w) {
+  const char *path = w->path.c_str();
+  if (w->n == 0) return mfx_db_write_flat_impl(path, w->k, nullptr, nullptr, 0);
+  const double t0 = db_now();
+  if (!w->ck.empty()) {                                          // the last, partial block
+    StreamHostOut out{w};
+    int rc = out.add(w->ck.data(), w->cv.data(), (uint32_t)w->ck.size());
+    if (rc == MFX_OK) rc = out.flush();
+    if (rc) return rc;
+  }
+  const uint64_t nblocks = w->dir.size() / 2, base = sizeof(FlatHeader) + 8 + (nblocks + 1) * 16, at = base + w->spool_bytes;
+  if (at >> 48) return mfx_fail(MFX_E_INVAL, "mfx_db_write_flat: the database is too large for the delta form");
+  for (uint64_t b = 0; b < nblocks; ++b) w->dir[2 * b + 1] += base;      // (offsets below 2^48: the widths above them stay)
+  w->dir.push_back(0);
+  w->dir.push_back(at);
+  FlatHeader h;
+  memcpy(h.magic, "MFXKMER1", 8);
+  h.k = (uint32_t)w->k;
+  h.flags = FLAT_DELTA;
+  h.n = w->n;
+  h.n_escape = w->ek.size();
+  FILE *f = fopen(path, "wb");
+  if (!f) return mfx_fail(MFX_E_IO, "cannot open '%s' for writing", path);
+  bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && fwrite(&nblocks, 8, 1, f) == 1 && fwrite(w->dir.data(), 8, w->dir.size(), f) == w->dir.size() && fflush(f) == 0;
+  int rc = ok ? spool_to_file(w, fileno(f), path) : mfx_fail(MFX_E_IO, "short write to '%s'", path);
+  if (rc == MFX_OK) {
+    ok = fseeko(f, 0, SEEK_END) == 0 &&
+         (w->ek.empty() || (fwrite(w->ek.data(), 8, w->ek.size(), f) == w->ek.size() && fwrite(w->ev.data(), 4, w->ev.size(), f) == w->ev.size()));
+    if (!ok) rc = mfx_fail(MFX_E_IO, "short write to '%s'", path);
+  }
+  if (fclose(f) != 0 && rc == MFX_OK) rc = mfx_fail(MFX_E_IO, "short write to '%s'", path);
+  if (rc != MFX_OK) unlink(path);
+  if (getenv("MFX_DB_TIMING"))
+    fprintf(stderr, "[mfx db] streamed writer: export %.2f s, sort %.2f s, plan %.2f s, pack %.2f s, copy %.2f s, spool write %.2f s, close %.2f s (%lu blocks, "
+            "%lu escapes)\n", w->t_export, w->t_sort, w->t_plan, w->t_pack, w->t_copy, w->t_spool, db_now() - t0, (unsigned long)nblocks, (unsigned long)w->ek.size());
+  return rc;
+}
+
 extern "C" int mfx_db_writer_close(mfx_db_writer *w, uint64_t *n_kmers) {
   if (!w) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_close: null argument");
   int rc;
   try {
-    if (n_kmers) *n_kmers = w->keys.size();
-    rc = mfx_db_write_flat_impl(w->path.c_str(), w->k, w->keys.data(), w->vals.data(), w->keys.size());
+    if (n_kmers) *n_kmers = w->streamed ? w->n : w->keys.size();
+    rc = w->streamed ? db_close_streamed(w) : mfx_db_write_flat_impl(w->path.c_str(), w->k, w->keys.data(), w->vals.data(), w->keys.size());
   }
   catch (const std::bad_alloc &) { rc = mfx_fail(MFX_E_NOMEM, "mfx_db_writer_close: out of memory"); }
   catch (const std::exception &e) { rc = mfx_fail(MFX_E_IO, "mfx_db_writer_close: %s", e.what()); }
@@ -1631,6 +2046,19 @@ static int mfx_index_write_db_impl(const mfx_index *ix, int side, const char *pa
   if (int rc = db_append_index(&w, ix, side, nullptr, "mfx_index_write_db")) return rc;
   if (n_kmers) *n_kmers = w.keys.size();
   return mfx_db_write_flat_impl(path, ix->k, w.keys.data(), w.vals.data(), w.keys.size());
+}
+
+extern "C" int mfx_index_write_db_streamed(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {
+  if (!ix || !path) return mfx_fail(MFX_E_INVAL, "mfx_index_write_db_streamed: null argument");
+  if (int rc = db_side_checks(ix, side, "mfx_index_write_db_streamed")) return rc;
+  mfx_db_writer *w = nullptr;
+  if (int rc = db_open_streamed(path, ix->k, &w)) return rc;
+  int rc;
+  try { rc = db_append_index(w, ix, side, nullptr, "mfx_index_write_db_streamed"); }
+  catch (const std::bad_alloc &) { rc = mfx_fail(MFX_E_NOMEM, "mfx_index_write_db_streamed: out of memory"); }
+  catch (const std::exception &e) { rc = mfx_fail(MFX_E_IO, "mfx_index_write_db_streamed: %s", e.what()); }
+  if (rc) { mfx_db_writer_abort(w); return rc; }
+  return mfx_db_writer_close(w, n_kmers);
 }
 
 extern "C" int mfx_index_write_db(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers) {

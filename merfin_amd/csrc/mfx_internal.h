@@ -10,6 +10,7 @@
 
 #include "../../include/merfin_amd.h"
 #include "mfx_kstar.h"
+#include "mfx_delta.h"
 
 // ---- error plumbing -------------------------------------------------------
 void mfx_set_error(const char *fmt, ...);
@@ -104,8 +105,7 @@ constexpr uint64_t MFX_EMPTY = ~0ull;
 constexpr int      MFX_PACKED_VBITS = 22;
 constexpr uint32_t MFX_PACKED_VMASK = (1u << MFX_PACKED_VBITS) - 1u;
 constexpr int      MFX_MAX_K_PACKED = 21;
-constexpr uint32_t MFX_DELTA_BLOCK = 4096;     // k-mers per delta-coded block of a sorted flat database (mfx_db.cpp FLAT_DELTA)
-constexpr int      MFX_DELTA_MAX_VBITS = 22;   // widest count field of a block; larger counts are escapes
+// MFX_DELTA_BLOCK, MFX_DELTA_MAX_VBITS: mfx_delta.h (the delta-coded blocks of a sorted flat database, mfx_db.cpp FLAT_DELTA)
 
 // 32 <= k <= 64: k-mers of up to 128 bits (mfx_wide.hip).  Four 32-byte slots per 128-byte line.
 struct mfx_wslot {

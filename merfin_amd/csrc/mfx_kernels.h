@@ -226,5 +226,11 @@ hipError_t mfx_k_db_export(mfx_table_view t, int side, int shift, uint32_t bin_l
 // ascending keys (bits [0, key_bits)) with their values; tmp == nullptr: only tmp_bytes is set
 int mfx_sort_db_pairs(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, uint64_t n, int key_bits,
                       hipStream_t st);
+// the encoder of the streamed database writer (mfx_sort.hip): full blocks of MFX_DELTA_BLOCK sorted pairs -> the words of mfx_db.cpp's pack_delta_block
+struct mfx_delta_plan { uint64_t first; uint32_t widths, nesc; };      // per block: its first k-mer, kb | vb << 8 (mfx_delta.h), its escapes
+hipError_t mfx_k_delta_plan(const uint64_t *keys, const uint32_t *vals, uint32_t nblocks, mfx_delta_plan *plan, hipStream_t st);
+// word_off / esc_off: where block b's words start in out, its escapes in esc_keys / esc_vals -- the scan of the plan's sizes
+hipError_t mfx_k_delta_pack(const uint64_t *keys, const uint32_t *vals, uint32_t nblocks, const mfx_delta_plan *plan, const uint64_t *word_off,
+                            const uint32_t *esc_off, uint64_t *out, uint64_t *esc_keys, uint32_t *esc_vals, hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);

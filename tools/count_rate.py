@@ -16,6 +16,11 @@ into an index created small; per pass the kernel seconds, per P the whole call w
 --passes-files adds, at the largest P, passes that take the reads from mfx_reads_add again (generated anew: what a pass from the files pays on
 the host).
 --max-gb G runs the driver of `-passes auto` under that limit: one range, a refused range cut in two at the median of its table's bins.
+
+--writers adds the leg of the two database writers: the claiming counter's table is written three times with each, alternating (host:
+mfx_db_writer_open, the k-mers collected and coded on the host; stream: mfx_db_writer_open_streamed, coded on the device and spooled),
+file in tmpfs; the rates, the host memory each held (mfx_db_writer_info) and the MFX_DB_TIMING split of every write are appended to
+--profile (default profiles/count_stream.txt).  --writers-only skips the other legs.
 """
 import argparse
 import ctypes as C
@@ -166,6 +171,82 @@ def _pass_legs(torch, m, world, a, nreads, db):
     store.close()
 
 
+def _with_stderr(fn):
+    """fn() with the process's stderr (the library's MFX_DB_TIMING lines) caught; (result, text)"""
+    sys.stderr.flush()
+    keep = os.dup(2)
+    with tempfile.TemporaryFile() as t:
+        os.dup2(t.fileno(), 2)
+        try:
+            res = fn()
+        finally:
+            os.dup2(keep, 2)
+            os.close(keep)
+        t.seek(0)
+        return res, t.read().decode(errors="replace")
+
+
+def _writer_leg(torch, m, L, world, a, nreads, db):
+    """the same table through both writers, alternating; the lines go to stdout and to a.profile"""
+    import filecmp
+    from merfin_amd.binding import _ReadsStats
+    ix = m.Index(a.k, 1024)
+    r = L.mfx_reads_begin_all(ix.h, 0)
+    assert r, L.mfx_last_error()
+    _feed(torch, L, r, world, a, nreads)
+    st = _ReadsStats()
+    assert L.mfx_reads_end(r, C.byref(st)) == 0, L.mfx_last_error()
+    info = ix.info()
+    lines = ["k=%d genome=%d Mb reads=%d x %d bases (%.0fx): %.3f G k-mers, %.3f G distinct, table %.2f GB; file in %s"
+             % (a.k, a.mb, nreads, a.len, a.cov, st.kmers / 1e9, info["distinct"] / 1e9, info["bytes"] / 1e9, os.path.dirname(db))]
+    print(lines[0], flush=True)
+    os.environ["MFX_DB_TIMING"] = "1"
+    other = db + ".other"
+    secs = {"host": [], "stream": []}
+    try:
+        for rep in range(3):
+            for kind in ("host", "stream"):
+                path = other if (rep == 0 and kind == "stream") else db
+
+                def write():
+                    t0 = time.time()
+                    w = m.DbWriter(path, a.k, streamed=(kind == "stream"))
+                    w.append(ix)
+                    held = w.info()
+                    return w.close(), held, time.time() - t0
+                (nk, held, tw), err = _with_stderr(write)
+                assert nk == info["distinct"]
+                secs[kind].append(tw)
+                size = os.path.getsize(path)
+                line = ("rep %d  %-6s %.3f G k-mers in %.2f s = %.1f M k-mers/s, file %.2f GB (%.2f bytes per k-mer); the writer held %.3f GB on the host "
+                        "before close (%d blocks in a spool of %.2f GB, %d escapes)"
+                        % (rep, kind, nk / 1e9, tw, nk / tw / 1e6, size / 1e9, size / max(nk, 1), held["held_bytes"] / 1e9, held["blocks"],
+                           held["spool_bytes"] / 1e9, held["escapes"]))
+                print(line, flush=True)
+                lines.append(line)
+                for x in err.splitlines():
+                    if x.startswith("[mfx db]"):
+                        print("        " + x, flush=True)
+                        lines.append("        " + x)
+                if rep == 0 and kind == "stream":
+                    same = filecmp.cmp(db, other, shallow=False)
+                    line = "rep 0  the two files are %s" % ("equal, byte for byte" if same else "DIFFERENT")
+                    print(line, flush=True)
+                    lines.append(line)
+                    os.remove(other)
+                    assert same
+        lines.append("host   %s s; stream %s s" % (", ".join("%.2f" % x for x in secs["host"]), ", ".join("%.2f" % x for x in secs["stream"])))
+        print(lines[-1], flush=True)
+    finally:
+        for x in (db, other):
+            if os.path.exists(x):
+                os.remove(x)
+        os.makedirs(os.path.dirname(os.path.abspath(a.profile)), exist_ok=True)
+        with open(a.profile, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    ix.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=int, default=256)
@@ -180,6 +261,9 @@ def main():
     ap.add_argument("--passes-files", action="store_true", help="with --passes: at the largest P also passes fed through mfx_reads_add again")
     ap.add_argument("--passes-only", action="store_true", help="only the legs of --passes / --max-gb")
     ap.add_argument("--max-gb", type=float, default=0.0, help="with --passes: also the driver of -passes auto under this table limit")
+    ap.add_argument("--writers", action="store_true", help="also the leg of the two database writers, three writes each, alternating")
+    ap.add_argument("--writers-only", action="store_true", help="only that leg")
+    ap.add_argument("--profile", default=os.path.join(ROOT, "profiles", "count_stream.txt"), help="the file --writers appends its lines to")
     a = ap.parse_args()
     import torch
     import merfin_amd as m
@@ -198,9 +282,11 @@ def main():
     out_dir = a.out or tempfile.mkdtemp(prefix="mfx_count_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     db = os.path.join(out_dir, "reads.mfxk")
     try:
-        if a.passes or a.max_gb > 0:
+        if a.writers or a.writers_only:
+            _writer_leg(torch, m, L, world, a, nreads, db)
+        if (a.passes or a.max_gb > 0) and not a.writers_only:
             _pass_legs(torch, m, world, a, nreads, db)
-        for rep in range(0 if a.passes_only else a.reps):
+        for rep in range(0 if a.passes_only or a.writers_only else a.reps):
             # ---- the claiming counter into a table created small
             ix = m.Index(a.k, 1024)
             r = L.mfx_reads_begin_all(ix.h, 0)
