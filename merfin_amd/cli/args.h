@@ -1,0 +1,348 @@
+// merfin (MI355X) -- the command line: the flags (Globals), their parser and the checks that refuse a run before any device is touched.
+#pragma once
+#include <ctype.h>
+#include <errno.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/merfin_amd.h"
+
+enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM };
+
+struct Globals {
+  const char *seqName = nullptr, *seqDBname = nullptr, *readDBname = nullptr, *pLookupTable = nullptr;
+  const char *vcfName = nullptr, *outName = nullptr, *indexName = nullptr, *convertName = nullptr;
+  bool placed = false;                 // -convert -placed: the records sorted by their place in the -hist table (mfx_db_convert_placed)
+  double peak = 0, maxMemory = 0;
+  uint64_t minV = 0, maxV = ~0ull;
+  int threads = 0, reportType = OP_NONE, device = 0;
+  std::vector<int> devices;          // -devices: the GPUs of this node one process drives (-hist); [0] == device
+  unsigned comb = 15;
+  bool nosplit = false, debug = false, skipMissing = false, sharded = false;
+  std::vector<uint32_t> copyKmerK;
+  std::vector<double> copyKmerP;
+  std::vector<const char *> readsNames;  // -reads: the read counts from these FASTA / FASTQ files instead of -readmers
+  int kArg = 0;                          // -k (0: not given); with -reads: the run's k once the flags are checked
+  uint64_t window = 1000;                // -window: k-mer start positions per window of -track
+  bool windowGiven = false;
+  bool peakAuto = false;                 // -peak auto: the haploid peak is read off the index's copy-number spectrum (mfx_spectrum_peak)
+  uint32_t copies = 4, maxMult = 10000;  // -copies / -maxmult of -spectrum
+  bool copiesGiven = false, maxMultGiven = false;
+  bool count = false;                    // -count: no report; the k-mers of -reads counted on the GPU and written as a database
+  bool peakGiven = false, devicesGiven = false;
+  bool passesGiven = false, passesAuto = false;   // -count -passes P|auto: the k-mers counted in passes over key ranges
+  uint32_t passes = 1;
+};
+
+typedef std::vector<std::string> Errors;
+
+static void usage(const char *exe) {
+  fprintf(stderr,
+          "usage: %s <report-type> -sequence <seq.fasta> -readmers <read.meryl> -peak <haploid_peak>\n"
+          "          [-prob <lookup_table>] [-seqmers <seq.meryl>] [-vcf <input.vcf>] -output <output>\n\n"
+          "  Evaluates every k-mer of <seq.fasta> against the read k-mer database on an MI355X GPU.\n"
+          "  Inputs: FASTA/FASTQ, plain or gz/bz2/xz.  K-mer databases: meryl directory, `meryl print`\n"
+          "  text, or the flat binary written by mfx_db_write_flat.  k is taken from -readmers.\n\n"
+          "    -min m / -max m   ignore read k-mers with value below / above m\n"
+          "    -memory m         do not use more than m GB (of HBM) for the k-mer tables\n"
+          "    -threads t        accepted for compatibility (host threads)\n"
+          "    -peak m           haploid k-mer coverage peak (required except -filter and -spectrum)\n"
+          "    -peak auto        -hist, -dump, -track, -spectrum on one device: the peak is read off the single-copy row of the index's\n"
+          "                      copy-number spectrum (one more pass over the table on the GPU) and reported on stderr\n"
+          "    -prob file        readK,prob rows; row n overrides -peak for multiplicity n\n"
+          "    -seqmers db       assembly k-mer database; default: counted from -sequence on the GPU\n"
+          "    -reads file       instead of -readmers: count the read k-mers of this FASTA / FASTQ file (plain, .gz, .bz2, .xz) on\n"
+          "                      the GPU into the k-mers the run asks for; repeatable.  -hist, -dump and the variant modes (k <= 31)\n"
+          "    -k k              k when no database gives it (-reads without -seqmers); must agree with -seqmers\n"
+          "    -convert db       no report: rewrite the k-mer database <db> (any accepted form) as -output <file> in the flat form\n"
+          "                      (sorted k-mers in delta-coded blocks; loads at the speed of the PCIe link)\n"
+          "    -count            no report: count every k-mer of the -reads files on the GPU (`meryl count`; -k K, K <= 31) and write\n"
+          "                      the sorted flat database -output <file>, which every mode takes as -readmers.  -min / -max are not\n"
+          "                      applied: a database holds every count, the filter acts when it is loaded.  One device.\n"
+          "    -passes P|auto    with -count: the k-mers are counted in P passes (1 to 4096) over ascending key ranges, each in a table\n"
+          "                      of its own, for read sets whose table does not fit the device (-memory); auto: one pass, and a range\n"
+          "                      whose table cannot grow is cut in two.  The reads are parsed once and kept packed in host memory.\n"
+          "    -placed           with -convert: the records sorted by their PLACE in the table -hist / -dump build (13 <= k <= 31,\n"
+          "                      canonical databases): such a database is applied to the table line after line\n"
+          "    -device d         HIP device (default 0)\n"
+          "    -devices list     several GPUs of this node driven by this one process, e.g. 0-7 or 0,2,5 (-hist: the index is\n"
+          "                      built once and copied to the others over xGMI, every GPU evaluates its share of the\n"
+          "                      sequence, the histograms are added; -dump and the variant modes: every GPU takes a contiguous\n"
+          "                      run of contigs, the outputs are concatenated in order; -completeness uses the first device)\n"
+          "    -sharded          with -devices: every GPU keeps only its share of the k-mer table (read databases too large\n"
+          "                      for one GPU).  -hist routes every k-mer to the GPU that owns it; -dump and the variant modes\n"
+          "                      look every k-mer up in all shards and add the answers; -completeness adds per-shard sums\n"
+          "    -index file       cache of the built HBM index: loaded if it exists (the k-mer databases are then not\n"
+          "                      read), otherwise written after the build\n"
+          "    -window W         with -track: k-mer start positions per window (default 1000)\n"
+          "    -copies C         with -spectrum: rows for assembly counts 1 .. C, one more for > C (1 to 6, default 4)\n"
+          "    -maxmult M        with -spectrum: read counts of M and more share the last column (4 to 65536, default 10000)\n\n"
+          "  Report types (exactly one):\n"
+          "    -hist           0-centred K* histogram to <output>; QV and QV* on stderr\n"
+          "    -dump           seqName, seqPos, readK, asmK, K* per k-mer to <output>  [-skipMissing]\n"
+          "    -completeness   k-mer completeness from -seqmers (or -sequence) and -readmers\n"
+          "    -track          K* summarised per window of every contig on the GPU -> <output>.track.tsv, <output>.kstar.bedgraph\n"
+          "                    (mean K*) and <output>.missing.bedgraph (missing fraction)  [-window W]; an <output> ending in\n"
+          "                    .gz / .bz2 / .xz compresses the three files (out.gz -> out.track.tsv.gz ...)\n"
+          "    -spectrum       copy-number spectrum (k-mers per read count and assembly count) -> <output>.spectra-cn.hist; the haploid\n"
+          "                    peak it shows on stderr.  No -peak needed.  [-copies C] [-maxmult M]\n"
+          "    -filter         keep variants (and combinations within k) that minimise missing k-mers -> <output>.filter.vcf\n"
+          "    -polish         choose variant combinations by missing k-mers, ties by k* -> <output>.polish.vcf\n"
+          "    -better -strict -loose   k*-free variants of -polish -> <output>.filter.vcf\n"
+          "                    [-comb N (15)] [-nosplit] [-debug -> <output>.00.debug.gz]\n\n",
+          exe);
+}
+
+// the usage text, then what is wrong with this command line; the exit code of a refused run
+static int fail_usage(const char *argv0, const Errors &err) {
+  usage(argv0);
+  for (auto &e : err) fputs(e.c_str(), stderr);
+  return 1;
+}
+
+// a knob of the environment that holds a number (docs/KNOBS.md): -1 when it is not set
+static int env_flag(const char *name) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : -1;
+}
+
+static bool variant_mode(int reportType) { return reportType >= OP_FILTER && reportType <= OP_LOOSE; }
+
+// The integer arguments: decimal digits and nothing else, a minus sign in front at the most (which only ever says "below lo").
+enum { UINT_OK, UINT_NOT_A_NUMBER, UINT_BELOW, UINT_ABOVE };
+static int parse_uint(const char *v, unsigned long long lo, unsigned long long hi, unsigned long long *out) {
+  const bool minus = v[0] == '-';
+  char *e = nullptr;
+  errno = 0;
+  const unsigned long long x = strtoull(v + minus, &e, 10);
+  if (!isdigit((unsigned char)v[minus]) || *e != 0 || errno != 0) return UINT_NOT_A_NUMBER;
+  if (x < lo || (minus && x > 0)) return UINT_BELOW;
+  if (x > hi) return UINT_ABOVE;
+  *out = x;
+  return UINT_OK;
+}
+
+// -devices "0-7", "0,2,5", "0-3,6": a device may be named twice (two evaluation contexts on one GPU)
+static bool parse_devices(const std::string &spec, std::vector<int> &devices) {
+  bool ok = !spec.empty();
+  for (size_t i = 0; ok && i < spec.size();) {
+    char *e = nullptr;
+    long a = strtol(spec.c_str() + i, &e, 10), b = a;
+    ok = e != spec.c_str() + i && a >= 0;
+    i = (size_t)(e - spec.c_str());
+    if (ok && i < spec.size() && spec[i] == '-') {
+      const char *s2 = spec.c_str() + i + 1;
+      b = strtol(s2, &e, 10);
+      ok = e != s2 && b >= a;
+      i = (size_t)(e - spec.c_str());
+    }
+    for (long d = a; ok && d <= b && d < 1024; ++d) devices.push_back((int)d);
+    if (ok && i < spec.size()) { ok = spec[i] == ','; ++i; }
+  }
+  if (!ok || devices.empty()) devices.clear();
+  return !devices.empty();
+}
+
+static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
+  for (int arg = 1; arg < argc; arg++) {
+    auto is = [&](const char *f) { return strcmp(argv[arg], f) == 0; };
+    auto val = [&]() -> const char * { return arg + 1 < argc ? argv[++arg] : ""; };
+    unsigned long long x = 0;
+    if (is("-sequence")) G.seqName = val();
+    else if (is("-seqmers")) G.seqDBname = val();
+    else if (is("-readmers")) G.readDBname = val();
+    else if (is("-reads")) G.readsNames.push_back(val());
+    else if (is("-k")) {
+      const char *v = val();
+      G.kArg = parse_uint(v, 1, 64, &x) == UINT_OK ? (int)x : -1;
+      if (G.kArg < 0) err.push_back(std::string("Invalid -k '") + v + "': k is 1 to 64.\n");
+    }
+    else if (is("-peak")) {
+      const char *v = val();
+      if (strcmp(v, "auto") == 0) G.peakAuto = true;
+      else G.peak = strtod(v, nullptr);
+      G.peakGiven = true;
+    }
+    else if (is("-spectrum")) G.reportType = OP_SPECTRUM;
+    else if (is("-copies") || is("-maxmult")) {
+      const bool cp = is("-copies");
+      const char *v = val();
+      const unsigned long long lo = cp ? 1 : 4, hi = cp ? 6 : 65536;
+      (cp ? G.copiesGiven : G.maxMultGiven) = true;
+      if (parse_uint(v, lo, hi, &x) != UINT_OK)
+        err.push_back(std::string("Invalid ") + (cp ? "-copies" : "-maxmult") + " '" + v + "': an integer from " + std::to_string(lo) + " to " + std::to_string(hi) + ".\n");
+      else (cp ? G.copies : G.maxMult) = (uint32_t)x;
+    }
+    else if (is("-prob")) G.pLookupTable = val();
+    else if (is("-vcf")) G.vcfName = val();
+    else if (is("-output")) G.outName = val();
+    else if (is("-min")) G.minV = strtoull(val(), nullptr, 10);
+    else if (is("-max")) G.maxV = strtoull(val(), nullptr, 10);
+    else if (is("-threads")) G.threads = atoi(val());
+    else if (is("-memory")) G.maxMemory = strtod(val(), nullptr);
+    else if (is("-device")) G.device = atoi(val());
+    else if (is("-devices")) {
+      const std::string spec = val();
+      if (!parse_devices(spec, G.devices)) err.push_back(std::string("Invalid device list '") + spec + "' (-devices 0-7 or 0,2,5).\n");
+    }
+    else if (is("-index")) G.indexName = val();
+    else if (is("-sharded")) G.sharded = true;
+    else if (is("-convert")) G.convertName = val();
+    else if (is("-count")) G.count = true;
+    else if (is("-passes")) {
+      const char *v = val();
+      const int bad = strcmp(v, "auto") == 0 ? UINT_OK : parse_uint(v, 1, 4096, &x);
+      G.passesGiven = true;
+      if (strcmp(v, "auto") == 0) G.passesAuto = true;
+      else if (bad == UINT_NOT_A_NUMBER) err.push_back(std::string("Invalid -passes '") + v + "': the passes of -count are a number from 1 to 4096, or auto.\n");
+      else if (bad == UINT_BELOW) err.push_back(std::string("Invalid -passes '") + v + "': -count takes at least one pass (1 to 4096, or auto).\n");
+      else if (bad == UINT_ABOVE) err.push_back(std::string("Invalid -passes '") + v + "': a pass takes at least one of the 4096 key bins, so there are 4096 at most (or auto).\n");
+      else G.passes = (uint32_t)x;
+    }
+    else if (is("-placed")) G.placed = true;
+    else if (is("-nosplit")) G.nosplit = true;
+    else if (is("-filter")) G.reportType = OP_FILTER;
+    else if (is("-better")) G.reportType = OP_BETTER;
+    else if (is("-strict")) G.reportType = OP_STRICT;
+    else if (is("-loose")) { fprintf(stderr, "*EXPERIMENTAL* Running in -loose mode\n"); G.reportType = OP_LOOSE; }
+    else if (is("-polish")) G.reportType = OP_POLISH;
+    else if (is("-hist")) G.reportType = OP_HIST;
+    else if (is("-dump")) G.reportType = OP_DUMP;
+    else if (is("-track")) G.reportType = OP_TRACK;
+    else if (is("-window")) {
+      const char *v = val();
+      G.windowGiven = true;
+      if (parse_uint(v, 1, ~0ull, &x) != UINT_OK) err.push_back(std::string("Invalid -window '") + v + "': a window is an integer of at least 1.\n");
+      else G.window = x;
+    }
+    else if (is("-skipMissing")) G.skipMissing = true;
+    else if (is("-completeness")) G.reportType = OP_COMPL;
+    else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
+    else if (is("-debug")) G.debug = true;
+    else err.push_back(std::string("Unknown option '") + argv[arg] + "'.\n");
+  }
+}
+
+// can every -reads file be read?  One line per file that cannot
+static void reads_files_readable(const Globals &G, Errors &err) {
+  for (const char *f : G.readsNames) {
+    struct stat rst;
+    if (stat(f, &rst) != 0 || !S_ISREG(rst.st_mode) || access(f, R_OK) != 0)
+      err.push_back(std::string("Cannot read the -reads file '") + f + "'.\n");
+  }
+}
+
+// false, with the reference's text: a device of the run is not there.  (Stays on the main thread, before anything else is started: the HIP
+// runtime coming up on a thread of its own while this one spawns a decompressor for -sequence was seen to come up with no device.)
+static bool devices_available(const std::vector<int> &devs) {
+  for (int d : devs)
+    if (mfx_device_count() <= d) {
+      fprintf(stderr, "ERROR: HIP device %d not available (%d visible). This program has no CPU path.\n", d, mfx_device_count());
+      return false;
+    }
+  return true;
+}
+
+// -count: every check before any device is touched (the checks of a report from -reads below do not apply to it)
+static void check_count_flags(const Globals &G, Errors &err) {
+  if (!G.count) {
+    if (G.passesGiven) err.push_back("-passes divides the work of -count: it has no meaning without -count.\n");
+    return;
+  }
+  if (G.convertName) err.push_back("-count and -convert are two operations: give one of them.\n");
+  if (G.reportType != OP_NONE) err.push_back("-count is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
+  if (G.readsNames.empty()) err.push_back("-count needs the reads it counts: give -reads <file> (repeatable).\n");
+  if (G.kArg == 0) err.push_back("-count needs -k: no database gives it.\n");
+  if (!G.outName) err.push_back("-count writes a k-mer database: give -output <file>.\n");
+  if (G.kArg > 31)
+    err.push_back("-count holds k <= 31 (here k = " + std::to_string(G.kArg) + "): count larger k-mers with `meryl count` and give the database as -readmers.\n");
+  if (G.readDBname) err.push_back("-count makes the read database: it does not take -readmers.\n");
+  if (G.seqDBname) err.push_back("-count counts reads: it does not take -seqmers.\n");
+  if (G.seqName) err.push_back("-count counts reads: it does not take -sequence.\n");
+  if (G.vcfName) err.push_back("-count does not take -vcf (the variant modes do).\n");
+  if (G.peakGiven) err.push_back("-count evaluates nothing: it does not take -peak.\n");
+  if (G.sharded) err.push_back("-count does not take -sharded: the table it counts into lives on one device.\n");
+  if (G.indexName) err.push_back("-count does not take -index: it writes a database, not a table image.\n");
+  if (G.devices.size() > 1) err.push_back("-count runs on one device (-device d, or -devices naming one).\n");
+  reads_files_readable(G, err);
+}
+
+// -reads: every check before any device is touched; G.kArg becomes the run's k.  false: -seqmers could not be opened (the error is printed)
+static bool check_reads_flags(Globals &G, Errors &err) {
+  const bool variants = variant_mode(G.reportType);
+  if (!G.readsNames.empty()) {
+    if (G.convertName) err.push_back("-convert rewrites a k-mer database; it does not take -reads.\n");
+    if (G.readDBname) err.push_back("-reads and -readmers cannot be combined: the read counts come from one source.\n");
+    if (G.reportType == OP_COMPL) err.push_back("-completeness needs every read k-mer: it takes a read database (-readmers), not -reads.\n");
+    if (G.sharded) err.push_back("-sharded does not take -reads (give the read database with -readmers).\n");
+    if (G.kArg == 0 && !G.seqDBname) err.push_back("-reads needs -k (or -seqmers, whose k it then takes).\n");
+    reads_files_readable(G, err);
+    if (variants && (G.indexName || G.devices.size() > 1))
+      err.push_back("The variant modes count -reads into the path-only index of the call set: one device, no -index.\n");
+    if (G.seqDBname && !G.convertName && !G.readDBname) {
+      mfx_db_info sdb;
+      if (mfx_db_probe(G.seqDBname, &sdb)) { fprintf(stderr, "ERROR: %s: %s\n", "opening -seqmers", mfx_last_error()); return false; }
+      if (G.kArg > 0 && sdb.k != G.kArg) err.push_back("-k " + std::to_string(G.kArg) + " disagrees with -seqmers, which holds " + std::to_string(sdb.k) + "-mers.\n");
+      else G.kArg = sdb.k;
+    }
+    if (variants && G.kArg > 31)
+      err.push_back("The variant modes count -reads into the path-only index, which holds k <= 31 (here k = " + std::to_string(G.kArg) + ").\n");
+  }
+  if (G.kArg > 0 && G.readDBname && G.readsNames.empty()) err.push_back("-k is taken from -readmers; give -k only with -reads.\n");
+  return true;
+}
+
+// -track: every check before any device is touched
+static void check_track_flags(const Globals &G, Errors &err) {
+  if (G.windowGiven && G.reportType != OP_TRACK) err.push_back("-window sets the window of -track; it has no meaning without -track.\n");
+  if (G.reportType != OP_TRACK) return;
+  if (G.sharded) err.push_back("-track does not take -sharded: a window's records need every k-mer's counts on one device.\n");
+  if (G.devices.size() > 1) err.push_back("-track runs on one device (-device d, or -devices naming one).\n");
+  if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -track always writes its windows.\n");
+  if (G.vcfName) err.push_back("-track does not take -vcf (the variant modes do).\n");
+}
+
+// -spectrum: every check before any device is touched
+static void check_spectrum_flags(const Globals &G, Errors &err) {
+  if ((G.copiesGiven || G.maxMultGiven) && G.reportType != OP_SPECTRUM)
+    err.push_back("-copies and -maxmult shape the image of -spectrum; they have no meaning without -spectrum.\n");
+  if (G.reportType != OP_SPECTRUM) return;
+  if (G.vcfName) err.push_back("-spectrum does not take -vcf (the variant modes do).\n");
+  if (G.sharded) err.push_back("-spectrum does not take -sharded: this version counts the spectrum of one table on one device.\n");
+  if (G.devices.size() > 1) err.push_back("-spectrum runs on one device (-device d, or -devices naming one).\n");
+  if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -spectrum counts every entry of the table.\n");
+  if (!G.seqName && !G.seqDBname) err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
+  if (!G.seqName && !G.readsNames.empty()) err.push_back("-spectrum counts -reads into the k-mers of -sequence: give -sequence.\n");
+}
+
+// -peak auto: every check before any device is touched
+static void check_peak_auto_flags(const Globals &G, Errors &err) {
+  if (!G.peakAuto) return;
+  if (G.peak != 0) err.push_back("-peak was given twice (a number and auto).\n");
+  if (G.reportType != OP_HIST && G.reportType != OP_DUMP && G.reportType != OP_TRACK && G.reportType != OP_SPECTRUM && G.reportType != OP_NONE)
+    err.push_back("-peak auto reads the peak off the table of -hist, -dump, -track or -spectrum; the variant modes and -completeness take -peak <number>.\n");
+  if (G.sharded) err.push_back("-peak auto does not take -sharded: no peak is defined on a sharded table.\n");
+  if (G.devices.size() > 1) err.push_back("-peak auto runs on one device (-device d, or -devices naming one).\n");
+}
+
+// what every report needs, merfin.C:159-181
+static void check_report_flags(const Globals &G, Errors &err) {
+  if (G.reportType == OP_SPECTRUM) {
+    if (!G.outName) err.push_back("No output (-output) supplied.\n");
+  } else if (G.reportType != OP_COMPL) {
+    if (!G.seqName) err.push_back("No input sequences (-sequence) supplied.\n");
+    if (!G.outName) err.push_back("No output (-output) supplied.\n");
+  }
+  if (variant_mode(G.reportType) && !G.vcfName) err.push_back("No variant call input (-vcf) supplied; mandatory for -filter or -polish.\n");
+  if (G.reportType != OP_FILTER && G.reportType != OP_SPECTRUM && G.peak == 0 && !G.peakAuto) err.push_back("No haploid peak (-peak) supplied.\n");
+  if (G.reportType == OP_COMPL && !G.seqName && !G.seqDBname)
+    err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
+  if (G.reportType == OP_NONE) err.push_back("No report type (-filter, -polish, -hist, -dump, -completeness) supplied.\n");
+  if (!G.readDBname && G.readsNames.empty()) err.push_back("No read meryl database (-readmers) supplied.\n");
+}

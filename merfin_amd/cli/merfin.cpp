@@ -6,14 +6,8 @@
 // Report types: -hist, -dump, -completeness, and the variant modes -filter /
 // -polish / -better / -strict / -loose (paths enumerated on the host, every
 // path k-mer scored on the GPU).
-#include <ctype.h>
-#include <errno.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <libgen.h>
 #include <dirent.h>
-#include <sys/stat.h>
 
 #include <algorithm>
 #include <atomic>
@@ -28,93 +22,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/merfin_amd.h"
+#include "args.h"                 // Globals, the flags' parser and checks
 #include "fasta.h"
 #include "../csrc/mfx_grow.h"     // mfx_cut_bins: the key ranges of -count -passes
-
-enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM };
-
-struct Globals {
-  const char *seqName = nullptr, *seqDBname = nullptr, *readDBname = nullptr, *pLookupTable = nullptr;
-  const char *vcfName = nullptr, *outName = nullptr, *indexName = nullptr, *convertName = nullptr;
-  bool placed = false;                 // -convert -placed: the records sorted by their place in the -hist table (mfx_db_convert_placed)
-  double peak = 0, maxMemory = 0;
-  uint64_t minV = 0, maxV = ~0ull;
-  int threads = 0, reportType = OP_NONE, device = 0;
-  std::vector<int> devices;          // -devices: the GPUs of this node one process drives (-hist); [0] == device
-  unsigned comb = 15;
-  bool nosplit = false, debug = false, skipMissing = false, sharded = false;
-  std::vector<uint32_t> copyKmerK;
-  std::vector<double> copyKmerP;
-  std::vector<const char *> readsNames;  // -reads: the read counts from these FASTA / FASTQ files instead of -readmers
-  int kArg = 0;                          // -k (0: not given); with -reads: the run's k once the flags are checked
-  uint64_t window = 1000;                // -window: k-mer start positions per window of -track
-  bool windowGiven = false;
-  bool peakAuto = false;                 // -peak auto: the haploid peak is read off the index's copy-number spectrum (mfx_spectrum_peak)
-  uint32_t copies = 4, maxMult = 10000;  // -copies / -maxmult of -spectrum
-  bool copiesGiven = false, maxMultGiven = false;
-  bool count = false;                    // -count: no report; the k-mers of -reads counted on the GPU and written as a database
-  bool peakGiven = false, devicesGiven = false;
-  bool passesGiven = false, passesAuto = false;   // -count -passes P|auto: the k-mers counted in passes over key ranges
-  uint32_t passes = 1;
-};
-
-static void usage(const char *exe) {
-  fprintf(stderr,
-          "usage: %s <report-type> -sequence <seq.fasta> -readmers <read.meryl> -peak <haploid_peak>\n"
-          "          [-prob <lookup_table>] [-seqmers <seq.meryl>] [-vcf <input.vcf>] -output <output>\n\n"
-          "  Evaluates every k-mer of <seq.fasta> against the read k-mer database on an MI355X GPU.\n"
-          "  Inputs: FASTA/FASTQ, plain or gz/bz2/xz.  K-mer databases: meryl directory, `meryl print`\n"
-          "  text, or the flat binary written by mfx_db_write_flat.  k is taken from -readmers.\n\n"
-          "    -min m / -max m   ignore read k-mers with value below / above m\n"
-          "    -memory m         do not use more than m GB (of HBM) for the k-mer tables\n"
-          "    -threads t        accepted for compatibility (host threads)\n"
-          "    -peak m           haploid k-mer coverage peak (required except -filter and -spectrum)\n"
-          "    -peak auto        -hist, -dump, -track, -spectrum on one device: the peak is read off the single-copy row of the index's\n"
-          "                      copy-number spectrum (one more pass over the table on the GPU) and reported on stderr\n"
-          "    -prob file        readK,prob rows; row n overrides -peak for multiplicity n\n"
-          "    -seqmers db       assembly k-mer database; default: counted from -sequence on the GPU\n"
-          "    -reads file       instead of -readmers: count the read k-mers of this FASTA / FASTQ file (plain, .gz, .bz2, .xz) on\n"
-          "                      the GPU into the k-mers the run asks for; repeatable.  -hist, -dump and the variant modes (k <= 31)\n"
-          "    -k k              k when no database gives it (-reads without -seqmers); must agree with -seqmers\n"
-          "    -convert db       no report: rewrite the k-mer database <db> (any accepted form) as -output <file> in the flat form\n"
-          "                      (sorted k-mers in delta-coded blocks; loads at the speed of the PCIe link)\n"
-          "    -count            no report: count every k-mer of the -reads files on the GPU (`meryl count`; -k K, K <= 31) and write\n"
-          "                      the sorted flat database -output <file>, which every mode takes as -readmers.  -min / -max are not\n"
-          "                      applied: a database holds every count, the filter acts when it is loaded.  One device.\n"
-          "    -passes P|auto    with -count: the k-mers are counted in P passes (1 to 4096) over ascending key ranges, each in a table\n"
-          "                      of its own, for read sets whose table does not fit the device (-memory); auto: one pass, and a range\n"
-          "                      whose table cannot grow is cut in two.  The reads are parsed once and kept packed in host memory.\n"
-          "    -placed           with -convert: the records sorted by their PLACE in the table -hist / -dump build (13 <= k <= 31,\n"
-          "                      canonical databases): such a database is applied to the table line after line\n"
-          "    -device d         HIP device (default 0)\n"
-          "    -devices list     several GPUs of this node driven by this one process, e.g. 0-7 or 0,2,5 (-hist: the index is\n"
-          "                      built once and copied to the others over xGMI, every GPU evaluates its share of the\n"
-          "                      sequence, the histograms are added; -dump and the variant modes: every GPU takes a contiguous\n"
-          "                      run of contigs, the outputs are concatenated in order; -completeness uses the first device)\n"
-          "    -sharded          with -devices: every GPU keeps only its share of the k-mer table (read databases too large\n"
-          "                      for one GPU).  -hist routes every k-mer to the GPU that owns it; -dump and the variant modes\n"
-          "                      look every k-mer up in all shards and add the answers; -completeness adds per-shard sums\n"
-          "    -index file       cache of the built HBM index: loaded if it exists (the k-mer databases are then not\n"
-          "                      read), otherwise written after the build\n"
-          "    -window W         with -track: k-mer start positions per window (default 1000)\n"
-          "    -copies C         with -spectrum: rows for assembly counts 1 .. C, one more for > C (1 to 6, default 4)\n"
-          "    -maxmult M        with -spectrum: read counts of M and more share the last column (4 to 65536, default 10000)\n\n"
-          "  Report types (exactly one):\n"
-          "    -hist           0-centred K* histogram to <output>; QV and QV* on stderr\n"
-          "    -dump           seqName, seqPos, readK, asmK, K* per k-mer to <output>  [-skipMissing]\n"
-          "    -completeness   k-mer completeness from -seqmers (or -sequence) and -readmers\n"
-          "    -track          K* summarised per window of every contig on the GPU -> <output>.track.tsv, <output>.kstar.bedgraph\n"
-          "                    (mean K*) and <output>.missing.bedgraph (missing fraction)  [-window W]; an <output> ending in\n"
-          "                    .gz / .bz2 / .xz compresses the three files (out.gz -> out.track.tsv.gz ...)\n"
-          "    -spectrum       copy-number spectrum (k-mers per read count and assembly count) -> <output>.spectra-cn.hist; the haploid\n"
-          "                    peak it shows on stderr.  No -peak needed.  [-copies C] [-maxmult M]\n"
-          "    -filter         keep variants (and combinations within k) that minimise missing k-mers -> <output>.filter.vcf\n"
-          "    -polish         choose variant combinations by missing k-mers, ties by k* -> <output>.polish.vcf\n"
-          "    -better -strict -loose   k*-free variants of -polish -> <output>.filter.vcf\n"
-          "                    [-comb N (15)] [-nosplit] [-debug -> <output>.00.debug.gz]\n\n",
-          exe);
-}
 
 // load_Kmetric, merfin-globals.C:21-62
 static bool load_Kmetric(Globals &G) {
@@ -203,14 +113,14 @@ static uint64_t input_fingerprint(const Globals &G, bool seqOnly) {
   return h ? h : 1;
 }
 
-static void print_hist(const std::vector<SeqRecord> &recs, const mfx_hist_result &r, int k, const char *outName, bool *ok) {
+static bool print_hist(const std::vector<SeqRecord> &recs, const mfx_hist_result &r, int k, const char *outName) {
   uint64_t cum = 0;
   for (size_t c = 0; c < recs.size(); ++c) {   // outputHistogram's per-sequence line, in input order
     cum += r.contig_kmissing[c];
     fprintf(stderr, "%s\t%lu\t%lu\t%lu\t%.2f\n", recs[c].name.c_str(), (unsigned long)r.contig_kmissing[c], (unsigned long)cum,
             (unsigned long)r.contig_kasm[c], mfx_histoQV((double)r.contig_kmissing[c], (double)r.contig_kasm[c], k));
   }
-  *ok = mfx_hist_report(&r, k, outName, "-") == 0;
+  return mfx_hist_report(&r, k, outName, "-") == 0;
 }
 
 static void print_completeness(const double *t64, const double *u64) {
@@ -225,6 +135,27 @@ static void print_completeness(const double *t64, const double *u64) {
   fprintf(stderr, "TOTAL undrcpy:    %15.5f\n", undrc);
   fprintf(stderr, "COMPLETENESS:             %0.5f\n", 1.0 - undrc / total);
 }
+
+// the epilogue of -count and -convert
+static void print_wrote(const char *path, uint64_t n) {
+  struct stat st;
+  fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
+  if (stat(path, &st) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", st.st_size / 1e9, (double)st.st_size / (double)n);
+  fprintf(stderr, ".\n");
+}
+
+// the per-contig line of -dump and -track on stderr: name, missing k-mers, and both running sums
+struct ContigCounts {
+  uint64_t cumMissing = 0, cumAsm = 0;
+  void line(const char *name, uint64_t kasm, uint64_t kmissing) {
+    cumMissing += kmissing;
+    cumAsm += kasm;
+    fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", name, (unsigned long)kmissing, (unsigned long)cumMissing, (unsigned long)cumAsm);
+  }
+  void lines(const std::vector<SeqRecord> &recs, const mfx_hist_result &r) {   // -dump -skipMissing: the counts of a -hist run
+    for (size_t c = 0; c < recs.size(); ++c) line(recs[c].name.c_str(), r.contig_kasm[c], r.contig_kmissing[c]);
+  }
+};
 
 // Upper bound of the bases in a sequence file WITHOUT reading it (0 = unknown): a plain file cannot hold more bases
 // than bytes; a gzip file records its uncompressed size modulo 2^32 in its last four bytes (RFC 1952 ISIZE), and DNA
@@ -256,6 +187,16 @@ static uint64_t bases_upper_bound(const char *path) {
   }
   if (best < 2 * size) return 0;
   return best;
+}
+
+// the options of the variant modes (OP_* values are the MFX_VAR_* values); debug_path: the -debug log, or only whether it is set
+static mfx_variant_opts variant_opts(const Globals &G, const char *debug_path) {
+  mfx_variant_opts o;
+  o.mode = G.reportType;
+  o.comb = G.comb;
+  o.nosplit = G.nosplit ? 1 : 0;
+  o.debug_path = debug_path;
+  return o;
 }
 
 // -hist and -dump with -sharded: PARTS of the assembly, one per slot (round 4).  They only ever ask the lookup tables for the
@@ -353,17 +294,10 @@ static int run_parts(const Globals &G, int k, const std::vector<SeqRecord> &recs
     else fprintf(stderr, "-- Dump per-base k* metric to '%s' on %u devices (one part of the sequences each).\n", G.outName, N);
     if (mfx_hist_run_parts(evs.data(), own.data(), idp.data(), N, NC, &r)) fail("-hist over the parts");
     else if (G.reportType == OP_HIST) {
-      bool ok = true;
-      print_hist(recs, r, k, G.outName, &ok);
-      if (!ok) fail("writing histogram");
+      if (!print_hist(recs, r, k, G.outName)) fail("writing histogram");
       mfx_hist_result_free(&r);
     } else {                               // -dump -skipMissing (merfin-dump.C:34,81-87): no dump file, only the per-contig counts
-      uint64_t cumMissing = 0, cumAsm = 0;
-      for (size_t c = 0; c < recs.size(); ++c) {
-        cumMissing += r.contig_kmissing[c];
-        cumAsm += r.contig_kasm[c];
-        fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)r.contig_kmissing[c], (unsigned long)cumMissing, (unsigned long)cumAsm);
-      }
+      ContigCounts().lines(recs, r);
       mfx_hist_result_free(&r);
     }
   } else if (!rc) {
@@ -371,14 +305,12 @@ static int run_parts(const Globals &G, int k, const std::vector<SeqRecord> &recs
     // every contig by the slot that holds it, in input order (merfin.C:384: -dump writes in order)
     std::vector<std::pair<uint32_t, uint32_t>> where(NC);           // contig -> (slot, number inside the slot)
     for (uint32_t d = 0; d < N; ++d) for (uint32_t i = 0; i < ids[d].size(); ++i) where[ids[d][i]] = {d, i};
-    uint64_t cumMissing = 0, cumAsm = 0;
+    ContigCounts counts;
     for (uint32_t c = 0; c < NC && !rc; ++c) {
       uint64_t ka = 0, km = 0;
       const uint32_t d = where[c].first;
       if (mfx_dump_contig(evs[d], own[d], where[c].second, recs[c].name.c_str(), G.outName, c > 0, &ka, &km)) { fail("-dump over the parts"); break; }
-      cumMissing += km;
-      cumAsm += ka;
-      fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)km, (unsigned long)cumMissing, (unsigned long)cumAsm);
+      counts.line(recs[c].name.c_str(), ka, km);
     }
     if (recs.empty()) { FILE *f = fopen(G.outName, "w"); if (f) fclose(f); }
   }
@@ -394,7 +326,8 @@ static int run_parts(const Globals &G, int k, const std::vector<SeqRecord> &recs
 // look every k-mer up in all shards and add the answers (mfx_dump_contig_sharded, mfx_variants_run_sharded).  The
 // databases are decoded once: every batch is sent to all shards (mfx_index_load_db_multi).
 static int run_sharded(const Globals &G, int k, const mfx_db_info &rdb, const mfx_db_info &adb, const std::vector<SeqRecord> &recs,
-                       const std::vector<const char *> &bases, const std::vector<uint64_t> &lens, uint64_t totalBases) {
+                       const std::vector<const char *> &bases, const std::vector<uint64_t> &lens, const std::vector<const char *> &names,
+                       uint64_t totalBases) {
   const uint32_t N = (uint32_t)G.devices.size();
   std::vector<mfx_index *> ixs(N, nullptr);
   std::vector<mfx_seq *> sqs(N, nullptr);
@@ -441,32 +374,24 @@ static int run_sharded(const Globals &G, int k, const mfx_db_info &rdb, const mf
     mfx_hist_result r;
     if (mfx_hist_run_sharded(evs.data(), rts.data(), sqs.data(), N, &r)) fail("-hist over the sharded index");
     else {
-      bool ok = true;
-      print_hist(recs, r, k, G.outName, &ok);
-      if (!ok) fail("writing histogram");
+      if (!print_hist(recs, r, k, G.outName)) fail("writing histogram");
       mfx_hist_result_free(&r);
     }
   } else if (!rc && G.reportType == OP_DUMP) {
     fprintf(stderr, "-- Dump per-base k* metric to '%s' on %u devices (sharded index).\n", G.outName, N);
-    uint64_t cumMissing = 0, cumAsm = 0;
+    ContigCounts counts;
     if (G.skipMissing) {                 // merfin-dump.C:34,81-87: no dump file, only the per-contig counts
       mfx_hist_result r;
       if (mfx_hist_run_sharded(evs.data(), rts.data(), sqs.data(), N, &r)) fail("-dump -skipMissing over the sharded index");
       else {
-        for (size_t c = 0; c < recs.size(); ++c) {
-          cumMissing += r.contig_kmissing[c];
-          cumAsm += r.contig_kasm[c];
-          fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)r.contig_kmissing[c], (unsigned long)cumMissing, (unsigned long)cumAsm);
-        }
+        counts.lines(recs, r);
         mfx_hist_result_free(&r);
       }
     } else {
       for (size_t c = 0; c < recs.size() && !rc; ++c) {
         uint64_t ka = 0, km = 0;
         if (mfx_dump_contig_sharded(evs.data(), sqs.data(), N, (uint32_t)c, recs[c].name.c_str(), G.outName, c > 0, &ka, &km)) { fail("-dump over the sharded index"); break; }
-        cumMissing += km;
-        cumAsm += ka;
-        fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)km, (unsigned long)cumMissing, (unsigned long)cumAsm);
+        counts.line(recs[c].name.c_str(), ka, km);
       }
       if (recs.empty()) { FILE *f = fopen(G.outName, "w"); if (f) fclose(f); }
     }
@@ -475,13 +400,7 @@ static int run_sharded(const Globals &G, int k, const mfx_db_info &rdb, const mf
     fprintf(stderr, "-- Generate variant mers and score them on %u devices (sharded index).\n", N);
     const std::string outName = std::string(G.outName) + (G.reportType == OP_POLISH ? ".polish.vcf" : ".filter.vcf");   // merfin-variants.C:324-327
     const std::string dbgName = std::string(G.outName) + ".00.debug.gz";
-    std::vector<const char *> names(recs.size());
-    for (size_t c = 0; c < recs.size(); ++c) names[c] = recs[c].name.c_str();
-    mfx_variant_opts vo;
-    vo.mode = G.reportType;
-    vo.comb = G.comb;
-    vo.nosplit = G.nosplit ? 1 : 0;
-    vo.debug_path = G.debug ? dbgName.c_str() : nullptr;
+    const mfx_variant_opts vo = variant_opts(G, G.debug ? dbgName.c_str() : nullptr);
     uint64_t ncl = 0;
     if (mfx_variants_run_sharded(evs.data(), N, G.vcfName, names.data(), bases.data(), lens.data(), (uint32_t)recs.size(), &vo, outName.c_str(), nullptr, &ncl))
       fail("variant scoring over the sharded index");
@@ -742,7 +661,7 @@ static bool count_reads_files(const Globals &G, mfx_index *ix, bool all = false,
   if (!all)
     fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu counted, %lu dropped.\n", G.kArg, (unsigned long)st.reads,
             (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)st.counted, (unsigned long)st.dropped);
-  if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
+  if (env_flag("MFX_CLI_TIMING") > 0)
     fprintf(stderr, "-- reads: %.3f s wall = %.3f s waiting for parsed records + %.3f s batching / encoding / waiting for a stage; device %.3f s kernel + "
                     "%.3f s copy (idle %.0f %% of the wall)\n", wall, t_wait, t_submit, st.seconds_kernel, st.seconds_copy,
             wall > 0 ? 100.0 * std::max(0.0, 1.0 - (st.seconds_kernel + st.seconds_copy) / wall) : 0.0);
@@ -1027,1097 +946,972 @@ static int count_in_passes(const Globals &G) {
   mfx_db_writer *w = C.w;
   C.w = nullptr;
   if (mfx_db_writer_close(w, &n)) DIE_MFX("-count: writing the database");
-  struct stat ost;
-  fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
-  if (stat(G.outName, &ost) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", ost.st_size / 1e9, (double)ost.st_size / (double)n);
-  fprintf(stderr, ".\n");
-  if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
+  print_wrote(G.outName, n);
+  if (env_flag("MFX_CLI_TIMING") > 0)
     fprintf(stderr, "-- count: %.3f s writing\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count());
   fprintf(stderr, "Bye!\n");
   return 0;
 }
 
-int main(int argc, char **argv) {
-  // MFX_CLI_TIMING=3: wall-clock stamps (seconds since the epoch) at main / after the device check / at the end, so that a
-  // caller who timed the whole process can tell start-up and tear-down from the phases (diagnostics)
-  auto epoch = [] { return std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count(); };
-  const double stamp_main = epoch();
-  Globals G;
-  std::vector<std::string> err;
-  for (int arg = 1; arg < argc; arg++) {
-    auto is = [&](const char *f) { return strcmp(argv[arg], f) == 0; };
-    auto val = [&]() -> const char * { return arg + 1 < argc ? argv[++arg] : ""; };
-    if (is("-sequence")) G.seqName = val();
-    else if (is("-seqmers")) G.seqDBname = val();
-    else if (is("-readmers")) G.readDBname = val();
-    else if (is("-reads")) G.readsNames.push_back(val());
-    else if (is("-k")) {
-      const char *v = val();
-      char *e = nullptr;
-      const long kk = strtol(v, &e, 10);
-      G.kArg = (e != v && *e == 0 && kk >= 1 && kk <= 64) ? (int)kk : -1;
-      if (G.kArg < 0) err.push_back(std::string("Invalid -k '") + v + "': k is 1 to 64.\n");
-    }
-    else if (is("-peak")) {
-      const char *v = val();
-      if (strcmp(v, "auto") == 0) G.peakAuto = true;
-      else G.peak = strtod(v, nullptr);
-      G.peakGiven = true;
-    }
-    else if (is("-spectrum")) G.reportType = OP_SPECTRUM;
-    else if (is("-copies") || is("-maxmult")) {
-      const bool cp = is("-copies");
-      const char *v = val();
-      char *e = nullptr;
-      errno = 0;
-      const unsigned long long x = strtoull(v, &e, 10);
-      const unsigned long long lo = cp ? 1 : 4, hi = cp ? 6 : 65536;
-      (cp ? G.copiesGiven : G.maxMultGiven) = true;
-      if (e == v || *e != 0 || errno != 0 || !isdigit((unsigned char)v[0]) || x < lo || x > hi)
-        err.push_back(std::string("Invalid ") + (cp ? "-copies" : "-maxmult") + " '" + v + "': an integer from " + std::to_string(lo) + " to " + std::to_string(hi) + ".\n");
-      else (cp ? G.copies : G.maxMult) = (uint32_t)x;
-    }
-    else if (is("-prob")) G.pLookupTable = val();
-    else if (is("-vcf")) G.vcfName = val();
-    else if (is("-output")) G.outName = val();
-    else if (is("-min")) G.minV = strtoull(val(), nullptr, 10);
-    else if (is("-max")) G.maxV = strtoull(val(), nullptr, 10);
-    else if (is("-threads")) G.threads = atoi(val());
-    else if (is("-memory")) G.maxMemory = strtod(val(), nullptr);
-    else if (is("-device")) G.device = atoi(val());
-    else if (is("-devices")) {
-      // "0-7", "0,2,5", "0-3,6": a device may be named twice (two evaluation contexts on one GPU)
-      std::string spec = val();
-      bool ok = !spec.empty();
-      for (size_t i = 0; ok && i < spec.size();) {
-        char *e = nullptr;
-        long a = strtol(spec.c_str() + i, &e, 10), b = a;
-        ok = e != spec.c_str() + i && a >= 0;
-        i = (size_t)(e - spec.c_str());
-        if (ok && i < spec.size() && spec[i] == '-') {
-          const char *s2 = spec.c_str() + i + 1;
-          b = strtol(s2, &e, 10);
-          ok = e != s2 && b >= a;
-          i = (size_t)(e - spec.c_str());
-        }
-        for (long d = a; ok && d <= b && d < 1024; ++d) G.devices.push_back((int)d);
-        if (ok && i < spec.size()) { ok = spec[i] == ','; ++i; }
-      }
-      if (!ok || G.devices.empty()) { G.devices.clear(); err.push_back(std::string("Invalid device list '") + spec + "' (-devices 0-7 or 0,2,5).\n"); }
-    }
-    else if (is("-index")) G.indexName = val();
-    else if (is("-sharded")) G.sharded = true;
-    else if (is("-convert")) G.convertName = val();
-    else if (is("-count")) G.count = true;
-    else if (is("-passes")) {
-      const char *v = val();
-      char *e = nullptr;
-      errno = 0;
-      const long long x = strtoll(v, &e, 10);
-      G.passesGiven = true;
-      if (strcmp(v, "auto") == 0) G.passesAuto = true;
-      else if (e == v || *e != 0 || errno != 0) err.push_back(std::string("Invalid -passes '") + v + "': the passes of -count are a number from 1 to 4096, or auto.\n");
-      else if (x < 1) err.push_back(std::string("Invalid -passes '") + v + "': -count takes at least one pass (1 to 4096, or auto).\n");
-      else if (x > 4096) err.push_back(std::string("Invalid -passes '") + v + "': a pass takes at least one of the 4096 key bins, so there are 4096 at most (or auto).\n");
-      else G.passes = (uint32_t)x;
-    }
-    else if (is("-placed")) G.placed = true;
-    else if (is("-nosplit")) G.nosplit = true;
-    else if (is("-filter")) G.reportType = OP_FILTER;
-    else if (is("-better")) G.reportType = OP_BETTER;
-    else if (is("-strict")) G.reportType = OP_STRICT;
-    else if (is("-loose")) { fprintf(stderr, "*EXPERIMENTAL* Running in -loose mode\n"); G.reportType = OP_LOOSE; }
-    else if (is("-polish")) G.reportType = OP_POLISH;
-    else if (is("-hist")) G.reportType = OP_HIST;
-    else if (is("-dump")) G.reportType = OP_DUMP;
-    else if (is("-track")) G.reportType = OP_TRACK;
-    else if (is("-window")) {
-      const char *v = val();
-      char *e = nullptr;
-      errno = 0;
-      const unsigned long long w = strtoull(v, &e, 10);
-      G.windowGiven = true;
-      if (e == v || *e != 0 || errno != 0 || w < 1 || !isdigit((unsigned char)v[0])) err.push_back(std::string("Invalid -window '") + v + "': a window is an integer of at least 1.\n");
-      else G.window = w;
-    }
-    else if (is("-skipMissing")) G.skipMissing = true;
-    else if (is("-completeness")) G.reportType = OP_COMPL;
-    else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
-    else if (is("-debug")) G.debug = true;
-    else err.push_back(std::string("Unknown option '") + argv[arg] + "'.\n");
-  }
+// what a run owns, released on every way out
+template <class T, void (*Free)(T *)>
+struct Owned {
+  T *p = nullptr;
+  Owned() = default;
+  Owned(const Owned &) = delete;
+  ~Owned() { reset(); }
+  void reset(T *q = nullptr) { if (p) Free(p); p = q; }
+  Owned &operator=(T *q) { reset(q); return *this; }
+  T *release() { T *q = p; p = nullptr; return q; }
+  operator T *() const { return p; }
+};
+// a call set that a thread of its own loads: waited for, and freed if nobody took it
+struct VcfFuture {
+  std::future<mfx_vcf *> f;
+  ~VcfFuture() { if (f.valid()) mfx_vcf_free(f.get()); }
+};
 
-  // -count: every check before any device is touched (the checks of a report from -reads below do not apply to it)
-  if (G.count) {
-    if (G.convertName) err.push_back("-count and -convert are two operations: give one of them.\n");
-    if (G.reportType != OP_NONE) err.push_back("-count is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
-    if (G.readsNames.empty()) err.push_back("-count needs the reads it counts: give -reads <file> (repeatable).\n");
-    if (G.kArg == 0) err.push_back("-count needs -k: no database gives it.\n");
-    if (!G.outName) err.push_back("-count writes a k-mer database: give -output <file>.\n");
-    if (G.kArg > 31)
-      err.push_back("-count holds k <= 31 (here k = " + std::to_string(G.kArg) + "): count larger k-mers with `meryl count` and give the database as -readmers.\n");
-    if (G.readDBname) err.push_back("-count makes the read database: it does not take -readmers.\n");
-    if (G.seqDBname) err.push_back("-count counts reads: it does not take -seqmers.\n");
-    if (G.seqName) err.push_back("-count counts reads: it does not take -sequence.\n");
-    if (G.vcfName) err.push_back("-count does not take -vcf (the variant modes do).\n");
-    if (G.peakGiven) err.push_back("-count evaluates nothing: it does not take -peak.\n");
-    if (G.sharded) err.push_back("-count does not take -sharded: the table it counts into lives on one device.\n");
-    if (G.indexName) err.push_back("-count does not take -index: it writes a database, not a table image.\n");
-    if (G.devices.size() > 1) err.push_back("-count runs on one device (-device d, or -devices naming one).\n");
-    for (const char *f : G.readsNames) {
-      struct stat rst;
-      if (stat(f, &rst) != 0 || !S_ISREG(rst.st_mode) || access(f, R_OK) != 0)
-        err.push_back(std::string("Cannot read the -reads file '") + f + "'.\n");
-    }
-    if (!err.empty()) {
-      usage(argv[0]);
-      for (auto &e : err) fputs(e.c_str(), stderr);
-      return 1;
-    }
-    if (!G.devices.empty()) G.device = G.devices[0];
-    if (mfx_device_count() <= G.device) {
-      fprintf(stderr, "ERROR: HIP device %d not available (%d visible). This program has no CPU path.\n", G.device, mfx_device_count());
-      return 1;
-    }
-    if (G.passesGiven) {
-      fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s in passes over key ranges.\n", G.kArg, (unsigned long)G.readsNames.size(),
-              G.readsNames.size() == 1 ? "" : "s");
-      return count_in_passes(G);
-    }
-    const int streamed = count_writer_streamed();
-    if (streamed < 0) return 1;
-    // the table is created small and grows with what the reads hold (mfx_reads_begin_all)
-    const auto tc0 = std::chrono::steady_clock::now();
-    uint64_t count_batch = 0;                                      // MFX_COUNT_BATCH (docs/KNOBS.md): bases per device batch; unset: the library's
-    if (const char *e = getenv("MFX_COUNT_BATCH")) count_batch = strtoull(e, nullptr, 10);
-    mfx_index *ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
-    if (!ix) DIE_MFX("creating the k-mer table");
-    struct IxGuard { mfx_index *ix; ~IxGuard() { mfx_index_free(ix); } } ixGuard{ix};
-    fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s.\n", G.kArg, (unsigned long)G.readsNames.size(), G.readsNames.size() == 1 ? "" : "s");
-    mfx_reads_stats st;
-    int count_code = MFX_OK;
-    std::string count_text;
-    if (!count_reads_files(G, ix, true, &st, count_batch, nullptr, &count_code, &count_text)) {
-      if (count_code != MFX_OK) fprintf(stderr, "ERROR: counting -reads: %s\n", count_text.c_str());
-      if (count_code == MFX_E_NOMEM)
-        fprintf(stderr, "-- Hint: -passes auto counts the k-mers in passes over key ranges, each in a table of its own that fits -memory and the device.\n");
-      return 1;
-    }
-    mfx_index_info info;
-    uint64_t growths = 0;
-    if (mfx_index_get_info(ix, &info) || mfx_index_growths(ix, &growths, nullptr, nullptr, nullptr)) DIE_MFX("-count");
-    fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu distinct; the table grew %lu time%s to %.3f GB.\n", G.kArg,
-            (unsigned long)st.reads, (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)info.distinct, (unsigned long)growths,
-            growths == 1 ? "" : "s", (double)info.bytes / 1e9);
-    const auto tc1 = std::chrono::steady_clock::now();
-    uint64_t n = 0;
-    if (streamed ? mfx_index_write_db_streamed(ix, 0, G.outName, &n) : mfx_index_write_db(ix, 0, G.outName, &n)) DIE_MFX("-count: writing the database");
-    struct stat ost;
-    fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
-    if (stat(G.outName, &ost) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", ost.st_size / 1e9, (double)ost.st_size / (double)n);
-    fprintf(stderr, ".\n");
-    if (getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING")))
-      fprintf(stderr, "-- count: %.3f s counting, %.3f s sorting and writing\n", std::chrono::duration<double>(tc1 - tc0).count(),
-              std::chrono::duration<double>(std::chrono::steady_clock::now() - tc1).count());
-    fprintf(stderr, "Bye!\n");
-    return 0;
+// ---- the operations that are not reports ----------------------------------------------------------------------------------------------
+// merfin -count -reads <files> -k K -output <file>: the table is created small and grows with what the reads hold (mfx_reads_begin_all)
+static int run_count(Globals &G) {
+  if (!G.devices.empty()) G.device = G.devices[0];
+  if (!devices_available({G.device})) return 1;
+  if (G.passesGiven) {
+    fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s in passes over key ranges.\n", G.kArg, (unsigned long)G.readsNames.size(),
+            G.readsNames.size() == 1 ? "" : "s");
+    return count_in_passes(G);
   }
-
-  if (G.passesGiven && !G.count) err.push_back("-passes divides the work of -count: it has no meaning without -count.\n");
-
-  // -reads: every check before any device is touched
-  const bool fromReads = !G.readsNames.empty();
-  const bool variantFlag = G.reportType == OP_POLISH || G.reportType == OP_FILTER || G.reportType == OP_BETTER ||
-                           G.reportType == OP_STRICT || G.reportType == OP_LOOSE;
-  if (fromReads) {
-    if (G.convertName) err.push_back("-convert rewrites a k-mer database; it does not take -reads.\n");
-    if (G.readDBname) err.push_back("-reads and -readmers cannot be combined: the read counts come from one source.\n");
-    if (G.reportType == OP_COMPL) err.push_back("-completeness needs every read k-mer: it takes a read database (-readmers), not -reads.\n");
-    if (G.sharded) err.push_back("-sharded does not take -reads (give the read database with -readmers).\n");
-    if (G.kArg == 0 && !G.seqDBname) err.push_back("-reads needs -k (or -seqmers, whose k it then takes).\n");
-    for (const char *f : G.readsNames) {
-      struct stat rst;
-      if (stat(f, &rst) != 0 || !S_ISREG(rst.st_mode) || access(f, R_OK) != 0)
-        err.push_back(std::string("Cannot read the -reads file '") + f + "'.\n");
-    }
-    if (variantFlag && (G.indexName || G.devices.size() > 1))
-      err.push_back("The variant modes count -reads into the path-only index of the call set: one device, no -index.\n");
-    if (G.seqDBname && !G.convertName && !G.readDBname) {
-      mfx_db_info sdb;
-      if (mfx_db_probe(G.seqDBname, &sdb)) DIE_MFX("opening -seqmers");
-      if (G.kArg > 0 && sdb.k != G.kArg) err.push_back("-k " + std::to_string(G.kArg) + " disagrees with -seqmers, which holds " + std::to_string(sdb.k) + "-mers.\n");
-      else G.kArg = sdb.k;
-    }
-    if (variantFlag && G.kArg > 31)
-      err.push_back("The variant modes count -reads into the path-only index, which holds k <= 31 (here k = " + std::to_string(G.kArg) + ").\n");
-  }
-
-  if (G.kArg > 0 && G.readDBname && !fromReads) err.push_back("-k is taken from -readmers; give -k only with -reads.\n");
-
-  // -track: every check before any device is touched
-  if (G.windowGiven && G.reportType != OP_TRACK) err.push_back("-window sets the window of -track; it has no meaning without -track.\n");
-  if (G.reportType == OP_TRACK) {
-    if (G.sharded) err.push_back("-track does not take -sharded: a window's records need every k-mer's counts on one device.\n");
-    if (G.devices.size() > 1) err.push_back("-track runs on one device (-device d, or -devices naming one).\n");
-    if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -track always writes its windows.\n");
-    if (G.vcfName) err.push_back("-track does not take -vcf (the variant modes do).\n");
-  }
-
-  // -spectrum / -peak auto: every check before any device is touched
-  if ((G.copiesGiven || G.maxMultGiven) && G.reportType != OP_SPECTRUM)
-    err.push_back("-copies and -maxmult shape the image of -spectrum; they have no meaning without -spectrum.\n");
-  if (G.reportType == OP_SPECTRUM) {
-    if (G.vcfName) err.push_back("-spectrum does not take -vcf (the variant modes do).\n");
-    if (G.sharded) err.push_back("-spectrum does not take -sharded: this version counts the spectrum of one table on one device.\n");
-    if (G.devices.size() > 1) err.push_back("-spectrum runs on one device (-device d, or -devices naming one).\n");
-    if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -spectrum counts every entry of the table.\n");
-    if (!G.seqName && !G.seqDBname) err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
-    if (!G.seqName && !G.readsNames.empty()) err.push_back("-spectrum counts -reads into the k-mers of -sequence: give -sequence.\n");
-  }
-  if (G.peakAuto) {
-    if (G.peak != 0) err.push_back("-peak was given twice (a number and auto).\n");
-    if (G.reportType != OP_HIST && G.reportType != OP_DUMP && G.reportType != OP_TRACK && G.reportType != OP_SPECTRUM && G.reportType != OP_NONE)
-      err.push_back("-peak auto reads the peak off the table of -hist, -dump, -track or -spectrum; the variant modes and -completeness take -peak <number>.\n");
-    if (G.sharded) err.push_back("-peak auto does not take -sharded: no peak is defined on a sharded table.\n");
-    if (G.devices.size() > 1) err.push_back("-peak auto runs on one device (-device d, or -devices naming one).\n");
-  }
-
-  if (G.convertName && err.empty()) {
-    // merfin -convert <db> -output <file>: a database in any accepted form rewritten as this program's flat form (sorted
-    // k-mers in delta-coded blocks), on the host -- no report, no device
-    if (!G.outName) { fprintf(stderr, "No output (-output) supplied.\n"); return 1; }
-    fprintf(stderr, "-- Converting '%s' to '%s'.\n", G.convertName, G.outName);
-    uint64_t n = 0;
-    if (G.placed ? mfx_db_convert_placed(G.convertName, G.outName, &n) : mfx_db_convert(G.convertName, G.outName, &n)) {
-      fprintf(stderr, "ERROR: -convert: %s\n", mfx_last_error());
-      return 1;
-    }
-    struct stat st;
-    fprintf(stderr, "-- Wrote %lu k-mers", (unsigned long)n);
-    if (stat(G.outName, &st) == 0 && n) fprintf(stderr, " in %.2f GB (%.2f bytes per k-mer)", st.st_size / 1e9, (double)st.st_size / (double)n);
-    fprintf(stderr, ".\nBye!\n");
-    return 0;
-  }
-
-  // merfin.C:159-181
-  const bool variantMode = G.reportType == OP_POLISH || G.reportType == OP_FILTER || G.reportType == OP_BETTER ||
-                           G.reportType == OP_STRICT || G.reportType == OP_LOOSE;
-  if (G.reportType == OP_SPECTRUM) {
-    if (!G.outName) err.push_back("No output (-output) supplied.\n");
-  } else if (G.reportType != OP_COMPL) {
-    if (!G.seqName) err.push_back("No input sequences (-sequence) supplied.\n");
-    if (!G.outName) err.push_back("No output (-output) supplied.\n");
-  }
-  if (variantMode && !G.vcfName) err.push_back("No variant call input (-vcf) supplied; mandatory for -filter or -polish.\n");
-  if (G.reportType != OP_FILTER && G.reportType != OP_SPECTRUM && G.peak == 0 && !G.peakAuto) err.push_back("No haploid peak (-peak) supplied.\n");
-  if (G.reportType == OP_COMPL && !G.seqName && !G.seqDBname)
-    err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
-  if (G.reportType == OP_NONE) err.push_back("No report type (-filter, -polish, -hist, -dump, -completeness) supplied.\n");
-  if (!G.readDBname && !fromReads) err.push_back("No read meryl database (-readmers) supplied.\n");
-  if (!err.empty()) {
-    usage(argv[0]);
-    for (auto &e : err) fputs(e.c_str(), stderr);
+  const int streamed = count_writer_streamed();
+  if (streamed < 0) return 1;
+  const auto tc0 = std::chrono::steady_clock::now();
+  uint64_t count_batch = 0;                                      // MFX_COUNT_BATCH (docs/KNOBS.md): bases per device batch; unset: the library's
+  if (const char *e = getenv("MFX_COUNT_BATCH")) count_batch = strtoull(e, nullptr, 10);
+  Owned<mfx_index, mfx_index_free> ix;
+  ix = mfx_index_create(G.kArg, 1024, G.maxMemory, G.device);
+  if (!ix) DIE_MFX("creating the k-mer table");
+  fprintf(stderr, "-- Counting the %d-mers of %lu -reads file%s.\n", G.kArg, (unsigned long)G.readsNames.size(), G.readsNames.size() == 1 ? "" : "s");
+  mfx_reads_stats st;
+  int count_code = MFX_OK;
+  std::string count_text;
+  if (!count_reads_files(G, ix, true, &st, count_batch, nullptr, &count_code, &count_text)) {
+    if (count_code != MFX_OK) fprintf(stderr, "ERROR: counting -reads: %s\n", count_text.c_str());
+    if (count_code == MFX_E_NOMEM)
+      fprintf(stderr, "-- Hint: -passes auto counts the k-mers in passes over key ranges, each in a table of its own that fits -memory and the device.\n");
     return 1;
   }
-  if (!G.devices.empty()) G.device = G.devices[0];
-  else G.devices.push_back(G.device);
-  // load_Kmetric first (merfin-globals.C:21-62 runs before the databases are opened; host only -- a compressed table's decompressor has
-  // come and gone before the HIP runtime starts)
-  if (!load_Kmetric(G)) return 1;
-  // (the device check stays on this thread, before anything else is started: the HIP runtime coming up on a thread of its own
-  // while this one spawns a decompressor for -sequence was seen to come up with no device)
-  for (int d : G.devices)
-    if (mfx_device_count() <= d) {
-      fprintf(stderr, "ERROR: HIP device %d not available (%d visible). This program has no CPU path.\n", d, mfx_device_count());
-      return 1;
-    }
+  mfx_index_info info;
+  uint64_t growths = 0;
+  if (mfx_index_get_info(ix, &info) || mfx_index_growths(ix, &growths, nullptr, nullptr, nullptr)) DIE_MFX("-count");
+  fprintf(stderr, "-- Counted the %d-mers of %lu reads (%lu bases): %lu k-mers, %lu distinct; the table grew %lu time%s to %.3f GB.\n", G.kArg,
+          (unsigned long)st.reads, (unsigned long)st.bases, (unsigned long)st.kmers, (unsigned long)info.distinct, (unsigned long)growths,
+          growths == 1 ? "" : "s", (double)info.bytes / 1e9);
+  const auto tc1 = std::chrono::steady_clock::now();
+  uint64_t n = 0;
+  if (streamed ? mfx_index_write_db_streamed(ix, 0, G.outName, &n) : mfx_index_write_db(ix, 0, G.outName, &n)) DIE_MFX("-count: writing the database");
+  print_wrote(G.outName, n);
+  if (env_flag("MFX_CLI_TIMING") > 0)
+    fprintf(stderr, "-- count: %.3f s counting, %.3f s sorting and writing\n", std::chrono::duration<double>(tc1 - tc0).count(),
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - tc1).count());
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
 
-  const double stamp_devices = epoch();
-  // MFX_CLI_TIMING=1: wall time per phase on stderr at exit (diagnostics; not part of merfin's output)
-  const bool timing = getenv("MFX_CLI_TIMING") && atoi(getenv("MFX_CLI_TIMING"));
-  auto t_last = std::chrono::steady_clock::now();
-  std::vector<std::pair<const char *, double>> phases;
-  auto lap = [&](const char *what) {
-    auto t = std::chrono::steady_clock::now();
-    phases.emplace_back(what, std::chrono::duration<double>(t - t_last).count());
-    t_last = t;
-  };
-  // MFX_CLI_TIMING=2: the steps of the index build as well
-  auto t_sub = t_last;
-  std::vector<std::pair<const char *, double>> steps;
-  auto step = [&](const char *what) {
-    auto t = std::chrono::steady_clock::now();
-    steps.emplace_back(what, std::chrono::duration<double>(t - t_sub).count());
-    t_sub = t;
-  };
+// merfin -convert <db> -output <file>: a database in any accepted form rewritten as this program's flat form (sorted
+// k-mers in delta-coded blocks), on the host -- no report, no device
+static int run_convert(const Globals &G) {
+  if (!G.outName) { fprintf(stderr, "No output (-output) supplied.\n"); return 1; }
+  fprintf(stderr, "-- Converting '%s' to '%s'.\n", G.convertName, G.outName);
+  uint64_t n = 0;
+  if (G.placed ? mfx_db_convert_placed(G.convertName, G.outName, &n) : mfx_db_convert(G.convertName, G.outName, &n)) DIE_MFX("-convert");
+  print_wrote(G.outName, n);
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
 
-  // load_Kmers, merfin-globals.C:114-163: the read DB defines k
-  mfx_db_info rdb, adb;
-  memset(&rdb, 0, sizeof(rdb));
-  if (!fromReads && mfx_db_probe(G.readDBname, &rdb)) DIE_MFX("opening -readmers");
-  const int k = fromReads ? G.kArg : rdb.k;                       // (-reads: -k, or the k of -seqmers, checked above)
-  memset(&adb, 0, sizeof(adb));
-  if (G.seqDBname) {
-    if (mfx_db_probe(G.seqDBname, &adb)) DIE_MFX("opening -seqmers");
-    if (adb.k != k) { fprintf(stderr, "ERROR: -seqmers holds %d-mers but -readmers holds %d-mers.\n", adb.k, k); return 1; }
+// ---- the run of a report: what its steps share ------------------------------------------------------------------------------------------
+static double epoch() { return std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count(); }
+
+// MFX_CLI_TIMING=1: wall time per phase on stderr at exit (diagnostics; not part of merfin's output); 2: the steps of the index build as well;
+// 3: wall-clock stamps (seconds since the epoch) at main / after the device check / at the end, so that a caller who timed the whole process
+// can tell start-up and tear-down from the phases
+struct PhaseClock {
+  typedef std::vector<std::pair<const char *, double>> Marks;
+  const int level = env_flag("MFX_CLI_TIMING");
+  double stamp_main = 0, stamp_devices = 0;
+  std::chrono::steady_clock::time_point t_last, t_sub;
+  Marks phases, steps;
+  void start(double at_main) { stamp_main = at_main; stamp_devices = epoch(); t_last = t_sub = std::chrono::steady_clock::now(); }
+  static void mark(Marks &m, std::chrono::steady_clock::time_point &since, const char *what) {
+    const auto t = std::chrono::steady_clock::now();
+    m.emplace_back(what, std::chrono::duration<double>(t - since).count());
+    since = t;
   }
+  void lap(const char *what) { mark(phases, t_last, what); }
+  void step(const char *what) { mark(steps, t_sub, what); }
+  void print() const {
+    if (level <= 0) return;
+    fprintf(stderr, "-- timing:");
+    for (auto &ph : phases) fprintf(stderr, "  %s %.2fs", ph.first, ph.second);
+    fprintf(stderr, "\n");
+    if (level > 1 && !steps.empty()) {
+      fprintf(stderr, "-- timing (index):");
+      for (auto &ph : steps) fprintf(stderr, "  %s %.3fs", ph.first, ph.second);
+      fprintf(stderr, "\n");
+    }
+    if (level > 2) fprintf(stderr, "-- stamps: main %.6f devices %.6f end %.6f\n", stamp_main, stamp_devices, epoch());
+  }
+};
 
-  if (rdb.format == MFX_DB_MERYL || (G.seqDBname && adb.format == MFX_DB_MERYL))
+// sequences (load_Sequence, merfin-globals.C:165-197; loadSequence, merfin.C:30-53).  The file is read (and, for .gz/.bz2/.xz, decompressed) by
+// its own thread from start() on; with -seqmers nothing needs the sequence before the evaluation, so the read then runs under the index build
+// and is only waited for afterwards (finish()).
+struct Sequences {
+  std::vector<SeqRecord> recs;
+  std::vector<const char *> bases, names;
+  std::vector<uint64_t> lens;
+  uint64_t totalBases = 0;
+  std::thread reader;
+  bool readFailed = false;               // written by the reader thread, read after the join
+  bool done = false;
+  ~Sequences() { if (reader.joinable()) reader.join(); }
+  uint32_t size() const { return (uint32_t)recs.size(); }
+  bool start(const char *path) {         // false: the file cannot be opened
+    auto sf = std::make_shared<SeqFile>(path);
+    if (!sf->ok()) return false;
+    const std::string seqPath = path;
+    reader = std::thread([this, sf, seqPath]() {
+      if (read_fasta_parallel(seqPath, recs)) { readFailed = sf->finish() != 0; return; }     // plain FASTA: all host threads
+      SeqRecord r;
+      while (sf->next(r)) recs.push_back(std::move(r));
+      readFailed = sf->finish() != 0;       // a decompressor that died mid-stream: the records read so far are NOT the file
+    });
+    return true;
+  }
+  bool finish() {                        // the records are in; false: reading the file failed
+    done = true;
+    if (reader.joinable()) reader.join();
+    if (readFailed) return false;
+    bases.resize(recs.size());
+    lens.resize(recs.size());
+    names.resize(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) { bases[i] = recs[i].data(); lens[i] = recs[i].size(); names[i] = recs[i].name.c_str(); totalBases += lens[i]; }
+    return true;
+  }
+};
+
+struct Run {
+  Globals &G;
+  int k = 0;
+  mfx_db_info rdb, adb;
+  const bool fromReads, variantMode;
+  const bool fullIndex = env_flag("MFX_CLI_FULL_INDEX") > 0;     // the full tables for every report type
+  const int vcfAheadKnob = env_flag("MFX_CLI_VCF_AHEAD");
+  bool seqOnly = false;                  // -hist, -dump, -track: the sequence-only index (decide_seq_only_and_defer)
+  bool pathOnly = false;                 // the variant modes on the path-only index of their call set (decide_path_only)
+  bool streamHist = false, deferSeq = false;
+  uint64_t basesBound = 0, fingerprint = 0, fingerprintFull = 0;
+  PhaseClock clock;
+  mfx_kparams kp;
+  Owned<mfx_db_stage, mfx_db_stage_free> stage, stageAsm;        // (stageAsm: -seqmers of the path-only index)
+  Owned<mfx_index, mfx_index_free> ix;
+  Owned<mfx_seq, mfx_seq_free> seq;
+  Owned<mfx_eval, mfx_eval_free> ev;
+  Sequences S;
+  std::string vcfAheadError;
+  Owned<mfx_vcf, mfx_vcf_free> vcfReady;                         // the call set taken from vcfLoad (prepared): report_variants uses it
+  VcfFuture vcfLoad, vcfAhead;                                   // (last: their threads read the members above)
+  explicit Run(Globals &g) : G(g), fromReads(!g.readsNames.empty()), variantMode(variant_mode(g.reportType)) {}
+};
+
+static size_t variant_slots(const Globals &G) {
+  const int vs = env_flag("MFX_VARIANT_SLOTS");
+  return vs > 0 ? (size_t)vs : G.devices.size();
+}
+
+// load_Kmers, merfin-globals.C:114-163: the read DB defines k
+static int probe_databases(Run &R) {
+  const Globals &G = R.G;
+  memset(&R.rdb, 0, sizeof(R.rdb));
+  if (!R.fromReads && mfx_db_probe(G.readDBname, &R.rdb)) DIE_MFX("opening -readmers");
+  R.k = R.fromReads ? G.kArg : R.rdb.k;                           // (-reads: -k, or the k of -seqmers, checked before)
+  memset(&R.adb, 0, sizeof(R.adb));
+  if (G.seqDBname) {
+    if (mfx_db_probe(G.seqDBname, &R.adb)) DIE_MFX("opening -seqmers");
+    if (R.adb.k != R.k) { fprintf(stderr, "ERROR: -seqmers holds %d-mers but -readmers holds %d-mers.\n", R.adb.k, R.k); return 1; }
+  }
+  if (R.rdb.format == MFX_DB_MERYL || (G.seqDBname && R.adb.format == MFX_DB_MERYL))
     fprintf(stderr, "-- NOTE: meryl database directories are decoded from a recalled description of the format; it has not been\n"
                     "--       checked against upstream meryl.  The decoder cross-checks every database against its own index\n"
                     "--       statistics; `meryl print` text is the verified interchange form.  To validate the decoder on this\n"
                     "--       database: python tools/meryl_conformance.py <db.meryl> <output of `meryl print db.meryl`>\n"
                     "--       (= MFX_REAL_MERYL_DB / MFX_REAL_MERYL_PRINT for tests/test_gpu_meryl_conformance.py).\n");
-  // `merfin -hist / -dump -sequence s -readmers db` on one device with a delta-coded database and no -seqmers: the database's bytes start
-  // moving into device memory NOW, on a thread of their own (mfx_db_stage_begin) -- under the FASTA read, the sequence upload, the
-  // table's allocation and the kernel that claims the sequence's k-mers.  Any other database form, too little free memory,
-  // MFX_DB_STAGE=0: no stage, the build reads the database when it gets there.
-  bool pathOnly = false;                                            // the variant modes on the path-only index of their call set (decided below)
-  mfx_db_stage *stage = nullptr, *stageAsm = nullptr;              // (stageAsm: -seqmers of the path-only index)
-  struct StageGuard { mfx_db_stage *&s; ~StageGuard() { if (s) mfx_db_stage_free(s); s = nullptr; } } stageGuard{stage}, stageAsmGuard{stageAsm};
+  return 0;
+}
+
+// `merfin -hist / -dump -sequence s -readmers db` on one device with a delta-coded database and no -seqmers: the database's bytes start
+// moving into device memory NOW, on a thread of their own (mfx_db_stage_begin) -- under the FASTA read, the sequence upload, the
+// table's allocation and the kernel that claims the sequence's k-mers.  Any other database form, too little free memory,
+// MFX_DB_STAGE=0: no stage, the build reads the database when it gets there.
+static void begin_stage(Run &R) {
+  const Globals &G = R.G;
+  const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && R.k <= 31 && G.seqName && !G.seqDBname &&
+                        !G.indexName && G.devices.size() == 1 && !R.fullIndex;
+  if (histLike && R.rdb.format == MFX_DB_FLAT) R.stage = mfx_db_stage_begin(G.readDBname, G.device);
+}
+// the path-only index of the variant modes: both databases move while the call set is prepared and its paths are claimed -- from the moment
+// the sequences are in (under the FASTA reader the stagers' threads cost it 0.2 s of a 3 Gb file on a 16-core quota)
+static void begin_path_stages(Run &R) {
+  const Globals &G = R.G;
+  if (R.rdb.format == MFX_DB_FLAT) R.stage = mfx_db_stage_begin(G.readDBname, G.device);
+  if (G.seqDBname && R.adb.format == MFX_DB_FLAT) R.stageAsm = mfx_db_stage_begin(G.seqDBname, G.device);
+}
+
+// The variant modes ask the lookup tables for the k-mers of the enumerated PATHS and nothing else (varMer::score, varMer.C:76-84): one slot
+// on one device can prepare the call set first (host work), claim exactly those k-mers on a sequence-only index while it does
+// (mfx_vcf_prepare_path_index) and let both databases update them -- the PATH-ONLY index, a thirteenth of the full tables (3 Gb, 3.7 M calls:
+// 10.3 GB instead of 137; device work of the build 0.27 instead of 0.65 s).  Its price is the order: the VCF and the clusters' paths come
+// BEFORE the index instead of under its build -- on a 16-core host 1.9-2.1 s against 1.55-1.65 s of wall (profiles/r06_cfg4_cli.txt).  So it
+// is what a run takes when the full tables do not fit (-memory, or 90 % of the device's free memory), and MFX_CLI_PATH_INDEX=1 / 0 says
+// so explicitly.  Not with -index (the image caches the full tables), k > 31, several slots, MFX_CLI_VCF_AHEAD=0.
+static int decide_path_only(Run &R) {
+  const Globals &G = R.G;
+  const int pe = env_flag("MFX_CLI_PATH_INDEX");
+  const bool can = R.variantMode && G.vcfName && G.seqName && variant_slots(G) == 1 && !G.sharded && R.k <= 31 && !G.indexName &&
+                   (R.fromReads || (R.vcfAheadKnob != 0 && !R.fullIndex));
+  if (R.fromReads && R.variantMode) {
+    // (the reads are counted into the k-mers the call set's paths ask for: there is no read database for the full tables)
+    if (!can) { fprintf(stderr, "ERROR: the variant modes count -reads into the path-only index of the call set, which this run cannot take.\n"); return 1; }
+    R.pathOnly = true;
+  } else if (can && pe >= 0) R.pathOnly = pe != 0;
+  else if (can) {
+    const uint64_t capacity = R.rdb.n_kmers + (G.seqDBname ? R.adb.n_kmers : bases_upper_bound(G.seqName)) + 1024;
+    const double fullGB = mfx_index_estimate_gb(R.k, capacity);
+    uint64_t freeB = 0, totalB = 0;
+    const bool known = mfx_device_memory(G.device, &freeB, &totalB) == MFX_OK;
+    R.pathOnly = (G.maxMemory > 0 && fullGB > G.maxMemory) || (known && fullGB * 1e9 > 0.9 * (double)freeB);
+    if (R.pathOnly)
+      fprintf(stderr, "-- The full lookup tables would take %.1f GB (%s %.1f GB): building the path-only index of the call set instead.\n", fullGB,
+              G.maxMemory > 0 && fullGB > G.maxMemory ? "-memory allows" : "free on the device:", G.maxMemory > 0 && fullGB > G.maxMemory ? G.maxMemory : freeB / 1e9);
+  }
+  // the path-only index is built FROM the call set: its VCF is read and parsed (host work only) while the FASTA file is
+  if (R.pathOnly)
+    R.vcfLoad.f = std::async(std::launch::async, [&R]() {
+      mfx_vcf *v = mfx_vcf_load(R.G.vcfName);
+      if (!v) R.vcfAheadError = mfx_last_error();                  // (errors are per thread: carried to the caller's)
+      return v;
+    });
+  return 0;
+}
+
+// -hist and -dump ask the lookup tables for the k-mers of -sequence and nothing else (merfin-histogram.C:54-64,
+// merfin-dump.C:44-61): they get a SEQUENCE-ONLY index -- the sequence's k-mers are claimed first, the databases only
+// update those (half of a 30x human read database, the error k-mers, never gets a slot; k <= 21: 8-byte slots).  The
+// other report types need the whole read database.  MFX_CLI_FULL_INDEX=1 builds the full tables for every type.
+// (-reads: always -- the reads are counted into claimed k-mers; there is no read database for the full tables)
+// (-spectrum: the full tables from -readmers -- its read-only row needs every read k-mer; with -reads the index -hist would build)
+// deferSeq: with -seqmers, and without it whenever the file tells an upper bound of its bases -- the table is sized by the bound, the
+// read database is loaded while the file is read, the assembly k-mers are counted once it is in.
+// Only compressed files are worth it: their decompression takes seconds per Gb on one core, while a plain file is parsed
+// at 2-5 GB/s and reading it under the build measurably slows the build's own readers (1 Gb: 1.8-3.0 s read first,
+// 2.4-3.2 s overlapped; MFX_CLI_OVERLAP=1 / 0 forces either).
+static void decide_seq_only_and_defer(Run &R, bool compressed) {
+  const Globals &G = R.G;
+  R.seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || (G.reportType == OP_SPECTRUM && R.fromReads)) && !G.sharded &&
+              R.k <= 31 && (R.fromReads || !R.fullIndex);
+  const int ov = env_flag("MFX_CLI_OVERLAP");
+  const bool wantOverlap = ov >= 0 ? ov != 0 : compressed;
+  R.basesBound = (G.seqName && !G.seqDBname && wantOverlap && !R.seqOnly) ? bases_upper_bound(G.seqName) : 0;
+  R.deferSeq = G.seqName && !G.sharded && !R.seqOnly && !R.pathOnly && wantOverlap && (G.seqDBname || R.basesBound > 0);   // (the path-only index needs the sequences first)
+}
+
+// the reader thread is joined, the records are in.  1: reading failed (the error is printed)
+static int finish_seq(Run &R) {
+  if (R.S.done) return 0;
+  if (!R.S.finish()) {
+    fprintf(stderr, "ERROR: reading '%s' failed (read error, or the decompressor exited with an error: truncated or corrupt file?).\n", R.G.seqName);
+    return 1;
+  }
+  R.clock.lap("read sequences");
+  return 0;
+}
+
+// the sequences to the device.  -hist on one device with the assembly k-mers coming from -seqmers (streamHist): nothing needs the sequence in
+// HBM before the evaluation, so its upload is streamed under the -hist kernel (mfx_hist_run_streamed).  Otherwise the index build
+// counts the assembly k-mers from the packed sequence and it goes up first.  false: mfx_last_error says why
+static bool make_seq(Run &R) {
+  const Globals &G = R.G;
+  if (!R.S.recs.empty() || G.seqName) {
+    R.seq = R.streamHist ? mfx_seq_create(G.device, R.S.lens.data(), R.S.size()) : mfx_seq_upload(G.device, R.S.bases.data(), R.S.lens.data(), R.S.size());
+    if (!R.seq) return false;
+  }
+  R.clock.lap("upload sequences");
+  if (R.stage) mfx_db_stage_boost(R.stage);                       // the host's threads are free: the database's readers may have them all
+  return true;
+}
+
+// -sharded: -hist / -dump take a part of the sequences per device, each on the sequence-only index of ITS k-mers (no exchange);
+// everything else -- and a non-canonical database -- takes the hash-sharded full tables (MFX_CLI_FULL_INDEX=1: always)
+static int run_on_shards(Run &R) {
+  const Globals &G = R.G;
+  if (G.devices.size() < 2) { fprintf(stderr, "ERROR: -sharded needs at least two -devices.\n"); return 1; }
+  if (G.indexName) { fprintf(stderr, "ERROR: -index caches a whole table; it cannot be combined with -sharded.\n"); return 1; }
+  if ((G.reportType == OP_HIST || G.reportType == OP_DUMP) && R.k <= 31 && !R.fullIndex) {
+    const int prc = run_parts(G, R.k, R.S.recs, R.S.bases, R.S.lens);
+    if (prc >= 0) return prc;
+  }
+  return run_sharded(G, R.k, R.rdb, R.adb, R.S.recs, R.S.bases, R.S.lens, R.S.names, R.S.totalBases);
+}
+
+// variant modes on one slot: the VCF is read and parsed (host work only) on a thread of its own while the index is built
+// (merfin opens it after load_Kmers, merfin-globals.C:201-219; 0.15 s of a 4 M-call set).  An error is reported where the
+// VCF is opened (report_variants).  Several slots split the file per slot instead.
+static void start_vcf_ahead(Run &R) {
+  const Globals &G = R.G;
+  if (!(R.variantMode && G.vcfName && variant_slots(G) == 1 && !G.sharded && R.vcfAheadKnob != 0 && !R.pathOnly)) return;
+  R.vcfAhead.f = std::async(std::launch::async, [&R]() {
+    const Globals &G = R.G;
+    mfx_vcf *v = mfx_vcf_load(G.vcfName);
+    if (!v) { R.vcfAheadError = mfx_last_error(); return v; }    // (errors are per thread: carried to the caller's)
+    // MFX_CLI_VCF_AHEAD=2: ... and its clusters merged, their allele combinations enumerated and packed here as well (mfx_vcf_prepare:
+    // stage A of the run needs the sequences, not the index).  Not the default: on a host whose cores the index build already
+    // keeps busy (the 16-core quota of the measured boxes: its readers copy 13 GB out of the page cache) the two slow each other
+    // down -- config 4 at 3 Gb 2.02-2.07 s with the load alone ahead, 2.67-2.75 s with stage A too (profiles/r05_cfg4_cli_ahead.txt).
+    // (never while the sequences are still being read -- deferSeq: finish_seq() fills recs / bases / lens on the main thread later)
+    if (R.vcfAheadKnob != 2 || R.deferSeq) return v;
+    const mfx_variant_opts o = variant_opts(G, G.debug ? "-" : nullptr);
+    if (mfx_vcf_prepare(v, R.k, R.S.names.data(), R.S.bases.data(), R.S.lens.data(), R.S.size(), &o)) {
+      R.vcfAheadError = mfx_last_error();
+      mfx_vcf_free(v);
+      v = nullptr;
+    }
+    return v;
+  });
+}
+
+// ---- the index: an image of it, or one of three builds ------------------------------------------------------------------------------------
+static void memory_banner(const Globals &G, double neededGB, const std::string &of_what = "") {
+  fprintf(stderr, "--\n-- Memory needed: %.3f GB%s\n-- Memory limit:  %.3f GB%s\n--\n", neededGB, of_what.c_str(), G.maxMemory, G.maxMemory > 0 ? "" : " (none)");
+}
+
+// A database into the table (side 1: -seqmers, 0: -readmers with -min / -max), from its stage when it has one.  Returns 0, or `tolerated`
+// for the caller to fall back on, or 1 with the error printed.  label: the step of the phase clock this was
+static int load_db_step(Run &R, const char *path, int side, mfx_db_stage *stage, const char *label, int tolerated = MFX_E_NONCANON) {
+  const uint64_t lo = side ? 0 : R.G.minV, hi = side ? ~0ull : R.G.maxV;
+  fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", path);
+  const int lrc = stage ? mfx_index_load_db_staged(R.ix, stage, side, lo, hi) : mfx_index_load_db(R.ix, path, side, lo, hi);
+  if (lrc && lrc != tolerated) DIE_MFX(side ? "loading -seqmers" : "loading -readmers");
+  if (label) R.clock.step(label);
+  return lrc;
+}
+
+static int save_index_image(Run &R) {
+  fprintf(stderr, "-- Writing the index image '%s'.\n", R.G.indexName);
+  if (mfx_index_set_fingerprint(R.ix, R.fingerprint) || mfx_index_save(R.ix, R.G.indexName)) DIE_MFX("writing the index image");
+  return 0;
+}
+
+// -index: the image is loaded if it exists and was built from these inputs; R.ix stays empty when the run has to build
+static int load_index_image(Run &R) {
+  const Globals &G = R.G;
+  FILE *probe = G.indexName ? fopen(G.indexName, "rb") : nullptr;
+  R.fingerprint = G.indexName ? input_fingerprint(G, R.seqOnly) : 0;
+  // a run that would build the sequence-only index also accepts a FULL image of the same inputs: that is what such a run
+  // saved when a database turned out not to be canonical (the fallback of main) -- without this every later run would
+  // build twice again and the cache would never take effect
+  R.fingerprintFull = (G.indexName && R.seqOnly) ? input_fingerprint(G, false) : R.fingerprint;
+  if (!probe) return 0;
+  fclose(probe);
+  fprintf(stderr, "-- Loading the index image '%s' (k-mer databases are not read).\n", G.indexName);
+  R.ix = mfx_index_load(G.indexName, G.maxMemory, G.device);
+  if (!R.ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+  mfx_index_info info;
+  if (mfx_index_get_info(R.ix, &info)) DIE_MFX("reading the index image");
+  if (info.k != R.k) { fprintf(stderr, "ERROR: the index image holds %d-mers but %s %d-mers.\n", info.k, R.fromReads ? "the run counts" : "-readmers holds", R.k); return 1; }
+  uint64_t fp = 0, imin = 0, imax = 0;
+  if (mfx_index_get_origin(R.ix, &fp, &imin, &imax)) DIE_MFX("reading the index image");
+  if (R.seqOnly && info.seq_only == 0 && fp == R.fingerprintFull && imin == G.minV && imax == G.maxV) {
+    R.seqOnly = false;                                              // the full tables of these inputs (a non-canonical database)
+    R.fingerprint = R.fingerprintFull;
+  } else if (fp != R.fingerprint || imin != G.minV || imax != G.maxV || (info.seq_only != 0) != R.seqOnly) {
+    // the image was built from other inputs (a re-polished -sequence, another database, other -min/-max):
+    // using it would give wrong asmK / readK with no diagnostic
+    fprintf(stderr, "-- The index image '%s' was built from other inputs (%s); rebuilding it.\n", G.indexName,
+            (imin != G.minV || imax != G.maxV) ? "-min/-max differ" : "a database or the sequence file changed");
+    R.ix.reset();
+  }
+  return 0;
+}
+
+// The three builds return 0 with R.ix built, 1 with the error printed, or -1: this index cannot be had, build the full tables.
+
+// The PATH-ONLY index of the variant modes, from the call set that vcfLoad read
+static int build_path_only_index(Run &R) {
+  const Globals &G = R.G;
+  R.vcfReady = R.vcfLoad.f.get();
+  if (!R.vcfReady) { fprintf(stderr, "ERROR: variant scoring: %s\n", R.vcfAheadError.c_str()); return 1; }
+  R.clock.step("(before the index: sequences, VCF)");
+  // the clusters merged, the table made from the bound of their path text, then batch by batch: the paths' tables packed on the host, their
+  // k-mers claimed on the device under the next batch's packing (mfx_vcf_prepare_path_index)
+  fprintf(stderr, "-- Claiming the %d-mers of the variants' paths on the GPU.\n", R.k);
+  const mfx_variant_opts o = variant_opts(G, G.debug ? "-" : nullptr);
+  mfx_index *claimed = nullptr;
+  if (mfx_vcf_prepare_path_index(R.vcfReady, R.k, R.S.names.data(), R.S.bases.data(), R.S.lens.data(), R.S.size(), &o, G.maxMemory, G.device, 0.7, &claimed))
+    DIE_MFX("preparing the call set");
+  R.ix = claimed;
+  if (!R.ix) fprintf(stderr, "-- %s\n-- Building the full lookup tables instead.\n", mfx_last_error());
+  if (R.ix) {
+    mfx_index_info info;
+    if (mfx_index_get_info(R.ix, &info)) DIE_MFX("reading the path-only index");
+    memory_banner(G, info.bytes / 1e9, " (the " + std::to_string(R.k) + "-mers of the variants' paths: " + std::to_string(info.distinct) + ")");
+  }
+  if (R.stage) mfx_db_stage_boost(R.stage);                         // the host's threads are free: the databases' readers may have them all
+  if (R.stageAsm) mfx_db_stage_boost(R.stageAsm);
+  R.clock.step("prepare the call set + claim the paths' k-mers");
+  int lrc = 0;
+  if (R.ix) {
+    if (G.seqDBname) {
+      lrc = load_db_step(R, G.seqDBname, 1, R.stageAsm, "load -seqmers");
+      if (lrc == 1) return 1;
+      R.stageAsm.reset();
+    } else {
+      // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186) for the k-mers that will be asked for
+      fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", R.k, G.seqName);
+      if (!R.seq && !make_seq(R)) DIE_MFX("uploading sequences");
+      if (mfx_index_count_claimed(R.ix, R.seq, nullptr)) DIE_MFX("counting sequence k-mers");
+      R.clock.step("count the sequence's k-mers");
+    }
+    if (!lrc && R.fromReads) {
+      if (!count_reads_files(G, R.ix)) return 1;
+      R.clock.step("count -reads");
+    } else if (!lrc) {
+      lrc = load_db_step(R, G.readDBname, 0, R.stage, "load -readmers");
+      if (lrc == 1) return 1;
+    }
+    if (lrc == MFX_E_NONCANON) {
+      fprintf(stderr, "-- A k-mer database is not canonical; building the full lookup tables instead.\n");
+      R.ix.reset();
+    }
+  }
+  // (the staged bytes are not needed by the run; a fall-back to the full tables reads the files)
+  R.stage.reset();
+  R.stageAsm.reset();
+  if (!R.ix && R.fromReads) { fprintf(stderr, "ERROR: -reads needs the path-only index of the call set, which could not be built.\n"); return 1; }
+  return R.ix ? 0 : -1;
+}
+
+// The SEQUENCE-ONLY index of -hist, -dump and -track
+static int build_seq_only_index(Run &R) {
+  const Globals &G = R.G;
+  const uint64_t capacity = R.S.totalBases + 1024;                // a sequence has at most one new k-mer per base
+  memory_banner(G, mfx_index_estimate_gb_for_seq(R.k, capacity));
+  R.clock.step("(before the index)");
+  // load factor of the table: 0.4 unless the user says otherwise (MFX_LOAD_FACTOR) -- the emptier tables the library would pick probe
+  // faster (3 Gb: 20 instead of 23 ms of -hist kernel) but a run that starts behind another waits seconds in hipMalloc for the driver
+  // to clear what that one freed, the longer the more of the HBM both ask for (profiles/r05_e2e_lf_ab.txt)
+  R.ix = mfx_index_create_for_seq_lf(R.k, capacity, G.maxMemory, G.device, 0.4);
+  if (!R.ix && R.stage) {                                           // (the staged database may be what the table lacks)
+    R.stage.reset();
+    R.ix = mfx_index_create_for_seq_lf(R.k, capacity, G.maxMemory, G.device, 0.4);
+  }
+  if (!R.ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+  R.clock.step("create the table");
+  int lrc = 0;
+  bool fused = false;
+  if (G.seqDBname) {
+    fprintf(stderr, "-- Claiming the %d-mers of '%s' on the GPU.\n", R.k, G.seqName);
+    if (mfx_index_claim_seq(R.ix, R.seq, nullptr)) DIE_MFX("claiming sequence k-mers");
+    R.clock.step("claim the sequence's k-mers");
+    lrc = load_db_step(R, G.seqDBname, 1, nullptr, "load -seqmers");
+    if (lrc == 1) return 1;
+  } else if (R.fromReads) {
+    fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", R.k, G.seqName);
+    if (mfx_index_count_asm(R.ix, R.seq, nullptr)) DIE_MFX("counting sequence k-mers");
+    R.clock.step("count the sequence's k-mers");
+  } else {
+    // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186)
+    // (this build says "No -seqmer given" before "Loading kmers", the full tables the other way round: each follows the order of its own calls)
+    fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", R.k, G.seqName);
+    // (one call for the counting and the load of -readmers: the database crosses PCIe while the k-mers are claimed)
+    fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
+    lrc = R.stage ? mfx_index_build_for_hist_staged(R.ix, R.seq, R.stage, G.minV, G.maxV) : mfx_index_build_for_hist(R.ix, R.seq, G.readDBname, G.minV, G.maxV);
+    R.stage.reset();                                                // its device memory is not needed by the evaluation
+    if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("counting sequence k-mers / loading -readmers");
+    R.clock.step("count the sequence's k-mers + load -readmers");
+    fused = true;
+  }
+  if (lrc == MFX_E_NONCANON && R.fromReads) { fprintf(stderr, "ERROR: -reads needs a canonical -seqmers database.\n"); return 1; }
+  if (!lrc && R.fromReads) {
+    if (!count_reads_files(G, R.ix)) return 1;
+    R.clock.step("count -reads");
+  } else if (!lrc && !fused) {
+    lrc = load_db_step(R, G.readDBname, 0, nullptr, "load -readmers");
+    if (lrc == 1) return 1;
+  }
+  if (lrc == MFX_E_NONCANON) {
+    // one slot per canonical k-mer cannot answer value(fmer) + value(rmer) of a non-canonical database
+    fprintf(stderr, "-- A k-mer database is not canonical; building the full lookup tables instead.\n");
+    R.ix.reset();
+    return -1;
+  }
+  return G.indexName ? save_index_image(R) : 0;
+}
+
+// The full lookup tables.  The table is sized before the sequence is in when the file promised a bound on its bases; a file that breaks the
+// promise (several gzip members, ...) costs a second build with the true number
+static int build_full_index(Run &R) {
+  const Globals &G = R.G;
+  for (int attempt = 0; !R.ix; ++attempt) {
+    const uint64_t capacity = R.rdb.n_kmers + (G.seqDBname ? R.adb.n_kmers : (R.S.done ? R.S.totalBases : R.basesBound)) + 1024;
+    memory_banner(G, mfx_index_estimate_gb(R.k, capacity));
+    // (the smallest table the library makes, load factor 0.7: the device stage of these report types is a hundredth of the run, and a
+    // table allocated behind another process waits for the driver to clear what that one freed -- the longer, the larger both are)
+    R.ix = mfx_index_create_lf(R.k, capacity, G.maxMemory, G.device, 0.7);
+    if (!R.ix && !G.seqDBname && !R.S.done && R.basesBound > 0) {
+      // the capacity came from the file's BOUND on its bases (a .gz of a human assembly sits near the 4 GiB step of that
+      // bound): read the file to the end, as the reference does before anything else, and size the table by the truth
+      fprintf(stderr, "-- The table sized by the bound on the bases of '%s' does not fit; reading the file first.\n", G.seqName);
+      if (finish_seq(R)) return 1;
+      continue;
+    }
+    if (!R.ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+    if (!R.fromReads && load_db_step(R, G.readDBname, 0, nullptr, nullptr, 0)) return 1;
+    if (G.seqDBname) {
+      if (load_db_step(R, G.seqDBname, 1, nullptr, nullptr, 0)) return 1;
+      break;
+    }
+    // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186)
+    if (R.deferSeq && !R.S.done) {            // the read database is in; now the sequence is needed
+      if (finish_seq(R)) return 1;
+      if (R.S.totalBases > R.basesBound && attempt == 0) {
+        fprintf(stderr, "-- NOTE: '%s' holds %lu bases, more than its size promised (%lu); rebuilding the table.\n", G.seqName,
+                (unsigned long)R.S.totalBases, (unsigned long)R.basesBound);
+        R.ix.reset();
+        continue;
+      }
+    }
+    if (!R.seq && !make_seq(R)) DIE_MFX("uploading sequences");
+    fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", R.k, G.seqName);
+    if (mfx_index_count_asm(R.ix, R.seq, nullptr)) DIE_MFX("counting sequence k-mers");
+  }
+  // -reads (k > 31: this table holds the assembly's k-mers only; the reads update them)
+  if (R.fromReads && !count_reads_files(G, R.ix)) return 1;
+  return G.indexName ? save_index_image(R) : 0;
+}
+
+// ---- the reports ---------------------------------------------------------------------------------------------------------------------------
+// -spectrum / -peak auto: one streaming pass over the table (mfx_spectrum_run), the haploid peak off its single-copy row
+static int run_spectrum_or_peak(Run &R) {
+  Globals &G = R.G;
+  const bool report = G.reportType == OP_SPECTRUM;
+  const uint32_t copies = report ? G.copies : 4u, maxMult = report ? G.maxMult : 10000u;
+  std::vector<uint64_t> img((size_t)(copies + 2) * (maxMult + 1));
+  uint64_t entries = 0;
+  if (mfx_spectrum_run(R.ix, copies, maxMult, img.data(), &entries)) DIE_MFX(report ? "-spectrum" : "-peak auto");
+  if (report) {
+    // a table that holds the k-mers of -sequence only (-reads) has no read-only k-mers: the row is left out, not written as zeros
+    const bool withReadOnly = !R.fromReads;
+    const std::string name = std::string(G.outName) + ".spectra-cn.hist";
+    fprintf(stderr, "-- Copy-number spectrum of the %d-mers to '%s'.\n", R.k, name.c_str());
+    if (mfx_spectrum_write(img.data(), copies, maxMult, withReadOnly ? 1 : 0, name.c_str())) DIE_MFX("writing the spectrum");
+    uint64_t asmOnly = 0, readOnly = 0;
+    for (uint32_t r = 1; r < copies + 2; ++r) asmOnly += img[(size_t)r * (maxMult + 1)];
+    for (uint32_t m = 0; m <= maxMult; ++m) readOnly += img[m];
+    fprintf(stderr, "Entries counted: %lu\nAssembly-only k-mers: %lu\n", (unsigned long)entries, (unsigned long)asmOnly);
+    if (withReadOnly) fprintf(stderr, "Read-only k-mers: %lu\n", (unsigned long)readOnly);
+    else fprintf(stderr, "The table holds the k-mers of -sequence only (-reads): the read-only row is left out.\n");
+  }
+  mfx_spectrum_peak_t pk;
+  if (mfx_spectrum_peak(img.data() + (size_t)(maxMult + 1), maxMult, &pk) == MFX_OK) {
+    fprintf(stderr, "Haploid peak (auto): %u  (main peak %u, valley %u, single-copy k-mers at the peak %lu)\n", pk.haploid_peak, pk.main_peak, pk.valley,
+            (unsigned long)pk.count_at_peak);
+    if (G.peakAuto) G.peak = (double)pk.haploid_peak;
+  } else if (report) {
+    fprintf(stderr, "No haploid peak found in the single-copy row (%s); the other report types need -peak <number>.\n", mfx_last_error());
+  } else {
+    fprintf(stderr, "ERROR: -peak auto found no haploid peak in the single-copy row of the spectrum (%s). Give -peak <number>.\n", mfx_last_error());
+    return 1;
+  }
+  R.clock.lap("spectrum");
+  return 0;
+}
+
+static int report_hist(Run &R) {
+  const Globals &G = R.G;
+  fprintf(stderr, "-- Generate histogram of the k* metric to '%s'.\n", G.outName);
+  mfx_hist_result r;
+  if (G.devices.size() > 1) {
+    // one process, N devices (the reference drives all its workers from one binary, merfin.C:366-414): replicas of
+    // the table and of the packed assembly by peer copy, every device evaluates its block-cyclic share
+    const size_t N = G.devices.size();
+    Slots S;
+    int bad = S.make(G, R.ix, R.seq, R.ev, &R.kp) ? 0 : 1;
+    R.clock.lap("replicate index");
+    fprintf(stderr, "-- Evaluating on %zu devices.\n", N);
+    if (!bad && mfx_hist_run_multi(S.evs.data(), S.sqs.data(), (uint32_t)N, &r)) bad = 1;
+    std::string why = bad ? mfx_last_error() : "";
+    S.release();
+    if (bad) { fprintf(stderr, "ERROR: -hist on %zu devices: %s\n", N, why.c_str()); return 1; }
+  } else if (R.streamHist) {
+    if (mfx_hist_run_streamed(R.ev, R.seq, R.S.bases.data(), &r)) DIE_MFX("-hist");
+  } else if (mfx_hist_run(R.ev, R.seq, &r)) DIE_MFX("-hist");
+  if (!print_hist(R.S.recs, r, R.k, G.outName)) DIE_MFX("writing histogram");
+  mfx_hist_result_free(&r);
+  return 0;
+}
+
+static int report_dump(Run &R) {
+  const Globals &G = R.G;
+  const std::vector<SeqRecord> &recs = R.S.recs;
+  fprintf(stderr, "-- Dump per-base k* metric to '%s'.\n", G.outName);
+  ContigCounts counts;
+  if (G.skipMissing) {
+    // merfin-dump.C:34,81-87: -skipMissing suppresses the dump file entirely; only the counts remain
+    mfx_hist_result r;
+    if (mfx_hist_run(R.ev, R.seq, &r)) DIE_MFX("-dump -skipMissing");
+    counts.lines(recs, r);
+    mfx_hist_result_free(&r);
+  } else if (G.devices.size() > 1) {
+    // per-contig ordered output on N devices: a contiguous run of contigs per slot (balanced by bases), one host
+    // thread per slot writes its part, the parts are concatenated in slot order
+    const size_t N = G.devices.size();
+    Slots S;
+    if (!S.make(G, R.ix, R.seq, R.ev, &R.kp)) { fprintf(stderr, "ERROR: -dump on %zu devices: %s\n", N, mfx_last_error()); return 1; }
+    R.clock.lap("replicate index");
+    fprintf(stderr, "-- Evaluating on %zu devices.\n", N);
+    const auto runs = contig_partition(std::vector<double>(R.S.lens.begin(), R.S.lens.end()), N);
+    std::vector<std::string> parts(N), errs(N);
+    std::vector<uint64_t> ka(recs.size(), 0), km(recs.size(), 0);
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < N; ++d) {
+      char suf[32];
+      snprintf(suf, sizeof(suf), ".part%04zu", d);
+      parts[d] = std::string(G.outName) + suf;
+      th.emplace_back([&, d]() {
+        mfx_host_threads_share((unsigned)N);
+        for (size_t c = runs[d].first; c < runs[d].second; ++c)
+          if (mfx_dump_contig(S.evs[d], S.sqs[d], (uint32_t)c, R.S.names[c], parts[d].c_str(), c > runs[d].first, &ka[c], &km[c])) { errs[d] = mfx_last_error(); return; }
+      });
+    }
+    for (auto &x : th) x.join();
+    S.release();
+    for (size_t d = 0; d < N; ++d) if (!errs[d].empty()) { fprintf(stderr, "ERROR: -dump (slot %zu): %s\n", d, errs[d].c_str()); return 1; }
+    if (!concat_parts(G.outName, parts, false)) { fprintf(stderr, "ERROR: cannot write '%s'.\n", G.outName); return 1; }
+    for (size_t c = 0; c < recs.size(); ++c) counts.line(R.S.names[c], ka[c], km[c]);     // (the runs are the contigs in order)
+  } else {
+    for (size_t c = 0; c < recs.size(); ++c) {
+      uint64_t ka = 0, km = 0;
+      if (mfx_dump_contig(R.ev, R.seq, (uint32_t)c, R.S.names[c], G.outName, c > 0, &ka, &km)) DIE_MFX("-dump");
+      counts.line(R.S.names[c], ka, km);
+    }
+    if (recs.empty()) { FILE *f = fopen(G.outName, "w"); if (f) fclose(f); }
+  }
+  return 0;
+}
+
+// K* per window of every contig, reduced on the device (mfx_track_run): what the README's "Assess collapses and duplications"
+// makes from the -dump text with awk and wigToBigWig.  The counts on stderr are those of -dump -skipMissing.
+static int report_track(Run &R) {
+  const Globals &G = R.G;
+  const size_t NC = R.S.recs.size();
+  // (a compressed -output name -- out.gz / .bz2 / .xz -- keeps its suffix at the end of the three names: out.track.tsv.gz)
+  std::string stem = G.outName, zsuf;
+  if (mfx_suffix_tool(stem)) { const size_t dot = stem.rfind('.'); zsuf = stem.substr(dot); stem.resize(dot); }
+  const std::string tsvName = stem + ".track.tsv" + zsuf, bgName = stem + ".kstar.bedgraph" + zsuf, missName = stem + ".missing.bedgraph" + zsuf;
+  fprintf(stderr, "-- Summarise the k* metric per window of %lu positions to '%s', '%s' and '%s'.\n", (unsigned long)G.window, tsvName.c_str(),
+          bgName.c_str(), missName.c_str());
+  const uint64_t nw = mfx_track_num_windows(R.seq, G.window);
+  std::vector<mfx_track_window> win((size_t)nw);
+  uint64_t got = 0, kasm = 0, kmissing = 0;
+  if (mfx_track_run(R.ev, R.seq, G.window, win.data(), nw, &got, &kasm, &kmissing)) DIE_MFX("-track");
+  if (mfx_track_write(win.data(), got, R.seq, R.S.names.data(), G.window, tsvName.c_str(), bgName.c_str())) DIE_MFX("writing the windows");
+  mfx_file mf = mfx_open_writer(missName.c_str(), false);
+  if (!mf.f) { fprintf(stderr, "ERROR: cannot open '%s' for writing.\n", missName.c_str()); return 1; }
+  fprintf(mf.f, "track type=bedGraph name=\"missing\"\n");
+  std::vector<uint64_t> cmiss(NC, 0), casm(NC, 0);
+  size_t i = 0;
+  for (size_t c = 0; c < NC; ++c)
+    for (uint64_t start = 0; start < R.S.lens[c]; start += G.window, ++i) {
+      const mfx_track_window &w = win[i];
+      cmiss[c] += w.n_missing;
+      casm[c] += w.n_kmers;
+      if (w.n_kmers)
+        fprintf(mf.f, "%s\t%lu\t%lu\t%.6f\n", R.S.names[c], (unsigned long)start, (unsigned long)std::min<uint64_t>(start + G.window, R.S.lens[c]),
+                (double)w.n_missing / (double)w.n_kmers);
+    }
+  if (mfx_close(mf)) { fprintf(stderr, "ERROR: writing '%s' failed.\n", missName.c_str()); return 1; }
+  ContigCounts counts;
+  for (size_t c = 0; c < NC; ++c) counts.line(R.S.names[c], casm[c], cmiss[c]);
+  if (counts.cumAsm != kasm || counts.cumMissing != kmissing) {
+    fprintf(stderr, "ERROR: -track: the windows hold %lu k-mers (%lu missing), the device counted %lu (%lu).\n", (unsigned long)counts.cumAsm,
+            (unsigned long)counts.cumMissing, (unsigned long)kasm, (unsigned long)kmissing);
+    return 1;
+  }
+  return 0;
+}
+
+// The call set of the variant modes in several slots: one pass over the VCF gives the records per contig (for the balance), and the lines
+// themselves, so that every slot is handed a VCF of ITS contigs only (each slot parsing all 4 M records of a human call set made N slots
+// N times the host work of one; the host is what bounds these modes)
+struct VcfBySlot {
+  std::string vtext;
+  std::vector<std::pair<size_t, size_t>> vhead;                          // header lines (offset, length incl. newline)
+  std::vector<std::vector<std::pair<size_t, size_t>>> vlines;           // data lines per contig, in file order
+  std::vector<double> w;                                                // the weight of every contig: its records
+
+  int read(const char *vcfName, const Sequences &S) {
+    const std::vector<SeqRecord> &recs = S.recs;
+    w.assign(recs.size(), 0.0);
+    vlines.resize(recs.size());
+    mfx_file vf = mfx_open_reader(vcfName);
+    if (!vf.f) { fprintf(stderr, "ERROR: cannot open VCF '%s'.\n", vcfName); return 1; }
+    {
+      std::vector<char> blk(1 << 22);
+      size_t n;
+      while ((n = fread(blk.data(), 1, blk.size(), vf.f)) > 0) vtext.append(blk.data(), n);
+    }
+    if (mfx_close(vf)) { fprintf(stderr, "ERROR: reading VCF '%s' failed.\n", vcfName); return 1; }
+    std::vector<std::pair<std::string, size_t>> idx;
+    for (size_t c = 0; c < recs.size(); ++c) idx.emplace_back(recs[c].name, c);
+    std::sort(idx.begin(), idx.end());
+    size_t last_c = recs.size();
+    std::string last_chr;
+    for (size_t o = 0; o < vtext.size();) {
+      const char *nl = (const char *)memchr(vtext.data() + o, '\n', vtext.size() - o);
+      const size_t e = nl ? (size_t)(nl - vtext.data()) + 1 : vtext.size(), n = e - o;
+      if (vtext[o] == '#') vhead.emplace_back(o, n);
+      else if (n > 1) {
+        const char *tab = (const char *)memchr(vtext.data() + o, '\t', n);
+        if (tab) {
+          const size_t cl = (size_t)(tab - (vtext.data() + o));
+          if (last_c == recs.size() || last_chr.size() != cl || memcmp(last_chr.data(), vtext.data() + o, cl) != 0) {
+            last_chr.assign(vtext.data() + o, cl);
+            auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(last_chr, (size_t)0));
+            last_c = (it != idx.end() && it->first == last_chr) ? it->second : recs.size() + 1;   // + 1: not a contig of -sequence
+          }
+          if (last_c < recs.size()) { w[last_c] += 1.0; vlines[last_c].emplace_back(o, n); }
+        }
+      }
+      o = e;
+    }
+    for (size_t c = 0; c < recs.size(); ++c) w[c] += 1e-9 * (double)S.lens[c];
+    return 0;
+  }
+  // a slot's VCF: all header lines + the lines of its contigs [run.first, run.second)
+  bool write(const std::string &path, std::pair<size_t, size_t> run) const {
+    FILE *vf = fopen(path.c_str(), "w");
+    bool ok = vf != nullptr;
+    for (const auto &h : vhead) ok = ok && fwrite(vtext.data() + h.first, 1, h.second, vf) == h.second;
+    for (size_t c = run.first; c < run.second && ok; ++c)
+      for (const auto &l : vlines[c]) {
+        ok = ok && fwrite(vtext.data() + l.first, 1, l.second, vf) == l.second;
+        if (ok && vtext[l.first + l.second - 1] != '\n') ok = fputc('\n', vf) != EOF;     // a last line without newline
+      }
+    if (vf && fclose(vf) != 0) ok = false;
+    return ok;
+  }
+};
+
+// open_Inputs + processVariants + outputVariants (merfin-globals.C:201-219, merfin-variants.C:131-345)
+static int report_variants(Run &R) {
+  Globals &G = R.G;
+  const Sequences &Q = R.S;
+  fprintf(stderr, "-- Opening vcf file '%s'.\n", G.vcfName);
+  fprintf(stderr, "-- Generate variant mers and score them.\n");
+  const std::string outName = std::string(G.outName) + (G.reportType == OP_POLISH ? ".polish.vcf" : ".filter.vcf");   // :324-327
+  const std::string dbgName = std::string(G.outName) + ".00.debug.gz";
+  const mfx_variant_opts vo = variant_opts(G, G.debug ? dbgName.c_str() : nullptr);
+  uint64_t ncl = 0;
+  // One device is run as ONE slot.  (Rounds 2-3 ran it as 4 slots sharing its table: the host phases of these modes then
+  // alternated between parallel and serial stretches and several slots filled one another's gaps -- 1 Gb: 2.0 s in 8 slots
+  // against 2.7 s in one.  With the host side of round 4 -- arenas per run of clusters, parallel VCF load, device scoring --
+  // one slot on all host threads is at least as fast and needs neither the per-slot VCF files nor the evaluator replicas:
+  // config 4 at 3 Gb, evaluate + write 1.11-1.14 s in one slot, 1.16-1.19 s in four + 0.13-0.15 s to set the slots up,
+  // profiles/r04_cfg4_fullsize.txt.)  MFX_VARIANT_SLOTS overrides; several -devices are one slot each.
+  {
+    const size_t want = variant_slots(G);
+    const std::vector<int> real = G.devices;
+    while (G.devices.size() < want) G.devices.push_back(real[G.devices.size() % real.size()]);
+  }
+  if (G.devices.size() > 1) {
+    // BASELINE config 4 names 8 GPUs: contigs cut into one contiguous run per slot, balanced by their VCF records;
+    // every slot scores its clusters on its own device and writes its part; one VCF header in the concatenation
+    const size_t N = G.devices.size();
+    VcfBySlot V;
+    if (V.read(G.vcfName, Q)) return 1;
+    Slots S;
+    if (!S.make(G, R.ix, nullptr, R.ev, &R.kp)) { fprintf(stderr, "ERROR: variant scoring on %zu devices: %s\n", N, mfx_last_error()); return 1; }
+    R.clock.lap("replicate index");
+    fprintf(stderr, "-- Evaluating in %zu slots.\n", N);
+    const auto runs = contig_partition(V.w, N);
+    std::vector<std::string> parts(N), errs(N), dbgs(N), vins(N), logs(N);
+    std::vector<uint64_t> ncls(N, 0);
+    auto drop_parts = [&]() { for (size_t e = 0; e < N; ++e) { if (!parts[e].empty()) remove(parts[e].c_str()); if (!vins[e].empty()) remove(vins[e].c_str()); if (!logs[e].empty()) remove(logs[e].c_str()); } };
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < N; ++d) {
+      char suf[48];
+      snprintf(suf, sizeof(suf), ".part%04zu.in.vcf", d);
+      vins[d] = outName + suf;
+      if (!V.write(vins[d], runs[d])) { fprintf(stderr, "ERROR: cannot write '%s'.\n", vins[d].c_str()); drop_parts(); return 1; }
+    }
+    std::string().swap(V.vtext);
+    for (size_t d = 0; d < N; ++d) {
+      char suf[48];
+      snprintf(suf, sizeof(suf), ".part%04zu", d);
+      parts[d] = outName + suf;
+      snprintf(suf, sizeof(suf), ".%02zu.debug.gz", d);
+      dbgs[d] = std::string(G.outName) + suf;
+      // every slot logs to its own file; they are replayed on stderr in slot order once all slots are done (N slots
+      // writing PANIC / progress lines to one stderr interleave them mid-line)
+      logs[d] = parts[d] + ".log";
+      th.emplace_back([&, d]() {
+        mfx_host_threads_share((unsigned)N);                 // N slots side by side: each takes its share of the host threads
+        mfx_variant_opts o = vo;
+        o.debug_path = G.debug ? dbgs[d].c_str() : nullptr;
+        const size_t lo = runs[d].first, hi = runs[d].second;
+        if (mfx_variants_run(S.evs[d], vins[d].c_str(), Q.names.data() + lo, Q.bases.data() + lo, Q.lens.data() + lo, (uint32_t)(hi - lo), &o, parts[d].c_str(),
+                             logs[d].c_str(), &ncls[d]))
+          errs[d] = mfx_last_error();
+      });
+    }
+    for (auto &x : th) x.join();
+    for (size_t d = 0; d < N; ++d) {
+      remove(vins[d].c_str());
+      vins[d].clear();
+      if (FILE *lf = fopen(logs[d].c_str(), "r")) {
+        if (N > 1) fprintf(stderr, "-- slot %zu (contigs %zu..%zu):\n", d, runs[d].first, runs[d].second);
+        char lb[1 << 14];
+        size_t n;
+        while ((n = fread(lb, 1, sizeof(lb), lf)) > 0) fwrite(lb, 1, n, stderr);
+        fclose(lf);
+      }
+      remove(logs[d].c_str());
+      logs[d].clear();
+    }
+    S.release();
+    for (size_t d = 0; d < N; ++d) if (!errs[d].empty()) { fprintf(stderr, "ERROR: variant scoring (slot %zu): %s\n", d, errs[d].c_str()); drop_parts(); return 1; }
+    if (!concat_parts(outName, parts, true)) { fprintf(stderr, "ERROR: cannot write '%s'.\n", outName.c_str()); drop_parts(); return 1; }
+    for (uint64_t x : ncls) ncl += x;
+  } else if (R.vcfReady || R.vcfAhead.f.valid()) {
+    Owned<mfx_vcf, mfx_vcf_free> vcf;
+    vcf = R.vcfReady ? R.vcfReady.release() : R.vcfAhead.f.get();
+    if (!vcf) { fprintf(stderr, "ERROR: variant scoring: %s\n", R.vcfAheadError.c_str()); return 1; }
+    const int vrc = mfx_variants_run_vcf(R.ev, vcf, Q.names.data(), Q.bases.data(), Q.lens.data(), Q.size(), &vo, outName.c_str(), nullptr, &ncl);
+    // (leaving the 4 M records to the process's exit instead of freeing them here was measured: 0.1 s less in this phase, the same wall --
+    // profiles/r05_exit_ab.txt)
+    vcf.reset();
+    if (vrc) DIE_MFX("variant scoring");
+  } else if (mfx_variants_run(R.ev, G.vcfName, Q.names.data(), Q.bases.data(), Q.lens.data(), Q.size(), &vo, outName.c_str(), nullptr, &ncl))
+    DIE_MFX("variant scoring");
+  return 0;
+}
+
+static int report_completeness(Run &R) {
+  fprintf(stderr, "-- Compute completeness.\n");
+  double t64[64], u64[64];
+  if (mfx_completeness_pieces(R.ev, t64, u64)) DIE_MFX("-completeness");
+  print_completeness(t64, u64);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  const double stamp_main = epoch();
+  Globals G;
+  Errors err;
+  // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
+  parse_args(argc, argv, G, err);
+  check_count_flags(G, err);
+  if (G.count) return err.empty() ? run_count(G) : fail_usage(argv[0], err);
+  if (!check_reads_flags(G, err)) return 1;
+  check_track_flags(G, err);
+  check_spectrum_flags(G, err);
+  check_peak_auto_flags(G, err);
+  if (G.convertName && err.empty()) return run_convert(G);
+  check_report_flags(G, err);
+  if (!err.empty()) return fail_usage(argv[0], err);
+  if (!G.devices.empty()) G.device = G.devices[0];
+  else G.devices.push_back(G.device);
+  // 2. load_Kmetric first (merfin-globals.C:21-62 runs before the databases are opened; host only -- a compressed table's decompressor has
+  // come and gone before the HIP runtime starts)
+  if (!load_Kmetric(G)) return 1;
+  // 3. (the device check stays on this thread, before anything else is started: see devices_available)
+  if (!devices_available(G.devices)) return 1;
+  Run R(G);
+  R.clock.start(stamp_main);
+  // 4. the databases are probed: the read DB defines k
+  if (probe_databases(R)) return 1;
+  // 5. the stage of the read database begins
   // (MFX_CLI_STAGE_FIRST=0: the stage begins after the device is warmed up.  Measured, profiles/r05_stager_diag.txt: the warm-up then takes
   // 0.06 instead of 0.25 s, but the 0.15-0.2 s that the process's first allocations / queue / kernel cost move into the stager's start, the
   // claim kernel is launched at the same 0.35 s, and with stager, FASTA reader and encoder all at full speed in the first 0.3 s the process
   // runs into the CPU quota of a 16-core box in some runs: 1.09-1.13 s or 1.27-1.29 s against 1.12-1.16 s this way)
-  const bool stageFirst = !(getenv("MFX_CLI_STAGE_FIRST") && atoi(getenv("MFX_CLI_STAGE_FIRST")) == 0);
-  auto begin_stage = [&]() {
-    const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && k <= 31 && G.seqName && !G.seqDBname && !G.indexName &&
-                          G.devices.size() == 1 && !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")));
-    if (histLike && rdb.format == MFX_DB_FLAT) stage = mfx_db_stage_begin(G.readDBname, G.device);
-  };
-  // the path-only index of the variant modes: both databases move while the call set is prepared and its paths are claimed -- from the moment
-  // the sequences are in (under the FASTA reader the stagers' threads cost it 0.2 s of a 3 Gb file on a 16-core quota)
-  auto begin_path_stages = [&]() {
-    if (pathOnly && rdb.format == MFX_DB_FLAT) stage = mfx_db_stage_begin(G.readDBname, G.device);
-    if (pathOnly && G.seqDBname && adb.format == MFX_DB_FLAT) stageAsm = mfx_db_stage_begin(G.seqDBname, G.device);
-  };
-  if (stageFirst) begin_stage();
-  lap("probe k-mer databases");
-  // sequences (load_Sequence, merfin-globals.C:165-197; loadSequence, merfin.C:30-53).  The file is read (and, for
-  // .gz/.bz2/.xz, decompressed) by its own thread from here on; with -seqmers nothing needs the sequence before the
-  // evaluation, so the read then runs under the index build and is only waited for afterwards.
-  std::vector<SeqRecord> recs;
-  std::vector<const char *> bases;
-  std::vector<uint64_t> lens;
-  uint64_t totalBases = 0;
-  std::thread seqReader;
-  bool seqReadFailed = false;            // written by the reader thread, read after the join
-  struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } seqJoiner{seqReader};
+  const bool stageFirst = env_flag("MFX_CLI_STAGE_FIRST") != 0;
+  if (stageFirst) begin_stage(R);
+  R.clock.lap("probe k-mer databases");
+  // 6. the FASTA reader starts: its own thread from here on
   if (G.seqName) {
     fprintf(stderr, "-- Opening sequences in '%s'.\n", G.seqName);
-    auto sf = std::make_shared<SeqFile>(G.seqName);
-    if (!sf->ok()) { fprintf(stderr, "ERROR: cannot open '%s'.\n", G.seqName); return 1; }
-    const std::string seqPath = G.seqName;
-    seqReader = std::thread([&recs, &seqReadFailed, sf, seqPath]() {
-      if (read_fasta_parallel(seqPath, recs)) { seqReadFailed = sf->finish() != 0; return; }     // plain FASTA: all host threads
-      SeqRecord r;
-      while (sf->next(r)) recs.push_back(std::move(r));
-      seqReadFailed = sf->finish() != 0;      // a decompressor that died mid-stream: the records read so far are NOT the file
-    });
+    if (!R.S.start(G.seqName)) { fprintf(stderr, "ERROR: cannot open '%s'.\n", G.seqName); return 1; }
   }
-  // The variant modes ask the lookup tables for the k-mers of the enumerated PATHS and nothing else (varMer::score, varMer.C:76-84): one slot
-  // on one device can prepare the call set first (host work), claim exactly those k-mers on a sequence-only index while it does
-  // (mfx_vcf_prepare_path_index) and let both databases update them -- the PATH-ONLY index, a thirteenth of the full tables (3 Gb, 3.7 M calls:
-  // 10.3 GB instead of 137; device work of the build 0.27 instead of 0.65 s).  Its price is the order: the VCF and the clusters' paths come
-  // BEFORE the index instead of under its build -- on a 16-core host 1.9-2.1 s against 1.55-1.65 s of wall (profiles/r06_cfg4_cli.txt).  So it
-  // is what a run takes when the full tables do not fit (-memory, or 90 % of the device's free memory), and MFX_CLI_PATH_INDEX=1 / 0 says
-  // so explicitly.  Not with -index (the image caches the full tables), k > 31, several slots, MFX_CLI_VCF_AHEAD=0.
-  {
-    const char *vs = getenv("MFX_VARIANT_SLOTS");
-    const size_t slots = (vs && atoi(vs) > 0) ? (size_t)atoi(vs) : G.devices.size();
-    const char *pe = getenv("MFX_CLI_PATH_INDEX"), *pa = getenv("MFX_CLI_VCF_AHEAD");
-    const bool can = variantMode && G.vcfName && G.seqName && slots == 1 && !G.sharded && k <= 31 && !G.indexName &&
-                     (fromReads || (!(pa && atoi(pa) == 0) && !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX")))));
-    if (fromReads && variantMode) {
-      // (the reads are counted into the k-mers the call set's paths ask for: there is no read database for the full tables)
-      if (!can) { fprintf(stderr, "ERROR: the variant modes count -reads into the path-only index of the call set, which this run cannot take.\n"); return 1; }
-      pathOnly = true;
-    } else if (can && pe) pathOnly = atoi(pe) != 0;
-    else if (can) {
-      const uint64_t capacity = rdb.n_kmers + (G.seqDBname ? adb.n_kmers : bases_upper_bound(G.seqName)) + 1024;
-      const double fullGB = mfx_index_estimate_gb(k, capacity);
-      uint64_t freeB = 0, totalB = 0;
-      const bool known = mfx_device_memory(G.device, &freeB, &totalB) == MFX_OK;
-      pathOnly = (G.maxMemory > 0 && fullGB > G.maxMemory) || (known && fullGB * 1e9 > 0.9 * (double)freeB);
-      if (pathOnly)
-        fprintf(stderr, "-- The full lookup tables would take %.1f GB (%s %.1f GB): building the path-only index of the call set instead.\n", fullGB,
-                G.maxMemory > 0 && fullGB > G.maxMemory ? "-memory allows" : "free on the device:", G.maxMemory > 0 && fullGB > G.maxMemory ? G.maxMemory : freeB / 1e9);
-    }
-  }
-  // the path-only index is built FROM the call set: its VCF is read and parsed (host work only) while the FASTA file is
-  std::future<mfx_vcf *> vcfLoad;
-  std::string vcfAheadError;
-  struct VcfLoadGuard { std::future<mfx_vcf *> &f; ~VcfLoadGuard() { if (f.valid()) mfx_vcf_free(f.get()); } } vcfLoadGuard{vcfLoad};
-  if (pathOnly)
-    vcfLoad = std::async(std::launch::async, [&G, &vcfAheadError]() {
-      mfx_vcf *v = mfx_vcf_load(G.vcfName);
-      if (!v) vcfAheadError = mfx_last_error();                    // (errors are per thread: carried to the caller's)
-      return v;
-    });
-  bool seqDone = false;
-  auto finish_seq = [&]() {
-    if (seqDone) return;
-    seqDone = true;
-    if (seqReader.joinable()) seqReader.join();
-    if (seqReadFailed) {
-      fprintf(stderr, "ERROR: reading '%s' failed (read error, or the decompressor exited with an error: truncated or corrupt file?).\n", G.seqName);
-      exit(1);
-    }
-    bases.resize(recs.size());
-    lens.resize(recs.size());
-    for (size_t i = 0; i < recs.size(); ++i) { bases[i] = recs[i].data(); lens[i] = recs[i].size(); totalBases += lens[i]; }
-    lap("read sequences");
-  };
-  // ... and without -seqmers whenever the file tells an upper bound of its bases: the table is sized by the bound, the
-  // read database is loaded while the file is read, the assembly k-mers are counted once it is in
-  // Only compressed files are worth it: their decompression takes seconds per Gb on one core, while a plain file is parsed
-  // at 2-5 GB/s and reading it under the build measurably slows the build's own readers (1 Gb: 1.8-3.0 s read first,
-  // 2.4-3.2 s overlapped; MFX_CLI_OVERLAP=1 / 0 forces either).
-  // -hist and -dump ask the lookup tables for the k-mers of -sequence and nothing else (merfin-histogram.C:54-64,
-  // merfin-dump.C:44-61): they get a SEQUENCE-ONLY index -- the sequence's k-mers are claimed first, the databases only
-  // update those (half of a 30x human read database, the error k-mers, never gets a slot; k <= 21: 8-byte slots).  The
-  // other report types need the whole read database.  MFX_CLI_FULL_INDEX=1 builds the full tables for every type.
-  // (-reads: always -- the reads are counted into claimed k-mers; there is no read database for the full tables)
-  // (-spectrum: the full tables from -readmers -- its read-only row needs every read k-mer; with -reads the index -hist would build)
-  bool seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || (G.reportType == OP_SPECTRUM && fromReads)) && !G.sharded && k <= 31 &&
-                 (fromReads || !(getenv("MFX_CLI_FULL_INDEX") && atoi(getenv("MFX_CLI_FULL_INDEX"))));
-  const char *ov = getenv("MFX_CLI_OVERLAP");
+  // 7. which index: path-only (its VCF then loads beside the FASTA reader), sequence-only or full; the sequence first or under the build
+  if (decide_path_only(R)) return 1;
   const bool compressed = G.seqName && mfx_suffix_tool(G.seqName) != nullptr;
-  const bool wantOverlap = ov ? atoi(ov) != 0 : compressed;
-  const uint64_t basesBound = (G.seqName && !G.seqDBname && wantOverlap && !seqOnly) ? bases_upper_bound(G.seqName) : 0;
-  const bool deferSeq = G.seqName && !G.sharded && !seqOnly && !pathOnly && wantOverlap && (G.seqDBname || basesBound > 0);   // (the path-only index needs the sequences first)
-  // while the reader thread is on the file: the device's context, the library's code object and the pinned-memory path come
+  decide_seq_only_and_defer(R, compressed);
+  // 8. while the reader thread is on the file: the device's context, the library's code object and the pinned-memory path come
   // up here instead of inside the first upload (~0.07 s; an error here is left to that upload to report).  Not with a
   // decompressor child around (see the device check above) and not for several devices (their slots come up in parallel).
-  if (G.seqName && !compressed && G.devices.size() == 1 && !(getenv("MFX_CLI_WARM") && !atoi(getenv("MFX_CLI_WARM")))) (void)mfx_device_warm(G.device);
-  if (!stageFirst) begin_stage();
-  if (!deferSeq) finish_seq();
-  if (pathOnly) begin_path_stages();
-  if (G.sharded) {
-    if (G.devices.size() < 2) {
-      fprintf(stderr, "ERROR: -sharded needs at least two -devices.\n");
-      return 1;
-    }
-    if (G.indexName) { fprintf(stderr, "ERROR: -index caches a whole table; it cannot be combined with -sharded.\n"); return 1; }
-    // -hist / -dump: a part of the sequences per device, each on the sequence-only index of ITS k-mers (no exchange);
-    // everything else -- and a non-canonical database -- takes the hash-sharded full tables (MFX_CLI_FULL_INDEX=1: always)
-    const char *fi = getenv("MFX_CLI_FULL_INDEX");
-    if ((G.reportType == OP_HIST || G.reportType == OP_DUMP) && k <= 31 && !(fi && atoi(fi))) {
-      const int prc = run_parts(G, k, recs, bases, lens);
-      if (prc >= 0) return prc;
-    }
-    return run_sharded(G, k, rdb, adb, recs, bases, lens, totalBases);
-  }
-  mfx_index *ix = nullptr;
-  mfx_seq *seq = nullptr;
-  // -hist on one device with the assembly k-mers coming from -seqmers: nothing needs the sequence in HBM before the
-  // evaluation, so its upload is streamed under the -hist kernel (mfx_hist_run_streamed).  Otherwise the index build
-  // counts the assembly k-mers from the packed sequence and it goes up first.
-  const bool streamHist = G.reportType == OP_HIST && G.seqDBname && G.devices.size() == 1 && !seqOnly;
-  auto make_seq = [&]() -> bool {
-    if (!recs.empty() || G.seqName) {
-      seq = streamHist ? mfx_seq_create(G.device, lens.data(), (uint32_t)recs.size())
-                       : mfx_seq_upload(G.device, bases.data(), lens.data(), (uint32_t)recs.size());
-      if (!seq) return false;
-    }
-    lap("upload sequences");
-    if (stage) mfx_db_stage_boost(stage);                         // the host's threads are free: the database's readers may have them all
-    return true;
-  };
-  // The variant modes never evaluate the assembly itself on the device -- the paths around the variants go up batch by batch
+  if (G.seqName && !compressed && G.devices.size() == 1 && env_flag("MFX_CLI_WARM") != 0) (void)mfx_device_warm(G.device);
+  if (!stageFirst) begin_stage(R);
+  // 9. the sequence is waited for, or left to read under the index build
+  if (!R.deferSeq && finish_seq(R)) return 1;
+  if (R.pathOnly) begin_path_stages(R);
+  // 10. -sharded is a run of its own
+  if (G.sharded) return run_on_shards(R);
+  // 11. upload.  The variant modes never evaluate the assembly itself on the device -- the paths around the variants go up batch by batch
   // (mfx_variants_run takes the host bases) --, so the assembly is uploaded only if its k-mers must be counted there (no
-  // -seqmers: the counting branch below makes the upload when it gets there).  3 Gb: 0.2 s and 1.1 GB of HBM not spent.
-  const bool seqOnDevice = !variantMode;
-  if (!deferSeq && seqOnDevice && !make_seq()) DIE_MFX("uploading sequences");
-  // variant modes on one slot: the VCF is read and parsed (host work only) on a thread of its own while the index is built
-  // (merfin opens it after load_Kmers, merfin-globals.C:201-219; 0.15 s of a 4 M-call set).  An error is reported where the
-  // VCF is opened below.  Several slots split the file per slot instead.
-  std::future<mfx_vcf *> vcfAhead;
-  {
-    const char *vs = getenv("MFX_VARIANT_SLOTS");
-    const size_t slots = (vs && atoi(vs) > 0) ? (size_t)atoi(vs) : G.devices.size();
-    const char *pa = getenv("MFX_CLI_VCF_AHEAD");
-    const bool dbgAhead = G.debug;
-    if (variantMode && G.vcfName && slots == 1 && !G.sharded && !(pa && atoi(pa) == 0) && !pathOnly)
-      vcfAhead = std::async(std::launch::async, [&G, &vcfAheadError, &recs, &bases, &lens, k, dbgAhead, deferSeq]() {
-        mfx_vcf *v = mfx_vcf_load(G.vcfName);
-        if (!v) { vcfAheadError = mfx_last_error(); return v; }    // (errors are per thread: carried to the caller's)
-        // MFX_CLI_VCF_AHEAD=2: ... and its clusters merged, their allele combinations enumerated and packed here as well (mfx_vcf_prepare:
-        // stage A of the run needs the sequences, not the index).  Not the default: on a host whose cores the index build already
-        // keeps busy (the 16-core quota of the measured boxes: its readers copy 13 GB out of the page cache) the two slow each other
-        // down -- config 4 at 3 Gb 2.02-2.07 s with the load alone ahead, 2.67-2.75 s with stage A too (profiles/r05_cfg4_cli_ahead.txt).
-        const char *pa2 = getenv("MFX_CLI_VCF_AHEAD");
-        // (never while the sequences are still being read -- deferSeq: finish_seq() fills recs / bases / lens on the main thread later)
-        if (!(pa2 && atoi(pa2) == 2) || deferSeq) return v;
-        std::vector<const char *> nm(recs.size());
-        for (size_t c = 0; c < recs.size(); ++c) nm[c] = recs[c].name.c_str();
-        mfx_variant_opts o;
-        o.mode = G.reportType;
-        o.comb = G.comb;
-        o.nosplit = G.nosplit ? 1 : 0;
-        o.debug_path = dbgAhead ? "-" : nullptr;                   // (only whether it is set matters here)
-        if (mfx_vcf_prepare(v, k, nm.data(), bases.data(), lens.data(), (uint32_t)recs.size(), &o)) {
-          vcfAheadError = mfx_last_error();
-          mfx_vcf_free(v);
-          v = nullptr;
-        }
-        return v;
-      });
+  // -seqmers: the counting branch of the build makes the upload when it gets there).  3 Gb: 0.2 s and 1.1 GB of HBM not spent.
+  R.streamHist = G.reportType == OP_HIST && G.seqDBname && G.devices.size() == 1 && !R.seqOnly;
+  const bool seqOnDevice = !R.variantMode;
+  if (!R.deferSeq && seqOnDevice && !make_seq(R)) DIE_MFX("uploading sequences");
+  // 12. the VCF of the variant modes loads ahead, under the index build
+  start_vcf_ahead(R);
+  // 13. the image of the index, or its build.  The path-only index falls back to the full tables when the device could not take it or a
+  // database is not canonical (the prepared call set runs on the full tables as well); the sequence-only index when a database is not
+  // canonical: what -index saves is then the full index of these inputs
+  if (load_index_image(R)) return 1;
+  if (!R.ix && (R.pathOnly || R.seqOnly)) {
+    const int brc = R.pathOnly ? build_path_only_index(R) : build_seq_only_index(R);
+    if (brc > 0) return brc;
+    if (brc < 0) { R.pathOnly = R.seqOnly = false; R.fingerprint = R.fingerprintFull; }
   }
-  struct VcfAheadGuard { std::future<mfx_vcf *> &f; ~VcfAheadGuard() { if (f.valid()) mfx_vcf_free(f.get()); } } vcfAheadGuard{vcfAhead};
-  FILE *probe = G.indexName ? fopen(G.indexName, "rb") : nullptr;
-  uint64_t fingerprint = G.indexName ? input_fingerprint(G, seqOnly) : 0;
-  // a run that would build the sequence-only index also accepts a FULL image of the same inputs: that is what such a run
-  // saved when a database turned out not to be canonical (the fallback below) -- without this every later run would
-  // build twice again and the cache would never take effect
-  const uint64_t fingerprintFull = (G.indexName && seqOnly) ? input_fingerprint(G, false) : fingerprint;
-  if (probe) {
-    fclose(probe);
-    fprintf(stderr, "-- Loading the index image '%s' (k-mer databases are not read).\n", G.indexName);
-    ix = mfx_index_load(G.indexName, G.maxMemory, G.device);
-    if (!ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
-    mfx_index_info info;
-    if (mfx_index_get_info(ix, &info)) DIE_MFX("reading the index image");
-    if (info.k != k) { fprintf(stderr, "ERROR: the index image holds %d-mers but %s %d-mers.\n", info.k, fromReads ? "the run counts" : "-readmers holds", k); return 1; }
-    uint64_t fp = 0, imin = 0, imax = 0;
-    if (mfx_index_get_origin(ix, &fp, &imin, &imax)) DIE_MFX("reading the index image");
-    if (seqOnly && info.seq_only == 0 && fp == fingerprintFull && imin == G.minV && imax == G.maxV) {
-      seqOnly = false;                                              // the full tables of these inputs (a non-canonical database)
-      fingerprint = fingerprintFull;
-    } else if (fp != fingerprint || imin != G.minV || imax != G.maxV || (info.seq_only != 0) != seqOnly) {
-      // the image was built from other inputs (a re-polished -sequence, another database, other -min/-max):
-      // using it would give wrong asmK / readK with no diagnostic
-      fprintf(stderr, "-- The index image '%s' was built from other inputs (%s); rebuilding it.\n", G.indexName,
-              (imin != G.minV || imax != G.maxV) ? "-min/-max differ" : "a database or the sequence file changed");
-      mfx_index_free(ix);
-      ix = nullptr;
-    }
+  if (!R.ix && build_full_index(R)) return 1;
+  R.clock.lap("build / load index");
+  if (R.deferSeq && !R.seq) {
+    if (finish_seq(R)) return 1;
+    if (seqOnDevice && !make_seq(R)) DIE_MFX("uploading sequences");
   }
-  mfx_vcf *vcfReady = nullptr;                                      // the call set taken from vcfAhead (prepared): the run below uses it
-  struct VcfReadyGuard { mfx_vcf *&v; ~VcfReadyGuard() { if (v) mfx_vcf_free(v); v = nullptr; } } vcfReadyGuard{vcfReady};
-  if (!ix && pathOnly && vcfLoad.valid()) {
-    vcfReady = vcfLoad.get();
-    if (!vcfReady) { fprintf(stderr, "ERROR: variant scoring: %s\n", vcfAheadError.c_str()); return 1; }
-    step("(before the index: sequences, VCF)");
-    // the clusters merged, the table made from the bound of their path text, then batch by batch: the paths' tables packed on the host, their
-    // k-mers claimed on the device under the next batch's packing (mfx_vcf_prepare_path_index)
-    fprintf(stderr, "-- Claiming the %d-mers of the variants' paths on the GPU.\n", k);
-    {
-      std::vector<const char *> nm(recs.size());
-      for (size_t c = 0; c < recs.size(); ++c) nm[c] = recs[c].name.c_str();
-      mfx_variant_opts o;
-      o.mode = G.reportType;
-      o.comb = G.comb;
-      o.nosplit = G.nosplit ? 1 : 0;
-      o.debug_path = G.debug ? "-" : nullptr;                       // (only whether it is set matters here)
-      if (mfx_vcf_prepare_path_index(vcfReady, k, nm.data(), bases.data(), lens.data(), (uint32_t)recs.size(), &o, G.maxMemory, G.device, 0.7, &ix))
-        DIE_MFX("preparing the call set");
-      if (!ix) fprintf(stderr, "-- %s\n-- Building the full lookup tables instead.\n", mfx_last_error());
-    }
-    if (ix) {
-      mfx_index_info info;
-      if (mfx_index_get_info(ix, &info)) DIE_MFX("reading the path-only index");
-      fprintf(stderr, "--\n-- Memory needed: %.3f GB (the %d-mers of the variants' paths: %lu)\n-- Memory limit:  %.3f GB%s\n--\n", info.bytes / 1e9, k,
-              (unsigned long)info.distinct, G.maxMemory, G.maxMemory > 0 ? "" : " (none)");
-    }
-    if (stage) mfx_db_stage_boost(stage);                           // the host's threads are free: the databases' readers may have them all
-    if (stageAsm) mfx_db_stage_boost(stageAsm);
-    step("prepare the call set + claim the paths' k-mers");
-    int lrc = 0;
-    if (ix) {
-      if (G.seqDBname) {
-        fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.seqDBname);
-        lrc = stageAsm ? mfx_index_load_db_staged(ix, stageAsm, 1, 0, ~0ull) : mfx_index_load_db(ix, G.seqDBname, 1, 0, ~0ull);
-        if (stageAsm) { mfx_db_stage_free(stageAsm); stageAsm = nullptr; }
-        if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -seqmers");
-        step("load -seqmers");
-      } else {
-        // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186) for the k-mers that will be asked for
-        fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
-        if (!seq && !make_seq()) DIE_MFX("uploading sequences");
-        if (mfx_index_count_claimed(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
-        step("count the sequence's k-mers");
-      }
-      if (!lrc && fromReads) {
-        if (!count_reads_files(G, ix)) return 1;
-        step("count -reads");
-      } else if (!lrc) {
-        fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
-        lrc = stage ? mfx_index_load_db_staged(ix, stage, 0, G.minV, G.maxV) : mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV);
-        if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -readmers");
-        step("load -readmers");
-      }
-      if (lrc == MFX_E_NONCANON) {
-        fprintf(stderr, "-- A k-mer database is not canonical; building the full lookup tables instead.\n");
-        mfx_index_free(ix);
-        ix = nullptr;
-      }
-    }
-    // (the staged bytes are not needed by the run; a fall-back to the full tables reads the files)
-    if (stage) { mfx_db_stage_free(stage); stage = nullptr; }
-    if (stageAsm) { mfx_db_stage_free(stageAsm); stageAsm = nullptr; }
-    if (!ix && fromReads) { fprintf(stderr, "ERROR: -reads needs the path-only index of the call set, which could not be built.\n"); return 1; }
-    if (!ix) pathOnly = false;                                      // (the prepared call set runs on the full tables as well)
+  // 14. -spectrum / -peak auto
+  if ((G.reportType == OP_SPECTRUM || G.peakAuto) && run_spectrum_or_peak(R)) return 1;
+  // 15. the evaluator
+  R.kp = mfx_kparams{G.peak, (uint32_t)G.copyKmerK.size(), G.copyKmerK.data(), G.copyKmerP.data()};
+  if (G.reportType != OP_SPECTRUM) {
+    R.ev = mfx_eval_create(R.ix, &R.kp, 0);
+    if (!R.ev) DIE_MFX("creating evaluator");
   }
-  if (!ix && seqOnly) {
-    const uint64_t capacity = totalBases + 1024;                  // a sequence has at most one new k-mer per base
-    fprintf(stderr, "--\n-- Memory needed: %.3f GB\n-- Memory limit:  %.3f GB%s\n--\n", mfx_index_estimate_gb_for_seq(k, capacity),
-            G.maxMemory, G.maxMemory > 0 ? "" : " (none)");
-    step("(before the index)");
-    // load factor of the table: 0.4 unless the user says otherwise (MFX_LOAD_FACTOR) -- the emptier tables the library would pick probe
-    // faster (3 Gb: 20 instead of 23 ms of -hist kernel) but a run that starts behind another waits seconds in hipMalloc for the driver
-    // to clear what that one freed, the longer the more of the HBM both ask for (profiles/r05_e2e_lf_ab.txt)
-    ix = mfx_index_create_for_seq_lf(k, capacity, G.maxMemory, G.device, 0.4);
-    if (!ix && stage) {                                             // (the staged database may be what the table lacks)
-      mfx_db_stage_free(stage);
-      stage = nullptr;
-      ix = mfx_index_create_for_seq_lf(k, capacity, G.maxMemory, G.device, 0.4);
-    }
-    if (!ix) {
-      fprintf(stderr, "\n%s\n\n", mfx_last_error());
-      return 1;
-    }
-    step("create the table");
-    int lrc = 0;
-    bool fused = false;
-    if (G.seqDBname) {
-      fprintf(stderr, "-- Claiming the %d-mers of '%s' on the GPU.\n", k, G.seqName);
-      if (mfx_index_claim_seq(ix, seq, nullptr)) DIE_MFX("claiming sequence k-mers");
-      step("claim the sequence's k-mers");
-      fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.seqDBname);
-      lrc = mfx_index_load_db(ix, G.seqDBname, 1, 0, ~0ull);
-      if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -seqmers");
-      step("load -seqmers");
-    } else if (fromReads) {
-      fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
-      if (mfx_index_count_asm(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
-      step("count the sequence's k-mers");
-    } else {
-      // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186)
-      fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
-      // (one call for the counting and the load of -readmers: the database crosses PCIe while the k-mers are claimed)
-      fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
-      lrc = stage ? mfx_index_build_for_hist_staged(ix, seq, stage, G.minV, G.maxV) : mfx_index_build_for_hist(ix, seq, G.readDBname, G.minV, G.maxV);
-      if (stage) { mfx_db_stage_free(stage); stage = nullptr; }     // its device memory is not needed by the evaluation
-      if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("counting sequence k-mers / loading -readmers");
-      step("count the sequence's k-mers + load -readmers");
-      fused = true;
-    }
-    if (lrc == MFX_E_NONCANON && fromReads) { fprintf(stderr, "ERROR: -reads needs a canonical -seqmers database.\n"); return 1; }
-    if (!lrc && fromReads) {
-      if (!count_reads_files(G, ix)) return 1;
-      step("count -reads");
-    } else if (!lrc && !fused) {
-      fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
-      lrc = mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV);
-      if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -readmers");
-      step("load -readmers");
-    }
-    if (lrc == MFX_E_NONCANON) {
-      // one slot per canonical k-mer cannot answer value(fmer) + value(rmer) of a non-canonical database
-      fprintf(stderr, "-- A k-mer database is not canonical; building the full lookup tables instead.\n");
-      mfx_index_free(ix);
-      ix = nullptr;
-      seqOnly = false;
-      fingerprint = fingerprintFull;                                // what is saved below is the full index of these inputs
-    } else if (G.indexName) {
-      fprintf(stderr, "-- Writing the index image '%s'.\n", G.indexName);
-      if (mfx_index_set_fingerprint(ix, fingerprint) || mfx_index_save(ix, G.indexName)) DIE_MFX("writing the index image");
-    }
-  }
-  if (!ix) {
-    // the table is sized before the sequence is in when the file promised a bound on its bases; a file that breaks the
-    // promise (several gzip members, ...) costs a second build with the true number
-    for (int attempt = 0; !ix; ++attempt) {
-      const uint64_t capacity = rdb.n_kmers + (G.seqDBname ? adb.n_kmers : (seqDone ? totalBases : basesBound)) + 1024;
-      fprintf(stderr, "--\n-- Memory needed: %.3f GB\n-- Memory limit:  %.3f GB%s\n--\n", mfx_index_estimate_gb(k, capacity),
-              G.maxMemory, G.maxMemory > 0 ? "" : " (none)");
-      // (the smallest table the library makes, load factor 0.7: the device stage of these report types is a hundredth of the run, and a
-      // table allocated behind another process waits for the driver to clear what that one freed -- the longer, the larger both are)
-      ix = mfx_index_create_lf(k, capacity, G.maxMemory, G.device, 0.7);
-      if (!ix && !G.seqDBname && !seqDone && basesBound > 0) {
-        // the capacity came from the file's BOUND on its bases (a .gz of a human assembly sits near the 4 GiB step of that
-        // bound): read the file to the end, as the reference does before anything else, and size the table by the truth
-        fprintf(stderr, "-- The table sized by the bound on the bases of '%s' does not fit; reading the file first.\n", G.seqName);
-        finish_seq();
-        continue;
-      }
-      if (!ix) {
-        fprintf(stderr, "\n%s\n\n", mfx_last_error());
-        return 1;
-      }
-      if (!fromReads) {
-        fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.readDBname);
-        if (mfx_index_load_db(ix, G.readDBname, 0, G.minV, G.maxV)) DIE_MFX("loading -readmers");
-      }
-      if (G.seqDBname) {
-        fprintf(stderr, "-- Loading kmers from '%s' into lookup table.\n", G.seqDBname);
-        if (mfx_index_load_db(ix, G.seqDBname, 1, 0, ~0ull)) DIE_MFX("loading -seqmers");
-        break;
-      }
-      // replaces `meryl count k=.. <seq> output <seq>.meryl` (merfin-globals.C:182-186)
-      if (deferSeq && !seqDone) {            // the read database is in; now the sequence is needed
-        finish_seq();
-        if (totalBases > basesBound && attempt == 0) {
-          fprintf(stderr, "-- NOTE: '%s' holds %lu bases, more than its size promised (%lu); rebuilding the table.\n", G.seqName,
-                  (unsigned long)totalBases, (unsigned long)basesBound);
-          mfx_index_free(ix);
-          ix = nullptr;
-          continue;
-        }
-      }
-      if (!seq && !make_seq()) DIE_MFX("uploading sequences");
-      fprintf(stderr, "-- No -seqmer given. Counting the %d-mers of '%s' on the GPU.\n", k, G.seqName);
-      if (mfx_index_count_asm(ix, seq, nullptr)) DIE_MFX("counting sequence k-mers");
-    }
-    // -reads (k > 31: this table holds the assembly's k-mers only; the reads update them)
-    if (fromReads && !count_reads_files(G, ix)) return 1;
-    if (G.indexName) {
-      fprintf(stderr, "-- Writing the index image '%s'.\n", G.indexName);
-      if (mfx_index_set_fingerprint(ix, fingerprint) || mfx_index_save(ix, G.indexName)) DIE_MFX("writing the index image");
-    }
-  }
-
-  lap("build / load index");
-  if (deferSeq && !seq) {
-    finish_seq();
-    if (seqOnDevice && !make_seq()) DIE_MFX("uploading sequences");
-  }
-  // -spectrum / -peak auto: one streaming pass over the table (mfx_spectrum_run), the haploid peak off its single-copy row
-  if (G.reportType == OP_SPECTRUM || G.peakAuto) {
-    const bool report = G.reportType == OP_SPECTRUM;
-    const uint32_t copies = report ? G.copies : 4u, maxMult = report ? G.maxMult : 10000u;
-    std::vector<uint64_t> img((size_t)(copies + 2) * (maxMult + 1));
-    uint64_t entries = 0;
-    if (mfx_spectrum_run(ix, copies, maxMult, img.data(), &entries)) DIE_MFX(report ? "-spectrum" : "-peak auto");
-    if (report) {
-      // a table that holds the k-mers of -sequence only (-reads) has no read-only k-mers: the row is left out, not written as zeros
-      const bool withReadOnly = !fromReads;
-      const std::string name = std::string(G.outName) + ".spectra-cn.hist";
-      fprintf(stderr, "-- Copy-number spectrum of the %d-mers to '%s'.\n", k, name.c_str());
-      if (mfx_spectrum_write(img.data(), copies, maxMult, withReadOnly ? 1 : 0, name.c_str())) DIE_MFX("writing the spectrum");
-      uint64_t asmOnly = 0, readOnly = 0;
-      for (uint32_t r = 1; r < copies + 2; ++r) asmOnly += img[(size_t)r * (maxMult + 1)];
-      for (uint32_t m = 0; m <= maxMult; ++m) readOnly += img[m];
-      fprintf(stderr, "Entries counted: %lu\nAssembly-only k-mers: %lu\n", (unsigned long)entries, (unsigned long)asmOnly);
-      if (withReadOnly) fprintf(stderr, "Read-only k-mers: %lu\n", (unsigned long)readOnly);
-      else fprintf(stderr, "The table holds the k-mers of -sequence only (-reads): the read-only row is left out.\n");
-    }
-    mfx_spectrum_peak_t pk;
-    if (mfx_spectrum_peak(img.data() + (size_t)(maxMult + 1), maxMult, &pk) == MFX_OK) {
-      fprintf(stderr, "Haploid peak (auto): %u  (main peak %u, valley %u, single-copy k-mers at the peak %lu)\n", pk.haploid_peak, pk.main_peak, pk.valley,
-              (unsigned long)pk.count_at_peak);
-      if (G.peakAuto) G.peak = (double)pk.haploid_peak;
-    } else if (report) {
-      fprintf(stderr, "No haploid peak found in the single-copy row (%s); the other report types need -peak <number>.\n", mfx_last_error());
-    } else {
-      fprintf(stderr, "ERROR: -peak auto found no haploid peak in the single-copy row of the spectrum (%s). Give -peak <number>.\n", mfx_last_error());
-      return 1;
-    }
-    lap("spectrum");
-  }
-  mfx_kparams kp{G.peak, (uint32_t)G.copyKmerK.size(), G.copyKmerK.data(), G.copyKmerP.data()};
-  mfx_eval *ev = G.reportType == OP_SPECTRUM ? nullptr : mfx_eval_create(ix, &kp, 0);
-  if (!ev && G.reportType != OP_SPECTRUM) DIE_MFX("creating evaluator");
-
-  int rc = 0;
-  if (G.reportType == OP_HIST) {
-    fprintf(stderr, "-- Generate histogram of the k* metric to '%s'.\n", G.outName);
-    mfx_hist_result r;
-    if (G.devices.size() > 1) {
-      // one process, N devices (the reference drives all its workers from one binary, merfin.C:366-414): replicas of
-      // the table and of the packed assembly by peer copy, every device evaluates its block-cyclic share
-      const size_t N = G.devices.size();
-      Slots S;
-      int bad = S.make(G, ix, seq, ev, &kp) ? 0 : 1;
-      lap("replicate index");
-      fprintf(stderr, "-- Evaluating on %zu devices.\n", N);
-      if (!bad && mfx_hist_run_multi(S.evs.data(), S.sqs.data(), (uint32_t)N, &r)) bad = 1;
-      std::string why = bad ? mfx_last_error() : "";
-      S.release();
-      if (bad) { fprintf(stderr, "ERROR: -hist on %zu devices: %s\n", N, why.c_str()); return 1; }
-    } else if (streamHist) {
-      if (mfx_hist_run_streamed(ev, seq, bases.data(), &r)) DIE_MFX("-hist");
-    } else if (mfx_hist_run(ev, seq, &r)) DIE_MFX("-hist");
-    bool ok = true;
-    print_hist(recs, r, k, G.outName, &ok);
-    if (!ok) DIE_MFX("writing histogram");
-    mfx_hist_result_free(&r);
-  } else if (G.reportType == OP_DUMP) {
-    fprintf(stderr, "-- Dump per-base k* metric to '%s'.\n", G.outName);
-    uint64_t cumMissing = 0, cumAsm = 0;
-    if (G.skipMissing) {
-      // merfin-dump.C:34,81-87: -skipMissing suppresses the dump file entirely; only the counts remain
-      mfx_hist_result r;
-      if (mfx_hist_run(ev, seq, &r)) DIE_MFX("-dump -skipMissing");
-      for (size_t c = 0; c < recs.size(); ++c) {
-        cumMissing += r.contig_kmissing[c];
-        cumAsm += r.contig_kasm[c];
-        fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)r.contig_kmissing[c], (unsigned long)cumMissing, (unsigned long)cumAsm);
-      }
-      mfx_hist_result_free(&r);
-    } else if (G.devices.size() > 1) {
-      // per-contig ordered output on N devices: a contiguous run of contigs per slot (balanced by bases), one host
-      // thread per slot writes its part, the parts are concatenated in slot order
-      const size_t N = G.devices.size();
-      Slots S;
-      if (!S.make(G, ix, seq, ev, &kp)) { fprintf(stderr, "ERROR: -dump on %zu devices: %s\n", N, mfx_last_error()); return 1; }
-      lap("replicate index");
-      fprintf(stderr, "-- Evaluating on %zu devices.\n", N);
-      std::vector<double> w(recs.size());
-      for (size_t c = 0; c < recs.size(); ++c) w[c] = (double)lens[c];
-      const auto runs = contig_partition(w, N);
-      std::vector<std::string> parts(N), errs(N);
-      std::vector<std::vector<uint64_t>> ka(N), km(N);
-      std::vector<std::thread> th;
-      for (size_t d = 0; d < N; ++d) {
-        char suf[32];
-        snprintf(suf, sizeof(suf), ".part%04zu", d);
-        parts[d] = std::string(G.outName) + suf;
-        th.emplace_back([&, d]() {
-          mfx_host_threads_share((unsigned)N);
-          for (size_t c = runs[d].first; c < runs[d].second; ++c) {
-            uint64_t a = 0, m2 = 0;
-            if (mfx_dump_contig(S.evs[d], S.sqs[d], (uint32_t)c, recs[c].name.c_str(), parts[d].c_str(), c > runs[d].first, &a, &m2)) { errs[d] = mfx_last_error(); return; }
-            ka[d].push_back(a);
-            km[d].push_back(m2);
-          }
-        });
-      }
-      for (auto &x : th) x.join();
-      S.release();
-      for (size_t d = 0; d < N; ++d) if (!errs[d].empty()) { fprintf(stderr, "ERROR: -dump (slot %zu): %s\n", d, errs[d].c_str()); return 1; }
-      if (!concat_parts(G.outName, parts, false)) { fprintf(stderr, "ERROR: cannot write '%s'.\n", G.outName); return 1; }
-      for (size_t d = 0; d < N; ++d)
-        for (size_t i = 0; i < ka[d].size(); ++i) {
-          cumMissing += km[d][i];
-          cumAsm += ka[d][i];
-          fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[runs[d].first + i].name.c_str(), (unsigned long)km[d][i], (unsigned long)cumMissing, (unsigned long)cumAsm);
-        }
-    } else {
-      for (size_t c = 0; c < recs.size(); ++c) {
-        uint64_t ka = 0, km = 0;
-        if (mfx_dump_contig(ev, seq, (uint32_t)c, recs[c].name.c_str(), G.outName, c > 0, &ka, &km)) DIE_MFX("-dump");
-        cumMissing += km;
-        cumAsm += ka;
-        fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)km, (unsigned long)cumMissing, (unsigned long)cumAsm);
-      }
-      if (recs.empty()) { FILE *f = fopen(G.outName, "w"); if (f) fclose(f); }
-    }
-  } else if (G.reportType == OP_TRACK) {
-    // K* per window of every contig, reduced on the device (mfx_track_run): what the README's "Assess collapses and duplications"
-    // makes from the -dump text with awk and wigToBigWig.  The counts on stderr are those of -dump -skipMissing.
-    // (a compressed -output name -- out.gz / .bz2 / .xz -- keeps its suffix at the end of the three names: out.track.tsv.gz)
-    std::string stem = G.outName, zsuf;
-    if (mfx_suffix_tool(stem)) { const size_t dot = stem.rfind('.'); zsuf = stem.substr(dot); stem.resize(dot); }
-    const std::string tsvName = stem + ".track.tsv" + zsuf, bgName = stem + ".kstar.bedgraph" + zsuf, missName = stem + ".missing.bedgraph" + zsuf;
-    fprintf(stderr, "-- Summarise the k* metric per window of %lu positions to '%s', '%s' and '%s'.\n", (unsigned long)G.window, tsvName.c_str(),
-            bgName.c_str(), missName.c_str());
-    const uint64_t nw = mfx_track_num_windows(seq, G.window);
-    std::vector<mfx_track_window> win((size_t)nw);
-    uint64_t got = 0, kasm = 0, kmissing = 0;
-    if (mfx_track_run(ev, seq, G.window, win.data(), nw, &got, &kasm, &kmissing)) DIE_MFX("-track");
-    std::vector<const char *> names(recs.size());
-    for (size_t c = 0; c < recs.size(); ++c) names[c] = recs[c].name.c_str();
-    if (mfx_track_write(win.data(), got, seq, names.data(), G.window, tsvName.c_str(), bgName.c_str())) DIE_MFX("writing the windows");
-    mfx_file mf = mfx_open_writer(missName.c_str(), false);
-    if (!mf.f) { fprintf(stderr, "ERROR: cannot open '%s' for writing.\n", missName.c_str()); return 1; }
-    fprintf(mf.f, "track type=bedGraph name=\"missing\"\n");
-    uint64_t cumMissing = 0, cumAsm = 0;
-    std::vector<uint64_t> cmiss(recs.size(), 0), casm(recs.size(), 0);
-    size_t i = 0;
-    for (size_t c = 0; c < recs.size(); ++c)
-      for (uint64_t start = 0; start < lens[c]; start += G.window, ++i) {
-        const mfx_track_window &w = win[i];
-        cmiss[c] += w.n_missing;
-        casm[c] += w.n_kmers;
-        if (w.n_kmers)
-          fprintf(mf.f, "%s\t%lu\t%lu\t%.6f\n", names[c], (unsigned long)start, (unsigned long)std::min<uint64_t>(start + G.window, lens[c]),
-                  (double)w.n_missing / (double)w.n_kmers);
-      }
-    if (mfx_close(mf)) { fprintf(stderr, "ERROR: writing '%s' failed.\n", missName.c_str()); return 1; }
-    for (size_t c = 0; c < recs.size(); ++c) {
-      cumMissing += cmiss[c];
-      cumAsm += casm[c];
-      fprintf(stderr, "%s\t%lu\t%lu\t%lu\n", recs[c].name.c_str(), (unsigned long)cmiss[c], (unsigned long)cumMissing, (unsigned long)cumAsm);
-    }
-    if (cumAsm != kasm || cumMissing != kmissing) {
-      fprintf(stderr, "ERROR: -track: the windows hold %lu k-mers (%lu missing), the device counted %lu (%lu).\n", (unsigned long)cumAsm,
-              (unsigned long)cumMissing, (unsigned long)kasm, (unsigned long)kmissing);
-      return 1;
-    }
-  } else if (variantMode) {
-    // open_Inputs + processVariants + outputVariants (merfin-globals.C:201-219, merfin-variants.C:131-345)
-    fprintf(stderr, "-- Opening vcf file '%s'.\n", G.vcfName);
-    fprintf(stderr, "-- Generate variant mers and score them.\n");
-    std::string outName = std::string(G.outName) + (G.reportType == OP_POLISH ? ".polish.vcf" : ".filter.vcf");   // :324-327
-    std::string dbgName = std::string(G.outName) + ".00.debug.gz";
-    std::vector<const char *> names(recs.size());
-    for (size_t c = 0; c < recs.size(); ++c) names[c] = recs[c].name.c_str();
-    mfx_variant_opts vo;
-    vo.mode = G.reportType;           // OP_* values are the MFX_VAR_* values
-    vo.comb = G.comb;
-    vo.nosplit = G.nosplit ? 1 : 0;
-    vo.debug_path = G.debug ? dbgName.c_str() : nullptr;
-    uint64_t ncl = 0;
-    // One device is run as ONE slot.  (Rounds 2-3 ran it as 4 slots sharing its table: the host phases of these modes then
-    // alternated between parallel and serial stretches and several slots filled one another's gaps -- 1 Gb: 2.0 s in 8 slots
-    // against 2.7 s in one.  With the host side of round 4 -- arenas per run of clusters, parallel VCF load, device scoring --
-    // one slot on all host threads is at least as fast and needs neither the per-slot VCF files nor the evaluator replicas:
-    // config 4 at 3 Gb, evaluate + write 1.11-1.14 s in one slot, 1.16-1.19 s in four + 0.13-0.15 s to set the slots up,
-    // profiles/r04_cfg4_fullsize.txt.)  MFX_VARIANT_SLOTS overrides; several -devices are one slot each.
-    {
-      size_t want = G.devices.size();
-      const char *vs = getenv("MFX_VARIANT_SLOTS");
-      if (vs && atoi(vs) > 0) want = (size_t)atoi(vs);
-      const std::vector<int> real = G.devices;
-      while (G.devices.size() < want) G.devices.push_back(real[G.devices.size() % real.size()]);
-    }
-    if (G.devices.size() > 1) {
-      // BASELINE config 4 names 8 GPUs: contigs cut into one contiguous run per slot, balanced by their VCF records;
-      // every slot scores its clusters on its own device and writes its part; one VCF header in the concatenation
-      const size_t N = G.devices.size();
-      std::vector<double> w(recs.size(), 0.0);
-      // one pass over the VCF: the records per contig (for the balance), and the lines themselves, so that every slot is
-      // handed a VCF of ITS contigs only (each slot parsing all 4 M records of a human call set made N slots N times the
-      // host work of one; the host is what bounds these modes)
-      std::string vtext;
-      std::vector<std::pair<size_t, size_t>> vhead;                          // header lines (offset, length incl. newline)
-      std::vector<std::vector<std::pair<size_t, size_t>>> vlines(recs.size());   // data lines per contig, in file order
-      {
-        mfx_file vf = mfx_open_reader(G.vcfName);
-        if (!vf.f) { fprintf(stderr, "ERROR: cannot open VCF '%s'.\n", G.vcfName); return 1; }
-        {
-          std::vector<char> blk(1 << 22);
-          size_t n;
-          while ((n = fread(blk.data(), 1, blk.size(), vf.f)) > 0) vtext.append(blk.data(), n);
-        }
-        if (mfx_close(vf)) { fprintf(stderr, "ERROR: reading VCF '%s' failed.\n", G.vcfName); return 1; }
-        std::vector<std::pair<std::string, size_t>> idx;
-        for (size_t c = 0; c < recs.size(); ++c) idx.emplace_back(recs[c].name, c);
-        std::sort(idx.begin(), idx.end());
-        size_t last_c = recs.size();
-        std::string last_chr;
-        for (size_t o = 0; o < vtext.size();) {
-          const char *nl = (const char *)memchr(vtext.data() + o, '\n', vtext.size() - o);
-          const size_t e = nl ? (size_t)(nl - vtext.data()) + 1 : vtext.size(), n = e - o;
-          if (vtext[o] == '#') vhead.emplace_back(o, n);
-          else if (n > 1) {
-            const char *tab = (const char *)memchr(vtext.data() + o, '\t', n);
-            if (tab) {
-              const size_t cl = (size_t)(tab - (vtext.data() + o));
-              if (last_c == recs.size() || last_chr.size() != cl || memcmp(last_chr.data(), vtext.data() + o, cl) != 0) {
-                last_chr.assign(vtext.data() + o, cl);
-                auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(last_chr, (size_t)0));
-                last_c = (it != idx.end() && it->first == last_chr) ? it->second : recs.size() + 1;   // + 1: not a contig of -sequence
-              }
-              if (last_c < recs.size()) { w[last_c] += 1.0; vlines[last_c].emplace_back(o, n); }
-            }
-          }
-          o = e;
-        }
-        for (size_t c = 0; c < recs.size(); ++c) w[c] += 1e-9 * (double)lens[c];
-      }
-      Slots S;
-      if (!S.make(G, ix, nullptr, ev, &kp)) { fprintf(stderr, "ERROR: variant scoring on %zu devices: %s\n", N, mfx_last_error()); return 1; }
-      lap("replicate index");
-      fprintf(stderr, "-- Evaluating in %zu slots.\n", N);
-      const auto runs = contig_partition(w, N);
-      std::vector<std::string> parts(N), errs(N), dbgs(N), vins(N), logs(N);
-      std::vector<uint64_t> ncls(N, 0);
-      auto drop_parts = [&]() { for (size_t e = 0; e < N; ++e) { if (!parts[e].empty()) remove(parts[e].c_str()); if (!vins[e].empty()) remove(vins[e].c_str()); if (!logs[e].empty()) remove(logs[e].c_str()); } };
-      std::vector<std::thread> th;
-      for (size_t d = 0; d < N; ++d) {                                      // slot d's VCF: all header lines + the lines of its contigs
-        char suf[48];
-        snprintf(suf, sizeof(suf), ".part%04zu.in.vcf", d);
-        vins[d] = outName + suf;
-        FILE *vf = fopen(vins[d].c_str(), "w");
-        bool ok = vf != nullptr;
-        for (const auto &h : vhead) ok = ok && fwrite(vtext.data() + h.first, 1, h.second, vf) == h.second;
-        for (size_t c = runs[d].first; c < runs[d].second && ok; ++c)
-          for (const auto &l : vlines[c]) {
-            ok = ok && fwrite(vtext.data() + l.first, 1, l.second, vf) == l.second;
-            if (ok && vtext[l.first + l.second - 1] != '\n') ok = fputc('\n', vf) != EOF;     // a last line without newline
-          }
-        if (vf && fclose(vf) != 0) ok = false;
-        if (!ok) { fprintf(stderr, "ERROR: cannot write '%s'.\n", vins[d].c_str()); drop_parts(); return 1; }
-      }
-      std::string().swap(vtext);
-      for (size_t d = 0; d < N; ++d) {
-        char suf[48];
-        snprintf(suf, sizeof(suf), ".part%04zu", d);
-        parts[d] = outName + suf;
-        snprintf(suf, sizeof(suf), ".%02zu.debug.gz", d);
-        dbgs[d] = std::string(G.outName) + suf;
-        // every slot logs to its own file; they are replayed on stderr in slot order once all slots are done (N slots
-        // writing PANIC / progress lines to one stderr interleave them mid-line)
-        logs[d] = parts[d] + ".log";
-        th.emplace_back([&, d]() {
-          mfx_host_threads_share((unsigned)N);                 // N slots side by side: each takes its share of the host threads
-          mfx_variant_opts o = vo;
-          o.debug_path = G.debug ? dbgs[d].c_str() : nullptr;
-          const size_t lo = runs[d].first, hi = runs[d].second;
-          if (mfx_variants_run(S.evs[d], vins[d].c_str(), names.data() + lo, bases.data() + lo, lens.data() + lo, (uint32_t)(hi - lo), &o, parts[d].c_str(),
-                               logs[d].c_str(), &ncls[d]))
-            errs[d] = mfx_last_error();
-        });
-      }
-      for (auto &x : th) x.join();
-      for (size_t d = 0; d < N; ++d) {
-        remove(vins[d].c_str());
-        vins[d].clear();
-        if (FILE *lf = fopen(logs[d].c_str(), "r")) {
-          if (N > 1) fprintf(stderr, "-- slot %zu (contigs %zu..%zu):\n", d, runs[d].first, runs[d].second);
-          char lb[1 << 14];
-          size_t n;
-          while ((n = fread(lb, 1, sizeof(lb), lf)) > 0) fwrite(lb, 1, n, stderr);
-          fclose(lf);
-        }
-        remove(logs[d].c_str());
-        logs[d].clear();
-      }
-      S.release();
-      for (size_t d = 0; d < N; ++d) if (!errs[d].empty()) { fprintf(stderr, "ERROR: variant scoring (slot %zu): %s\n", d, errs[d].c_str()); drop_parts(); return 1; }
-      if (!concat_parts(outName, parts, true)) { fprintf(stderr, "ERROR: cannot write '%s'.\n", outName.c_str()); drop_parts(); return 1; }
-      for (uint64_t x : ncls) ncl += x;
-    } else if (vcfReady || vcfAhead.valid()) {
-      mfx_vcf *vcf = vcfReady ? vcfReady : vcfAhead.get();
-      vcfReady = nullptr;
-      if (!vcf) { fprintf(stderr, "ERROR: variant scoring: %s\n", vcfAheadError.c_str()); return 1; }
-      const int vrc = mfx_variants_run_vcf(ev, vcf, names.data(), bases.data(), lens.data(), (uint32_t)recs.size(), &vo, outName.c_str(), nullptr, &ncl);
-      // (leaving the 4 M records to the process's exit instead of freeing them here was measured: 0.1 s less in this phase, the same wall --
-      // profiles/r05_exit_ab.txt)
-      mfx_vcf_free(vcf);
-      if (vrc) DIE_MFX("variant scoring");
-    } else if (mfx_variants_run(ev, G.vcfName, names.data(), bases.data(), lens.data(), (uint32_t)recs.size(), &vo, outName.c_str(), nullptr, &ncl))
-      DIE_MFX("variant scoring");
-  } else if (G.reportType == OP_COMPL) {
-    fprintf(stderr, "-- Compute completeness.\n");
-    double t64[64], u64[64];
-    if (mfx_completeness_pieces(ev, t64, u64)) DIE_MFX("-completeness");
-    print_completeness(t64, u64);
-  }
-
-  lap("evaluate + write");
-  if (ev) mfx_eval_free(ev);
-  if (seq) mfx_seq_free(seq);
-  mfx_index_free(ix);
-  lap("release");
-  if (timing) {
-    fprintf(stderr, "-- timing:");
-    for (auto &ph : phases) fprintf(stderr, "  %s %.2fs", ph.first, ph.second);
-    fprintf(stderr, "\n");
-    if (atoi(getenv("MFX_CLI_TIMING")) > 1 && !steps.empty()) {
-      fprintf(stderr, "-- timing (index):");
-      for (auto &ph : steps) fprintf(stderr, "  %s %.3fs", ph.first, ph.second);
-      fprintf(stderr, "\n");
-    }
-    if (atoi(getenv("MFX_CLI_TIMING")) > 2)
-      fprintf(stderr, "-- stamps: main %.6f devices %.6f end %.6f\n", stamp_main, stamp_devices, epoch());
-  }
+  // 16. the report
+  const int rc = G.reportType == OP_HIST ? report_hist(R) : G.reportType == OP_DUMP ? report_dump(R) : G.reportType == OP_TRACK ? report_track(R) :
+                 R.variantMode ? report_variants(R) : G.reportType == OP_COMPL ? report_completeness(R) : 0;
+  if (rc) return rc;
+  R.clock.lap("evaluate + write");
+  // 17. release
+  R.ev.reset();
+  R.seq.reset();
+  R.ix.reset();
+  R.clock.lap("release");
+  // 18. timing, 19. Bye!
+  R.clock.print();
   fprintf(stderr, "Bye!\n");
   // MFX_CLI_QUICK_EXIT=1: every output is written and closed by now; leave without the tear-down of the HIP runtime's statics
   // (not under a profiler: its tool library writes its files from an exit handler)
-  if (const char *qe = getenv("MFX_CLI_QUICK_EXIT")) if (atoi(qe)) { fflush(nullptr); _exit(rc); }
-  return rc;
+  if (env_flag("MFX_CLI_QUICK_EXIT") > 0) { fflush(nullptr); _exit(0); }
+  return 0;
 }
