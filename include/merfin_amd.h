@@ -299,6 +299,35 @@ int  mfx_db_writer_append_sorted(mfx_db_writer *w, const uint64_t *kmers, const 
 int  mfx_db_writer_info(const mfx_db_writer *w, uint64_t *kmers, uint64_t *blocks, uint64_t *escapes, uint64_t *spool_bytes, uint64_t *held_bytes);
 int  mfx_index_write_db_streamed(const mfx_index *ix, int side, const char *path, uint64_t *n_kmers);
 
+/* mfx_db_merge: sorted databases combined on the device, window by window (`meryl union-sum` and its kin; one input: a filter).  The inputs
+ * are 1 to 64 files in the sorted, delta-coded flat form (what -count, -convert and mfx_db_write_flat of ascending k-mers write; k <= 31), all
+ * of one k; a flat file of no k-mers is an input of none in whatever form it was written.  Refused before any device is touched, with a text that names the file (MFX_E_INVAL / MFX_E_FORMAT): a placed file; a packed or
+ * plain flat file, `meryl print` text or a meryl directory (run `merfin -convert` first); inputs of different k; out_path that is an input;
+ * n_in of 0 or above 64; an unknown op; minV > maxV.
+ * A k-mer is written iff the operation yields it and minV <= combined count <= maxV: the filter acts after the operation.  The result is byte
+ * for byte what mfx_db_write_flat writes for the resulting ascending arrays, through the streamed writer above (MFX_DB_BOUNCE applies,
+ * MFX_COUNT_WRITER does not); on any failure nothing exists at out_path and no spool stays.  A result of no k-mers is a valid file.
+ * The key space is cut into half-open windows [lo, hi) at first k-mers of the inputs' blocks (csrc/mfx_merge.h), so that the blocks that may
+ * overlap a window hold at most MFX_MERGE_RANGE pairs (default and largest value 2^26; read per call) summed over the inputs -- one block per
+ * input more where no boundary allows less.  Per window the blocks are read with pread, decoded on the device into one ascending run per
+ * input (records outside the window dropped), the runs merged pairwise by merge path, equal k-mers combined, the survivors compacted in
+ * order and handed to the writer's encoder.  No hash table and no sort.  Host memory: 16 bytes per 4096 k-mers and 12 per escape of every
+ * input, plus one window's blocks.  A block that decodes what no writer makes (k-mers that do not ascend, an escape missing from the list, a
+ * count of zero) ends the call in MFX_E_FORMAT.  MFX_DB_TIMING adds read, decode, merge and combine to the writer's split.
+ * stats (may be NULL): the k-mers of all inputs, the k-mers written, the k-mers the operation yields and the filter drops, the sums clamped to
+ * 2^32 - 1, and the windows that held blocks. */
+#define MFX_MERGE_SUM 0        /* union, counts added (saturating at 2^32 - 1) */
+#define MFX_MERGE_MAX 1        /* union, largest count */
+#define MFX_MERGE_MIN 2        /* union, smallest count among the inputs that hold the k-mer */
+#define MFX_MERGE_INTERSECT 3  /* k-mers held by EVERY input, smallest count */
+typedef struct { int op; uint64_t minV, maxV; int device; } mfx_db_merge_opts;
+typedef struct { uint64_t n_in, n_out, n_filtered, n_saturated, windows; } mfx_db_merge_stats;
+int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st /* may be NULL */);
+/* the window plan of mfx_db_merge alone (host only; tests): input i has n[i] k-mers in ceil(n[i] / 4096) blocks whose first k-mers are
+ * first[i][..], ascending.  Row w of out (3 + 2 n_in words, at most cap rows are written): lo, hi, the pairs of its blocks, then per input
+ * the blocks [b0, b1).  *n_windows: the windows of the plan. */
+int mfx_db_merge_plan(const uint64_t *const *first, const uint64_t *n, uint32_t n_in, int k, uint64_t R, uint64_t *out, uint64_t cap, uint64_t *n_windows);
+
 /* ------------------------------------------------------------------------ */
 /* Read k-mer counting: the read counts of a run straight from its reads     */
 /* (FASTA / FASTQ records), no k-mer database in between.                   */

@@ -73,7 +73,7 @@ SYMBOLS = [
     "mfx_last_error", "mfx_last_error_code", "mfx_version", "mfx_device_count", "mfx_device_warm", "mfx_device_memory",
     "mfx_index_create", "mfx_index_free", "mfx_index_estimate_gb", "mfx_index_add_read", "mfx_index_add_asm",
     "mfx_index_count_asm", "mfx_index_build_for_hist", "mfx_index_count_claimed", "mfx_hist_run_parts", "mfx_index_create_for_seq", "mfx_index_create_for_seq_lf", "mfx_index_create_lf", "mfx_db_stage_begin", "mfx_index_build_for_hist_staged", "mfx_index_load_db_staged", "mfx_db_stage_free", "mfx_db_stage_boost", "mfx_index_estimate_gb_for_seq", "mfx_index_claim_seq", "mfx_index_value", "mfx_index_get_info", "mfx_index_export",
-    "mfx_db_probe", "mfx_index_load_db", "mfx_index_load_db_multi", "mfx_db_write_flat", "mfx_db_convert", "mfx_db_convert_placed", "mfx_db_write_flat_placed", "mfx_db_place_keys", "mfx_index_save", "mfx_index_load",
+    "mfx_db_probe", "mfx_index_load_db", "mfx_index_load_db_multi", "mfx_db_write_flat", "mfx_db_convert", "mfx_db_merge", "mfx_db_merge_plan", "mfx_db_convert_placed", "mfx_db_write_flat_placed", "mfx_db_place_keys", "mfx_index_save", "mfx_index_load",
     "mfx_index_set_fingerprint", "mfx_index_get_origin",
     "mfx_host_alloc", "mfx_host_free", "mfx_seq_create", "mfx_hist_run_streamed",
     "mfx_hist_run_streamed_multi", "mfx_hist_run_streamed_range", "mfx_hist_stream_share",
@@ -191,6 +191,8 @@ def load_library():
     L.mfx_db_write_flat.argtypes = [C.c_char_p, C.c_int, u64p, u32p, C.c_uint64]
     L.mfx_db_convert.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
     L.mfx_db_convert_placed.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+    L.mfx_db_merge.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(DbMergeOpts), C.POINTER(DbMergeStats)]
+    L.mfx_db_merge_plan.argtypes = [C.POINTER(u64p), u64p, C.c_uint32, C.c_int, C.c_uint64, u64p, C.c_uint64, u64p]
     L.mfx_db_write_flat_placed.argtypes = [C.c_char_p, C.c_int, u64p, u32p, C.c_uint64]
     L.mfx_db_place_keys.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_int, C.c_int]
     L.mfx_index_load_db_multi.argtypes = [C.POINTER(vp), C.c_uint32, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64]
@@ -441,6 +443,47 @@ def db_convert(in_path, out_path):
     n = C.c_uint64(0)
     _check(load_library().mfx_db_convert(in_path.encode(), out_path.encode(), C.byref(n)))
     return n.value
+
+
+MERGE_OPS = {"sum": 0, "max": 1, "min": 2, "intersect": 3}       # MFX_MERGE_*
+
+
+class DbMergeOpts(C.Structure):
+    _fields_ = [("op", C.c_int), ("minV", C.c_uint64), ("maxV", C.c_uint64), ("device", C.c_int)]
+
+
+class DbMergeStats(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_filtered", C.c_uint64), ("n_saturated", C.c_uint64), ("windows", C.c_uint64)]
+
+
+def db_merge(paths, out_path, op="sum", min_count=0, max_count=2**32 - 1, device=0):
+    """sorted flat databases combined on the GPU, window by window (mfx_db_merge): op "sum", "max", "min" (unions) or "intersect" (or a
+    number, passed on as it is); a k-mer is written iff min_count <= combined count <= max_count.  One path: a filter.  The file is what
+    db_write_flat makes of the result.  Returns the stats: n_in, n_out, n_filtered, n_saturated, windows."""
+    paths = [paths] if isinstance(paths, (str, bytes)) else list(paths)
+    arr = (C.c_char_p * max(1, len(paths)))(*[p.encode() if isinstance(p, str) else p for p in paths])
+    o = DbMergeOpts(MERGE_OPS[op] if isinstance(op, str) else int(op), int(min_count), int(max_count), int(device))
+    st = DbMergeStats()
+    _check(load_library().mfx_db_merge(arr, len(paths), out_path.encode(), C.byref(o), C.byref(st)))
+    return {name: int(getattr(st, name)) for name, _ in DbMergeStats._fields_}
+
+
+def db_merge_plan(firsts, counts, k, R):
+    """the key windows mfx_db_merge cuts for inputs whose blocks start at firsts[i] (ascending uint64, ceil(counts[i] / 4096) of them): a list of
+    (lo, hi, pairs, [(b0, b1) per input]) (mfx_db_merge_plan, host only)"""
+    L = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    n_in = len(firsts)
+    keep = [np.ascontiguousarray(f, dtype=np.uint64) for f in firsts]
+    fp = (u64p * max(1, n_in))(*[f.ctypes.data_as(u64p) for f in keep])
+    n = np.asarray(counts, dtype=np.uint64)
+    nw = C.c_uint64(0)
+    _check(L.mfx_db_merge_plan(fp, n.ctypes.data_as(u64p), n_in, k, R, None, 0, C.byref(nw)))
+    row = 3 + 2 * n_in
+    out = np.zeros(nw.value * row, dtype=np.uint64)
+    _check(L.mfx_db_merge_plan(fp, n.ctypes.data_as(u64p), n_in, k, R, out.ctypes.data_as(u64p), nw.value, C.byref(nw)))
+    out = out.reshape(-1, row)
+    return [(int(r[0]), int(r[1]), int(r[2]), [(int(r[3 + 2 * i]), int(r[4 + 2 * i])) for i in range(n_in)]) for r in out]
 
 
 def db_convert_placed(in_path, out_path):

@@ -38,6 +38,9 @@ struct Globals {
   bool peakGiven = false, devicesGiven = false;
   bool passesGiven = false, passesAuto = false;   // -count -passes P|auto: the k-mers counted in passes over key ranges
   uint32_t passes = 1;
+  std::vector<const char *> mergeNames;  // -merge: no report; these sorted databases combined on the GPU into -output (mfx_db_merge)
+  const char *opName = nullptr;          // -op of -merge: sum (default), max, min, intersect
+  int mergeOp = MFX_MERGE_SUM;
 };
 
 typedef std::vector<std::string> Errors;
@@ -99,9 +102,22 @@ static void usage(const char *exe) {
           exe);
 }
 
+// the entries of -merge and -op: printed behind the text above for a command line that names one of them
+static void usage_merge() {
+  fprintf(stderr,
+          "  Merging k-mer databases (an operation of its own, like -count and -convert):\n"
+          "    -merge db         no report: combine sorted flat databases (what -count and -convert write; one k) on the GPU, window by window,\n"
+          "                      into the sorted flat database -output <file>; repeatable, 1 to 64 inputs (`meryl union-sum` and its kin).\n"
+          "                      Here -min / -max ARE applied, to the combined count: one input and -min 2 drops the singletons.  One device.\n"
+          "    -op o             with -merge: sum (default; saturating at 2^32 - 1), max, min (all three keep every k-mer of any input) or\n"
+          "                      intersect (the k-mers every input holds, with their smallest count)\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
-static int fail_usage(const char *argv0, const Errors &err) {
+static int fail_usage(const char *argv0, const Errors &err, bool merge = false) {
   usage(argv0);
+  if (merge) usage_merge();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -195,6 +211,15 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
     else if (is("-sharded")) G.sharded = true;
     else if (is("-convert")) G.convertName = val();
     else if (is("-count")) G.count = true;
+    else if (is("-merge")) G.mergeNames.push_back(val());
+    else if (is("-op")) {
+      G.opName = val();
+      static const char *const names[] = {"sum", "max", "min", "intersect"};      // MFX_MERGE_*
+      int op = -1;
+      for (int i = 0; i < 4; ++i) if (strcmp(G.opName, names[i]) == 0) op = i;
+      if (op < 0) err.push_back(std::string("Invalid -op '") + G.opName + "': the operations of -merge are sum, max, min and intersect.\n");
+      else G.mergeOp = op;
+    }
     else if (is("-passes")) {
       const char *v = val();
       const int bad = strcmp(v, "auto") == 0 ? UINT_OK : parse_uint(v, 1, 4096, &x);
@@ -247,6 +272,34 @@ static bool devices_available(const std::vector<int> &devs) {
       return false;
     }
   return true;
+}
+
+// -merge: every check before any device is touched (what the inputs hold is checked by mfx_db_merge, before it touches one)
+static void check_merge_flags(const Globals &G, Errors &err) {
+  if (G.mergeNames.empty()) {
+    if (G.opName) err.push_back("-op names the operation of -merge: it has no meaning without -merge.\n");
+    return;
+  }
+  if (G.reportType != OP_NONE) err.push_back("-merge is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
+  if (G.count) err.push_back("-merge and -count are two operations: give one of them.\n");
+  if (G.convertName) err.push_back("-merge and -convert are two operations: give one of them.\n");
+  if (!G.readsNames.empty()) err.push_back("-merge combines databases: it does not take -reads (count them first: -count).\n");
+  if (G.readDBname) err.push_back("-merge takes its databases as -merge <file>: it does not take -readmers.\n");
+  if (G.seqDBname) err.push_back("-merge takes its databases as -merge <file>: it does not take -seqmers.\n");
+  if (G.seqName) err.push_back("-merge evaluates nothing: it does not take -sequence.\n");
+  if (G.vcfName) err.push_back("-merge does not take -vcf (the variant modes do).\n");
+  if (G.peakGiven) err.push_back("-merge evaluates nothing: it does not take -peak.\n");
+  if (G.sharded) err.push_back("-merge does not take -sharded: the windows it merges live on one device.\n");
+  if (G.indexName) err.push_back("-merge does not take -index: it writes a database, not a table image.\n");
+  if (G.placed) err.push_back("-merge writes k-mer-sorted databases: it does not take -placed (convert the result: -convert -placed).\n");
+  if (G.passesGiven) err.push_back("-passes divides the work of -count: -merge does not take it (MFX_MERGE_RANGE sizes its windows).\n");
+  if (G.devices.size() > 1) err.push_back("-merge runs on one device (-device d, or -devices naming one).\n");
+  if (!G.outName) err.push_back("-merge writes a k-mer database: give -output <file>.\n");
+  if (G.mergeNames.size() > 64) err.push_back("-merge takes 1 to 64 databases (here " + std::to_string(G.mergeNames.size()) + "): merge them in groups.\n");
+  for (const char *f : G.mergeNames) {
+    struct stat mst;
+    if (stat(f, &mst) != 0 || access(f, R_OK) != 0) err.push_back(std::string("Cannot read the -merge database '") + f + "'.\n");
+  }
 }
 
 // -count: every check before any device is touched (the checks of a report from -reads below do not apply to it)

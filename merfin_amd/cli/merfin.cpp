@@ -1028,6 +1028,27 @@ static int run_convert(const Globals &G) {
   return 0;
 }
 
+// merfin -merge a -merge b ... -output <file>: sorted flat databases combined on the GPU window by window (mfx_db_merge); -min / -max act on
+// the combined count
+static int run_merge(Globals &G) {
+  if (!G.devices.empty()) G.device = G.devices[0];
+  if (!devices_available({G.device})) return 1;
+  static const char *const names[] = {"sum", "max", "min", "intersect"};
+  fprintf(stderr, "-- Merging %lu database%s (%s) into '%s'.\n", (unsigned long)G.mergeNames.size(), G.mergeNames.size() == 1 ? "" : "s", names[G.mergeOp], G.outName);
+  mfx_db_merge_opts o;
+  o.op = G.mergeOp;
+  o.minV = G.minV;
+  o.maxV = G.maxV;
+  o.device = G.device;
+  mfx_db_merge_stats st;
+  if (mfx_db_merge(G.mergeNames.data(), (uint32_t)G.mergeNames.size(), G.outName, &o, &st)) DIE_MFX("-merge");
+  fprintf(stderr, "-- Merged: %lu k-mers read, %lu written, %lu filtered, %lu saturated, %lu window%s.\n", (unsigned long)st.n_in, (unsigned long)st.n_out,
+          (unsigned long)st.n_filtered, (unsigned long)st.n_saturated, (unsigned long)st.windows, st.windows == 1 ? "" : "s");
+  print_wrote(G.outName, st.n_out);
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
 // ---- the run of a report: what its steps share ------------------------------------------------------------------------------------------
 static double epoch() { return std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count(); }
 
@@ -1819,6 +1840,8 @@ int main(int argc, char **argv) {
   Errors err;
   // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
   parse_args(argc, argv, G, err);
+  check_merge_flags(G, err);
+  if (!G.mergeNames.empty() || G.opName) return err.empty() ? run_merge(G) : fail_usage(argv[0], err, true);
   check_count_flags(G, err);
   if (G.count) return err.empty() ? run_count(G) : fail_usage(argv[0], err);
   if (!check_reads_flags(G, err)) return 1;

@@ -17,6 +17,7 @@
 #include "mfx_internal.h"
 #include "mfx_kernels.h"
 #include "mfx_grow.h"
+#include "mfx_merge.h"
 #include "mfx_pipe.h"
 #include "mfx_place.h"
 
@@ -1524,6 +1525,8 @@ struct mfx_db_writer {
   uint64_t last = 0;                                           // the last k-mer appended (n > 0)
   size_t bounce = 16u << 20;                                   // bytes of one pinned bounce buffer (MFX_DB_BOUNCE, read at open)
   double t_export = 0, t_sort = 0, t_plan = 0, t_pack = 0, t_copy = 0, t_spool = 0;      // MFX_DB_TIMING
+  bool merging = false;                                        // mfx_db_merge's writer: its split has these in the place of export and sort
+  double t_read = 0, t_decode = 0, t_merge = 0, t_combine = 0;
   ~mfx_db_writer() {
     if (fd >= 0) close(fd);
     if (streamed && !spool.empty()) unlink(spool.c_str());
@@ -1652,8 +1655,118 @@ static int spool_from_device(mfx_db_writer *w, DbBounce &B, const char *src, uin
   return MFX_OK;
 }
 
-// the device part of the streamed kind: per key range export and sort as below, the sort's output behind the carry; the full blocks are
-// planned and packed on the device (mfx_sort.hip) and reach the spool through the bounce buffers; what is left is the next carry
+namespace {
+// what stream_append_device needs beside the pairs, for appends of at most `cap` pairs (the carry in front of them counted): plan and offsets
+// of the blocks on the device and on the host, the escapes' buffers (grown to what an append escapes), the bounce buffers
+struct StreamDev {
+  DbDev D;                                                     // p[0]: plan and offsets of the blocks; p[1], p[2]: the escapes' k-mers and counts
+  DbBounce B;
+  uint64_t cap = 0, maxb = 0, esc_cap = 0;
+  std::vector<mfx_delta_plan> plan;
+  std::vector<uint64_t> woff;
+  std::vector<uint32_t> eoff;
+};
+}  // namespace
+
+static int stream_dev_init(StreamDev &S, const mfx_db_writer *w, uint64_t cap, const char *who, const char *knob) {
+  S.cap = cap;
+  S.maxb = cap / MFX_DELTA_BLOCK;
+  if (hipMalloc(&S.D.p[0], (S.maxb ? S.maxb : 1) * (sizeof(mfx_delta_plan) + 8 + 4)) != hipSuccess) {
+    (void)hipGetLastError();
+    return mfx_fail(MFX_E_NOMEM, "%s: the block plan of %lu k-mers does not fit the device; lower %s", who, (unsigned long)cap, knob);
+  }
+  for (int i = 0; i < 2; ++i) {
+    MFX_HIP(hipHostMalloc(&S.B.pin[i], w->bounce, hipHostMallocDefault));
+    MFX_HIP(hipEventCreateWithFlags(&S.B.ev[i], hipEventDisableTiming));
+  }
+  return MFX_OK;
+}
+
+// Ascending pairs on the device behind what a streamed writer holds: rn > 0 pairs stand at s_keys + c and s_vals + c, c the pairs of the
+// writer's carry (w->ck.size() when the arrays were filled), c + rn <= S.cap.  The carry is uploaded in front of them, the full blocks are
+// planned and packed on the device (mfx_sort.hip) into d_out (out_bytes of it; 12 bytes a pair hold any block) and reach the spool through
+// the bounce buffers; what is left is the next carry.  The first k-mer must lie above the writer's last.  A failure adds nothing.
+static int stream_append_device(mfx_db_writer *w, StreamDev &S, uint64_t *s_keys, uint32_t *s_vals, uint64_t rn, uint64_t *d_out, uint64_t out_bytes,
+                                const char *who, const char *knob) {
+  StreamUndo undo(w);
+  const uint64_t c = w->ck.size(), m = c + rn, nb = m / MFX_DELTA_BLOCK, rem = m % MFX_DELTA_BLOCK;
+  if (rn == 0 || m > S.cap) return mfx_fail(MFX_E_INVAL, "%s: an append of %lu pairs behind a carry of %lu (buffers for %lu)", who, (unsigned long)rn, (unsigned long)c, (unsigned long)S.cap);
+  if (c) {
+    MFX_HIP(hipMemcpyAsync(s_keys, w->ck.data(), c * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
+    MFX_HIP(hipMemcpyAsync(s_vals, w->cv.data(), c * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+  }
+  uint64_t ends[2] = {0, 0};                                   // the first and the last k-mer appended
+  MFX_HIP(hipMemcpyAsync(&ends[0], s_keys + c, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+  MFX_HIP(hipMemcpyAsync(&ends[1], s_keys + m - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+  MFX_HIP(hipStreamSynchronize(nullptr));
+  double t0 = db_now(), t1;
+  if (w->n != 0 && ends[0] <= w->last)
+    return mfx_fail(MFX_E_INVAL, "%s: the appended k-mers start at %llu, not above the writer's last k-mer %llu: tables are appended in ascending key order, "
+                    "their key ranges apart", who, (unsigned long long)ends[0], (unsigned long long)w->last);
+  mfx_delta_plan *d_plan = (mfx_delta_plan *)S.D.p[0];
+  uint64_t *d_woff = (uint64_t *)(d_plan + S.maxb);
+  uint32_t *d_eoff = (uint32_t *)(d_woff + S.maxb);
+  if (nb) {
+    MFX_HIP(mfx_k_delta_plan(s_keys, s_vals, (uint32_t)nb, d_plan, nullptr));
+    S.plan.resize(nb);
+    MFX_HIP(hipMemcpy(S.plan.data(), d_plan, nb * sizeof(mfx_delta_plan), hipMemcpyDeviceToHost));
+    S.woff.resize(nb);
+    S.eoff.resize(nb);
+    uint64_t words = 0, escapes = 0;
+    for (uint64_t b = 0; b < nb; ++b) {                        // the plain scan: where every block's words and escapes start
+      const uint32_t kb = S.plan[b].widths & 0xffu, vb = S.plan[b].widths >> 8;
+      S.woff[b] = words;
+      S.eoff[b] = (uint32_t)escapes;
+      w->dir.push_back(S.plan[b].first);
+      w->dir.push_back((w->spool_bytes + words * 8) | ((uint64_t)kb << 48) | ((uint64_t)vb << 56));
+      words += mfx_delta_bytes(MFX_DELTA_BLOCK, kb, vb) / 8;
+      escapes += S.plan[b].nesc;
+    }
+    if (words * 8 > out_bytes || escapes > m) return mfx_fail(MFX_E_HIP, "%s: the block plan of a key range is damaged", who);      // (nothing is packed beyond the buffers)
+    if (escapes > S.esc_cap) {
+      for (int i = 1; i < 3; ++i) if (S.D.p[i]) { (void)hipFree(S.D.p[i]); S.D.p[i] = nullptr; }
+      S.esc_cap = 0;
+      hipError_t ee = hipMalloc(&S.D.p[1], escapes * sizeof(uint64_t));
+      if (ee == hipSuccess) ee = hipMalloc(&S.D.p[2], escapes * sizeof(uint32_t));
+      if (ee != hipSuccess) {
+        (void)hipGetLastError();
+        return mfx_fail(MFX_E_NOMEM, "%s: the %lu escapes of a key range do not fit the device: %s; lower %s", who, (unsigned long)escapes, hipGetErrorString(ee), knob);
+      }
+      S.esc_cap = escapes;
+    }
+    MFX_HIP(hipMemcpyAsync(d_woff, S.woff.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
+    MFX_HIP(hipMemcpyAsync(d_eoff, S.eoff.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+    t1 = db_now();
+    w->t_plan += t1 - t0;
+    MFX_HIP(mfx_k_delta_pack(s_keys, s_vals, (uint32_t)nb, d_plan, d_woff, d_eoff, d_out, (uint64_t *)S.D.p[1], (uint32_t *)S.D.p[2], nullptr));
+    MFX_HIP(hipStreamSynchronize(nullptr));                    // (woff / eoff are pageable: their copies are done before the next append changes them)
+    t0 = db_now();
+    w->t_pack += t0 - t1;
+    if (int rc = spool_from_device(w, S.B, (const char *)d_out, words * 8, w->t_copy, w->t_spool)) return rc;
+    if (escapes) {
+      const size_t held = w->ek.size();
+      w->ek.resize(held + escapes);
+      w->ev.resize(held + escapes);
+      MFX_HIP(hipMemcpy(w->ek.data() + held, S.D.p[1], escapes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      MFX_HIP(hipMemcpy(w->ev.data() + held, S.D.p[2], escapes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+  }
+  w->ck.resize(rem);
+  w->cv.resize(rem);
+  if (rem && nb) {                                             // (no block made: the carry only grew, by what stands behind it)
+    MFX_HIP(hipMemcpy(w->ck.data(), s_keys + nb * MFX_DELTA_BLOCK, rem * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    MFX_HIP(hipMemcpy(w->cv.data(), s_vals + nb * MFX_DELTA_BLOCK, rem * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  } else if (rem) {
+    MFX_HIP(hipMemcpy(w->ck.data() + c, s_keys + c, rn * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    MFX_HIP(hipMemcpy(w->cv.data() + c, s_vals + c, rn * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  w->n += rn;
+  w->last = ends[1];
+  undo.keep = true;
+  return MFX_OK;
+}
+
+// the device part of the streamed kind: per key range export and sort as below, the sort's output behind the carry, then stream_append_device
 static int db_append_index_streamed(mfx_db_writer *w, const mfx_index *ix, int side, uint64_t *n_added, const char *who) {
   if (n_added) *n_added = 0;
   if (int rc = db_side_checks(ix, side, who)) return rc;
@@ -1681,15 +1794,14 @@ static int db_append_index_streamed(mfx_db_writer *w, const mfx_index *ix, int s
   if (n == 0) return MFX_OK;
   StreamUndo undo(w);
   // cap pairs: a range behind a carry.  p[1]: the export's k-mers, then its counts -- 12 bytes a pair, free again after the sort: a block
-  // takes at most (62 + 22) bits a pair, so the packed words go there.  p[2], p[4]: the sorted pairs.  p[3]: plan and offsets of the blocks.
-  const uint64_t cap = maxn + MFX_DELTA_BLOCK - 1, maxb = cap / MFX_DELTA_BLOCK;
+  // takes at most (62 + 22) bits a pair, so the packed words go there.  p[2], p[4]: the sorted pairs.
+  const uint64_t cap = maxn + MFX_DELTA_BLOCK - 1;
   size_t tmp_bytes = 0;
   if (int rc = mfx_sort_db_pairs(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, maxn, key_bits, nullptr)) return rc;
   hipError_t e = hipMalloc(&D.p[1], cap * 12);
   if (e == hipSuccess) e = hipMalloc(&D.p[2], cap * sizeof(uint64_t));
   if (e == hipSuccess) e = hipMalloc(&D.p[4], cap * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&D.p[5], tmp_bytes ? tmp_bytes : 1);
-  if (e == hipSuccess) e = hipMalloc(&D.p[3], (maxb ? maxb : 1) * (sizeof(mfx_delta_plan) + 8 + 4));
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a key range of %lu k-mers (%.3f GB) do not fit the device: %s; lower MFX_WRITE_DB_RANGE", who,
@@ -1697,21 +1809,8 @@ static int db_append_index_streamed(mfx_db_writer *w, const mfx_index *ix, int s
   }
   uint64_t *x_keys = (uint64_t *)D.p[1], *s_keys = (uint64_t *)D.p[2], *d_out = (uint64_t *)D.p[1];
   uint32_t *x_vals = (uint32_t *)((char *)D.p[1] + cap * 8), *s_vals = (uint32_t *)D.p[4];
-  mfx_delta_plan *d_plan = (mfx_delta_plan *)D.p[3];
-  uint64_t *d_woff = (uint64_t *)(d_plan + maxb);
-  uint32_t *d_eoff = (uint32_t *)(d_woff + maxb);
-  uint64_t esc_cap = 0;                                        // pairs p[6] (k-mers) and p[7] (counts) hold: grown to what a range escapes
-  DbBounce B;
-  for (int i = 0; i < 2; ++i) {
-    MFX_HIP(hipHostMalloc(&B.pin[i], w->bounce, hipHostMallocDefault));
-    MFX_HIP(hipEventCreateWithFlags(&B.ev[i], hipEventDisableTiming));
-  }
-  std::vector<mfx_delta_plan> plan;
-  std::vector<uint64_t> woff;
-  std::vector<uint32_t> eoff;
-  const bool had = w->n != 0;
-  const uint64_t before = w->last;
-  bool first = true;
+  StreamDev S;
+  if (int rc = stream_dev_init(S, w, cap, who, "MFX_WRITE_DB_RANGE")) return rc;
   for (const auto &r : ranges) {
     double t0 = db_now();
     MFX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), nullptr));
@@ -1725,78 +1824,11 @@ static int db_append_index_streamed(mfx_db_writer *w, const mfx_index *ix, int s
     double t1 = db_now();
     w->t_export += t1 - t0;
     if (r.n == 0) continue;
-    const uint64_t c = w->ck.size(), m = c + r.n, nb = m / MFX_DELTA_BLOCK, rem = m % MFX_DELTA_BLOCK;      // m <= cap: c < MFX_DELTA_BLOCK, r.n <= maxn
-    if (c) {
-      MFX_HIP(hipMemcpyAsync(s_keys, w->ck.data(), c * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
-      MFX_HIP(hipMemcpyAsync(s_vals, w->cv.data(), c * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
-    }
+    const uint64_t c = w->ck.size();                             // c + r.n <= cap: c < MFX_DELTA_BLOCK, r.n <= maxn
     if (int rc = mfx_sort_db_pairs(D.p[5], tmp_bytes, x_keys, s_keys + c, x_vals, s_vals + c, r.n, key_bits, nullptr)) return rc;
-    uint64_t ends[2] = {0, 0};                                   // the range's first and last k-mer
-    MFX_HIP(hipMemcpyAsync(&ends[0], s_keys + c, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
-    MFX_HIP(hipMemcpyAsync(&ends[1], s_keys + m - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
     MFX_HIP(hipStreamSynchronize(nullptr));
-    t0 = db_now();
-    w->t_sort += t0 - t1;
-    if (first && had && ends[0] <= before)
-      return mfx_fail(MFX_E_INVAL, "%s: the appended k-mers start at %llu, not above the writer's last k-mer %llu: tables are appended in ascending key order, "
-                      "their key ranges apart", who, (unsigned long long)ends[0], (unsigned long long)before);
-    first = false;
-    if (nb) {
-      MFX_HIP(mfx_k_delta_plan(s_keys, s_vals, (uint32_t)nb, d_plan, nullptr));
-      plan.resize(nb);
-      MFX_HIP(hipMemcpy(plan.data(), d_plan, nb * sizeof(mfx_delta_plan), hipMemcpyDeviceToHost));
-      woff.resize(nb);
-      eoff.resize(nb);
-      uint64_t words = 0, escapes = 0;
-      for (uint64_t b = 0; b < nb; ++b) {                      // the plain scan: where every block's words and escapes start
-        const uint32_t kb = plan[b].widths & 0xffu, vb = plan[b].widths >> 8;
-        woff[b] = words;
-        eoff[b] = (uint32_t)escapes;
-        w->dir.push_back(plan[b].first);
-        w->dir.push_back((w->spool_bytes + words * 8) | ((uint64_t)kb << 48) | ((uint64_t)vb << 56));
-        words += mfx_delta_bytes(MFX_DELTA_BLOCK, kb, vb) / 8;
-        escapes += plan[b].nesc;
-      }
-      if (words * 8 > cap * 12 || escapes > m) return mfx_fail(MFX_E_HIP, "%s: the block plan of a key range is damaged", who);      // (nothing is packed beyond the buffers)
-      if (escapes > esc_cap) {
-        for (int i = 6; i < 8; ++i) if (D.p[i]) { (void)hipFree(D.p[i]); D.p[i] = nullptr; }
-        hipError_t ee = hipMalloc(&D.p[6], escapes * sizeof(uint64_t));
-        if (ee == hipSuccess) ee = hipMalloc(&D.p[7], escapes * sizeof(uint32_t));
-        if (ee != hipSuccess) {
-          (void)hipGetLastError();
-          return mfx_fail(MFX_E_NOMEM, "%s: the %lu escapes of a key range do not fit the device: %s; lower MFX_WRITE_DB_RANGE", who, (unsigned long)escapes,
-                          hipGetErrorString(ee));
-        }
-        esc_cap = escapes;
-      }
-      MFX_HIP(hipMemcpyAsync(d_woff, woff.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr));
-      MFX_HIP(hipMemcpyAsync(d_eoff, eoff.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
-      t1 = db_now();
-      w->t_plan += t1 - t0;
-      MFX_HIP(mfx_k_delta_pack(s_keys, s_vals, (uint32_t)nb, d_plan, d_woff, d_eoff, d_out, (uint64_t *)D.p[6], (uint32_t *)D.p[7], nullptr));
-      MFX_HIP(hipStreamSynchronize(nullptr));                  // (woff / eoff are pageable: their copies are done before the next range changes them)
-      t0 = db_now();
-      w->t_pack += t0 - t1;
-      if (int rc = spool_from_device(w, B, (const char *)d_out, words * 8, w->t_copy, w->t_spool)) return rc;
-      if (escapes) {
-        const size_t held = w->ek.size();
-        w->ek.resize(held + escapes);
-        w->ev.resize(held + escapes);
-        MFX_HIP(hipMemcpy(w->ek.data() + held, D.p[6], escapes * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        MFX_HIP(hipMemcpy(w->ev.data() + held, D.p[7], escapes * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      }
-    }
-    w->ck.resize(rem);
-    w->cv.resize(rem);
-    if (rem && nb) {                                           // (no block made: the carry only grew, by what the sort put behind it)
-      MFX_HIP(hipMemcpy(w->ck.data(), s_keys + nb * MFX_DELTA_BLOCK, rem * sizeof(uint64_t), hipMemcpyDeviceToHost));
-      MFX_HIP(hipMemcpy(w->cv.data(), s_vals + nb * MFX_DELTA_BLOCK, rem * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    } else if (rem) {
-      MFX_HIP(hipMemcpy(w->ck.data() + c, s_keys + c, r.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-      MFX_HIP(hipMemcpy(w->cv.data() + c, s_vals + c, r.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    w->n += r.n;
-    w->last = ends[1];
+    w->t_sort += db_now() - t1;
+    if (int rc = stream_append_device(w, S, s_keys, s_vals, r.n, d_out, cap * 12, who, "MFX_WRITE_DB_RANGE")) return rc;
   }
   undo.keep = true;
   if (n_added) *n_added = n;
@@ -2017,7 +2049,11 @@ static int db_close_streamed(mfx_db_writer *w) {
   }
   if (fclose(f) != 0 && rc == MFX_OK) rc = mfx_fail(MFX_E_IO, "short write to '%s'", path);
   if (rc != MFX_OK) unlink(path);
-  if (getenv("MFX_DB_TIMING"))
+  if (getenv("MFX_DB_TIMING") && w->merging)
+    fprintf(stderr, "[mfx db] merge: read %.2f s, decode %.2f s, merge %.2f s, combine %.2f s, plan %.2f s, pack %.2f s, copy %.2f s, spool write %.2f s, close %.2f s "
+            "(%lu blocks, %lu escapes)\n", w->t_read, w->t_decode, w->t_merge, w->t_combine, w->t_plan, w->t_pack, w->t_copy, w->t_spool, db_now() - t0,
+            (unsigned long)nblocks, (unsigned long)w->ek.size());
+  else if (getenv("MFX_DB_TIMING"))
     fprintf(stderr, "[mfx db] streamed writer: export %.2f s, sort %.2f s, plan %.2f s, pack %.2f s, copy %.2f s, spool write %.2f s, close %.2f s (%lu blocks, "
             "%lu escapes)\n", w->t_export, w->t_sort, w->t_plan, w->t_pack, w->t_copy, w->t_spool, db_now() - t0, (unsigned long)nblocks, (unsigned long)w->ek.size());
   return rc;
@@ -2065,6 +2101,310 @@ extern "C" int mfx_index_write_db(const mfx_index *ix, int side, const char *pat
   try { return mfx_index_write_db_impl(ix, side, path, n_kmers); }                     // (nothing leaves the C ABI as an exception)
   catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_index_write_db: out of memory (12 bytes of host memory per k-mer written)"); }
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_index_write_db: %s", e.what()); }
+}
+
+
+// ---------------------------------------------------------------------------
+// mfx_db_merge: sorted, delta-coded databases combined window by window (include/merfin_amd.h; the windows: mfx_merge.h; the kernels:
+// mfx_merge.hip).  file blocks -> ascending runs on the device -> merged and combined -> stream_append_device; no table in between.
+// ---------------------------------------------------------------------------
+static_assert(MFX_MERGE_BLOCK == MFX_DELTA_BLOCK, "mfx_merge.h plans in blocks of the delta form");
+
+namespace {
+struct MergeIn {                                               // one input: header, directory and escapes on the host, the blocks in the file
+  std::string path;
+  int fd = -1;
+  FlatHeader h;
+  std::vector<uint64_t> dir;
+  uint64_t nblocks = 0;
+  std::vector<uint64_t> ek;
+  std::vector<uint32_t> ev;
+  MergeIn() = default;
+  MergeIn(const MergeIn &) = delete;
+  MergeIn &operator=(const MergeIn &) = delete;
+  ~MergeIn() { if (fd >= 0) close(fd); }
+  uint64_t off(uint64_t b) const { return dir[2 * b + 1] & 0xffffffffffffull; }
+};
+struct WriterAbort {                                           // the writer of a call that does not reach close: the spool goes with it
+  mfx_db_writer *w = nullptr;
+  ~WriterAbort() { if (w) mfx_db_writer_abort(w); }
+};
+}  // namespace
+
+// header, directory and escape list of an input, by the loader's checks; every refusal names the file
+static int merge_open_input(const char *path, MergeIn &in) {
+  in.path = path;
+  const int fmt = detect(in.path);
+  if (!fmt) return mfx_fail(MFX_E_IO, "mfx_db_merge: the input '%s' does not exist", path);
+  if (fmt == MFX_DB_MERYL) return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a meryl directory; the inputs are sorted flat databases: run `merfin -convert` first", path);
+  if (fmt == MFX_DB_TEXT) return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is not a flat k-mer file (`meryl print` text?); the inputs are sorted flat databases: run `merfin -convert` first", path);
+  in.fd = open(path, O_RDONLY | O_CLOEXEC);
+  struct stat st;
+  if (in.fd < 0 || fstat(in.fd, &st) != 0) return mfx_fail(MFX_E_IO, "cannot open '%s'", path);
+  const uint64_t fsize = (uint64_t)st.st_size;
+  if (fsize < sizeof(in.h) || pread(in.fd, &in.h, sizeof(in.h), 0) != (ssize_t)sizeof(in.h)) return mfx_fail(MFX_E_FORMAT, "'%s': truncated header", path);
+  if (const char *why = flat_header_problem(in.h, fsize)) return mfx_fail(MFX_E_FORMAT, "'%s': %s", path, why);
+  if (in.h.flags & FLAT_PLACED)
+    return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a placed database; the inputs are sorted by k-mer: merge those, then place the result (merfin -convert -placed)", path);
+  if (in.h.n == 0) return MFX_OK;                               // (no k-mers: what mfx_db_write_flat writes for none has no blocks in any form)
+  if (!(in.h.flags & FLAT_DELTA))
+    return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a %s flat file, not a sorted one: run `merfin -convert` first", path, (in.h.flags & FLAT_PACKED) ? "packed" : "plain");
+  uint64_t expect = 0;
+  if (int rc = read_delta_directory(in.fd, path, in.h, fsize, in.dir, &in.nblocks, &expect)) return rc;
+  const uint64_t ne = in.h.n_escape;
+  try { in.ek.resize(ne); in.ev.resize(ne); }
+  catch (const std::exception &) { return mfx_fail(MFX_E_NOMEM, "'%s': no memory for %lu escapes", path, (unsigned long)ne); }
+  if (ne && (pread(in.fd, in.ek.data(), ne * 8, (off_t)expect) != (ssize_t)(ne * 8) || pread(in.fd, in.ev.data(), ne * 4, (off_t)(expect + ne * 8)) != (ssize_t)(ne * 4)))
+    return mfx_fail(MFX_E_IO, "reading '%s' failed", path);
+  for (uint64_t i = 0; i < ne; ++i) {
+    if (!flat_key_fits(in.ek[i], in.h.k)) return mfx_fail(MFX_E_FORMAT, "'%s': an escaped k-mer is wider than 2k bits", path);
+    if (i && in.ek[i] <= in.ek[i - 1]) return mfx_fail(MFX_E_FORMAT, "'%s': the escape list of a sorted database does not ascend", path);
+  }
+  return MFX_OK;
+}
+
+// every check of mfx_db_merge that needs no device: the arguments, the inputs (opened into `ins`), their k, the output's identity
+static int merge_check(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, std::vector<std::unique_ptr<MergeIn>> &ins) {
+  if (!in_paths || !out_path || !o) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: null argument");
+  if (n_in == 0 || n_in > MFX_MERGE_MAX_INPUTS) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: %u inputs (1 to %u)", n_in, MFX_MERGE_MAX_INPUTS);
+  if (o->op != MFX_MERGE_SUM && o->op != MFX_MERGE_MAX && o->op != MFX_MERGE_MIN && o->op != MFX_MERGE_INTERSECT)
+    return mfx_fail(MFX_E_INVAL, "mfx_db_merge: unknown operation %d (MFX_MERGE_SUM, _MAX, _MIN, _INTERSECT)", o->op);
+  if (o->minV > o->maxV) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: the filter keeps nothing (min %llu > max %llu)", (unsigned long long)o->minV, (unsigned long long)o->maxV);
+  for (uint32_t i = 0; i < n_in; ++i) {
+    if (!in_paths[i]) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: null argument");
+    ins.emplace_back(new MergeIn);
+    if (int rc = merge_open_input(in_paths[i], *ins.back())) return rc;
+    if (ins[i]->h.k != ins[0]->h.k)
+      return mfx_fail(MFX_E_INVAL, "mfx_db_merge: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", in_paths[i], ins[i]->h.k, in_paths[0], ins[0]->h.k);
+  }
+  struct stat so;
+  if (stat(out_path, &so) == 0)
+    for (uint32_t i = 0; i < n_in; ++i) {
+      struct stat si;
+      if (fstat(ins[i]->fd, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)
+        return mfx_fail(MFX_E_INVAL, "mfx_db_merge: the output '%s' is the input '%s'", out_path, in_paths[i]);
+    }
+  return MFX_OK;
+}
+
+static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
+  const char *who = "mfx_db_merge";
+  if (st) memset(st, 0, sizeof(*st));
+  std::vector<std::unique_ptr<MergeIn>> ins;
+  if (int rc = merge_check(in_paths, n_in, out_path, o, ins)) return rc;
+  const int k = (int)ins[0]->h.k;
+  const uint64_t END = mfx_merge_end(k);
+  uint64_t R = MFX_MERGE_RANGE_DEFAULT;
+  if (const char *e = getenv("MFX_MERGE_RANGE")) {             // read per call: tests reach many windows on small files
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
+  }
+  // ---- the windows, and what the largest of them takes
+  std::vector<mfx_merge_input> pin(n_in);
+  uint64_t n_all = 0;
+  for (uint32_t i = 0; i < n_in; ++i) { pin[i] = mfx_merge_input{ins[i]->dir.data(), 2u, ins[i]->nblocks, ins[i]->h.n}; n_all += ins[i]->h.n; }
+  std::vector<mfx_merge_window> win;
+  std::vector<uint64_t> blk;
+  mfx_merge_plan(pin.data(), n_in, k, R, win, blk);
+  uint64_t max_pairs = 0, max_bytes = 0, max_tasks = 0, max_esc = 0;
+  for (size_t w = 0; w < win.size(); ++w) {
+    uint64_t bytes = 0, tasks = 0, esc = 0;
+    for (uint32_t i = 0; i < n_in; ++i) {
+      const uint64_t b0 = blk[2 * (w * n_in + i)], b1 = blk[2 * (w * n_in + i) + 1];
+      if (b1 <= b0) continue;
+      bytes += ins[i]->off(b1) - ins[i]->off(b0);
+      tasks += b1 - b0;
+      uint64_t e0, e1;
+      mfx_merge_escape_slice(ins[i]->ek.data(), ins[i]->ek.size(), win[w].lo, win[w].hi, &e0, &e1);
+      esc += e1 - e0;
+    }
+    max_pairs = std::max(max_pairs, win[w].pairs); max_bytes = std::max(max_bytes, bytes);
+    max_tasks = std::max(max_tasks, tasks); max_esc = std::max(max_esc, esc);
+  }
+  if (max_pairs > 0x7fffffffull || max_esc > 0x7fffffffull) return mfx_fail(MFX_E_INVAL, "%s: a window of %lu pairs (at most 2^31 - 1); lower MFX_MERGE_RANGE", who, (unsigned long)max_pairs);
+  mfx_db_writer *w = nullptr;
+  if (int rc = db_open_streamed(out_path, k, &w)) return rc;
+  WriterAbort guard{w};
+  w->merging = true;
+  if (max_pairs) {
+    DeviceBack back;
+    MFX_HIP(hipSetDevice(o->device));
+    // p[0], p[1]: two buffers of cap pairs, the k-mers in front of the counts: decoded runs, merge levels, combined pairs behind the writer's carry,
+    // and the packed words of the one that is free by then.  p[2]: the window's blocks.  p[3]: tasks, their below / above, the inputs' error words,
+    // the stats, the combine's tile offsets.  p[4], p[5]: the window's escapes.
+    const uint64_t cap = max_pairs + MFX_DELTA_BLOCK, tiles = mfx_combine_tiles(max_pairs);
+    const uint64_t small = max_tasks * (sizeof(mfx_merge_task) + 8) + (tiles + 1 + 2) * 8 + n_in * 4 + 64;
+    DbDev D;
+    hipError_t e = hipMalloc(&D.p[0], cap * 12);
+    if (e == hipSuccess) e = hipMalloc(&D.p[1], cap * 12);
+    if (e == hipSuccess) e = hipMalloc(&D.p[2], max_bytes + 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[3], small);
+    if (e == hipSuccess) e = hipMalloc(&D.p[4], (max_esc + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[5], (max_esc + 1) * 4);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who, (unsigned long)max_pairs,
+                      ((double)cap * 24 + (double)max_bytes + (double)max_esc * 12 + (double)small) / 1e9, hipGetErrorString(e));
+    }
+    uint64_t *bk[2] = {(uint64_t *)D.p[0], (uint64_t *)D.p[1]};
+    uint32_t *bv[2] = {(uint32_t *)((char *)D.p[0] + cap * 8), (uint32_t *)((char *)D.p[1] + cap * 8)};
+    uint64_t *d_tile = (uint64_t *)D.p[3], *d_stats = d_tile + tiles + 1;
+    mfx_merge_task *d_tasks = (mfx_merge_task *)(d_stats + 2);
+    uint32_t *d_below = (uint32_t *)(d_tasks + max_tasks), *d_above = d_below + max_tasks, *d_err = d_above + max_tasks;
+    MFX_HIP(mfx_memset_now(d_stats, 0, 16));
+    StreamDev S;
+    if (int rc = stream_dev_init(S, w, cap, who, "MFX_MERGE_RANGE")) return rc;
+    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
+    std::vector<mfx_merge_task> tasks;
+    struct Pinned { void *p = nullptr; ~Pinned() { if (p) (void)hipHostFree(p); } } pinned;      // the window's blocks on their way from the files to the device
+    MFX_HIP(hipHostMalloc(&pinned.p, max_bytes + 8, hipHostMallocDefault));
+    uint64_t *words = (uint64_t *)pinned.p;
+    std::vector<uint64_t> hek, run_off(n_in), run_len(n_in), first_task(n_in);
+    std::vector<uint32_t> hev, cnt, errs(n_in);
+    struct Run { uint64_t off, len; };
+    std::vector<Run> runs, next;
+    for (size_t wi = 0; wi < win.size(); ++wi) {
+      if (win[wi].pairs == 0) continue;
+      const uint64_t lo = win[wi].lo, hi = win[wi].hi;
+      double t0 = db_now();
+      // ---- the window's blocks and escapes, input after input
+      tasks.clear(); hek.clear(); hev.clear();
+      uint64_t nwords = 0, npairs = 0;
+      for (uint32_t i = 0; i < n_in; ++i) {
+        const MergeIn &in = *ins[i];
+        const uint64_t b0 = blk[2 * (wi * n_in + i)], b1 = blk[2 * (wi * n_in + i) + 1];
+        run_off[i] = npairs; run_len[i] = 0; first_task[i] = tasks.size();
+        if (b1 <= b0) continue;
+        const uint64_t from = in.off(b0), bytes = in.off(b1) - from;
+        if ((nwords * 8 + bytes) > max_bytes) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is read beyond the buffer)
+        for (uint64_t got = 0; got < bytes;) {
+          const ssize_t r = pread(in.fd, (char *)(words + nwords) + got, bytes - got, (off_t)(from + got));
+          if (r <= 0) return mfx_fail(MFX_E_IO, "reading '%s' failed", in.path.c_str());
+          got += (uint64_t)r;
+        }
+        uint64_t e0, e1;
+        mfx_merge_escape_slice(in.ek.data(), in.ek.size(), lo, hi, &e0, &e1);
+        const uint32_t esc_lo = (uint32_t)hek.size(), esc_hi = esc_lo + (uint32_t)(e1 - e0);
+        hek.insert(hek.end(), in.ek.begin() + e0, in.ek.begin() + e1);
+        hev.insert(hev.end(), in.ev.begin() + e0, in.ev.begin() + e1);
+        for (uint64_t b = b0; b < b1; ++b) {
+          mfx_merge_task t;
+          t.word_off = nwords + (in.off(b) - from) / 8;
+          t.first = in.dir[2 * b];
+          t.limit = b + 1 < in.nblocks ? in.dir[2 * (b + 1)] : END;
+          t.out = npairs + (b - b0) * MFX_DELTA_BLOCK;
+          t.kb = (uint32_t)(in.dir[2 * b + 1] >> 48) & 0xffu;
+          t.vb = (uint32_t)(in.dir[2 * b + 1] >> 56) & 0xffu;
+          t.cnt = (uint32_t)std::min<uint64_t>(MFX_DELTA_BLOCK, in.h.n - b * MFX_DELTA_BLOCK);
+          t.esc_lo = esc_lo; t.esc_hi = esc_hi; t.input = i;
+          tasks.push_back(t);
+        }
+        run_len[i] = mfx_merge_block_pairs(pin[i], b0, b1);
+        npairs += run_len[i];
+        nwords += bytes / 8;
+      }
+      const uint32_t nt = (uint32_t)tasks.size();
+      if (npairs != win[wi].pairs || npairs > max_pairs || nwords * 8 > max_bytes || nt > max_tasks || hek.size() > max_esc)
+        return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is decoded beyond the buffers)
+      MFX_HIP(hipMemcpyAsync(D.p[2], words, nwords * 8, hipMemcpyHostToDevice, nullptr));
+      MFX_HIP(hipMemcpyAsync(d_tasks, tasks.data(), nt * sizeof(mfx_merge_task), hipMemcpyHostToDevice, nullptr));
+      if (!hek.empty()) {
+        MFX_HIP(hipMemcpyAsync(D.p[4], hek.data(), hek.size() * 8, hipMemcpyHostToDevice, nullptr));
+        MFX_HIP(hipMemcpyAsync(D.p[5], hev.data(), hev.size() * 4, hipMemcpyHostToDevice, nullptr));
+      }
+      MFX_HIP(hipMemsetAsync(d_err, 0, n_in * 4, nullptr));
+      MFX_HIP(hipStreamSynchronize(nullptr));                  // (the host arrays are filled again for the next window)
+      double t1 = db_now();
+      w->t_read += t1 - t0;
+      // ---- decode: one ascending run per input in buffer 0
+      MFX_HIP(mfx_k_delta_decode(d_tasks, nt, (const uint64_t *)D.p[2], (const uint64_t *)D.p[4], (const uint32_t *)D.p[5], lo, hi, bk[0], bv[0], d_below, d_above, d_err, nullptr));
+      cnt.resize(2 * (size_t)nt);
+      MFX_HIP(hipMemcpyAsync(cnt.data(), d_below, nt * 4, hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipMemcpyAsync(cnt.data() + nt, d_above, nt * 4, hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipMemcpyAsync(errs.data(), d_err, n_in * 4, hipMemcpyDeviceToHost, nullptr));
+      MFX_HIP(hipStreamSynchronize(nullptr));
+      t0 = db_now();
+      w->t_decode += t0 - t1;
+      for (uint32_t i = 0; i < n_in; ++i)
+        if (errs[i])
+          return mfx_fail(MFX_E_FORMAT, "'%s': a block holds what no writer makes (%s%s%s): the file is damaged", ins[i]->path.c_str(),
+                          (errs[i] & MFX_MERGE_ERR_ORDER) ? "k-mers that do not ascend below the next block's first; " : "",
+                          (errs[i] & MFX_MERGE_ERR_ESCAPE) ? "an escaped count that is not in the escape list; " : "", (errs[i] & MFX_MERGE_ERR_ZERO) ? "a count of zero; " : "");
+      runs.clear();
+      for (uint32_t i = 0; i < n_in; ++i) {
+        const uint64_t f = first_task[i], l = (i + 1 < n_in ? first_task[i + 1] : nt);
+        uint64_t below = 0, above = 0;
+        for (uint64_t j = f; j < l; ++j) { below += cnt[j]; above += cnt[nt + j]; }
+        // (ascending k-mers below every block's limit: only an input's first block reaches under lo, only its last to hi and beyond)
+        if (below + above > run_len[i] || (l > f && (below != cnt[f] || above != cnt[nt + l - 1])))
+          return mfx_fail(MFX_E_FORMAT, "'%s': the k-mers of a block lie outside its place in the directory", ins[i]->path.c_str());
+        runs.push_back(Run{run_off[i] + below, run_len[i] - below - above});
+      }
+      // ---- merge: a pairwise tree, from one buffer to the other
+      int cur = 0;
+      while (runs.size() > 1) {
+        next.clear();
+        uint64_t at = 0;
+        for (size_t j = 0; j < runs.size(); j += 2) {
+          const Run a = runs[j], b = j + 1 < runs.size() ? runs[j + 1] : Run{0, 0};
+          MFX_HIP(mfx_k_merge_pairs(bk[cur] + a.off, bv[cur] + a.off, a.len, bk[cur] + b.off, bv[cur] + b.off, b.len, bk[cur ^ 1] + at, bv[cur ^ 1] + at, nullptr));
+          next.push_back(Run{at, a.len + b.len});
+          at += a.len + b.len;
+        }
+        runs.swap(next);
+        cur ^= 1;
+      }
+      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
+      t1 = db_now();
+      w->t_merge += t1 - t0;
+      // ---- combine and filter: behind the place of the writer's carry in the other buffer
+      const uint64_t M = runs[0].len, c = w->ck.size();
+      uint64_t n_out = 0;
+      if (M) {
+        const uint64_t mt = mfx_combine_tiles(M);
+        MFX_HIP(mfx_k_combine(bk[cur] + runs[0].off, bv[cur] + runs[0].off, M, n_in, o->op, o->minV, o->maxV, d_tile, bk[cur ^ 1] + c, bv[cur ^ 1] + c, d_stats, nullptr));
+        MFX_HIP(hipMemcpyAsync(&n_out, d_tile + mt, 8, hipMemcpyDeviceToHost, nullptr));
+        MFX_HIP(hipStreamSynchronize(nullptr));
+      }
+      w->t_combine += db_now() - t1;
+      if (st) ++st->windows;
+      if (n_out > M) return mfx_fail(MFX_E_HIP, "%s: the combined pairs of a window are damaged", who);
+      if (n_out)
+        if (int rc = stream_append_device(w, S, bk[cur ^ 1], bv[cur ^ 1], n_out, bk[cur], cap * 12, who, "MFX_MERGE_RANGE")) return rc;
+    }
+    uint64_t stats[2] = {0, 0};
+    MFX_HIP(hipMemcpy(stats, d_stats, 16, hipMemcpyDeviceToHost));
+    if (st) { st->n_saturated = stats[0]; st->n_filtered = stats[1]; }
+  }
+  guard.w = nullptr;
+  uint64_t n = 0;
+  if (int rc = mfx_db_writer_close(w, &n)) return rc;
+  if (st) { st->n_in = n_all; st->n_out = n; }
+  return MFX_OK;
+}
+
+extern "C" int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
+  try { return mfx_db_merge_impl(in_paths, n_in, out_path, o, st); }                   // (nothing leaves the C ABI as an exception)
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge: %s", e.what()); }
+}
+
+extern "C" int mfx_db_merge_plan(const uint64_t *const *first, const uint64_t *n, uint32_t n_in, int k, uint64_t R, uint64_t *out, uint64_t cap, uint64_t *n_windows) {
+  if (!first || !n || !n_windows || n_in == 0 || n_in > MFX_MERGE_MAX_INPUTS || k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "mfx_db_merge_plan: bad argument");
+  try {
+    std::vector<mfx_merge_input> in(n_in);
+    for (uint32_t i = 0; i < n_in; ++i) in[i] = mfx_merge_input{first[i], 1u, (n[i] + MFX_MERGE_BLOCK - 1) / MFX_MERGE_BLOCK, n[i]};
+    std::vector<mfx_merge_window> win;
+    std::vector<uint64_t> blk;
+    mfx_merge_plan(in.data(), n_in, k, R, win, blk);
+    *n_windows = win.size();
+    const uint64_t row = 3 + 2 * (uint64_t)n_in;
+    for (uint64_t w = 0; out && w < win.size() && w < cap; ++w) {
+      out[w * row] = win[w].lo; out[w * row + 1] = win[w].hi; out[w * row + 2] = win[w].pairs;
+      for (uint64_t j = 0; j < 2 * (uint64_t)n_in; ++j) out[w * row + 3 + j] = blk[w * 2 * n_in + j];
+    }
+    return MFX_OK;
+  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge_plan: out of memory"); }
 }
 
 

@@ -21,6 +21,62 @@ __device__ __forceinline__ uint32_t mfx_range32(uint64_t x, uint64_t n) {
 }
 
 // ===========================================================================
+// The decode of a delta-coded block (mfx_delta.h; mfx_db.cpp FLAT_DELTA), shared by the kernels that insert the blocks into a table
+// (mfx_kernels.hip: mfx_table_add_delta_kernel) and the one that decodes them into sorted arrays (mfx_merge.hip: mfx_delta_decode_kernel).
+// ===========================================================================
+// (a field is at most 64 bits wide -- the differences of a placed 31-mer file, whose stored numbers have 64 bits: mfx_place.h -- and its
+// mask is the same for every field of a block: made once per block, not per entry)
+__device__ __forceinline__ uint64_t mfx_field_mask(uint32_t nbits) { return nbits >= 64u ? ~0ull : (1ull << nbits) - 1ull; }
+__device__ __forceinline__ uint64_t mfx_bits_at(const uint64_t *w, uint64_t bit, uint32_t nbits, uint64_t mask) {     // nbits <= 64, mask = mfx_field_mask(nbits)
+  const uint64_t i = bit >> 6;
+  const uint32_t sh = (uint32_t)bit & 63u;
+  uint64_t x = w[i] >> sh;
+  if (sh + nbits > 64u) x |= w[i + 1] << (64u - sh);
+  return x & mask;
+}
+
+// one block as a workgroup of 256 lanes reads it: lane tid decodes the MFX_DELTA_BLOCK / 256 consecutive entries from tid * 16 on
+struct mfx_delta_blk {
+  const uint64_t *pw;          // the block's words: the differences, then (from bit vbit0) the count fields
+  uint64_t first, kmask, vmask, vbit0;
+  uint32_t kb, vb, cnt;
+};
+constexpr uint32_t MFX_DELTA_PER_LANE = MFX_DELTA_BLOCK / 256;
+
+__device__ __forceinline__ mfx_delta_blk mfx_delta_blk_open(const uint64_t *pw, uint64_t first, uint32_t kb, uint32_t vb, uint32_t cnt) {
+  mfx_delta_blk B;
+  B.pw = pw; B.first = first; B.kb = kb; B.vb = vb; B.cnt = cnt;
+  B.kmask = mfx_field_mask(kb); B.vmask = mfx_field_mask(vb);
+  B.vbit0 = (((uint64_t)(cnt - 1u) * kb + 63u) >> 6) << 6;    // the values start at a word boundary
+  return B;
+}
+// entry e > 0 has difference e - 1; entry 0 is the block's first k-mer
+__device__ __forceinline__ uint64_t mfx_delta_diff(const mfx_delta_blk &B, uint32_t e) { return mfx_bits_at(B.pw, (uint64_t)(e - 1u) * B.kb, B.kb, B.kmask); }
+__device__ __forceinline__ uint32_t mfx_delta_field(const mfx_delta_blk &B, uint32_t e) { return (uint32_t)mfx_bits_at(B.pw, B.vbit0 + (uint64_t)e * B.vb, B.vb, B.vmask); }
+
+// The k-mer BEFORE this lane's first entry (the block's first k-mer for lane 0, whose entry 0 adds no difference): the sum of the lane's
+// differences, an inclusive scan over the workgroup.  The caller then adds mfx_delta_diff(e) entry after entry.  Called by all 256 lanes;
+// wsum: four words of LDS (a barrier in here lets the previous call's readers finish first).
+__device__ __forceinline__ uint64_t mfx_delta_lane_start(const mfx_delta_blk &B, uint64_t *wsum) {
+  const uint32_t tid = threadIdx.x, wv = tid >> 6, ln = tid & 63u, e0 = tid * MFX_DELTA_PER_LANE;
+  uint64_t mine = 0;
+#pragma unroll 4
+  for (uint32_t i = 0; i < MFX_DELTA_PER_LANE; ++i) {
+    const uint32_t e = e0 + i;
+    if (e > 0u && e < B.cnt && B.kb) mine += mfx_delta_diff(B, e);
+  }
+  uint64_t inc = mine;                                         // inclusive scan over the workgroup
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(inc, o, 64); if ((int)ln >= o) inc += u; }
+  __syncthreads();                                             // wsum of the previous block is read by now
+  if (ln == 63u) wsum[wv] = inc;
+  __syncthreads();
+  uint64_t run = B.first + inc - mine;
+  for (uint32_t w2 = 0; w2 < wv; ++w2) run += wsum[w2];
+  return run;
+}
+
+// ===========================================================================
 // sequence tile in LDS: 2-bit codes packed MSB-first in 64-bit words + one
 // validity bit per base, so a lane extracts the k-mer starting at ANY position
 // with two LDS reads and a funnel shift (no rolling dependency between lanes).

@@ -232,5 +232,21 @@ hipError_t mfx_k_delta_plan(const uint64_t *keys, const uint32_t *vals, uint32_t
 // word_off / esc_off: where block b's words start in out, its escapes in esc_keys / esc_vals -- the scan of the plan's sizes
 hipError_t mfx_k_delta_pack(const uint64_t *keys, const uint32_t *vals, uint32_t nblocks, const mfx_delta_plan *plan, const uint64_t *word_off,
                             const uint32_t *esc_off, uint64_t *out, uint64_t *esc_keys, uint32_t *esc_vals, hipStream_t st);
+// mfx_db_merge (mfx_merge.hip).  One block of one input in a window: its words at payload + word_off, its cnt records to keys / vals from
+// `out` on; every k-mer of it lies below `limit` (the next block's first k-mer, or the end of the key space); [esc_lo, esc_hi): the
+// window's slice of its input's escape list in esc_keys / esc_vals; input: which input the block is of
+struct mfx_merge_task { uint64_t word_off, first, limit, out; uint32_t kb, vb, cnt, esc_lo, esc_hi, input; };
+constexpr uint32_t MFX_MERGE_ERR_ORDER = 1u, MFX_MERGE_ERR_ESCAPE = 2u, MFX_MERGE_ERR_ZERO = 4u;      // err[input] of the decode: what no writer makes
+// below[t] / above[t]: the records of task t under lo / at or above hi
+hipError_t mfx_k_delta_decode(const mfx_merge_task *tasks, uint32_t ntasks, const uint64_t *payload, const uint64_t *esc_keys, const uint32_t *esc_vals, uint64_t lo,
+                              uint64_t hi, uint64_t *keys, uint32_t *vals, uint32_t *below, uint32_t *above, uint32_t *err, hipStream_t st);
+// two ascending runs into one of la + lb pairs; equal k-mers stay, a's first
+hipError_t mfx_k_merge_pairs(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, uint64_t *ko, uint32_t *vo,
+                             hipStream_t st);
+// one record per k-mer of a merged run: op (MFX_MERGE_*), then the filter; tile_off: mfx_combine_tiles(n) + 1 words, the last ends as the number of
+// records written; stats[0] += sums clamped, stats[1] += k-mers filtered
+uint64_t mfx_combine_tiles(uint64_t n);
+hipError_t mfx_k_combine(const uint64_t *keys, const uint32_t *vals, uint64_t n, uint32_t n_in, int op, uint64_t minV, uint64_t maxV, uint64_t *tile_off,
+                         uint64_t *out_keys, uint32_t *out_vals, uint64_t *stats, hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);

@@ -933,49 +933,22 @@ __global__ __launch_bounds__(256) void mfx_table_update_kernel(mfx_table_view t,
 // and puts them into the table itself -- the decoded k-mers never exist in memory.
 // dir[b] = {first k-mer, payload byte offset (48 bits) | kbits << 48 | vbits << 56}; dir[nblocks] closes the last block.
 // ---------------------------------------------------------------------------
-// (a field is at most 64 bits wide -- the differences of a placed 31-mer file, whose stored numbers have 64 bits: mfx_place.h -- and its
-// mask is the same for every field of a block: made once per block, not per entry)
-__device__ __forceinline__ uint64_t mfx_field_mask(uint32_t nbits) { return nbits >= 64u ? ~0ull : (1ull << nbits) - 1ull; }
-__device__ __forceinline__ uint64_t mfx_bits_at(const uint64_t *w, uint64_t bit, uint32_t nbits, uint64_t mask) {     // nbits <= 64, mask = mfx_field_mask(nbits)
-  const uint64_t i = bit >> 6;
-  const uint32_t sh = (uint32_t)bit & 63u;
-  uint64_t x = w[i] >> sh;
-  if (sh + nbits > 64u) x |= w[i + 1] << (64u - sh);
-  return x & mask;
-}
-
+// (mfx_field_mask, mfx_bits_at and the decode of a block as a workgroup reads it: mfx_device.h, shared with mfx_merge.hip)
 __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view t, const uint64_t *payload, const uint64_t *dir,
                                                                   uint32_t nblocks, uint64_t n, uint64_t payload_base, int side,
                                                                   uint64_t *meta) {
-  constexpr int PER = MFX_DELTA_BLOCK / 256;                   // entries per lane
+  constexpr int PER = MFX_DELTA_PER_LANE;                      // entries per lane
   static_assert(PER == 16, "a lane decodes 16 entries, four at a time");
   __shared__ uint64_t wsum[4];
   mfx_tally T;
-  const uint32_t tid = threadIdx.x, wv = tid >> 6, ln = tid & 63u;
+  const uint32_t tid = threadIdx.x;
   for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
     const uint64_t first = dir[2 * (uint64_t)b], info = dir[2 * (uint64_t)b + 1];
-    const uint32_t kb = (uint32_t)(info >> 48) & 0xffu, vb = (uint32_t)(info >> 56) & 0xffu;
-    const uint64_t kmask = mfx_field_mask(kb), vmask = mfx_field_mask(vb);
     const uint64_t left = n - (uint64_t)b * MFX_DELTA_BLOCK;
-    const uint32_t cnt = left < MFX_DELTA_BLOCK ? (uint32_t)left : (uint32_t)MFX_DELTA_BLOCK;
-    const uint64_t *pw = payload + (((info & 0xffffffffffffull) - payload_base) >> 3);
-    const uint64_t vbit0 = (((uint64_t)(cnt - 1u) * kb + 63u) >> 6) << 6;      // the values start at a word boundary
+    const mfx_delta_blk B = mfx_delta_blk_open(payload + (((info & 0xffffffffffffull) - payload_base) >> 3), first, (uint32_t)(info >> 48) & 0xffu,
+                                               (uint32_t)(info >> 56) & 0xffu, left < MFX_DELTA_BLOCK ? (uint32_t)left : (uint32_t)MFX_DELTA_BLOCK);
     const uint32_t e0 = tid * PER;
-    // ---- the sum of this lane's differences (entry e > 0 has difference e - 1; entry 0 is the block's first k-mer)
-    uint64_t mine = 0;
-#pragma unroll 4
-    for (uint32_t i = 0; i < PER; ++i) {
-      const uint32_t e = e0 + i;
-      if (e > 0u && e < cnt && kb) mine += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb, kmask);
-    }
-    uint64_t inc = mine;                                       // inclusive scan over the workgroup
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(inc, o, 64); if ((int)ln >= o) inc += u; }
-    __syncthreads();                                           // wsum of the previous block is read by now
-    if (ln == 63u) wsum[wv] = inc;
-    __syncthreads();
-    uint64_t run = first + inc - mine;
-    for (uint32_t w2 = 0; w2 < wv; ++w2) run += wsum[w2];
+    uint64_t run = mfx_delta_lane_start(B, wsum);              // the sum of the differences before this lane's entries
     // ---- the entries, four at a time
 #pragma unroll 1
     for (uint32_t g = 0; g < PER; g += 4) {
@@ -985,11 +958,11 @@ __global__ __launch_bounds__(256) void mfx_table_add_delta_kernel(mfx_table_view
       for (uint32_t i = 0; i < 4; ++i) {
         const uint32_t e = e0 + g + i;
         key[i] = 0; v[i] = 0u;
-        if (e < cnt) {
-          if (e > 0u && kb) run += mfx_bits_at(pw, (uint64_t)(e - 1u) * kb, kb, kmask);
+        if (e < B.cnt) {
+          if (e > 0u && B.kb) run += mfx_delta_diff(B, e);
           key[i] = run;
-          v[i] = (uint32_t)mfx_bits_at(pw, vbit0 + (uint64_t)e * vb, vb, vmask);
-          if (v[i] == (1u << vb) - 1u) v[i] = 0u;              // escape: added separately (the file's escape list)
+          v[i] = mfx_delta_field(B, e);
+          if (v[i] == (1u << B.vb) - 1u) v[i] = 0u;            // escape: added separately (the file's escape list)
         }
       }
       mfx_apply_batch<4>(t, key, v, side, meta, T);
