@@ -328,6 +328,41 @@ int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_pat
  * the blocks [b0, b1).  *n_windows: the windows of the plan. */
 int mfx_db_merge_plan(const uint64_t *const *first, const uint64_t *n, uint32_t n_in, int k, uint64_t R, uint64_t *out, uint64_t cap, uint64_t *n_windows);
 
+/* mfx_db_join_*: -completeness and -spectrum of a read database and an assembly's database WITHOUT a table: the sorted join of the two
+ * files, window by window, ending in a reduction (csrc/mfx_join.hip).  Device memory holds one window (MFX_MERGE_RANGE pairs, the knob and
+ * the windows of mfx_db_merge above), the host 16 bytes per 4096 k-mers and 12 per escape of each input: the size of the read database does
+ * not matter.  The inputs are what mfx_db_merge takes -- sorted, delta-coded flat files of one k <= 31 (an assembly's: `merfin -count` of
+ * its FASTA) -- and are refused in the same way before any device is touched: a placed file, a packed or plain flat file, text, a meryl
+ * directory (run `merfin -convert` first), different k, null outputs, and for the spectrum copies / max_mult outside mfx_spectrum_run's
+ * bounds.  A file of no k-mers is valid on either side.  A block that decodes what no writer makes ends the call in MFX_E_FORMAT, naming
+ * the file; on every failure the outputs are left as they were.
+ *   completeness: total64[p] / undrcpy64[p] as mfx_completeness_pieces gives them for a full index of the two files -- the same doubles
+ *     (readK is an integer: the sums are exact in any order); peak, n_prob, probK, probP as in mfx_kparams; the raw read count is used,
+ *     minV / maxV do not apply (as there).
+ *   spectrum: img and *n_entries as mfx_spectrum_run gives them for a full index loaded with minV / maxV on the read side: a read count
+ *     outside [minV, maxV] counts as 0, a read-only k-mer that becomes (0, 0) is no entry.  MFX_SPECTRUM_AGG applies.
+ * stats (may be NULL): the k-mers of the two inputs, the k-mers both hold, the windows that held blocks; seconds spent in pread + copy,
+ * in the decode, in launching the join (the kernel itself only with MFX_DB_TIMING set, which waits for it per window) and in the call. */
+typedef struct {
+  int             device;
+  uint64_t        minV, maxV;          /* spectrum: -min / -max on the read count */
+  double          peak;                /* completeness: mfx_kparams */
+  uint32_t        n_prob;
+  const uint32_t *probK;
+  const double   *probP;
+  uint32_t        copies, max_mult;    /* spectrum: as mfx_spectrum_run */
+} mfx_db_join_opts;
+typedef struct { uint64_t n_read, n_asm, n_both, windows; double t_read, t_decode, t_join, t_total; } mfx_db_join_stats;
+int mfx_db_join_completeness(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, double *total64, double *undrcpy64, mfx_db_join_stats *st /* may be NULL */);
+int mfx_db_join_spectrum(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, uint64_t *img, uint64_t *n_entries, mfx_db_join_stats *st /* may be NULL */);
+/* Host only (tests, tools/native/db_join_sanitize.cpp).  grain: the merged positions a lane and a workgroup of the join kernel take at a
+ * time (csrc/mfx_join.h).  host: the kernel's walk -- tiles, lane shares, the ownership of a k-mer both runs hold -- over two strictly
+ * ascending host runs: one (k-mer, read count, asm count) per distinct k-mer in the order the lanes meet them, 0 for "not in that run";
+ * at most cap are stored, *n_pairs counts them all. */
+void mfx_db_join_grain(uint32_t *per_lane, uint32_t *tile);
+int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *asm_keys, const uint32_t *asm_vals, uint64_t n_asm,
+                     uint64_t *keys, uint32_t *readV, uint32_t *asmV, uint64_t cap, uint64_t *n_pairs);
+
 /* ------------------------------------------------------------------------ */
 /* Read k-mer counting: the read counts of a run straight from its reads     */
 /* (FASTA / FASTQ records), no k-mer database in between.                   */

@@ -73,7 +73,7 @@ SYMBOLS = [
     "mfx_last_error", "mfx_last_error_code", "mfx_version", "mfx_device_count", "mfx_device_warm", "mfx_device_memory",
     "mfx_index_create", "mfx_index_free", "mfx_index_estimate_gb", "mfx_index_add_read", "mfx_index_add_asm",
     "mfx_index_count_asm", "mfx_index_build_for_hist", "mfx_index_count_claimed", "mfx_hist_run_parts", "mfx_index_create_for_seq", "mfx_index_create_for_seq_lf", "mfx_index_create_lf", "mfx_db_stage_begin", "mfx_index_build_for_hist_staged", "mfx_index_load_db_staged", "mfx_db_stage_free", "mfx_db_stage_boost", "mfx_index_estimate_gb_for_seq", "mfx_index_claim_seq", "mfx_index_value", "mfx_index_get_info", "mfx_index_export",
-    "mfx_db_probe", "mfx_index_load_db", "mfx_index_load_db_multi", "mfx_db_write_flat", "mfx_db_convert", "mfx_db_merge", "mfx_db_merge_plan", "mfx_db_convert_placed", "mfx_db_write_flat_placed", "mfx_db_place_keys", "mfx_index_save", "mfx_index_load",
+    "mfx_db_probe", "mfx_index_load_db", "mfx_index_load_db_multi", "mfx_db_write_flat", "mfx_db_convert", "mfx_db_merge", "mfx_db_merge_plan", "mfx_db_join_completeness", "mfx_db_join_spectrum", "mfx_db_join_grain", "mfx_db_join_host", "mfx_db_convert_placed", "mfx_db_write_flat_placed", "mfx_db_place_keys", "mfx_index_save", "mfx_index_load",
     "mfx_index_set_fingerprint", "mfx_index_get_origin",
     "mfx_host_alloc", "mfx_host_free", "mfx_seq_create", "mfx_hist_run_streamed",
     "mfx_hist_run_streamed_multi", "mfx_hist_run_streamed_range", "mfx_hist_stream_share",
@@ -193,6 +193,12 @@ def load_library():
     L.mfx_db_convert_placed.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
     L.mfx_db_merge.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(DbMergeOpts), C.POINTER(DbMergeStats)]
     L.mfx_db_merge_plan.argtypes = [C.POINTER(u64p), u64p, C.c_uint32, C.c_int, C.c_uint64, u64p, C.c_uint64, u64p]
+    L.mfx_db_join_completeness.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(DbJoinOpts), f64p, f64p, C.POINTER(DbJoinStats)]
+    L.mfx_db_join_spectrum.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(DbJoinOpts), u64p, u64p, C.POINTER(DbJoinStats)]
+    L.mfx_db_join_grain.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mfx_db_join_grain.restype = None
+    L.mfx_db_join_host.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                   C.c_uint64, u64p]
     L.mfx_db_write_flat_placed.argtypes = [C.c_char_p, C.c_int, u64p, u32p, C.c_uint64]
     L.mfx_db_place_keys.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_int, C.c_int]
     L.mfx_index_load_db_multi.argtypes = [C.POINTER(vp), C.c_uint32, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64]
@@ -466,6 +472,73 @@ def db_merge(paths, out_path, op="sum", min_count=0, max_count=2**32 - 1, device
     st = DbMergeStats()
     _check(load_library().mfx_db_merge(arr, len(paths), out_path.encode(), C.byref(o), C.byref(st)))
     return {name: int(getattr(st, name)) for name, _ in DbMergeStats._fields_}
+
+
+class DbJoinOpts(C.Structure):
+    _fields_ = [("device", C.c_int), ("minV", C.c_uint64), ("maxV", C.c_uint64), ("peak", C.c_double), ("n_prob", C.c_uint32), ("probK", C.POINTER(C.c_uint32)),
+                ("probP", C.POINTER(C.c_double)), ("copies", C.c_uint32), ("max_mult", C.c_uint32)]
+
+
+class DbJoinStats(C.Structure):
+    _fields_ = [("n_read", C.c_uint64), ("n_asm", C.c_uint64), ("n_both", C.c_uint64), ("windows", C.c_uint64), ("t_read", C.c_double), ("t_decode", C.c_double),
+                ("t_join", C.c_double), ("t_total", C.c_double)]
+
+
+def _join_stats(st):
+    return {name: (float if name.startswith("t_") else int)(getattr(st, name)) for name, _ in DbJoinStats._fields_}
+
+
+def db_join_completeness(read_path, asm_path, kparams, device=0, with_stats=False, min_count=0, max_count=2**32 - 1):
+    """-completeness of two sorted flat databases without a table (mfx_db_join_completeness): (total[64], undrcpy[64]) per piece, the
+    doubles Evaluator.completeness_pieces gives for a full index of the two files; with_stats: also n_read, n_asm, n_both, windows and
+    the call's time split.  min_count / max_count are passed on and take no part: -completeness uses the raw read count"""
+    kp = kparams if isinstance(kparams, KParams) else KParams(kparams)
+    o = DbJoinOpts(int(device), int(min_count), int(max_count), kp.peak, len(kp.probK), kp.probK.ctypes.data_as(C.POINTER(C.c_uint32)), kp.probP.ctypes.data_as(C.POINTER(C.c_double)), 0, 0)
+    t = np.zeros(64, dtype=np.float64)
+    u = np.zeros(64, dtype=np.float64)
+    st = DbJoinStats()
+    _check(load_library().mfx_db_join_completeness(read_path.encode(), asm_path.encode(), C.byref(o), t.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   u.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st)))
+    return (t, u, _join_stats(st)) if with_stats else (t, u)
+
+
+def db_join_spectrum(read_path, asm_path, copies=4, max_mult=10000, min_count=0, max_count=2**32 - 1, device=0, with_entries=False, with_stats=False):
+    """the copy-number spectrum of two sorted flat databases without a table (mfx_db_join_spectrum): the (copies + 2, max_mult + 1) uint64
+    array Index.spectrum gives for a full index of the two files, the read counts through min_count / max_count; with_entries: also the
+    number of counted entries; with_stats: also the stats"""
+    o = DbJoinOpts(int(device), int(min_count), int(max_count), 0.0, 0, None, None, int(copies), int(max_mult))
+    img = np.zeros((max(int(copies), 0) + 2, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    st = DbJoinStats()
+    _check(load_library().mfx_db_join_spectrum(read_path.encode(), asm_path.encode(), C.byref(o), img.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), C.byref(st)))
+    out = (img,) + ((n.value,) if with_entries else ()) + ((_join_stats(st),) if with_stats else ())
+    return out if len(out) > 1 else img
+
+
+def db_join_grain():
+    """(merged positions per lane, per workgroup tile) of the join kernel (csrc/mfx_join.h)"""
+    per, tile = C.c_uint32(0), C.c_uint32(0)
+    load_library().mfx_db_join_grain(C.byref(per), C.byref(tile))
+    return per.value, tile.value
+
+
+def db_join_host(read_keys, read_vals, asm_keys, asm_vals):
+    """the join kernel's walk on the host (mfx_db_join_host): (k-mers, read counts, asm counts), one per distinct k-mer, in the order the
+    lanes meet them"""
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    rk = np.ascontiguousarray(read_keys, dtype=np.uint64)
+    rv = np.ascontiguousarray(read_vals, dtype=np.uint32)
+    ak = np.ascontiguousarray(asm_keys, dtype=np.uint64)
+    av = np.ascontiguousarray(asm_vals, dtype=np.uint32)
+    cap = len(rk) + len(ak)
+    keys = np.zeros(max(cap, 1), dtype=np.uint64)
+    orv = np.zeros(max(cap, 1), dtype=np.uint32)
+    oav = np.zeros(max(cap, 1), dtype=np.uint32)
+    n = C.c_uint64(0)
+    _check(load_library().mfx_db_join_host(rk.ctypes.data_as(u64p), rv.ctypes.data_as(u32p), len(rk), ak.ctypes.data_as(u64p), av.ctypes.data_as(u32p), len(ak),
+                                           keys.ctypes.data_as(u64p), orv.ctypes.data_as(u32p), oav.ctypes.data_as(u32p), cap, C.byref(n)))
+    assert n.value <= cap
+    return keys[:n.value], orv[:n.value], oav[:n.value]
 
 
 def db_merge_plan(firsts, counts, k, R):

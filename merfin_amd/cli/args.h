@@ -41,6 +41,7 @@ struct Globals {
   std::vector<const char *> mergeNames;  // -merge: no report; these sorted databases combined on the GPU into -output (mfx_db_merge)
   const char *opName = nullptr;          // -op of -merge: sum (default), max, min, intersect
   int mergeOp = MFX_MERGE_SUM;
+  bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
 };
 
 typedef std::vector<std::string> Errors;
@@ -114,10 +115,21 @@ static void usage_merge() {
           "\n");
 }
 
+// the entry of -join: printed behind the text above for a command line that names it
+static void usage_join() {
+  fprintf(stderr,
+          "  -completeness and -spectrum without a table:\n"
+          "    -join             with -completeness and -spectrum: -readmers and -seqmers, both sorted flat databases (what -count and -convert\n"
+          "                      write; one k <= 31), are joined on the GPU window by window, so neither has to fit the device.  An assembly's\n"
+          "                      database is made by: merfin -count -reads asm.fasta -k K -output asm.mfxk.  -peak <number>, not auto.  One device.\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
-static int fail_usage(const char *argv0, const Errors &err, bool merge = false) {
+static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false) {
   usage(argv0);
   if (merge) usage_merge();
+  if (join) usage_join();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -212,6 +224,7 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
     else if (is("-convert")) G.convertName = val();
     else if (is("-count")) G.count = true;
     else if (is("-merge")) G.mergeNames.push_back(val());
+    else if (is("-join")) G.join = true;
     else if (is("-op")) {
       G.opName = val();
       static const char *const names[] = {"sum", "max", "min", "intersect"};      // MFX_MERGE_*
@@ -372,6 +385,21 @@ static void check_spectrum_flags(const Globals &G, Errors &err) {
   if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -spectrum counts every entry of the table.\n");
   if (!G.seqName && !G.seqDBname) err.push_back("No sequence meryl database (-seqmers) nor sequence (-sequence) supplied.\n");
   if (!G.seqName && !G.readsNames.empty()) err.push_back("-spectrum counts -reads into the k-mers of -sequence: give -sequence.\n");
+}
+
+// -join: every check before any device is touched (what the databases hold is checked by mfx_db_join_*, before it touches one)
+static void check_join_flags(const Globals &G, Errors &err) {
+  if (!G.join) return;
+  if (G.reportType != OP_COMPL && G.reportType != OP_SPECTRUM)
+    err.push_back("-join is a way to run -completeness and -spectrum: it does not take another report type (-hist, -dump, -track, the variant modes).\n");
+  if (!G.readsNames.empty()) err.push_back("-join joins two databases: it does not take -reads (count them first: -count).\n");
+  if (!G.seqDBname)
+    err.push_back(G.seqName ? "-join joins two databases: it takes the assembly as -seqmers, not as -sequence (merfin -count -reads asm.fasta -k K -output asm.mfxk).\n"
+                            : "-join joins two databases: give the assembly's as -seqmers (merfin -count -reads asm.fasta -k K -output asm.mfxk).\n");
+  if (G.sharded) err.push_back("-join does not take -sharded: the windows it joins live on one device, and no table is built.\n");
+  if (G.devices.size() > 1) err.push_back("-join runs on one device (-device d, or -devices naming one).\n");
+  if (G.indexName) err.push_back("-join does not take -index: it builds no table.\n");
+  if (G.peakAuto) err.push_back("-join does not take -peak auto: the peak is read off a table; give -peak <number>.\n");
 }
 
 // -peak auto: every check before any device is touched

@@ -1494,7 +1494,14 @@ static int build_full_index(Run &R) {
       if (finish_seq(R)) return 1;
       continue;
     }
-    if (!R.ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+    if (!R.ix) {
+      const bool nomem = mfx_last_error_code() == MFX_E_NOMEM;
+      fprintf(stderr, "\n%s\n\n", mfx_last_error());
+      if (nomem && (G.reportType == OP_COMPL || G.reportType == OP_SPECTRUM) && !R.fromReads && G.seqDBname && R.rdb.format == MFX_DB_FLAT && !R.rdb.placed &&
+          R.adb.format == MFX_DB_FLAT && !R.adb.placed)
+        fprintf(stderr, "-- Hint: -join runs this report from the two sorted databases window by window, without a table: neither has to fit the device.\n");
+      return 1;
+    }
     if (!R.fromReads && load_db_step(R, G.readDBname, 0, nullptr, nullptr, 0)) return 1;
     if (G.seqDBname) {
       if (load_db_step(R, G.seqDBname, 1, nullptr, nullptr, 0)) return 1;
@@ -1521,6 +1528,21 @@ static int build_full_index(Run &R) {
 
 // ---- the reports ---------------------------------------------------------------------------------------------------------------------------
 // -spectrum / -peak auto: one streaming pass over the table (mfx_spectrum_run), the haploid peak off its single-copy row
+// the spectrum's file and what stderr says of it: shared by the table route and -join
+static int write_spectrum_report(const Globals &G, int k, const std::vector<uint64_t> &img, uint64_t entries, bool withReadOnly) {
+  const uint32_t copies = G.copies, maxMult = G.maxMult;
+  const std::string name = std::string(G.outName) + ".spectra-cn.hist";
+  fprintf(stderr, "-- Copy-number spectrum of the %d-mers to '%s'.\n", k, name.c_str());
+  if (mfx_spectrum_write(img.data(), copies, maxMult, withReadOnly ? 1 : 0, name.c_str())) DIE_MFX("writing the spectrum");
+  uint64_t asmOnly = 0, readOnly = 0;
+  for (uint32_t r = 1; r < copies + 2; ++r) asmOnly += img[(size_t)r * (maxMult + 1)];
+  for (uint32_t m = 0; m <= maxMult; ++m) readOnly += img[m];
+  fprintf(stderr, "Entries counted: %lu\nAssembly-only k-mers: %lu\n", (unsigned long)entries, (unsigned long)asmOnly);
+  if (withReadOnly) fprintf(stderr, "Read-only k-mers: %lu\n", (unsigned long)readOnly);
+  else fprintf(stderr, "The table holds the k-mers of -sequence only (-reads): the read-only row is left out.\n");
+  return 0;
+}
+
 static int run_spectrum_or_peak(Run &R) {
   Globals &G = R.G;
   const bool report = G.reportType == OP_SPECTRUM;
@@ -1528,19 +1550,8 @@ static int run_spectrum_or_peak(Run &R) {
   std::vector<uint64_t> img((size_t)(copies + 2) * (maxMult + 1));
   uint64_t entries = 0;
   if (mfx_spectrum_run(R.ix, copies, maxMult, img.data(), &entries)) DIE_MFX(report ? "-spectrum" : "-peak auto");
-  if (report) {
-    // a table that holds the k-mers of -sequence only (-reads) has no read-only k-mers: the row is left out, not written as zeros
-    const bool withReadOnly = !R.fromReads;
-    const std::string name = std::string(G.outName) + ".spectra-cn.hist";
-    fprintf(stderr, "-- Copy-number spectrum of the %d-mers to '%s'.\n", R.k, name.c_str());
-    if (mfx_spectrum_write(img.data(), copies, maxMult, withReadOnly ? 1 : 0, name.c_str())) DIE_MFX("writing the spectrum");
-    uint64_t asmOnly = 0, readOnly = 0;
-    for (uint32_t r = 1; r < copies + 2; ++r) asmOnly += img[(size_t)r * (maxMult + 1)];
-    for (uint32_t m = 0; m <= maxMult; ++m) readOnly += img[m];
-    fprintf(stderr, "Entries counted: %lu\nAssembly-only k-mers: %lu\n", (unsigned long)entries, (unsigned long)asmOnly);
-    if (withReadOnly) fprintf(stderr, "Read-only k-mers: %lu\n", (unsigned long)readOnly);
-    else fprintf(stderr, "The table holds the k-mers of -sequence only (-reads): the read-only row is left out.\n");
-  }
+  // a table that holds the k-mers of -sequence only (-reads) has no read-only k-mers: the row is left out, not written as zeros
+  if (report && write_spectrum_report(G, R.k, img, entries, !R.fromReads)) return 1;
   mfx_spectrum_peak_t pk;
   if (mfx_spectrum_peak(img.data() + (size_t)(maxMult + 1), maxMult, &pk) == MFX_OK) {
     fprintf(stderr, "Haploid peak (auto): %u  (main peak %u, valley %u, single-copy k-mers at the peak %lu)\n", pk.haploid_peak, pk.main_peak, pk.valley,
@@ -1553,6 +1564,42 @@ static int run_spectrum_or_peak(Run &R) {
     return 1;
   }
   R.clock.lap("spectrum");
+  return 0;
+}
+
+// merfin -completeness -join / -spectrum -join: the report from the sorted join of -readmers and -seqmers (mfx_db_join_*), no table.  The
+// texts are the table route's.
+static int run_join(const Globals &G) {
+  mfx_db_join_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = G.device;
+  o.minV = G.minV; o.maxV = G.maxV;
+  o.peak = G.peak;
+  o.n_prob = (uint32_t)G.copyKmerK.size(); o.probK = G.copyKmerK.data(); o.probP = G.copyKmerP.data();
+  o.copies = G.copies; o.max_mult = G.maxMult;
+  mfx_db_join_stats st;
+  fprintf(stderr, "-- Joining '%s' and '%s' window by window.\n", G.readDBname, G.seqDBname);
+  if (G.reportType == OP_COMPL) {
+    fprintf(stderr, "-- Compute completeness.\n");
+    double t64[64], u64[64];
+    if (mfx_db_join_completeness(G.readDBname, G.seqDBname, &o, t64, u64, &st)) DIE_MFX("-completeness -join");
+    print_completeness(t64, u64);
+  } else {
+    mfx_db_info rdb;
+    if (mfx_db_probe(G.readDBname, &rdb)) DIE_MFX("opening -readmers");
+    std::vector<uint64_t> img((size_t)(G.copies + 2) * (G.maxMult + 1));
+    uint64_t entries = 0;
+    if (mfx_db_join_spectrum(G.readDBname, G.seqDBname, &o, img.data(), &entries, &st)) DIE_MFX("-spectrum -join");
+    if (write_spectrum_report(G, rdb.k, img, entries, true)) return 1;
+    mfx_spectrum_peak_t pk;
+    if (mfx_spectrum_peak(img.data() + (size_t)(G.maxMult + 1), G.maxMult, &pk) == MFX_OK)
+      fprintf(stderr, "Haploid peak (auto): %u  (main peak %u, valley %u, single-copy k-mers at the peak %lu)\n", pk.haploid_peak, pk.main_peak, pk.valley,
+              (unsigned long)pk.count_at_peak);
+    else fprintf(stderr, "No haploid peak found in the single-copy row (%s); the other report types need -peak <number>.\n", mfx_last_error());
+  }
+  fprintf(stderr, "-- Joined: %lu read k-mers, %lu assembly k-mers, %lu in both, %lu window%s.\n", (unsigned long)st.n_read, (unsigned long)st.n_asm,
+          (unsigned long)st.n_both, (unsigned long)st.windows, st.windows == 1 ? "" : "s");
+  fprintf(stderr, "Bye!\n");
   return 0;
 }
 
@@ -1844,13 +1891,15 @@ int main(int argc, char **argv) {
   if (!G.mergeNames.empty() || G.opName) return err.empty() ? run_merge(G) : fail_usage(argv[0], err, true);
   check_count_flags(G, err);
   if (G.count) return err.empty() ? run_count(G) : fail_usage(argv[0], err);
+  check_join_flags(G, err);
+  if (G.join && !G.readsNames.empty()) return fail_usage(argv[0], err, false, true);      // (the checks of -reads open -seqmers for its k)
   if (!check_reads_flags(G, err)) return 1;
   check_track_flags(G, err);
   check_spectrum_flags(G, err);
   check_peak_auto_flags(G, err);
   if (G.convertName && err.empty()) return run_convert(G);
   check_report_flags(G, err);
-  if (!err.empty()) return fail_usage(argv[0], err);
+  if (!err.empty()) return fail_usage(argv[0], err, false, G.join);
   if (!G.devices.empty()) G.device = G.devices[0];
   else G.devices.push_back(G.device);
   // 2. load_Kmetric first (merfin-globals.C:21-62 runs before the databases are opened; host only -- a compressed table's decompressor has
@@ -1858,6 +1907,7 @@ int main(int argc, char **argv) {
   if (!load_Kmetric(G)) return 1;
   // 3. (the device check stays on this thread, before anything else is started: see devices_available)
   if (!devices_available(G.devices)) return 1;
+  if (G.join) return run_join(G);
   Run R(G);
   R.clock.start(stamp_main);
   // 4. the databases are probed: the read DB defines k

@@ -18,6 +18,8 @@
 #include "mfx_kernels.h"
 #include "mfx_grow.h"
 #include "mfx_merge.h"
+#include "mfx_join.h"
+#include "mfx_spectrum.h"
 #include "mfx_pipe.h"
 #include "mfx_place.h"
 
@@ -2132,12 +2134,12 @@ struct WriterAbort {                                           // the writer of 
 }  // namespace
 
 // header, directory and escape list of an input, by the loader's checks; every refusal names the file
-static int merge_open_input(const char *path, MergeIn &in) {
+static int merge_open_input(const char *path, MergeIn &in, const char *who = "mfx_db_merge") {
   in.path = path;
   const int fmt = detect(in.path);
-  if (!fmt) return mfx_fail(MFX_E_IO, "mfx_db_merge: the input '%s' does not exist", path);
-  if (fmt == MFX_DB_MERYL) return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a meryl directory; the inputs are sorted flat databases: run `merfin -convert` first", path);
-  if (fmt == MFX_DB_TEXT) return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is not a flat k-mer file (`meryl print` text?); the inputs are sorted flat databases: run `merfin -convert` first", path);
+  if (!fmt) return mfx_fail(MFX_E_IO, "%s: the input '%s' does not exist", who, path);
+  if (fmt == MFX_DB_MERYL) return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a meryl directory; the inputs are sorted flat databases: run `merfin -convert` first", who, path);
+  if (fmt == MFX_DB_TEXT) return mfx_fail(MFX_E_FORMAT, "%s: '%s' is not a flat k-mer file (`meryl print` text?); the inputs are sorted flat databases: run `merfin -convert` first", who, path);
   in.fd = open(path, O_RDONLY | O_CLOEXEC);
   struct stat st;
   if (in.fd < 0 || fstat(in.fd, &st) != 0) return mfx_fail(MFX_E_IO, "cannot open '%s'", path);
@@ -2145,10 +2147,10 @@ static int merge_open_input(const char *path, MergeIn &in) {
   if (fsize < sizeof(in.h) || pread(in.fd, &in.h, sizeof(in.h), 0) != (ssize_t)sizeof(in.h)) return mfx_fail(MFX_E_FORMAT, "'%s': truncated header", path);
   if (const char *why = flat_header_problem(in.h, fsize)) return mfx_fail(MFX_E_FORMAT, "'%s': %s", path, why);
   if (in.h.flags & FLAT_PLACED)
-    return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a placed database; the inputs are sorted by k-mer: merge those, then place the result (merfin -convert -placed)", path);
+    return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a placed database; the inputs are sorted by k-mer: merge those, then place the result (merfin -convert -placed)", who, path);
   if (in.h.n == 0) return MFX_OK;                               // (no k-mers: what mfx_db_write_flat writes for none has no blocks in any form)
   if (!(in.h.flags & FLAT_DELTA))
-    return mfx_fail(MFX_E_FORMAT, "mfx_db_merge: '%s' is a %s flat file, not a sorted one: run `merfin -convert` first", path, (in.h.flags & FLAT_PACKED) ? "packed" : "plain");
+    return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a %s flat file, not a sorted one: run `merfin -convert` first", who, path, (in.h.flags & FLAT_PACKED) ? "packed" : "plain");
   uint64_t expect = 0;
   if (int rc = read_delta_directory(in.fd, path, in.h, fsize, in.dir, &in.nblocks, &expect)) return rc;
   const uint64_t ne = in.h.n_escape;
@@ -2187,41 +2189,162 @@ static int merge_check(const char *const *in_paths, uint32_t n_in, const char *o
   return MFX_OK;
 }
 
+// ---- what mfx_db_merge and mfx_db_join_* share: the windows of the opened inputs, and a window's blocks decoded into one dense run per input
+namespace {
+struct MergeWindows {                                          // the plan (mfx_merge.h) and what the largest window takes
+  std::vector<mfx_merge_input> pin;
+  std::vector<mfx_merge_window> win;
+  std::vector<uint64_t> blk;
+  uint64_t n_all = 0, max_pairs = 0, max_bytes = 0, max_tasks = 0, max_esc = 0;
+};
+struct MergeRun { uint64_t off, len; };
+struct MergeDecoder {                                          // a window's way from the files to the runs; the caller owns the device buffers
+  void *d_words = nullptr;                                     // max_bytes + 8: the window's blocks
+  mfx_merge_task *d_tasks = nullptr;                           // max_tasks
+  uint32_t *d_below = nullptr, *d_above = nullptr, *d_err = nullptr;      // max_tasks, max_tasks, one per input
+  uint64_t *d_ek = nullptr;                                    // max_esc + 1: the window's escapes
+  uint32_t *d_ev = nullptr;
+  void *pinned = nullptr;                                      // max_bytes + 8 on the host: the blocks on their way to the device
+  std::vector<mfx_merge_task> tasks;
+  std::vector<uint64_t> hek, run_off, run_len, first_task;
+  std::vector<uint32_t> hev, cnt, errs;
+  std::vector<MergeRun> runs;                                  // per input: its dense run of the window in the decoded buffer
+  double t_read = 0, t_decode = 0;                             // of the last window
+  MergeDecoder() = default;
+  MergeDecoder(const MergeDecoder &) = delete;
+  MergeDecoder &operator=(const MergeDecoder &) = delete;
+  ~MergeDecoder() { if (pinned) (void)hipHostFree(pinned); }
+};
+}  // namespace
+
+static uint64_t merge_range_knob() {
+  uint64_t R = MFX_MERGE_RANGE_DEFAULT;
+  if (const char *e = getenv("MFX_MERGE_RANGE")) {             // read per call: tests reach many windows on small files
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
+  }
+  return R;
+}
+
+static int merge_plan_windows(const std::vector<std::unique_ptr<MergeIn>> &ins, int k, const char *who, MergeWindows &P) {
+  const uint32_t n_in = (uint32_t)ins.size();
+  P.pin.resize(n_in);
+  for (uint32_t i = 0; i < n_in; ++i) { P.pin[i] = mfx_merge_input{ins[i]->dir.data(), 2u, ins[i]->nblocks, ins[i]->h.n}; P.n_all += ins[i]->h.n; }
+  mfx_merge_plan(P.pin.data(), n_in, k, merge_range_knob(), P.win, P.blk);
+  for (size_t w = 0; w < P.win.size(); ++w) {
+    uint64_t bytes = 0, tasks = 0, esc = 0;
+    for (uint32_t i = 0; i < n_in; ++i) {
+      const uint64_t b0 = P.blk[2 * (w * n_in + i)], b1 = P.blk[2 * (w * n_in + i) + 1];
+      if (b1 <= b0) continue;
+      bytes += ins[i]->off(b1) - ins[i]->off(b0);
+      tasks += b1 - b0;
+      uint64_t e0, e1;
+      mfx_merge_escape_slice(ins[i]->ek.data(), ins[i]->ek.size(), P.win[w].lo, P.win[w].hi, &e0, &e1);
+      esc += e1 - e0;
+    }
+    P.max_pairs = std::max(P.max_pairs, P.win[w].pairs); P.max_bytes = std::max(P.max_bytes, bytes);
+    P.max_tasks = std::max(P.max_tasks, tasks); P.max_esc = std::max(P.max_esc, esc);
+  }
+  if (P.max_pairs > 0x7fffffffull || P.max_esc > 0x7fffffffull)
+    return mfx_fail(MFX_E_INVAL, "%s: a window of %lu pairs (at most 2^31 - 1); lower MFX_MERGE_RANGE", who, (unsigned long)P.max_pairs);
+  return MFX_OK;
+}
+
+// window wi: its blocks read (pread) and decoded on the device into keys / vals, D.runs the inputs' dense runs in them.  A block that decodes
+// what no writer makes ends in MFX_E_FORMAT, naming the file.
+static int merge_decode_window(const std::vector<std::unique_ptr<MergeIn>> &ins, const MergeWindows &P, size_t wi, int k, const char *who, MergeDecoder &D,
+                               uint64_t *keys, uint32_t *vals) {
+  const uint32_t n_in = (uint32_t)ins.size();
+  const uint64_t lo = P.win[wi].lo, hi = P.win[wi].hi, END = mfx_merge_end(k);
+  uint64_t *words = (uint64_t *)D.pinned;
+  D.run_off.resize(n_in); D.run_len.resize(n_in); D.first_task.resize(n_in); D.errs.resize(n_in);
+  D.t_read = D.t_decode = 0;
+  double t0 = db_now();
+  // ---- the window's blocks and escapes, input after input
+  D.tasks.clear(); D.hek.clear(); D.hev.clear();
+  uint64_t nwords = 0, npairs = 0;
+  for (uint32_t i = 0; i < n_in; ++i) {
+    const MergeIn &in = *ins[i];
+    const uint64_t b0 = P.blk[2 * (wi * n_in + i)], b1 = P.blk[2 * (wi * n_in + i) + 1];
+    D.run_off[i] = npairs; D.run_len[i] = 0; D.first_task[i] = D.tasks.size();
+    if (b1 <= b0) continue;
+    const uint64_t from = in.off(b0), bytes = in.off(b1) - from;
+    if ((nwords * 8 + bytes) > P.max_bytes) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is read beyond the buffer)
+    for (uint64_t got = 0; got < bytes;) {
+      const ssize_t r = pread(in.fd, (char *)(words + nwords) + got, bytes - got, (off_t)(from + got));
+      if (r <= 0) return mfx_fail(MFX_E_IO, "reading '%s' failed", in.path.c_str());
+      got += (uint64_t)r;
+    }
+    uint64_t e0, e1;
+    mfx_merge_escape_slice(in.ek.data(), in.ek.size(), lo, hi, &e0, &e1);
+    const uint32_t esc_lo = (uint32_t)D.hek.size(), esc_hi = esc_lo + (uint32_t)(e1 - e0);
+    D.hek.insert(D.hek.end(), in.ek.begin() + e0, in.ek.begin() + e1);
+    D.hev.insert(D.hev.end(), in.ev.begin() + e0, in.ev.begin() + e1);
+    for (uint64_t b = b0; b < b1; ++b) {
+      mfx_merge_task t;
+      t.word_off = nwords + (in.off(b) - from) / 8;
+      t.first = in.dir[2 * b];
+      t.limit = b + 1 < in.nblocks ? in.dir[2 * (b + 1)] : END;
+      t.out = npairs + (b - b0) * MFX_DELTA_BLOCK;
+      t.kb = (uint32_t)(in.dir[2 * b + 1] >> 48) & 0xffu;
+      t.vb = (uint32_t)(in.dir[2 * b + 1] >> 56) & 0xffu;
+      t.cnt = (uint32_t)std::min<uint64_t>(MFX_DELTA_BLOCK, in.h.n - b * MFX_DELTA_BLOCK);
+      t.esc_lo = esc_lo; t.esc_hi = esc_hi; t.input = i;
+      D.tasks.push_back(t);
+    }
+    D.run_len[i] = mfx_merge_block_pairs(P.pin[i], b0, b1);
+    npairs += D.run_len[i];
+    nwords += bytes / 8;
+  }
+  const uint32_t nt = (uint32_t)D.tasks.size();
+  if (npairs != P.win[wi].pairs || npairs > P.max_pairs || nwords * 8 > P.max_bytes || nt > P.max_tasks || D.hek.size() > P.max_esc)
+    return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is decoded beyond the buffers)
+  MFX_HIP(hipMemcpyAsync(D.d_words, words, nwords * 8, hipMemcpyHostToDevice, nullptr));
+  MFX_HIP(hipMemcpyAsync(D.d_tasks, D.tasks.data(), nt * sizeof(mfx_merge_task), hipMemcpyHostToDevice, nullptr));
+  if (!D.hek.empty()) {
+    MFX_HIP(hipMemcpyAsync(D.d_ek, D.hek.data(), D.hek.size() * 8, hipMemcpyHostToDevice, nullptr));
+    MFX_HIP(hipMemcpyAsync(D.d_ev, D.hev.data(), D.hev.size() * 4, hipMemcpyHostToDevice, nullptr));
+  }
+  MFX_HIP(hipMemsetAsync(D.d_err, 0, n_in * 4, nullptr));
+  MFX_HIP(hipStreamSynchronize(nullptr));                      // (the host arrays are filled again for the next window)
+  double t1 = db_now();
+  D.t_read = t1 - t0;
+  // ---- decode: one ascending run per input
+  MFX_HIP(mfx_k_delta_decode(D.d_tasks, nt, (const uint64_t *)D.d_words, D.d_ek, D.d_ev, lo, hi, keys, vals, D.d_below, D.d_above, D.d_err, nullptr));
+  D.cnt.resize(2 * (size_t)nt);
+  MFX_HIP(hipMemcpyAsync(D.cnt.data(), D.d_below, nt * 4, hipMemcpyDeviceToHost, nullptr));
+  MFX_HIP(hipMemcpyAsync(D.cnt.data() + nt, D.d_above, nt * 4, hipMemcpyDeviceToHost, nullptr));
+  MFX_HIP(hipMemcpyAsync(D.errs.data(), D.d_err, n_in * 4, hipMemcpyDeviceToHost, nullptr));
+  MFX_HIP(hipStreamSynchronize(nullptr));
+  D.t_decode = db_now() - t1;
+  for (uint32_t i = 0; i < n_in; ++i)
+    if (D.errs[i])
+      return mfx_fail(MFX_E_FORMAT, "'%s': a block holds what no writer makes (%s%s%s): the file is damaged", ins[i]->path.c_str(),
+                      (D.errs[i] & MFX_MERGE_ERR_ORDER) ? "k-mers that do not ascend below the next block's first; " : "",
+                      (D.errs[i] & MFX_MERGE_ERR_ESCAPE) ? "an escaped count that is not in the escape list; " : "", (D.errs[i] & MFX_MERGE_ERR_ZERO) ? "a count of zero; " : "");
+  D.runs.clear();
+  for (uint32_t i = 0; i < n_in; ++i) {
+    const uint64_t f = D.first_task[i], l = (i + 1 < n_in ? D.first_task[i + 1] : nt);
+    MergeRun r{0, 0};
+    // (ascending k-mers below every block's limit: only an input's first block reaches under lo, only its last to hi and beyond)
+    if (!mfx_join_trim(D.run_off[i], D.run_len[i], D.cnt.data() + f, D.cnt.data() + nt + f, l - f, &r.off, &r.len))
+      return mfx_fail(MFX_E_FORMAT, "'%s': the k-mers of a block lie outside its place in the directory", ins[i]->path.c_str());
+    D.runs.push_back(r);
+  }
+  return MFX_OK;
+}
+
 static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
   const char *who = "mfx_db_merge";
   if (st) memset(st, 0, sizeof(*st));
   std::vector<std::unique_ptr<MergeIn>> ins;
   if (int rc = merge_check(in_paths, n_in, out_path, o, ins)) return rc;
   const int k = (int)ins[0]->h.k;
-  const uint64_t END = mfx_merge_end(k);
-  uint64_t R = MFX_MERGE_RANGE_DEFAULT;
-  if (const char *e = getenv("MFX_MERGE_RANGE")) {             // read per call: tests reach many windows on small files
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
-  }
   // ---- the windows, and what the largest of them takes
-  std::vector<mfx_merge_input> pin(n_in);
-  uint64_t n_all = 0;
-  for (uint32_t i = 0; i < n_in; ++i) { pin[i] = mfx_merge_input{ins[i]->dir.data(), 2u, ins[i]->nblocks, ins[i]->h.n}; n_all += ins[i]->h.n; }
-  std::vector<mfx_merge_window> win;
-  std::vector<uint64_t> blk;
-  mfx_merge_plan(pin.data(), n_in, k, R, win, blk);
-  uint64_t max_pairs = 0, max_bytes = 0, max_tasks = 0, max_esc = 0;
-  for (size_t w = 0; w < win.size(); ++w) {
-    uint64_t bytes = 0, tasks = 0, esc = 0;
-    for (uint32_t i = 0; i < n_in; ++i) {
-      const uint64_t b0 = blk[2 * (w * n_in + i)], b1 = blk[2 * (w * n_in + i) + 1];
-      if (b1 <= b0) continue;
-      bytes += ins[i]->off(b1) - ins[i]->off(b0);
-      tasks += b1 - b0;
-      uint64_t e0, e1;
-      mfx_merge_escape_slice(ins[i]->ek.data(), ins[i]->ek.size(), win[w].lo, win[w].hi, &e0, &e1);
-      esc += e1 - e0;
-    }
-    max_pairs = std::max(max_pairs, win[w].pairs); max_bytes = std::max(max_bytes, bytes);
-    max_tasks = std::max(max_tasks, tasks); max_esc = std::max(max_esc, esc);
-  }
-  if (max_pairs > 0x7fffffffull || max_esc > 0x7fffffffull) return mfx_fail(MFX_E_INVAL, "%s: a window of %lu pairs (at most 2^31 - 1); lower MFX_MERGE_RANGE", who, (unsigned long)max_pairs);
+  MergeWindows P;
+  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
+  const std::vector<mfx_merge_window> &win = P.win;
+  const uint64_t n_all = P.n_all, max_pairs = P.max_pairs, max_bytes = P.max_bytes, max_tasks = P.max_tasks, max_esc = P.max_esc;
   mfx_db_writer *w = nullptr;
   if (int rc = db_open_streamed(out_path, k, &w)) return rc;
   WriterAbort guard{w};
@@ -2255,91 +2378,19 @@ static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const c
     StreamDev S;
     if (int rc = stream_dev_init(S, w, cap, who, "MFX_MERGE_RANGE")) return rc;
     const bool timing = getenv("MFX_DB_TIMING") != nullptr;
-    std::vector<mfx_merge_task> tasks;
-    struct Pinned { void *p = nullptr; ~Pinned() { if (p) (void)hipHostFree(p); } } pinned;      // the window's blocks on their way from the files to the device
-    MFX_HIP(hipHostMalloc(&pinned.p, max_bytes + 8, hipHostMallocDefault));
-    uint64_t *words = (uint64_t *)pinned.p;
-    std::vector<uint64_t> hek, run_off(n_in), run_len(n_in), first_task(n_in);
-    std::vector<uint32_t> hev, cnt, errs(n_in);
-    struct Run { uint64_t off, len; };
-    std::vector<Run> runs, next;
+    MergeDecoder dec;
+    dec.d_words = D.p[2]; dec.d_tasks = d_tasks; dec.d_below = d_below; dec.d_above = d_above; dec.d_err = d_err;
+    dec.d_ek = (uint64_t *)D.p[4]; dec.d_ev = (uint32_t *)D.p[5];
+    MFX_HIP(hipHostMalloc(&dec.pinned, max_bytes + 8, hipHostMallocDefault));
+    typedef MergeRun Run;
+    std::vector<Run> &runs = dec.runs, next;
     for (size_t wi = 0; wi < win.size(); ++wi) {
       if (win[wi].pairs == 0) continue;
-      const uint64_t lo = win[wi].lo, hi = win[wi].hi;
-      double t0 = db_now();
-      // ---- the window's blocks and escapes, input after input
-      tasks.clear(); hek.clear(); hev.clear();
-      uint64_t nwords = 0, npairs = 0;
-      for (uint32_t i = 0; i < n_in; ++i) {
-        const MergeIn &in = *ins[i];
-        const uint64_t b0 = blk[2 * (wi * n_in + i)], b1 = blk[2 * (wi * n_in + i) + 1];
-        run_off[i] = npairs; run_len[i] = 0; first_task[i] = tasks.size();
-        if (b1 <= b0) continue;
-        const uint64_t from = in.off(b0), bytes = in.off(b1) - from;
-        if ((nwords * 8 + bytes) > max_bytes) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is read beyond the buffer)
-        for (uint64_t got = 0; got < bytes;) {
-          const ssize_t r = pread(in.fd, (char *)(words + nwords) + got, bytes - got, (off_t)(from + got));
-          if (r <= 0) return mfx_fail(MFX_E_IO, "reading '%s' failed", in.path.c_str());
-          got += (uint64_t)r;
-        }
-        uint64_t e0, e1;
-        mfx_merge_escape_slice(in.ek.data(), in.ek.size(), lo, hi, &e0, &e1);
-        const uint32_t esc_lo = (uint32_t)hek.size(), esc_hi = esc_lo + (uint32_t)(e1 - e0);
-        hek.insert(hek.end(), in.ek.begin() + e0, in.ek.begin() + e1);
-        hev.insert(hev.end(), in.ev.begin() + e0, in.ev.begin() + e1);
-        for (uint64_t b = b0; b < b1; ++b) {
-          mfx_merge_task t;
-          t.word_off = nwords + (in.off(b) - from) / 8;
-          t.first = in.dir[2 * b];
-          t.limit = b + 1 < in.nblocks ? in.dir[2 * (b + 1)] : END;
-          t.out = npairs + (b - b0) * MFX_DELTA_BLOCK;
-          t.kb = (uint32_t)(in.dir[2 * b + 1] >> 48) & 0xffu;
-          t.vb = (uint32_t)(in.dir[2 * b + 1] >> 56) & 0xffu;
-          t.cnt = (uint32_t)std::min<uint64_t>(MFX_DELTA_BLOCK, in.h.n - b * MFX_DELTA_BLOCK);
-          t.esc_lo = esc_lo; t.esc_hi = esc_hi; t.input = i;
-          tasks.push_back(t);
-        }
-        run_len[i] = mfx_merge_block_pairs(pin[i], b0, b1);
-        npairs += run_len[i];
-        nwords += bytes / 8;
-      }
-      const uint32_t nt = (uint32_t)tasks.size();
-      if (npairs != win[wi].pairs || npairs > max_pairs || nwords * 8 > max_bytes || nt > max_tasks || hek.size() > max_esc)
-        return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is decoded beyond the buffers)
-      MFX_HIP(hipMemcpyAsync(D.p[2], words, nwords * 8, hipMemcpyHostToDevice, nullptr));
-      MFX_HIP(hipMemcpyAsync(d_tasks, tasks.data(), nt * sizeof(mfx_merge_task), hipMemcpyHostToDevice, nullptr));
-      if (!hek.empty()) {
-        MFX_HIP(hipMemcpyAsync(D.p[4], hek.data(), hek.size() * 8, hipMemcpyHostToDevice, nullptr));
-        MFX_HIP(hipMemcpyAsync(D.p[5], hev.data(), hev.size() * 4, hipMemcpyHostToDevice, nullptr));
-      }
-      MFX_HIP(hipMemsetAsync(d_err, 0, n_in * 4, nullptr));
-      MFX_HIP(hipStreamSynchronize(nullptr));                  // (the host arrays are filled again for the next window)
-      double t1 = db_now();
-      w->t_read += t1 - t0;
-      // ---- decode: one ascending run per input in buffer 0
-      MFX_HIP(mfx_k_delta_decode(d_tasks, nt, (const uint64_t *)D.p[2], (const uint64_t *)D.p[4], (const uint32_t *)D.p[5], lo, hi, bk[0], bv[0], d_below, d_above, d_err, nullptr));
-      cnt.resize(2 * (size_t)nt);
-      MFX_HIP(hipMemcpyAsync(cnt.data(), d_below, nt * 4, hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipMemcpyAsync(cnt.data() + nt, d_above, nt * 4, hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipMemcpyAsync(errs.data(), d_err, n_in * 4, hipMemcpyDeviceToHost, nullptr));
-      MFX_HIP(hipStreamSynchronize(nullptr));
-      t0 = db_now();
-      w->t_decode += t0 - t1;
-      for (uint32_t i = 0; i < n_in; ++i)
-        if (errs[i])
-          return mfx_fail(MFX_E_FORMAT, "'%s': a block holds what no writer makes (%s%s%s): the file is damaged", ins[i]->path.c_str(),
-                          (errs[i] & MFX_MERGE_ERR_ORDER) ? "k-mers that do not ascend below the next block's first; " : "",
-                          (errs[i] & MFX_MERGE_ERR_ESCAPE) ? "an escaped count that is not in the escape list; " : "", (errs[i] & MFX_MERGE_ERR_ZERO) ? "a count of zero; " : "");
-      runs.clear();
-      for (uint32_t i = 0; i < n_in; ++i) {
-        const uint64_t f = first_task[i], l = (i + 1 < n_in ? first_task[i + 1] : nt);
-        uint64_t below = 0, above = 0;
-        for (uint64_t j = f; j < l; ++j) { below += cnt[j]; above += cnt[nt + j]; }
-        // (ascending k-mers below every block's limit: only an input's first block reaches under lo, only its last to hi and beyond)
-        if (below + above > run_len[i] || (l > f && (below != cnt[f] || above != cnt[nt + l - 1])))
-          return mfx_fail(MFX_E_FORMAT, "'%s': the k-mers of a block lie outside its place in the directory", ins[i]->path.c_str());
-        runs.push_back(Run{run_off[i] + below, run_len[i] - below - above});
-      }
+      // ---- read and decode: one ascending run per input in buffer 0
+      const int rc_dec = merge_decode_window(ins, P, wi, k, who, dec, bk[0], bv[0]);
+      w->t_read += dec.t_read; w->t_decode += dec.t_decode;
+      if (rc_dec) return rc_dec;
+      double t0 = db_now(), t1;
       // ---- merge: a pairwise tree, from one buffer to the other
       int cur = 0;
       while (runs.size() > 1) {
@@ -2387,6 +2438,173 @@ extern "C" int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const ch
   try { return mfx_db_merge_impl(in_paths, n_in, out_path, o, st); }                   // (nothing leaves the C ABI as an exception)
   catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge: out of memory"); }
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge: %s", e.what()); }
+}
+
+// ---------------------------------------------------------------------------
+// mfx_db_join_*: -completeness and -spectrum from two sorted databases, window by window (include/merfin_amd.h).  mfx_db_merge's windows and
+// decode, then mfx_join_kernel (mfx_join.hip): the join ends in the piece sums or in the image, nothing is merged into memory or written.
+// ---------------------------------------------------------------------------
+namespace { enum JoinKind { JOIN_COMPLETENESS, JOIN_SPECTRUM }; }
+
+static int db_join_impl(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, JoinKind kind, double *total64, double *undrcpy64, uint64_t *img,
+                        uint64_t *n_entries, mfx_db_join_stats *st) {
+  const char *who = kind == JOIN_COMPLETENESS ? "mfx_db_join_completeness" : "mfx_db_join_spectrum";
+  const double t_begin = db_now();
+  if (st) memset(st, 0, sizeof(*st));
+  // ---- every check that needs no device
+  if (!read_path || !asm_path || !o || (kind == JOIN_COMPLETENESS ? (!total64 || !undrcpy64) : (!img || !n_entries))) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if (kind == JOIN_COMPLETENESS && o->n_prob && (!o->probK || !o->probP)) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if (kind == JOIN_SPECTRUM) {                                 // (mfx_spectrum_run's bounds and texts)
+    if (o->copies < MFX_SPEC_MIN_COPIES || o->copies > MFX_SPEC_MAX_COPIES)
+      return mfx_fail(MFX_E_INVAL, "%s: copies = %u is outside [%u, %u]", who, o->copies, MFX_SPEC_MIN_COPIES, MFX_SPEC_MAX_COPIES);
+    if (o->max_mult < MFX_SPEC_MIN_MULT || o->max_mult > MFX_SPEC_MAX_MULT)
+      return mfx_fail(MFX_E_INVAL, "%s: max_mult = %u is outside [%u, %u]", who, o->max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
+  }
+  std::vector<std::unique_ptr<MergeIn>> ins;
+  const char *paths[2] = {read_path, asm_path};
+  for (int i = 0; i < 2; ++i) {
+    ins.emplace_back(new MergeIn);
+    mfx_db_info info;                                            // (k > 31 has no sorted form: said as that, not as "a plain flat file")
+    if (detect(paths[i]) == MFX_DB_FLAT && mfx_db_probe_impl(paths[i], &info) == MFX_OK && info.k > MFX_MAX_K_NARROW)
+      return mfx_fail(MFX_E_INVAL, "mfx_db_join: '%s' holds %d-mers: the sorted join takes k <= %d", paths[i], info.k, MFX_MAX_K_NARROW);
+    if (int rc = merge_open_input(paths[i], *ins.back(), "mfx_db_join")) return rc;
+  }
+  if (ins[1]->h.k != ins[0]->h.k)
+    return mfx_fail(MFX_E_INVAL, "mfx_db_join: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", paths[1], ins[1]->h.k, paths[0], ins[0]->h.k);
+  const int k = (int)ins[0]->h.k;
+  MergeWindows P;
+  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
+  const size_t cells = kind == JOIN_SPECTRUM ? (size_t)(o->copies + 2u) * (o->max_mult + 1u) : 0;
+  // res: stats word [0] (the k-mers of both), then the 128 piece sums or the image and its entry counter
+  const size_t res_words = 2 + (kind == JOIN_COMPLETENESS ? 128 : cells + 1);
+  std::vector<uint64_t> res(res_words, 0);
+  uint64_t got[2] = {0, 0}, windows = 0;
+  double t_read = 0, t_decode = 0, t_join = 0;
+  if (P.max_pairs) {
+    DeviceBack back;
+    MFX_HIP(hipSetDevice(o->device));
+    // p[0]: one buffer of cap pairs, the k-mers in front of the counts: the decoded runs.  p[1]: the window's blocks.  p[2]: tasks, their below /
+    // above, the inputs' error words.  p[3], p[4]: the window's escapes.  p[5]: the result.  p[6], p[7]: the -prob table.
+    const uint64_t cap = P.max_pairs + 1, small = P.max_tasks * (sizeof(mfx_merge_task) + 8) + 2 * 4 + 64;
+    const size_t np = o->n_prob && kind == JOIN_COMPLETENESS ? o->n_prob : 1;
+    DbDev D;
+    hipError_t e = hipMalloc(&D.p[0], cap * 12);
+    if (e == hipSuccess) e = hipMalloc(&D.p[1], P.max_bytes + 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[2], small);
+    if (e == hipSuccess) e = hipMalloc(&D.p[3], (P.max_esc + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[4], (P.max_esc + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc(&D.p[5], res_words * 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[6], np * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[7], np * sizeof(double));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who, (unsigned long)P.max_pairs,
+                      ((double)cap * 12 + (double)P.max_bytes + (double)P.max_esc * 12 + (double)small + (double)res_words * 8) / 1e9, hipGetErrorString(e));
+    }
+    uint64_t *d_keys = (uint64_t *)D.p[0], *d_res = (uint64_t *)D.p[5];
+    uint32_t *d_vals = (uint32_t *)((char *)D.p[0] + cap * 8);
+    MergeDecoder dec;
+    dec.d_words = D.p[1];
+    dec.d_tasks = (mfx_merge_task *)D.p[2];
+    dec.d_below = (uint32_t *)(dec.d_tasks + P.max_tasks); dec.d_above = dec.d_below + P.max_tasks; dec.d_err = dec.d_above + P.max_tasks;
+    dec.d_ek = (uint64_t *)D.p[3]; dec.d_ev = (uint32_t *)D.p[4];
+    MFX_HIP(hipHostMalloc(&dec.pinned, P.max_bytes + 8, hipHostMallocDefault));
+    MFX_HIP(mfx_memset_now(d_res, 0, res_words * 8));
+    if (kind == JOIN_COMPLETENESS && o->n_prob) {
+      MFX_HIP(hipMemcpy(D.p[6], o->probK, o->n_prob * sizeof(uint32_t), hipMemcpyHostToDevice));
+      MFX_HIP(hipMemcpy(D.p[7], o->probP, o->n_prob * sizeof(double), hipMemcpyHostToDevice));
+    }
+    int cus = 0;
+    MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
+    const int grid = (cus > 0 ? cus : 256) * (kind == JOIN_COMPLETENESS ? 4 : 2);      // the workgroups a CU holds at once (mfx_join.hip: LDS)
+    mfx_spectrum_args sa{};
+    if (kind == JOIN_SPECTRUM) {
+      sa.copies = o->copies;
+      sa.max_mult = o->max_mult;
+      sa.lds_cols = mfx_spec_lds_cols(o->copies, o->max_mult);
+      const char *ag = getenv("MFX_SPECTRUM_AGG");                 // as mfx_spectrum_run reads it (docs/KNOBS.md)
+      sa.aggregate = ag ? (atoi(ag) != 0) : MFX_SPEC_AGG_DEFAULT;
+      sa.img = d_res + 2;
+    }
+    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
+    for (size_t wi = 0; wi < P.win.size(); ++wi) {
+      if (P.win[wi].pairs == 0) continue;
+      // ---- read and decode: the read run and the asm run of the window.  (One stream: the blocks of this window are copied behind the join of
+      // the window before it, whose kernel runs while the host reads.)
+      const int rc = merge_decode_window(ins, P, wi, k, who, dec, d_keys, d_vals);
+      t_read += dec.t_read; t_decode += dec.t_decode;
+      if (rc) return rc;
+      const double t0 = db_now();
+      const MergeRun a = dec.runs[0], b = dec.runs[1];
+      got[0] += a.len; got[1] += b.len;
+      if (kind == JOIN_COMPLETENESS)
+        MFX_HIP(mfx_k_join_completeness(d_keys + a.off, d_vals + a.off, a.len, d_keys + b.off, d_vals + b.off, b.len, k, o->peak, o->n_prob, (const uint32_t *)D.p[6],
+                                        (const double *)D.p[7], reinterpret_cast<double *>(d_res + 2), d_res, grid, nullptr));
+      else
+        MFX_HIP(mfx_k_join_spectrum(d_keys + a.off, d_vals + a.off, a.len, d_keys + b.off, d_vals + b.off, b.len, sa, o->minV, o->maxV, d_res, grid, nullptr));
+      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
+      t_join += db_now() - t0;
+      ++windows;
+    }
+    MFX_HIP(hipMemcpy(res.data(), d_res, res_words * 8, hipMemcpyDeviceToHost));
+  }
+  // ---- what the windows held against what the files say, the image against its counter: no partial result is handed out
+  for (int i = 0; i < 2; ++i)
+    if (got[i] != ins[i]->h.n)
+      return mfx_fail(MFX_E_FORMAT, "'%s': the windows hold %lu of its %lu k-mers: the directory does not describe the blocks", paths[i], (unsigned long)got[i], (unsigned long)ins[i]->h.n);
+  const uint64_t n_both = res[0];
+  if (n_both > got[0] || n_both > got[1]) return mfx_fail(MFX_E_HIP, "%s: %lu k-mers in both inputs, more than an input holds", who, (unsigned long)n_both);
+  if (kind == JOIN_SPECTRUM) {
+    uint64_t sum = 0;
+    for (size_t i = 0; i < cells; ++i) sum += res[2 + i];
+    if (sum != res[2 + cells]) return mfx_fail(MFX_E_HIP, "%s: the image sums to %lu, the join counted %lu entries", who, (unsigned long)sum, (unsigned long)res[2 + cells]);
+    const bool filtered = o->minV > 1 || o->maxV < 0xffffffffull;      // (a count is 1 at the least: no other filter makes a pair (0, 0))
+    if (!filtered && sum != got[0] + got[1] - n_both)
+      return mfx_fail(MFX_E_HIP, "%s: the join counted %lu entries, the inputs hold %lu distinct k-mers", who, (unsigned long)sum, (unsigned long)(got[0] + got[1] - n_both));
+    memcpy(img, res.data() + 2, cells * 8);
+    *n_entries = sum;
+  } else {
+    memcpy(total64, res.data() + 2, 64 * sizeof(double));
+    memcpy(undrcpy64, res.data() + 2 + 64, 64 * sizeof(double));
+  }
+  if (st) {
+    st->n_read = got[0]; st->n_asm = got[1]; st->n_both = n_both; st->windows = windows;
+    st->t_read = t_read; st->t_decode = t_decode; st->t_join = t_join; st->t_total = db_now() - t_begin;
+  }
+  return MFX_OK;
+}
+
+extern "C" int mfx_db_join_completeness(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, double *total64, double *undrcpy64, mfx_db_join_stats *st) {
+  try { return db_join_impl(read_path, asm_path, o, JOIN_COMPLETENESS, total64, undrcpy64, nullptr, nullptr, st); }      // (nothing leaves the C ABI as an exception)
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_completeness: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_join_completeness: %s", e.what()); }
+}
+
+extern "C" int mfx_db_join_spectrum(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, uint64_t *img, uint64_t *n_entries, mfx_db_join_stats *st) {
+  try { return db_join_impl(read_path, asm_path, o, JOIN_SPECTRUM, nullptr, nullptr, img, n_entries, st); }
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_spectrum: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_join_spectrum: %s", e.what()); }
+}
+
+extern "C" void mfx_db_join_grain(uint32_t *per_lane, uint32_t *tile) {
+  if (per_lane) *per_lane = MFX_JOIN_PER;
+  if (tile) *tile = MFX_JOIN_TILE;
+}
+
+extern "C" int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *asm_keys, const uint32_t *asm_vals, uint64_t n_asm,
+                                uint64_t *keys, uint32_t *readV, uint32_t *asmV, uint64_t cap, uint64_t *n_pairs) {
+  if ((n_read && (!read_keys || !read_vals)) || (n_asm && (!asm_keys || !asm_vals)) || !n_pairs || (cap && (!keys || !readV || !asmV)))
+    return mfx_fail(MFX_E_INVAL, "mfx_db_join_host: null argument");
+  uint64_t n = 0;
+  try {
+    mfx_join_host(read_keys, read_vals, n_read, asm_keys, asm_vals, n_asm, [&](bool have, uint64_t key, uint32_t rv, uint32_t av) {
+      if (!have) return;
+      if (n < cap) { keys[n] = key; readV[n] = rv; asmV[n] = av; }
+      ++n;
+    });
+  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_host: out of memory"); }
+  *n_pairs = n;
+  return MFX_OK;
 }
 
 extern "C" int mfx_db_merge_plan(const uint64_t *const *first, const uint64_t *n, uint32_t n_in, int k, uint64_t R, uint64_t *out, uint64_t cap, uint64_t *n_windows) {

@@ -248,5 +248,13 @@ hipError_t mfx_k_merge_pairs(const uint64_t *ka, const uint32_t *va, uint64_t la
 uint64_t mfx_combine_tiles(uint64_t n);
 hipError_t mfx_k_combine(const uint64_t *keys, const uint32_t *vals, uint64_t n, uint32_t n_in, int op, uint64_t minV, uint64_t maxV, uint64_t *tile_off,
                          uint64_t *out_keys, uint32_t *out_vals, uint64_t *stats, hipStream_t st);
+// mfx_db_join_* (mfx_join.hip): the sorted join of a read run a and an asm run b, both strictly ascending, into -completeness' piece sums
+// (pieces[128], added to) or the -spectrum image (a.img, added to; a.t takes no part); stats[0] += the k-mers both runs hold.  grid: the
+// persistent workgroups.
+struct mfx_spectrum_args;
+hipError_t mfx_k_join_completeness(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, int k, double peak,
+                                   uint32_t n_prob, const uint32_t *probK, const double *probP, double *pieces, uint64_t *stats, int grid, hipStream_t st);
+hipError_t mfx_k_join_spectrum(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, const mfx_spectrum_args &a,
+                               uint64_t minV, uint64_t maxV, uint64_t *stats, int grid, hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);

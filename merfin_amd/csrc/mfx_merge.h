@@ -21,6 +21,24 @@ constexpr uint32_t MFX_MERGE_MAX_INPUTS = 64;
 struct mfx_merge_input { const uint64_t *first; uint32_t stride; uint64_t nblocks, n; };
 struct mfx_merge_window { uint64_t lo, hi, pairs; };            // pairs: what the window's blocks hold, summed over the inputs
 
+#if defined(__HIPCC__)
+#define MFX_MERGE_HD __host__ __device__ inline __attribute__((always_inline))      // (no HIP header needed)
+#else
+#define MFX_MERGE_HD inline
+#endif
+
+// merge path: how many of the first d pairs of two ascending runs merged come from a (la of them) -- with equal k-mers a's first.  The merge
+// kernel and the join kernel (mfx_merge.hip, mfx_join.hip) cut their tiles and their lanes' shares with it, mfx_join.h restates both on the host.
+template <class I>
+MFX_MERGE_HD I mfx_merge_cut(const uint64_t *a, I la, const uint64_t *b, I lb, I d) {
+  I x = d > lb ? d - lb : 0, y = d < la ? d : la;
+  while (x < y) {
+    const I m = x + (y - x) / 2;
+    if (a[m] <= b[d - 1 - m]) x = m + 1; else y = m;
+  }
+  return x;
+}
+
 inline uint64_t mfx_merge_end(int k) { return 1ull << (2 * k); }      // k <= 31: one past the largest k-mer
 
 // the blocks [b0, b1) of an input that may hold a k-mer of [lo, hi): from the last block that starts at or below lo (its k-mers reach up to

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mfx_device.h"
+#include "mfx_merge.h"                                         // mfx_merge_cut
 
 // ---------------------------------------------------------------------------
 // mfx_delta_decode_kernel: one workgroup per (input, block) of a window; the decode is mfx_table_add_delta_kernel's (mfx_device.h).  The
@@ -71,17 +72,6 @@ __global__ __launch_bounds__(256) void mfx_delta_decode_kernel(const mfx_merge_t
 // ---------------------------------------------------------------------------
 constexpr uint32_t MFX_MERGE_PER = 8;
 constexpr uint32_t MFX_MERGE_TILE = 256u * MFX_MERGE_PER;
-
-// how many of the first d merged pairs come from a (la of them) -- with equal k-mers a's first
-template <class I>
-__device__ __forceinline__ I mfx_merge_cut(const uint64_t *a, I la, const uint64_t *b, I lb, I d) {
-  I x = d > lb ? d - lb : 0, y = d < la ? d : la;
-  while (x < y) {
-    const I m = x + (y - x) / 2;
-    if (a[m] <= b[d - 1 - m]) x = m + 1; else y = m;
-  }
-  return x;
-}
 
 __global__ __launch_bounds__(256) void mfx_merge_pairs_kernel(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb,
                                                               uint64_t lb, uint64_t *ko, uint32_t *vo) {
