@@ -459,6 +459,11 @@ uint64_t mfx_seq_num_bases(const mfx_seq *s);
 /* work units (contig-aligned position tiles) -- the sharding granule for
  * multi-GPU runs: rank r of N evaluates tiles [T*r/N, T*(r+1)/N). */
 uint64_t mfx_seq_num_tiles(const mfx_seq *s);
+/* 1: the evaluations of this sequence read its packed planes (2-bit codes + validity bits, 0.375 B per base) -- a packed upload,
+ * mfx_seq_pack, a replica, and every resident sequence the library made its own copy of (mfx_seq_from_device, the one-byte-per-base
+ * mfx_seq_upload): the planes are made once, where the copy is made, unless MFX_SEQ_PACK=0 or the device has no room for them;
+ * 0: its launches encode their tiles from one byte per base */
+int      mfx_seq_is_packed(const mfx_seq *s);
 
 /* ------------------------------------------------------------------------ */
 /* Evaluator: the K* parameters of merfinGlobal (merfin-globals.H:222-239)  */

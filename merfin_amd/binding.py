@@ -83,7 +83,7 @@ SYMBOLS = [
     "mfx_hist_allreduce", "mfx_hist_allgather_overflow", "mfx_hist_result_add_overflow",
     "mfx_index_image_header", "mfx_index_create_from_header", "mfx_index_device_image", "mfx_index_commit",
     "mfx_seq_upload", "mfx_seq_from_device", "mfx_seq_free", "mfx_seq_num_contigs", "mfx_seq_num_bases",
-    "mfx_seq_num_tiles",
+    "mfx_seq_num_tiles", "mfx_seq_is_packed",
     "mfx_diag_gather_rate",
     "mfx_eval_create", "mfx_eval_free", "mfx_eval_nbins", "mfx_eval_debug_enable", "mfx_eval_debug_counters", "mfx_eval_debug_worklist", "mfx_eval_debug_worklist_read", "mfx_getK", "mfx_getKmetric", "mfx_histoQV",
     "mfx_hist_run", "mfx_hist_result_free", "mfx_hist_launch", "mfx_hist_launch_cyclic", "mfx_hist_result_from_counts",
@@ -1048,6 +1048,13 @@ class Sequences:
     def pack(self):
         """build the packed planes (2-bit codes + validity bits) from the resident bases, on the device"""
         _check(load_library().mfx_seq_pack(self.h))
+
+    @property
+    def packed(self):
+        """the evaluations read the packed planes (made once for every resident sequence; MFX_SEQ_PACK=0: not made), not one byte per base"""
+        f = load_library().mfx_seq_is_packed           # (looked up here: an A/B library of older sources, MFX_LIB, has no such symbol)
+        f.argtypes = [C.c_void_p]
+        return bool(f(self.h))
 
     @property
     def ncontigs(self):

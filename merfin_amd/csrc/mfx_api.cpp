@@ -1514,6 +1514,32 @@ int mfx_check_seq_of_index(const mfx_index *ix, const mfx_seq *s, const char *wh
 
 static int seq_upload_packed(mfx_seq *seq, const char *const *bases);
 
+// A sequence that has just been copied into d_bases (the library's own copy: nobody rewrites it) gets its packed planes here, once
+// (mfx_seq_planes_once, mfx_internal.h): the resident -hist of 3 Gb read 3.05 GB of bytes and spent ~12 of its 200 wave instructions per
+// k-mer encoding them, on every launch.  MFX_SEQ_PACK=0: the sequence stays one byte per base (A/B; docs/KNOBS.md).  The object is
+// not shared yet: no lock.  Never fails -- without room for the planes the sequence is evaluated from its bytes.
+static void seq_pack_resident(mfx_seq *s) {
+  const char *e = getenv("MFX_SEQ_PACK");
+  if ((e && atoi(e) == 0) || !s->d_bases) return;
+  const bool timing = getenv("MFX_UPLOAD_TIMING") != nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t pw = seq_plane_words(s);
+  const bool ok = mfx_seq_planes_once(
+      s, pw,
+      [](void **p, size_t bytes) { const bool got = hipMalloc(p, bytes) == hipSuccess; if (!got) { *p = nullptr; (void)hipGetLastError(); } return got; },
+      [](void *p) { (void)hipFree(p); },
+      [pw](mfx_seq *q) {
+        const bool done = mfx_memset_now(q->d_valid, 0, pw * sizeof(uint32_t)) == hipSuccess &&              // no valid base behind the sequence
+                          mfx_memset_now(q->d_codes, 0, pw * sizeof(uint64_t)) == hipSuccess &&
+                          mfx_k_pack(q->d_bases, q->d_codes, q->d_valid, q->buf_bytes / 32, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        if (!done) (void)hipGetLastError();
+        return done;
+      });
+  if (timing)
+    fprintf(stderr, "-- resident sequence: packed planes %s, %.3f s (%.1f MB)\n", ok ? "made" : "NOT made (evaluated from its bytes)",
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), pw * 12 / 1e6);
+}
+
 extern "C" mfx_seq *mfx_seq_upload(int device, const char *const *bases, const uint64_t *lens, uint32_t ncontigs) {
   if ((ncontigs && (!bases || !lens)) || device < 0 || device >= mfx_device_count()) {
     mfx_fail(device < 0 || device >= mfx_device_count() ? MFX_E_NODEVICE : MFX_E_INVAL,
@@ -1607,6 +1633,7 @@ extern "C" mfx_seq *mfx_seq_upload(int device, const char *const *bases, const u
     mfx_seq_free(s);
     return nullptr;
   }
+  seq_pack_resident(s);
   return s;
 }
 
@@ -1630,6 +1657,7 @@ extern "C" mfx_seq *mfx_seq_from_device(int device, const void *const *d_bases, 
     mfx_seq_free(s);
     return nullptr;
   }
+  seq_pack_resident(s);
   return s;
 }
 
@@ -1649,6 +1677,7 @@ extern "C" void mfx_seq_free(mfx_seq *s) {
 extern "C" uint32_t mfx_seq_num_contigs(const mfx_seq *s) { return s ? s->ncontigs : 0; }
 extern "C" uint64_t mfx_seq_num_bases(const mfx_seq *s) { return s ? s->total_bases : 0; }
 extern "C" uint64_t mfx_seq_num_tiles(const mfx_seq *s) { return s ? s->ntiles : 0; }
+extern "C" int mfx_seq_is_packed(const mfx_seq *s) { return s && (s->planes_ok || s->bases_stale) ? 1 : 0; }
 
 // ---------------------------------------------------------------------------
 // evaluator

@@ -208,6 +208,31 @@ struct mfx_seq {
   mutable uint32_t digest = 0;       // content digest (mfx_seq_digest32), computed on first use; 0: not computed / the content changed
 };
 
+// The planes of a sequence whose bytes the library owns and nobody rewrites (mfx_seq_from_device, the resident one-byte-per-base
+// upload), made ONCE where the copy is made: every -hist / -dump / -track / claim launch then copies its tiles (0.375 B per base)
+// instead of encoding them from d_bases again (1 B per base and ~10 instructions per base, on every tile of every launch).
+// The device work is the caller's: alloc(void **, bytes) -> bool and release(void *) for the two planes, fill(s) -> bool = clear +
+// mfx_k_pack + wait.  No room for the planes (or a failed fill) is NOT an error: both planes are released, planes_ok stays false and
+// the sequence is evaluated from d_bases as before.  d_bases stays either way (the 128-bit kernels and the variant modes read it).
+// Returns whether the planes are there.  (tools/native/seq_planes_check.cpp runs the bookkeeping without a device.)
+template <class Alloc, class Release, class Fill>
+inline bool mfx_seq_planes_once(mfx_seq *s, uint64_t plane_words, Alloc alloc, Release release, Fill fill) {
+  if (s->planes_ok || s->bases_stale) return true;           // (a packed upload, a replica: the planes are the sequence)
+  void *c = s->d_codes, *v = s->d_valid;                     // (planes a streamed run left behind: reused)
+  bool ok = (c || alloc(&c, plane_words * sizeof(uint64_t))) && (v || alloc(&v, plane_words * sizeof(uint32_t)));
+  s->d_codes = static_cast<uint64_t *>(c);
+  s->d_valid = static_cast<uint32_t *>(v);
+  ok = ok && fill(s);
+  if (!ok) {
+    if (c) release(c);
+    if (v) release(v);
+    s->d_codes = nullptr;
+    s->d_valid = nullptr;
+  }
+  s->planes_ok = ok;
+  return ok;
+}
+
 // content digest of a sequence (never 0): contig lengths + the codes and validity of every base, whatever form it is held in
 int mfx_seq_digest32(const mfx_seq *s, uint32_t *out);
 // refuses (MFX_E_INVAL) the evaluation of a sequence other than the one a sequence-only index was claimed from
