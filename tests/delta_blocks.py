@@ -46,7 +46,8 @@ class Raw:
         self.k, self.flags, self.records, self.fields, self.widths, self.escapes = k, flags, records, fields, widths, escapes
 
 
-def decode_raw(path):
+def decode_raw(path, matched=True):
+    """matched=False: a file whose escape fields and escape list do not match (tests/damaged_blocks.py) is read as it is"""
     raw, k, flags, n, n_esc = read_flat(path)
     assert flags & F_DELTA
     (nblocks,) = struct.unpack_from("<Q", raw, 32)
@@ -73,7 +74,7 @@ def decode_raw(path):
     assert len(raw) == end + 12 * n_esc
     ek = np.frombuffer(raw, dtype="<u8", count=n_esc, offset=end).tolist()
     ev = np.frombuffer(raw, dtype="<u4", count=n_esc, offset=end + 8 * n_esc).tolist()
-    assert sum(f is None for f in fields) == n_esc
+    assert not matched or sum(f is None for f in fields) == n_esc
     return Raw(k, flags, records, fields, widths, list(zip(ek, ev)))
 
 

@@ -48,6 +48,11 @@ def _check(m, tmp_path, k, read, asm, peak=17.3, prob=None, copies=4, max_mult=1
     rp, ap = str(tmp_path / (tag + "_r.mfxk")), str(tmp_path / (tag + "_a.mfxk"))
     m.db_write_flat(rp, k, read[0], read[1])
     m.db_write_flat(ap, k, asm[0], asm[1])
+    return check_paths(m, k, rp, ap, read, asm, peak, prob, copies, max_mult, lo, hi, table, tag)
+
+
+def check_paths(m, k, rp, ap, read, asm, peak=17.3, prob=None, copies=4, max_mult=10000, lo=0, hi=TOP, table=True, tag="x"):
+    """... of two files that exist, whoever wrote them: rp holds the arrays read, ap the arrays asm"""
     kp = m.KParams(peak, *(prob or (None, None)))
     t, u, st = m.db_join_completeness(rp, ap, kp, with_stats=True, min_count=lo, max_count=hi)
     wt, wu = _want_completeness(k, peak, prob, read, asm)

@@ -65,6 +65,11 @@ def _bytes(path):
 def _check(m, tmp_path, k, inputs, op, lo=0, hi=TOP, load_back=True, tag="x"):
     """one merge against the reference: the bytes, the stats, no spool, the inputs unchanged, the file through the decode kernel"""
     paths = [_write(m, tmp_path / ("%s_in%d.mfxk" % (tag, i)), k, a, b) for i, (a, b) in enumerate(inputs)]
+    return check_paths(m, tmp_path, k, paths, inputs, op, lo, hi, load_back, tag)
+
+
+def check_paths(m, tmp_path, k, paths, inputs, op, lo=0, hi=TOP, load_back=True, tag="x"):
+    """... of input files that exist, whoever wrote them: paths[i] holds the arrays inputs[i]"""
     before = [_bytes(p) for p in paths]
     rk, rv, nfilt, nsat = reference(inputs, op, lo, hi)
     want = _bytes(_write(m, tmp_path / (tag + "_want.mfxk"), k, rk, rv))
