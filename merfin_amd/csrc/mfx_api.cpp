@@ -7,6 +7,8 @@
 #include "mfx_place.h"
 #include "mfx_kernels.h"
 #include "mfx_pipe.h"
+#include "mfx_pool.h"
+#include "mfx_stream_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -15,15 +17,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
-#include <sched.h>
-#include <pthread.h>
-#include <sys/syscall.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <memory>
-#include <map>
 #include <mutex>
 #include <functional>
 #include <condition_variable>
@@ -136,61 +134,6 @@ extern "C" int mfx_device_count(void) {
   return n;
 }
 
-void mfx_pin_spread(unsigned w);          // pins the calling thread to L3 domain w mod n (all NUMA nodes); defined with the encoder placement below
-
-// Host threads that stay parked between the streamed runs of an evaluator: starting 16 threads costs ~0.45 ms, 1.3 % of a
-// 3 Gb run, waking them ~0.05 ms.
-namespace {
-struct WorkerPool {
-  unsigned W;
-  std::vector<std::thread> th;
-  std::mutex m;
-  std::condition_variable wake, idle;
-  std::function<void(unsigned)> job;
-  uint64_t gen = 0;
-  unsigned running = 0;
-  bool quit = false;
-  // spread: thread i is pinned to L3 domain i mod n of the machine (pack_spread_cpus, below) -- threads that move memory
-  // share their CCD's link to it, and threads started by one parent tend to land next to each other
-  explicit WorkerPool(unsigned w, bool spread = false) : W(w) {
-    for (unsigned i = 0; i < W; ++i)
-      th.emplace_back([this, i, spread]() {
-        if (spread) mfx_pin_spread(i);
-        uint64_t seen = 0;
-        for (;;) {
-          std::function<void(unsigned)> f;
-          {
-            std::unique_lock<std::mutex> lk(m);
-            wake.wait(lk, [&] { return quit || gen != seen; });
-            if (quit) return;
-            seen = gen;
-            f = job;
-          }
-          f(i);
-          std::lock_guard<std::mutex> lk(m);
-          if (--running == 0) idle.notify_all();
-        }
-      });
-  }
-  void start(std::function<void(unsigned)> f) {
-    std::lock_guard<std::mutex> lk(m);
-    job = std::move(f);
-    running = W;
-    ++gen;
-    wake.notify_all();
-  }
-  void wait() {
-    std::unique_lock<std::mutex> lk(m);
-    idle.wait(lk, [&] { return running == 0; });
-  }
-  ~WorkerPool() {
-    { std::lock_guard<std::mutex> lk(m); quit = true; }
-    wake.notify_all();
-    for (auto &t : th) t.join();
-  }
-};
-}  // namespace
-
 namespace {
 // Table fill target.  MFX_LOAD_FACTOR fixes it; otherwise it is chosen per index between MFX_LF_MAX (the least
 // memory a table may take: what mfx_index_estimate_gb reports and -memory is checked against) and MFX_LF_MIN,
@@ -279,7 +222,7 @@ uint64_t side_lines_for(uint64_t capacity_kmers) {
 
 // host-side copy into the pinned staging buffer, split over a few threads for large pieces
 // (a single thread moves ~12 GB/s, well under PCIe Gen5)
-static void par_memcpy(uint8_t *dst, const char *src, size_t n) {
+void par_memcpy(uint8_t *dst, const char *src, size_t n) {
   const unsigned nt = std::min<unsigned>(8u, std::max(1u, mfx_host_threads()));
   if (n < (8u << 20) || nt == 1) { memcpy(dst, src, n); return; }
   std::vector<std::thread> th;
@@ -1394,28 +1337,14 @@ extern "C" int mfx_index_export(const mfx_index *ix, uint64_t *kmers, uint32_t *
 static mfx_seq *seq_layout(int device, const uint64_t *lens, uint32_t ncontigs) {
   mfx_seq *s = new mfx_seq;
   s->device = device;
-  s->ncontigs = ncontigs;
-  s->off.resize(ncontigs);
-  s->len.assign(lens, lens + ncontigs);
-  s->tile_start.resize((size_t)ncontigs + 1);
-  uint64_t o = 0, t = 0;
-  for (uint32_t c = 0; c < ncontigs; ++c) {
-    s->off[c] = o;
-    s->tile_start[c] = t;
-    t += (lens[c] + MFX_TILE - 1) / MFX_TILE;
-    s->total_bases += lens[c];
-    o = (o + lens[c] + 1 + MFX_ALIGN - 1) / MFX_ALIGN * MFX_ALIGN;   // >= 1 separator byte, next contig 128-byte aligned
-  }
-  s->tile_start[ncontigs] = t;
-  s->ntiles = t;
-  s->buf_bytes = o + MFX_TILE + 2 * MFX_ALIGN;                        // tail tiles read one tile + halo past the end
+  seq_layout_fill(s, lens, ncontigs);                                 // mfx_stream_plan.h
   return s;
 }
 
 // One byte per base (mfx_seq::d_bases) is what the 128-bit kernels, -dump, the router and the variant modes read; a sequence
 // that arrives packed and is only ever counted and evaluated by the k <= 31 -hist kernels never needs it (3 GB for a human assembly,
 // 0.05-0.15 s of its upload): it is made on first use (mfx_seq_ensure_ascii).
-static int seq_need_bases(mfx_seq *s) {
+int seq_need_bases(mfx_seq *s) {
   if (s->d_bases) return MFX_OK;
   MFX_HIP(hipMalloc((void **)&s->d_bases, s->buf_bytes));
   MFX_HIP(mfx_memset_now(s->d_bases, 0, s->buf_bytes));                    // byte 0 is not ACGT: separators + padding
@@ -1469,7 +1398,7 @@ int mfx_seq_ensure_ascii(const mfx_seq *cs) {
 }
 
 // h: the device's sum over the words (mfx_seq_digest_kernel)
-static void seq_digest_finish(const mfx_seq *s, uint64_t h) {
+void seq_digest_finish(const mfx_seq *s, uint64_t h) {
   for (uint32_t c = 0; c < s->ncontigs; ++c) h = (h ^ s->len[c]) * 0x100000001B3ULL + c;       // the contig structure
   const uint32_t f = (uint32_t)(h ^ (h >> 32));
   s->digest = f ? f : 1u;
@@ -1511,8 +1440,6 @@ int mfx_check_seq_of_index(const mfx_index *ix, const mfx_seq *s, const char *wh
                     "mfx_index_count_asm / mfx_index_claim_seq) or use a full index", who, ix->seq_digest, d);
   return MFX_OK;
 }
-
-static int seq_upload_packed(mfx_seq *seq, const char *const *bases);
 
 // A sequence that has just been copied into d_bases (the library's own copy: nobody rewrites it) gets its packed planes here, once
 // (mfx_seq_planes_once, mfx_internal.h): the resident -hist of 3 Gb read 3.05 GB of bytes and spent ~12 of its 200 wave instructions per
@@ -1756,7 +1683,7 @@ extern "C" void mfx_eval_free(mfx_eval *ev) {
   if (ev->d_dbg) (void)hipFree(ev->d_dbg);
   for (auto &p : ev->h_stage) if (p) (void)hipHostFree(p);
   for (auto &p : ev->h_pack) if (p) (void)hipHostFree(p);
-  if (ev->pool) delete static_cast<WorkerPool *>(ev->pool);
+  delete ev->pool;
   if (ev->d_var_scratch) (void)hipFree(ev->d_var_scratch);
   if (ev->sr.d_counts) (void)hipFree(ev->sr.d_counts);
   if (ev->sr.d_kover) (void)hipFree(ev->sr.d_kover);
@@ -1841,7 +1768,7 @@ static int eval_canonical(mfx_eval *ev, int *canon) {
   return MFX_OK;
 }
 
-static int ensure_tile_partials(mfx_eval *ev, uint64_t ntiles) {
+int ensure_tile_partials(mfx_eval *ev, uint64_t ntiles) {
   const uint64_t need = mfx_k_tile_partials_words(ntiles);
   if (need > ev->tile_partials_cap) {
     if (ev->d_tile_partials) (void)hipFree(ev->d_tile_partials);
@@ -1875,9 +1802,8 @@ static int ensure_worklist(mfx_eval *ev, int slot, uint64_t ntl) {
 // chunk_of_total  > 0: one chunk of a streamed evaluation over `chunk_of_total` tiles in all: the values land at
 // their tile's place in ev->d_tile_partials (sized by the caller) and are summed ONCE after the last chunk, so
 // koverCpy is bit-identical to a single launch over the whole range, however the upload was cut.
-static int hist_launch(mfx_eval *ev, const mfx_seq *seq, uint64_t tile_begin, uint64_t tile_end, uint32_t part_rank, uint32_t part_n,
-                       uint32_t part_shift, uint64_t *d_counts, double *d_kover, void *stream, uint64_t chunk_of_total = 0, int ctr_slot = 0,
-                       uint64_t partials_tile0 = 0) {
+int hist_launch(mfx_eval *ev, const mfx_seq *seq, uint64_t tile_begin, uint64_t tile_end, uint32_t part_rank, uint32_t part_n,
+                uint32_t part_shift, uint64_t *d_counts, double *d_kover, void *stream, uint64_t chunk_of_total, int ctr_slot, uint64_t partials_tile0) {
   uint64_t ntl = tile_end - tile_begin;
   if (part_n > 1) {
     const uint64_t blk = 1ull << part_shift, nblk = (seq->ntiles + blk - 1) / blk;
@@ -1986,7 +1912,7 @@ extern "C" int mfx_hist_launch_cyclic(mfx_eval *ev, const mfx_seq *seq, uint32_t
 
 // The evaluator's table of far K* bins emptied for the next launches, asynchronously on `st`: what an earlier launch left there
 // and nobody collected is not the next run's.  16 MB of fills: ~10 us of device time.
-static hipError_t ovf_reset_hip(mfx_eval *ev, hipStream_t st) {
+hipError_t ovf_reset_hip(mfx_eval *ev, hipStream_t st) {
   const hipError_t e = hipMemsetAsync(ev->d_ovf, 0, (2 + (size_t)MFX_OVF_SLOTS) * sizeof(uint64_t), st);
   return e != hipSuccess ? e : hipMemsetAsync(ev->d_ovf + 2 + MFX_OVF_SLOTS, 0xff, (size_t)MFX_OVF_SLOTS * sizeof(uint64_t), st);
 }
@@ -2108,7 +2034,7 @@ extern "C" int mfx_hist_result_add_overflow(mfx_hist_result *r, const uint64_t *
 // What a whole-assembly run needs besides the evaluator's tables -- a stream, the counts image, its pinned mirror -- belongs
 // to the evaluator and is made once (mfx_eval::sr): creating and releasing it per call costs ~2.5 ms, which is most of an
 // 8-device evaluation (4 ms of kernel per device at 3 Gb).  The device of `ev` must be current.
-static int eval_run_resources(mfx_eval *ev, size_t words) {
+int eval_run_resources(mfx_eval *ev, size_t words) {
   auto &R = ev->sr;
   if (R.words < words) {
     if (R.d_counts) (void)hipFree(R.d_counts);
@@ -2168,28 +2094,7 @@ int result_take_overflow(mfx_eval *ev, uint64_t novf, mfx_hist_result *out) {
   return result_add_overflow(out, pairs);
 }
 
-// ---------------------------------------------------------------------------
-// Streamed -hist: the assembly arrives as HOST buffers (what loadSequence hands over, merfin.C:30-53) and its
-// upload is overlapped with the evaluation -- SURVEY 8(d)'s timed region "first tile H2D start -> final reduced
-// histogram on host".  The tiles are cut into chunks; chunk i's bytes travel on a copy stream while the -hist
-// kernel of chunk i-1 runs on the compute stream (one event per chunk orders them), and the counts image comes
-// back with one D2H copy at the end.  Buffers from mfx_host_alloc (pinned) are DMA'd in place; pageable buffers
-// go through two pinned staging buffers filled by host threads.
-// ---------------------------------------------------------------------------
-extern "C" void *mfx_host_alloc(size_t bytes) {
-  void *p = nullptr;
-  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    mfx_fail(MFX_E_NOMEM, "mfx_host_alloc: cannot pin %zu bytes of host memory", bytes);
-    return nullptr;
-  }
-  return p;
-}
-
-extern "C" void mfx_host_free(void *p) {
-  if (p) (void)hipHostFree(p);
-}
-
+// a sequence object without content: what a streamed run (mfx_stream.cpp) uploads into
 extern "C" mfx_seq *mfx_seq_create(int device, const uint64_t *lens, uint32_t ncontigs) {
   if ((ncontigs && !lens) || device < 0 || device >= mfx_device_count()) {
     mfx_fail(device < 0 || device >= mfx_device_count() ? MFX_E_NODEVICE : MFX_E_INVAL,
@@ -2200,814 +2105,6 @@ extern "C" mfx_seq *mfx_seq_create(int device, const uint64_t *lens, uint32_t nc
   mfx_seq *s = seq_layout(device, lens, ncontigs);
   if (seq_alloc(s, false) != MFX_OK) { mfx_seq_free(s); return nullptr; }      // what fills it decides which form it holds
   return s;
-}
-
-static bool host_ptr_is_pinned(const void *p) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return at.type == hipMemoryTypeHost;
-}
-
-namespace {
-struct Piece { uint32_t contig; uint64_t pos, n; };      // bases [pos, pos+n) of a contig
-
-// the bases the tiles [t0, t1) read: their own positions plus the (k-1)-base halo behind the last tile of a contig
-// piece (a whole 128-byte line of it: the next chunk re-sends those bytes, same values)
-void chunk_pieces(const mfx_seq *s, uint64_t t0, uint64_t t1, std::vector<Piece> &out) {
-  out.clear();
-  uint32_t c = (uint32_t)(std::upper_bound(s->tile_start.begin(), s->tile_start.end(), t0) - s->tile_start.begin()) - 1;
-  for (; c < s->ncontigs && s->tile_start[c] < t1; ++c) {
-    const uint64_t cb = std::max(t0, s->tile_start[c]), ce = std::min(t1, s->tile_start[c + 1]);
-    if (ce <= cb) continue;                                 // an empty contig owns no tile
-    const uint64_t p0 = (cb - s->tile_start[c]) * MFX_TILE;
-    const uint64_t p1 = std::min<uint64_t>(s->len[c], (ce - s->tile_start[c]) * MFX_TILE + MFX_ALIGN);
-    if (p1 > p0) out.push_back({c, p0, p1 - p0});
-  }
-}
-}  // namespace
-
-extern "C" void mfx_pack_bases(const uint8_t *src, uint64_t n, uint64_t *codes, uint32_t *valid);      // mfx_pack.cpp
-
-// The CPUs of the NUMA node that holds `addr` (two-socket hosts: an encoder thread on the other socket reads the assembly over
-// the inter-socket links).  false: unknown (no such call in this container, one node, too few of its CPUs allowed) -- no binding.
-static bool cpus_near(const void *addr, cpu_set_t *out, int *node_out = nullptr) {
-  const char *e = getenv("MFX_NUMA_BIND");
-  if (e && atoi(e) == 0) return false;
-  int node = -1;
-  if (syscall(SYS_get_mempolicy, &node, nullptr, 0UL, const_cast<void *>(addr), 3UL /* MPOL_F_NODE | MPOL_F_ADDR */) != 0 || node < 0) return false;
-  char path[96];
-  snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
-  FILE *f = fopen(path, "r");
-  if (!f) return false;
-  char buf[4096];
-  const bool got = fgets(buf, sizeof(buf), f) != nullptr;
-  fclose(f);
-  if (!got) return false;
-  cpu_set_t allowed, near;
-  CPU_ZERO(&near);
-  if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return false;
-  for (char *p = buf; *p;) {                                  // "0-63,128-191"
-    char *q;
-    const long a = strtol(p, &q, 10);
-    if (q == p) break;
-    long b = a;
-    if (*q == '-') { p = q + 1; b = strtol(p, &q, 10); }
-    for (long c = a; c <= b && c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &allowed)) CPU_SET(c, &near);
-    p = *q == ',' ? q + 1 : q;
-    if (*q != ',' ) break;
-  }
-  if (node_out) *node_out = node;
-  if ((unsigned)CPU_COUNT(&near) < std::max(1u, mfx_host_threads())) return false;
-  if (CPU_COUNT(&near) == CPU_COUNT(&allowed)) return false;  // one node: nothing to choose
-  *out = near;
-  return true;
-}
-
-// Where the W encoder threads of a streamed run go.  A core reads memory through its CCD's link to the I/O die, and a few
-// threads saturate one link (EPYC 9575F, tools/native/pack_bench.cpp: 8 threads in one CCD encode 55 GB/s of bases, 8 threads in 8
-// CCDs 130-147 GB/s), so WHERE the scheduler happens to put the threads decides the rate of the whole pipeline: 16 threads that
-// share two CCDs encode 99 GB/s, spread over the CCDs 145-193 GB/s.  MFX_PACK_PLACE:
-//   spread (default) worker w is pinned to L3 domain w mod n of the source's NUMA node (every node if that is unknown), on the
-//                    first hardware thread of its cores;   node  the CPUs of the source's node (the round-3 behaviour);
-//   all              L3 domains of every node;   os  no binding
-struct PackTopology {
-  std::vector<std::vector<int>> l3_of_node[8];        // [node][domain] -> primary hardware threads
-  cpu_set_t allowed;
-  bool ok = false;
-  PackTopology() {
-    CPU_ZERO(&allowed);
-    if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return;
-    auto read_int = [](const char *p) { int v = -1; if (FILE *f = fopen(p, "r")) { if (fscanf(f, "%d", &v) != 1) v = -1; fclose(f); } return v; };
-    std::map<std::pair<int, int>, std::vector<int>> dom;
-    for (int c = 0; c < CPU_SETSIZE; ++c) {
-      if (!CPU_ISSET(c, &allowed)) continue;
-      char p[160];
-      snprintf(p, sizeof(p), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
-      if (read_int(p) != c) continue;                  // a second hardware thread of its core
-      snprintf(p, sizeof(p), "/sys/devices/system/cpu/cpu%d/cache/index3/id", c);
-      const int l3 = read_int(p);
-      int node = -1;
-      for (int nd = 0; nd < 8 && node < 0; ++nd) {
-        snprintf(p, sizeof(p), "/sys/devices/system/cpu/cpu%d/node%d", c, nd);
-        if (access(p, F_OK) == 0) node = nd;
-      }
-      if (l3 < 0) continue;
-      dom[{node < 0 ? 0 : node, l3}].push_back(c);
-    }
-    for (auto &kv : dom) l3_of_node[kv.first.first].push_back(kv.second);
-    size_t n = 0;
-    for (auto &v : l3_of_node) n += v.size();
-    ok = n > 1;
-  }
-};
-static const PackTopology &pack_topology() { static PackTopology t; return t; }
-
-void mfx_pin_spread(unsigned w) {
-  const char *e = getenv("MFX_POOL_SPREAD");
-  if (e && atoi(e) == 0) return;
-  cpu_set_t mine;
-  const PackTopology &T = pack_topology();
-  if (!T.ok) return;
-  std::vector<const std::vector<int> *> doms;
-  for (auto &nd : T.l3_of_node) for (auto &d : nd) doms.push_back(&d);
-  if (doms.empty()) return;
-  CPU_ZERO(&mine);
-  for (int c : *doms[w % doms.size()]) CPU_SET(c, &mine);
-  if (CPU_COUNT(&mine) > 0) (void)pthread_setaffinity_np(pthread_self(), sizeof(mine), &mine);
-}
-
-// the CPU set worker w of W runs on under `mode` (0 os, 1 node, 2 spread, 3 all); false: leave the thread where it is allowed
-static bool pack_cpus(int mode, int node, const cpu_set_t *near, unsigned w, cpu_set_t *out) {
-  const PackTopology &T = pack_topology();
-  if (mode == 0) { *out = T.allowed; return CPU_COUNT(&T.allowed) > 0; }
-  if (mode == 1) { if (near) { *out = *near; return true; } *out = T.allowed; return CPU_COUNT(&T.allowed) > 0; }
-  if (!T.ok) { *out = T.allowed; return CPU_COUNT(&T.allowed) > 0; }
-  std::vector<const std::vector<int> *> doms;
-  if (mode == 2 && node >= 0 && node < 8) for (auto &d : T.l3_of_node[node]) doms.push_back(&d);
-  if (doms.empty()) for (auto &nd : T.l3_of_node) for (auto &d : nd) doms.push_back(&d);
-  CPU_ZERO(out);
-  for (int c : *doms[w % doms.size()]) CPU_SET(c, out);
-  return CPU_COUNT(out) > 0;
-}
-
-// The streamed -hist with the assembly crossing PCIe PACKED (0.375 B per base): host threads encode every chunk into
-// the tile form (2-bit codes + validity bits, csrc/mfx_pack.cpp) while the previous chunk is on the bus and the one
-// before is being evaluated; the kernel reads its tiles from the packed planes (mfx_tile_fill_packed).  One byte per
-// base never reaches the device (seq->bases_stale; unpacked on demand by mfx_seq_ensure_ascii).
-// part != nullptr: only the tiles [part->tl, part->th) are encoded, uploaded and evaluated (one device's share of a run over several:
-// mfx_hist_run_streamed_multi / mfx_hist_run_streamed_range); the sequence object then holds that part only (mfx_seq::partial).
-// The two rates that decide how a streamed run's bases cross the link (hist_run_streamed_packed): what W host threads ENCODE (GB of
-// bases per second, all of them at once: they share the memory system) and what the device's LINK moves from pinned host memory.
-// Measured once per process and (W | device) on the caller's own buffers -- every thread encodes 4 MB of the first contig into a scratch of
-// its own, 32 MB of it are copied to the device buffer they go to anyway -- ~1.5 ms together; MFX_STREAM_ENC_GBS / MFX_STREAM_LINK_GBS override.
-static double stream_encode_gbs(WorkerPool *pool, unsigned W, const uint8_t *src, uint64_t n) {
-  static std::mutex mu;
-  static std::map<unsigned, double> cache;
-  if (const char *e = getenv("MFX_STREAM_ENC_GBS")) if (atof(e) > 0) return atof(e);
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(W);
-    if (it != cache.end()) return it->second;
-  }
-  const uint64_t per = std::min<uint64_t>(4u << 20, n / std::max(1u, W) / 32 * 32);
-  if (!pool || per < (1u << 16)) return 0.0;                  // too little to measure: no estimate
-  std::vector<std::vector<uint64_t>> sc(W);
-  for (auto &v : sc) v.assign(per / 32 + per / 64 + 2, 1);      // (written: the scratch's pages exist before the clock starts)
-  // ONE pass over bases nobody has read yet (the tail of the contig: a second pass over the same 4 MB per thread would be served by the L3)
-  const uint8_t *from = src + (n - (uint64_t)W * per) / 128 * 128;
-  auto run = [&](unsigned w) {
-    uint64_t *codes = sc[w].data();
-    mfx_pack_bases(from + (uint64_t)w * per, per, codes, reinterpret_cast<uint32_t *>(codes + per / 32 + 1));
-  };
-  const auto t0 = std::chrono::steady_clock::now();
-  pool->start(run); pool->wait();
-  const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const double gbs = dt > 0 ? (double)per * W / dt / 1e9 : 0.0;
-  std::lock_guard<std::mutex> lk(mu);
-  cache[W] = gbs;
-  return gbs;
-}
-static double stream_link_gbs(int device, uint8_t *d_dst, const uint8_t *pinned_src, uint64_t n, hipStream_t st) {
-  static std::mutex mu;
-  static std::map<int, double> cache;
-  if (const char *e = getenv("MFX_STREAM_LINK_GBS")) if (atof(e) > 0) return atof(e);
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(device);
-    if (it != cache.end()) return it->second;
-  }
-  const uint64_t m = std::min<uint64_t>(32u << 20, n);
-  if (m < (4u << 20)) return 0.0;
-  hipEvent_t a = nullptr, b = nullptr;
-  double gbs = 0.0;
-  if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess &&
-      hipMemcpyAsync(d_dst, pinned_src, 1u << 20, hipMemcpyHostToDevice, st) == hipSuccess &&          // (wakes the link up)
-      hipEventRecord(a, st) == hipSuccess && hipMemcpyAsync(d_dst, pinned_src, m, hipMemcpyHostToDevice, st) == hipSuccess &&
-      hipEventRecord(b, st) == hipSuccess && hipEventSynchronize(b) == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess && ms > 0) gbs = (double)m / (ms * 1e-3) / 1e9;
-  } else (void)hipGetLastError();
-  if (a) (void)hipEventDestroy(a);
-  if (b) (void)hipEventDestroy(b);
-  if (gbs > 0) { std::lock_guard<std::mutex> lk(mu); cache[device] = gbs; }
-  return gbs;
-}
-
-int hist_run_streamed_packed(mfx_eval *ev, mfx_seq *seq, const char *const *bases, mfx_hist_result *out, const StreamPart *part) {      // StreamPart: mfx_host.h
-  DevGuard g(ev->device);
-  const int timing = getenv("MFX_STREAM_TIMING") ? atoi(getenv("MFX_STREAM_TIMING")) : 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = now();
-  double t_mark[6] = {0, 0, 0, 0, 0, 0};
-  // MFX_STREAM_TIMING=2: the timeline of every chunk (host clocks of the packers and of the enqueue loop, device events around
-  // its copy and behind its launch) -- what tools/stream_phases.py prints; costs a few events, never on by default
-  struct ChunkTimes { double pack_first = 0, pack_last = 0, wait_buf = 0, enq = 0; hipEvent_t c0 = nullptr, c1 = nullptr, k1 = nullptr; };
-  std::vector<ChunkTimes> ct;
-  hipEvent_t ev_base = nullptr;
-  const size_t words = MFX_HIST_WORDS(ev->nbins, seq->ncontigs);
-  const uint64_t TL = part ? part->tl : 0, TH = part ? part->th : seq->ntiles;
-  const uint64_t T = TH - TL;                                 // tiles of this run
-  const bool whole = TL == 0 && TH == seq->ntiles;
-  // chunks grow from 8 MB to 128 MB of bases: the first tile reaches the kernel after ~0.2 ms, and the bulk runs in few,
-  // long launches (every launch pays a ramp-up and a tail of its persistent blocks: 47 launches of 64 MB cost 38 ms of
-  // kernel time for 3 Gb, one launch 33.4 ms)
-  const uint64_t CH0 = 2048, CH = 32768;
-  constexpr int NB = 3;
-  const uint64_t plane_words = seq->buf_bytes / 32 + (MFX_TILE + 64) / 32 + 1;   // a tile reads 130 words from its first one
-  struct Chunk { std::vector<Piece> pieces; uint64_t lo = 0, hi = 0, t0 = 0, t1 = 0; };
-  std::vector<Chunk> chunks;
-  // ... and shrink again at the end (64, 32, 16 MB): what follows the last upload is the evaluation of the last chunk alone
-  std::vector<uint64_t> cuts;                                 // chunk boundaries, ascending
-  {
-    std::vector<uint64_t> tail;                               // sizes of the closing chunks, last first
-    uint64_t back = 0;
-    for (uint64_t sz = 2 * CH0; sz < CH && back + sz + CH <= T / 2; sz *= 2) { tail.push_back(sz); back += sz; }
-    const uint64_t front_end = T - back;
-    uint64_t t0 = 0;
-    for (uint64_t sz = CH0; t0 < front_end; sz = std::min(CH, sz * 2)) {
-      uint64_t t1 = std::min(front_end, t0 + sz);
-      if (front_end - t1 < sz / 2) t1 = front_end;            // no short launch in the middle (at most 1.5 x CH tiles)
-      cuts.push_back(t1);
-      t0 = t1;
-    }
-    for (size_t i = tail.size(); i-- > 0;) { t0 += tail[i]; cuts.push_back(t0); }
-  }
-  for (uint64_t t0 = 0, ci = 0; ci < cuts.size(); ++ci) {
-    Chunk c;
-    c.t0 = TL + t0;
-    c.t1 = TL + cuts[ci];
-    t0 = cuts[ci];
-    chunk_pieces(seq, c.t0, c.t1, c.pieces);
-    if (!c.pieces.empty()) {
-      c.lo = seq->off[c.pieces.front().contig] + c.pieces.front().pos;                 // a multiple of 128
-      c.hi = (seq->off[c.pieces.back().contig] + c.pieces.back().pos + c.pieces.back().n + 31) / 32 * 32;
-    }
-    chunks.push_back(std::move(c));
-  }
-  size_t STAGE_W = 0;                                         // words of the largest chunk, rounded up to 1 MB of them
-  for (const Chunk &c : chunks) STAGE_W = std::max<size_t>(STAGE_W, (c.hi - c.lo) / 32);
-  STAGE_W = (STAGE_W + 2 + 131071) / 131072 * 131072;
-  std::atomic<int64_t> allowed{NB - 1};                     // chunks <= allowed may be packed (their staging buffer is free)
-  std::atomic<bool> stop{false};
-  std::vector<std::atomic<uint32_t>> done(chunks.size());
-  for (auto &d : done) d.store(0);
-  int rc = MFX_OK;
-  auto &R = ev->sr;
-  std::mutex ct_mu;
-  if (timing >= 2) {
-    ct.resize(chunks.size());
-    (void)hipEventCreate(&ev_base);
-    for (auto &x : ct) { (void)hipEventCreate(&x.c0); (void)hipEventCreate(&x.c1); (void)hipEventCreate(&x.k1); }
-  }
-  auto cleanup = [&]() {
-    stop.store(true);
-    if (ev->pool) static_cast<WorkerPool *>(ev->pool)->wait();
-    if (R.copy) (void)hipStreamSynchronize(R.copy);
-    for (auto &k : R.kern) if (k) (void)hipStreamSynchronize(k);
-  };
-#define STREAMED_HIP(call)                                                                                        \
-  do {                                                                                                            \
-    hipError_t e_ = (call);                                                                                       \
-    if (e_ != hipSuccess) { rc = mfx_fail(MFX_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); cleanup(); return rc; } \
-  } while (0)
-  if (!seq->d_codes) {
-    STREAMED_HIP(hipMalloc((void **)&seq->d_codes, plane_words * sizeof(uint64_t)));
-    STREAMED_HIP(hipMalloc((void **)&seq->d_valid, plane_words * sizeof(uint32_t)));
-    STREAMED_HIP(mfx_memset_now(seq->d_valid, 0, plane_words * sizeof(uint32_t)));           // no valid base outside the uploads
-    STREAMED_HIP(mfx_memset_now(seq->d_codes, 0, plane_words * sizeof(uint64_t)));
-  }
-  // pinned staging (codes words, then validity words) belongs to the evaluator: pinning costs more than the evaluation
-  if (ev->h_pack_words != STAGE_W) {
-    for (auto &p : ev->h_pack) { if (p) (void)hipHostFree(p); p = nullptr; }
-    ev->h_pack_words = STAGE_W;
-  }
-  // The validity plane crosses the link SPARSE: a word of it is all ones wherever 32 consecutive bases are ACGT, so a chunk sends
-  // its code words and the few validity words that are not (contig ends, gaps, N runs); the plane's range is filled with ones on the
-  // device and those are put in (mfx_k_valid_scatter): 0.25 instead of 0.375 bytes per base over PCIe, the bound of the streamed run.
-  // Every packer lists the exceptional words of its share behind the staging buffer (room for 1/8 of its words: a chunk with more goes whole).
-  const char *spv = getenv("MFX_STREAM_SPARSE_VALID");
-  const bool sparse_valid = !(spv && atoi(spv) == 0);
-  const size_t EXC_TOTAL = STAGE_W / 8 + 64 * 64;               // entries behind a staging buffer (up to 64 packers)
-  for (int b = 0; b < NB && b < (int)chunks.size(); ++b)
-    if (!ev->h_pack[b]) STREAMED_HIP(hipHostMalloc((void **)&ev->h_pack[b], STAGE_W * 12 + EXC_TOTAL * 8, hipHostMallocDefault));
-  if (sparse_valid && R.exc_cap < EXC_TOTAL) {
-    for (auto &x : R.d_exc) { if (x) (void)hipFree(x); x = nullptr; }
-    for (auto &x : R.d_exc) STREAMED_HIP(hipMalloc((void **)&x, EXC_TOTAL * 8));
-    R.exc_cap = EXC_TOTAL;
-  }
-  std::vector<uint32_t> nexc(chunks.size() * 64, 0);           // exceptional words listed by packer w of chunk ci: nexc[ci * 64 + w]
-  std::vector<std::atomic<uint32_t>> dense(chunks.size());     // a packer ran out of room: the chunk's validity words go whole
-  for (auto &d : dense) d.store(0);
-  seq->bases_stale = true;
-  seq->planes_ok = true;
-  seq->digest = 0;                                           // new content
-  seq->partial = !whole;
-  seq->part_lo = TL;
-  seq->part_hi = TH;
-
-  // the packers: worker w encodes its share of the words of every chunk, in chunk order
-  const unsigned W = std::max(1u, std::min(mfx_host_threads(), 64u));
-  if (ev->pool && static_cast<WorkerPool *>(ev->pool)->W != W) { delete static_cast<WorkerPool *>(ev->pool); ev->pool = nullptr; }
-  if (!ev->pool) ev->pool = new WorkerPool(W);
-  uint8_t *const *stage = ev->h_pack;
-  // TRANSPORT.  Host-packed (0.25-0.375 bytes per base over the link, the encoders' work in front of it) is the faster way while the
-  // host threads THIS call has encode faster than its link moves plain bytes -- one process with the host's cores to itself: 150-190 GB/s
-  // against 56.  A rank of N processes has 1/N of the cores but a link of its own: from N = 4 on (16-core quota) its threads are slower than
-  // its link, and the run of the whole node is bound by the host's encoders whatever N.  Then the bases cross as they
-  // are -- DMA straight out of the caller's pinned buffers, no host thread touches them -- and mfx_pack_kernel makes the planes on the
-  // device (3 GB of bytes: 1.5 ms of its HBM); the evaluation is the same launches over the same planes, bit for bit.  Pinned sources
-  // only (pageable ones would need a host copy as dear as the encoding).  MFX_STREAM_TRANSPORT=pack | ascii forces either.
-  bool link_ascii = false;
-  {
-    bool all_pinned = seq->ncontigs > 0;
-    for (uint32_t c = 0; c < seq->ncontigs && all_pinned; ++c) all_pinned = seq->len[c] == 0 || host_ptr_is_pinned(bases[c]);
-    const char *tp = getenv("MFX_STREAM_TRANSPORT");
-    if (tp && !strcmp(tp, "ascii")) link_ascii = all_pinned;
-    else if (tp && !strcmp(tp, "pack")) link_ascii = false;
-    else if (all_pinned && seq->ncontigs && seq->len[0] >= (32u << 20)) {
-      if (int brc = seq_need_bases(seq)) return brc;
-      if (!R.copy) MFX_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
-      const double enc = stream_encode_gbs(static_cast<WorkerPool *>(ev->pool), W, reinterpret_cast<const uint8_t *>(bases[0]), seq->len[0]);
-      const double link = stream_link_gbs(ev->device, seq->d_bases, reinterpret_cast<const uint8_t *>(bases[0]), seq->len[0], R.copy);
-      link_ascii = enc > 0 && link > 0 && enc < link;
-      if (timing) fprintf(stderr, "[mfx stream] transport: %u host threads encode %.1f GB/s, the link moves %.1f GB/s -> %s\n", W, enc, link, link_ascii ? "plain bytes + device-side packing" : "host-packed planes");
-    }
-    if (link_ascii) if (int brc = seq_need_bases(seq)) return brc;
-  }
-  cpu_set_t near_cpus;
-  int src_node = -1;
-  const bool bind = seq->ncontigs && bases[0] && cpus_near(bases[0], &near_cpus, &src_node);      // the encoders run next to the memory they read
-  int place = 2;
-  if (const char *pp = getenv("MFX_PACK_PLACE")) place = !strcmp(pp, "os") ? 0 : !strcmp(pp, "node") ? 1 : !strcmp(pp, "all") ? 3 : 2;
-  if (const char *nb = getenv("MFX_NUMA_BIND")) if (atoi(nb) == 0) place = 0;
-  auto work = [&, W](unsigned w) {
-    if (link_ascii) return;                                      // the bases cross the link as they are
-    cpu_set_t mine;
-    if (pack_cpus(place, src_node, bind ? &near_cpus : nullptr, w, &mine)) (void)pthread_setaffinity_np(pthread_self(), sizeof(mine), &mine);
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      while (allowed.load(std::memory_order_acquire) < (int64_t)ci) {
-        if (stop.load()) return;
-        std::this_thread::yield();
-      }
-      const Chunk &c = chunks[ci];
-      const uint64_t nw = (c.hi - c.lo) / 32, w0 = nw * w / W, w1 = nw * (w + 1) / W;
-      uint64_t *codes = reinterpret_cast<uint64_t *>(stage[ci % NB]);
-      uint32_t *valid = reinterpret_cast<uint32_t *>(stage[ci % NB] + (size_t)STAGE_W * 8);
-      const double t_p0 = timing >= 2 ? now() : 0.0;
-      if (w1 > w0) {
-        memset(codes + w0, 0, (w1 - w0) * 8);                // gaps between contigs and the words behind a contig's end
-        memset(valid + w0, 0, (w1 - w0) * 4);
-        const uint64_t my_lo = c.lo + 32 * w0, my_hi = c.lo + 32 * w1;
-        for (const Piece &pc : c.pieces) {
-          const uint64_t at = seq->off[pc.contig] + pc.pos;      // a multiple of 128
-          const uint64_t s = std::max(my_lo, at), e = std::min(my_hi, at + pc.n);
-          if (e > s) mfx_pack_bases(reinterpret_cast<const uint8_t *>(bases[pc.contig]) + pc.pos + (s - at), e - s, codes + (s - c.lo) / 32, valid + (s - c.lo) / 32);
-        }
-        if (sparse_valid) {
-          const size_t cap_w = STAGE_W / (8 * (size_t)W) + 64;
-          uint64_t *mine_exc = reinterpret_cast<uint64_t *>(stage[ci % NB] + (size_t)STAGE_W * 12) + (size_t)w * cap_w;
-          uint32_t cnt = 0;
-          for (uint64_t i = w0; i < w1; ++i) {
-            const uint32_t vw = valid[i];
-            if (vw == 0xffffffffu) continue;
-            if (cnt == cap_w) { dense[ci].store(1, std::memory_order_relaxed); break; }
-            mine_exc[cnt++] = (uint64_t)i | ((uint64_t)vw << 32);
-          }
-          nexc[ci * 64 + w] = cnt;
-        }
-      }
-      if (timing >= 2) {
-        const double t_p1 = now();
-        std::lock_guard<std::mutex> lk(ct_mu);
-        if (ct[ci].pack_first == 0 || t_p0 < ct[ci].pack_first) ct[ci].pack_first = t_p0;
-        if (t_p1 > ct[ci].pack_last) ct[ci].pack_last = t_p1;
-      }
-      done[ci].fetch_add(1, std::memory_order_release);
-    }
-  };
-  t_mark[0] = now();
-  static_cast<WorkerPool *>(ev->pool)->start(work);
-  t_mark[1] = now();
-  // streams, events, the counts image and its pinned mirror: created once per evaluator (while the packers start)
-  if (R.words < words) {
-    if (R.d_counts) (void)hipFree(R.d_counts);
-    if (R.h_img) (void)hipHostFree(R.h_img);
-    R.d_counts = nullptr; R.h_img = nullptr; R.words = 0;
-    STREAMED_HIP(hipMalloc((void **)&R.d_counts, words * sizeof(uint64_t)));
-    STREAMED_HIP(hipHostMalloc((void **)&R.h_img, (words + 2) * sizeof(uint64_t), hipHostMallocDefault));
-    R.words = words;
-  }
-  if (!R.d_kover) STREAMED_HIP(hipMalloc((void **)&R.d_kover, 2 * sizeof(double)));    // [1]: the uploaded sequence's content digest (a uint64)
-  if (!R.copy) STREAMED_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
-  for (auto &k : R.kern) if (!k) STREAMED_HIP(hipStreamCreateWithFlags(&k, hipStreamNonBlocking));
-  for (auto &e : R.up) if (!e) STREAMED_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (!R.kdone) STREAMED_HIP(hipEventCreateWithFlags(&R.kdone, hipEventDisableTiming));
-  hipStream_t cs = R.copy, ks = R.kern[0];
-  const bool own_image = !(part && part->d_counts);
-  uint64_t *const d_counts = own_image ? R.d_counts : part->d_counts, *const h_img = R.h_img;
-  double *const d_kover = own_image ? R.d_kover : part->d_kover;
-  hipEvent_t *const up = R.up;
-  if (own_image) {
-    STREAMED_HIP(hipMemsetAsync(d_counts, 0, words * sizeof(uint64_t), ks));
-    STREAMED_HIP(hipMemsetAsync(d_kover, 0, sizeof(double), ks));
-  }
-  STREAMED_HIP(hipMemsetAsync(ev->d_tile_ctr, 0, 2 * sizeof(uint64_t), ks));
-  STREAMED_HIP(ovf_reset_hip(ev, ks));
-  STREAMED_HIP(hipEventRecord(R.kdone, ks));
-  STREAMED_HIP(hipStreamWaitEvent(R.kern[1], R.kdone, 0));          // the second kernel stream starts behind the clears
-  if ((rc = ensure_tile_partials(ev, T)) != MFX_OK) { cleanup(); return rc; }
-  double t_base_host = 0;
-  if (timing >= 2) { (void)hipEventRecord(ev_base, cs); (void)hipEventSynchronize(ev_base); t_base_host = now(); }
-
-  for (size_t ci = 0; ci < chunks.size(); ++ci) {
-    const Chunk &c = chunks[ci];
-    const int b = (int)(ci % NB);
-    if (ci >= 1) {
-      // the copy of chunk ci-1 has left its buffer: chunk ci-1+NB may be packed into it
-      STREAMED_HIP(hipEventSynchronize(up[(ci - 1) % NB]));
-      allowed.store((int64_t)(ci - 1 + NB), std::memory_order_release);
-    }
-    if (timing >= 2) ct[ci].wait_buf = now();
-    if (!link_ascii) while (done[ci].load(std::memory_order_acquire) < W) std::this_thread::yield();
-    if (timing >= 2) { ct[ci].enq = now(); (void)hipEventRecord(ct[ci].c0, cs); }
-    if (link_ascii && c.hi > c.lo) {
-      // the chunk's pieces by DMA out of the caller's pinned buffers (the gaps between contigs stay the buffer's zero bytes), then the
-      // planes of its words on the device, behind the copies on the same stream; a word shared with the chunk before is rewritten with
-      // the value it has (that chunk's kernel may still read it)
-      for (const Piece &pc : c.pieces)
-        STREAMED_HIP(hipMemcpyAsync(seq->d_bases + seq->off[pc.contig] + pc.pos, bases[pc.contig] + pc.pos, pc.n, hipMemcpyHostToDevice, cs));
-      STREAMED_HIP(mfx_k_pack(seq->d_bases + c.lo, seq->d_codes + c.lo / 32, seq->d_valid + c.lo / 32, (c.hi - c.lo) / 32, cs));
-    } else if (c.hi > c.lo) {
-      const uint64_t nw = (c.hi - c.lo) / 32;
-      STREAMED_HIP(hipMemcpyAsync(seq->d_codes + c.lo / 32, stage[b], nw * 8, hipMemcpyHostToDevice, cs));
-      // the sparse form pays (8 bytes per listed word against 4 per word sent whole) only while fewer than half of the chunk's
-      // validity words are exceptional; a chunk of short or gappy contigs goes whole
-      size_t n_exc = 0;
-      for (unsigned w = 0; w < W; ++w) n_exc += nexc[ci * 64 + w];
-      if (sparse_valid && !dense[ci].load(std::memory_order_relaxed) && 2 * n_exc < nw) {
-        // the packers' lists, one behind the other, at the head of the (now free) validity words of the staging buffer
-        const size_t cap_w = STAGE_W / (8 * (size_t)W) + 64;
-        uint64_t *all = reinterpret_cast<uint64_t *>(stage[b] + (size_t)STAGE_W * 8);
-        const uint64_t *lists = reinterpret_cast<const uint64_t *>(stage[b] + (size_t)STAGE_W * 12);
-        size_t n = 0;
-        for (unsigned w = 0; w < W; ++w) {
-          const uint32_t m_ = nexc[ci * 64 + w];
-          if (m_) memcpy(all + n, lists + (size_t)w * cap_w, (size_t)m_ * 8);
-          n += m_;
-        }
-        // A chunk that starts inside a contig begins with the MFX_ALIGN bases the previous chunk already sent as the halo of its last
-        // tile, and that chunk's kernel may still be reading them (the copy stream does not wait for it): those words are left out of
-        // the fill -- they hold their final values, and the listed ones among them are only rewritten with the same value.  Filling
-        // them with ones first would let the running kernel see an N or a contig end behind the cut as valid bases for a moment.
-        const uint64_t keep = (ci > 0 && c.pieces.front().pos) ? std::min<uint64_t>(nw, MFX_ALIGN / 32) : 0;   // (the first chunk of a part has nobody before it)
-        if (nw > keep) STREAMED_HIP(hipMemsetAsync(seq->d_valid + c.lo / 32 + keep, 0xff, (nw - keep) * 4, cs));
-        if (n) {
-          STREAMED_HIP(hipMemcpyAsync(R.d_exc[b], all, n * 8, hipMemcpyHostToDevice, cs));
-          STREAMED_HIP(mfx_k_valid_scatter(seq->d_valid + c.lo / 32, R.d_exc[b], (uint32_t)n, cs));
-        }
-      } else {
-        STREAMED_HIP(hipMemcpyAsync(seq->d_valid + c.lo / 32, stage[b] + (size_t)STAGE_W * 8, nw * 4, hipMemcpyHostToDevice, cs));
-      }
-    }
-    if (timing >= 2) (void)hipEventRecord(ct[ci].c1, cs);
-    STREAMED_HIP(hipEventRecord(up[b], cs));
-    // two kernel streams (and tile counters) alternate: the first blocks of a launch fill the CUs the previous launch's
-    // last blocks leave behind, instead of waiting for its tail
-    hipStream_t kst = R.kern[ci & 1];
-    STREAMED_HIP(hipStreamWaitEvent(kst, up[b], 0));
-    rc = hist_launch(ev, seq, c.t0, c.t1, 0, 1, 0, d_counts, d_kover, kst, T, (int)(ci & 1), TL);
-    if (rc) { cleanup(); return rc; }
-    if (timing >= 2) (void)hipEventRecord(ct[ci].k1, kst);
-  }
-  t_mark[2] = now();
-  // a sequence-only index answers for the k-mers of ONE sequence: the content digest of what was just uploaded is taken on
-  // the copy stream, behind the last chunk and under the last launches, and compared before the result is handed out
-  // (a part cannot be checked: its digest is not the sequence's; the caller of the parts vouches for the sequence)
-  const bool want_digest = whole && ev->ix->seq_only && ev->ix->seq_digest != 0;
-  if (want_digest) {
-    uint64_t *d_dig = reinterpret_cast<uint64_t *>(R.d_kover + 1);      // the evaluator's own word (eval_run_resources), never the caller's one-double buffer of a range run
-    STREAMED_HIP(hipMemsetAsync(d_dig, 0, sizeof(uint64_t), cs));
-    STREAMED_HIP(mfx_k_seq_digest(nullptr, seq->d_codes, seq->d_valid, seq->buf_bytes / 32, d_dig, cs));
-    STREAMED_HIP(hipMemcpyAsync(h_img + words + 1, d_dig, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
-  }
-  STREAMED_HIP(hipEventRecord(R.kdone, R.kern[1]));
-  STREAMED_HIP(hipStreamWaitEvent(ks, R.kdone, 0));
-  if (T) STREAMED_HIP(mfx_k_sum_tile_partials(ev->d_tile_partials, T, d_kover, ev->d_tile_ctr, ks, ev->ix->wide() ? 0 : 1));
-  if (own_image) {
-    STREAMED_HIP(hipMemcpyAsync(h_img, d_counts, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ks));
-    STREAMED_HIP(hipMemcpyAsync(h_img + words, d_kover, sizeof(double), hipMemcpyDeviceToHost, ks));
-  }
-  STREAMED_HIP(hipStreamSynchronize(ks));
-  if (want_digest) STREAMED_HIP(hipStreamSynchronize(cs));
-  if (part && part->chunk_sums) {
-    // the first-level sums behind the (tile, wave) values: what mfx_sum_partials_kernel added up; the caller adds the parts' in the same order
-    const uint64_t nv = T * (MFX_BLOCK / 64), nch = (nv + 4095) / 4096;
-    part->chunk_sums->assign(nch, 0.0);
-    if (nch) STREAMED_HIP(hipMemcpy(part->chunk_sums->data(), ev->d_tile_partials + nv, nch * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  t_mark[3] = now();
-#undef STREAMED_HIP
-  if (want_digest) {
-    seq_digest_finish(seq, h_img[words + 1]);
-    if ((rc = mfx_check_seq_of_index(ev->ix, seq, "-hist (streamed)")) != MFX_OK) { cleanup(); return rc; }
-  }
-  double kover;
-  memcpy(&kover, h_img + words, sizeof(double));
-  const bool want_result = !part || (part->want_result && own_image);
-  if (want_result) rc = mfx_hist_result_from_counts(ev->nbins, h_img, kover, seq->ncontigs, out);
-  const uint64_t novf = own_image ? h_img[mfx_histsum::novf(ev->nbins)] : 0;
-  t_mark[4] = now();
-  cleanup();
-  t_mark[5] = now();
-  if (timing)
-    fprintf(stderr, "[mfx stream] %zu chunks: setup %.2f ms, spawn %.2f, enqueue loop %.2f, drain %.2f, result %.2f, cleanup %.2f; total %.2f ms%s\n", chunks.size(),
-            (t_mark[0] - t_begin) * 1e3, (t_mark[1] - t_mark[0]) * 1e3, (t_mark[2] - t_mark[1]) * 1e3, (t_mark[3] - t_mark[2]) * 1e3,
-            (t_mark[4] - t_mark[3]) * 1e3, (t_mark[5] - t_mark[4]) * 1e3, (t_mark[5] - t_begin) * 1e3, place == 0 ? "; encoders unbound" : place == 1 ? "; encoders on the source's NUMA node" : place == 2 ? "; encoders spread over the L3 domains of the source's node" : "; encoders spread over all L3 domains");
-  if (timing >= 2) {
-    // all times in ms since the function was entered; device times are placed on the host clock through ev_base
-    fprintf(stderr, "[mfx stream] chunk   Mbases  pack:first..last   buf-wait   enqueue   copy:start..end   kernel-end   (ms since entry; %u packer threads)\n", W);
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      float a = 0, b2 = 0, k2 = 0;
-      (void)hipEventElapsedTime(&a, ev_base, ct[ci].c0);
-      (void)hipEventElapsedTime(&b2, ev_base, ct[ci].c1);
-      (void)hipEventElapsedTime(&k2, ev_base, ct[ci].k1);
-      const double off = (t_base_host - t_begin) * 1e3;
-      fprintf(stderr, "[mfx stream] %5zu %8.1f %8.2f %8.2f %10.2f %9.2f %9.2f %8.2f %11.2f\n", ci, (chunks[ci].hi - chunks[ci].lo) / 1e6,
-              (ct[ci].pack_first - t_begin) * 1e3, (ct[ci].pack_last - t_begin) * 1e3, (ct[ci].wait_buf - t_begin) * 1e3, (ct[ci].enq - t_begin) * 1e3,
-              off + a, off + b2, off + k2);
-    }
-    for (auto &x : ct) { (void)hipEventDestroy(x.c0); (void)hipEventDestroy(x.c1); (void)hipEventDestroy(x.k1); }
-    (void)hipEventDestroy(ev_base);
-  }
-  if (rc || !want_result) return rc;
-  rc = result_take_overflow(ev, novf, out);
-  if (rc) mfx_hist_result_free(out);
-  return rc;
-}
-
-// mfx_seq_upload's transport: the same encoder and chunking as the streamed -hist, without the evaluation -- three small
-// pinned buffers (32 M bases = 12 MB each: pinning costs 0.4 ms per MB, the old 2 x 64 MB of bytes cost 50 ms before
-// the first base moved), the host threads encode chunk i+1 and i+2 while chunk i is on the bus.
-static int seq_upload_packed(mfx_seq *seq, const char *const *bases) {
-  const bool timing = getenv("MFX_UPLOAD_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tm[5] = {now(), 0, 0, 0, 0};
-  const uint64_t T = seq->ntiles, CH = 8192;                   // tiles per chunk
-  constexpr int NB = 3;
-  struct Chunk { std::vector<Piece> pieces; uint64_t lo = 0, hi = 0; };
-  std::vector<Chunk> chunks;
-  for (uint64_t t0 = 0; t0 < T; t0 += CH) {
-    Chunk c;
-    chunk_pieces(seq, t0, std::min(T, t0 + CH), c.pieces);
-    if (c.pieces.empty()) continue;
-    c.lo = seq->off[c.pieces.front().contig] + c.pieces.front().pos;                 // a multiple of 128
-    c.hi = (seq->off[c.pieces.back().contig] + c.pieces.back().pos + c.pieces.back().n + 31) / 32 * 32;
-    chunks.push_back(std::move(c));
-  }
-  tm[1] = now();
-  int rc = seq_alloc_planes(seq);
-  if (rc) return rc;
-  seq->bases_stale = true;
-  seq->planes_ok = true;
-  seq->digest = 0;
-  seq->partial = false;
-  if (chunks.empty()) return MFX_OK;
-  tm[2] = now();
-  size_t STAGE_W = 0;
-  for (const Chunk &c : chunks) STAGE_W = std::max<size_t>(STAGE_W, (c.hi - c.lo) / 32);
-  STAGE_W = (STAGE_W + 2 + 4095) / 4096 * 4096;
-  uint8_t *stage[NB] = {nullptr, nullptr, nullptr};
-  hipEvent_t up[NB] = {nullptr, nullptr, nullptr};
-  hipStream_t cs = nullptr;
-  std::atomic<int64_t> allowed{NB - 1};
-  std::atomic<bool> stop{false};
-  std::vector<std::atomic<uint32_t>> done(chunks.size());
-  for (auto &d : done) d.store(0);
-  const unsigned W = std::max(1u, std::min(mfx_host_threads(), 64u));
-  std::unique_ptr<WorkerPool> pool;
-  bool ok = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess;
-  for (int b = 0; b < NB && b < (int)chunks.size() && ok; ++b)
-    ok = hipHostMalloc((void **)&stage[b], STAGE_W * 12, hipHostMallocDefault) == hipSuccess &&
-         hipEventCreateWithFlags(&up[b], hipEventDisableTiming) == hipSuccess;
-  auto work = [&, W](unsigned w) {
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      while (allowed.load(std::memory_order_acquire) < (int64_t)ci) {
-        if (stop.load()) return;
-        std::this_thread::yield();
-      }
-      const Chunk &c = chunks[ci];
-      const uint64_t nw = (c.hi - c.lo) / 32, w0 = nw * w / W, w1 = nw * (w + 1) / W;
-      uint64_t *codes = reinterpret_cast<uint64_t *>(stage[ci % NB]);
-      uint32_t *valid = reinterpret_cast<uint32_t *>(stage[ci % NB] + (size_t)STAGE_W * 8);
-      if (w1 > w0) {
-        memset(codes + w0, 0, (w1 - w0) * 8);                // gaps between contigs and the words behind a contig's end
-        memset(valid + w0, 0, (w1 - w0) * 4);
-        const uint64_t my_lo = c.lo + 32 * w0, my_hi = c.lo + 32 * w1;
-        for (const Piece &pc : c.pieces) {
-          const uint64_t at = seq->off[pc.contig] + pc.pos;      // a multiple of 128
-          const uint64_t s = std::max(my_lo, at), e = std::min(my_hi, at + pc.n);
-          if (e > s) mfx_pack_bases(reinterpret_cast<const uint8_t *>(bases[pc.contig]) + pc.pos + (s - at), e - s, codes + (s - c.lo) / 32, valid + (s - c.lo) / 32);
-        }
-      }
-      done[ci].fetch_add(1, std::memory_order_release);
-    }
-  };
-  tm[3] = now();
-  if (ok) {
-    // (not spread over the L3 domains: 3 Gb are encoded + copied in 0.024-0.034 s as the threads fall, 0.034-0.070 s pinned; what an upload costs
-    // is its device buffers -- 0.05-0.15 s for 3 GB: profiles/r04_cli_startup_1gb.txt)
-    pool.reset(new WorkerPool(W));
-    pool->start(work);
-    for (size_t ci = 0; ci < chunks.size() && ok; ++ci) {
-      const Chunk &c = chunks[ci];
-      const int b = (int)(ci % NB);
-      if (ci >= 1) {                                          // the copy of chunk ci-1 has left its buffer: chunk ci-1+NB may be packed into it
-        ok = hipEventSynchronize(up[(ci - 1) % NB]) == hipSuccess;
-        allowed.store((int64_t)(ci - 1 + NB), std::memory_order_release);
-      }
-      while (done[ci].load(std::memory_order_acquire) < W) std::this_thread::yield();
-      const uint64_t nw = (c.hi - c.lo) / 32;
-      ok = ok && hipMemcpyAsync(seq->d_codes + c.lo / 32, stage[b], nw * 8, hipMemcpyHostToDevice, cs) == hipSuccess &&
-           hipMemcpyAsync(seq->d_valid + c.lo / 32, stage[b] + (size_t)STAGE_W * 8, nw * 4, hipMemcpyHostToDevice, cs) == hipSuccess &&
-           hipEventRecord(up[b], cs) == hipSuccess;
-    }
-    stop.store(!ok);
-    if (!ok) allowed.store((int64_t)chunks.size());
-    pool->wait();
-    if (hipStreamSynchronize(cs) != hipSuccess) ok = false;
-  }
-  tm[4] = now();
-  for (int b = 0; b < NB; ++b) { if (stage[b]) (void)hipHostFree(stage[b]); if (up[b]) (void)hipEventDestroy(up[b]); }
-  if (cs) (void)hipStreamDestroy(cs);
-  if (timing)
-    fprintf(stderr, "-- packed upload: chunk plan %.3f s, planes %.3f, pinned staging + stream %.3f, encode + copy %.3f (%u threads, %zu chunks), release %.3f\n",
-            tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], W, chunks.size(), now() - tm[4]);
-  return ok ? MFX_OK : mfx_fail(MFX_E_HIP, "packed upload of the sequence failed: %s", hipGetErrorString(hipGetLastError()));
-}
-
-// The two rates of the transport decision, measured on demand (bench.py's model of SURVEY 8(d)'s metric at N GPUs: a rank of N has
-// host_threads / N encoders and a link of its own): `threads` host threads encoding `src` (pinned or not) at once, and -- src pinned --
-// 32 MB of it over this device's link.  Nothing is cached.
-extern "C" int mfx_diag_stream_rates(int device, const char *src, uint64_t n, uint32_t threads, double *enc_gbs, double *link_gbs) {
-  if (!src || !enc_gbs || !link_gbs || threads == 0 || threads > 256) return mfx_fail(MFX_E_INVAL, "mfx_diag_stream_rates: bad argument");
-  if (device < 0 || device >= mfx_device_count()) return mfx_fail(MFX_E_NODEVICE, "mfx_diag_stream_rates: device %d of %d", device, mfx_device_count());
-  *enc_gbs = *link_gbs = 0.0;
-  {
-    WorkerPool pool(threads, true);                              // (spread over the L3 domains, as the run's own encoders are)
-    // every pass reads bases no pass before it has read (a second pass over the same bytes would be served by the L3: 256 MB on the EPYC
-    // of the measured boxes): up to three passes of `threads` x 32 MB, as far as n reaches; the best one counts
-    const uint64_t per = std::min<uint64_t>(32u << 20, n / threads / 128 * 128);
-    if (per >= (1u << 16)) {
-      std::vector<std::vector<uint64_t>> sc(threads);
-      for (auto &v : sc) v.assign(per / 32 + per / 64 + 2, 1);  // (written: the scratch's pages exist before the clock starts)
-      const uint64_t passes = std::max<uint64_t>(1, std::min<uint64_t>(3, n / (per * threads)));
-      double best = 0;
-      for (uint64_t rep = 0; rep < passes; ++rep) {
-        const uint8_t *from = reinterpret_cast<const uint8_t *>(src) + rep * per * threads;
-        auto run = [&](unsigned w) { mfx_pack_bases(from + (uint64_t)w * per, per, sc[w].data(), reinterpret_cast<uint32_t *>(sc[w].data() + per / 32 + 1)); };
-        const auto t0 = std::chrono::steady_clock::now();
-        pool.start(run); pool.wait();
-        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (dt > 0) best = std::max(best, (double)per * threads / dt / 1e9);
-      }
-      *enc_gbs = best;
-    }
-  }
-  if (host_ptr_is_pinned(src) && n >= (4u << 20)) {
-    DevGuard g(device);
-    const uint64_t m = std::min<uint64_t>(256u << 20, n);
-    uint8_t *d = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (hipMalloc((void **)&d, m) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&a) == hipSuccess &&
-        hipEventCreate(&b) == hipSuccess && hipMemcpyAsync(d, src, 1u << 20, hipMemcpyHostToDevice, st) == hipSuccess) {
-      for (int rep = 0; rep < 2; ++rep) {
-        float ms = 0;
-        if (hipEventRecord(a, st) == hipSuccess && hipMemcpyAsync(d, src, m, hipMemcpyHostToDevice, st) == hipSuccess && hipEventRecord(b, st) == hipSuccess &&
-            hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess && ms > 0)
-          *link_gbs = std::max(*link_gbs, (double)m / (ms * 1e-3) / 1e9);
-      }
-    } else (void)hipGetLastError();
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    if (st) (void)hipStreamDestroy(st);
-    if (d) (void)hipFree(d);
-  }
-  return MFX_OK;
-}
-
-extern "C" int mfx_hist_run_streamed(mfx_eval *ev, mfx_seq *seq, const char *const *bases, mfx_hist_result *out) {
-  if (!ev || !seq || !out || (seq->ncontigs && !bases)) return mfx_fail(MFX_E_INVAL, "mfx_hist_run_streamed: null argument");
-  if (ev->device != seq->device) return mfx_fail(MFX_E_INVAL, "evaluator and sequence live on different devices");
-  {
-    // default: the assembly crosses the bus packed; MFX_STREAM_ASCII=1 (and the 128-bit k-mer kernels) send one byte per base
-    const char *asc = getenv("MFX_STREAM_ASCII");
-    if (!ev->ix->wide() && !(asc && atoi(asc))) return hist_run_streamed_packed(ev, seq, bases, out);
-  }
-  DevGuard g(ev->device);
-  if (int brc = seq_need_bases(seq)) return brc;
-  seq->bases_stale = false;                                 // this path writes d_bases
-  seq->planes_ok = false;
-  seq->digest = 0;
-  seq->partial = false;
-  const size_t words = MFX_HIST_WORDS(ev->nbins, seq->ncontigs);
-  const uint64_t T = seq->ntiles;
-  const uint64_t CH = 16384;                                // tiles per chunk: 64 MB of bases
-  const size_t STAGE = (size_t)CH * (MFX_TILE + 2 * MFX_ALIGN) + MFX_TILE;   // worst case: every tile its own contig
-  DevBuf<uint64_t> dc;
-  DevBuf<double> dk;
-  uint64_t *h_img = nullptr;                                // pinned: counts image + koverCpy
-  // the pinned staging buffers (pageable sources only) belong to the evaluator: pinning 2 x 71 MB costs ~60 ms, more
-  // than the whole evaluation of 3 Gb, so it is paid once per evaluator, not per call
-  if (ev->h_stage_bytes != STAGE) {
-    for (auto &p : ev->h_stage) { if (p) (void)hipHostFree(p); p = nullptr; }
-    ev->h_stage_bytes = STAGE;
-  }
-  uint8_t **stage = ev->h_stage;
-  hipStream_t cs = nullptr, ks = nullptr;
-  hipEvent_t up[2] = {nullptr, nullptr}, staged[2] = {nullptr, nullptr};
-  int rc = MFX_OK;
-  auto cleanup = [&]() {
-    if (cs) (void)hipStreamSynchronize(cs);
-    if (ks) (void)hipStreamSynchronize(ks);
-    for (int i = 0; i < 2; ++i) {
-      if (up[i]) (void)hipEventDestroy(up[i]);
-      if (staged[i]) (void)hipEventDestroy(staged[i]);
-    }
-    if (h_img) (void)hipHostFree(h_img);
-    if (cs) (void)hipStreamDestroy(cs);
-    if (ks) (void)hipStreamDestroy(ks);
-  };
-#define STREAMED_HIP(call)                                                                                        \
-  do {                                                                                                            \
-    hipError_t e_ = (call);                                                                                       \
-    if (e_ != hipSuccess) { rc = mfx_fail(MFX_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); cleanup(); return rc; } \
-  } while (0)
-  STREAMED_HIP(dc.alloc(words));
-  STREAMED_HIP(dk.alloc(1));
-  STREAMED_HIP(hipHostMalloc((void **)&h_img, (words + 1) * sizeof(uint64_t), hipHostMallocDefault));
-  STREAMED_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  STREAMED_HIP(hipStreamCreateWithFlags(&ks, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    STREAMED_HIP(hipEventCreateWithFlags(&up[i], hipEventDisableTiming));
-    STREAMED_HIP(hipEventCreateWithFlags(&staged[i], hipEventDisableTiming));
-  }
-  STREAMED_HIP(hipMemsetAsync(dc.p, 0, words * sizeof(uint64_t), ks));
-  STREAMED_HIP(hipMemsetAsync(dk.p, 0, sizeof(double), ks));
-  STREAMED_HIP(hipMemsetAsync(ev->d_tile_ctr, 0, sizeof(uint64_t), ks));
-  STREAMED_HIP(ovf_reset_hip(ev, ks));
-  if ((rc = ensure_tile_partials(ev, T)) != MFX_OK) { cleanup(); return rc; }
-  std::vector<char> pinned(seq->ncontigs);
-  for (uint32_t c = 0; c < seq->ncontigs; ++c) pinned[c] = seq->len[c] && host_ptr_is_pinned(bases[c]);
-  std::vector<Piece> pieces;
-  bool stage_busy[2] = {false, false};
-  for (uint64_t t0 = 0, ci = 0; t0 < T; t0 += CH, ++ci) {
-    const uint64_t t1 = std::min(T, t0 + CH);
-    const int b = (int)(ci & 1);
-    chunk_pieces(seq, t0, t1, pieces);
-    bool direct = pieces.size() <= 64;                       // many small contigs: one assembled copy instead of many tiny ones
-    for (const Piece &pc : pieces) direct = direct && pinned[pc.contig];
-    if (direct) {
-      for (const Piece &pc : pieces)
-        STREAMED_HIP(hipMemcpyAsync(seq->d_bases + seq->off[pc.contig] + pc.pos, bases[pc.contig] + pc.pos, pc.n, hipMemcpyHostToDevice, cs));
-    } else if (!pieces.empty()) {
-      if (!stage[b]) STREAMED_HIP(hipHostMalloc((void **)&stage[b], STAGE, hipHostMallocDefault));
-      if (stage_busy[b]) STREAMED_HIP(hipEventSynchronize(staged[b]));   // its previous copy has left the buffer
-      // the staging buffer mirrors the device range [lo, hi) of this chunk; gaps between contigs stay non-ACGT
-      const uint64_t lo = seq->off[pieces.front().contig] + pieces.front().pos;
-      const uint64_t hi = seq->off[pieces.back().contig] + pieces.back().pos + pieces.back().n;
-      if (hi - lo > STAGE) { rc = mfx_fail(MFX_E_INVAL, "mfx_hist_run_streamed: chunk of %lu bytes exceeds the staging buffer", (unsigned long)(hi - lo)); cleanup(); return rc; }
-      uint64_t filled = lo;
-      for (const Piece &pc : pieces) {
-        const uint64_t at = seq->off[pc.contig] + pc.pos;
-        if (at > filled) memset(stage[b] + (filled - lo), 0, at - filled);
-        par_memcpy(stage[b] + (at - lo), bases[pc.contig] + pc.pos, pc.n);
-        filled = at + pc.n;
-      }
-      STREAMED_HIP(hipMemcpyAsync(seq->d_bases + lo, stage[b], hi - lo, hipMemcpyHostToDevice, cs));
-      STREAMED_HIP(hipEventRecord(staged[b], cs));
-      stage_busy[b] = true;
-    }
-    STREAMED_HIP(hipEventRecord(up[b], cs));
-    STREAMED_HIP(hipStreamWaitEvent(ks, up[b], 0));
-    rc = hist_launch(ev, seq, t0, t1, 0, 1, 0, dc.p, dk.p, ks, T);
-    if (rc) { cleanup(); return rc; }
-  }
-  if (T) STREAMED_HIP(mfx_k_sum_tile_partials(ev->d_tile_partials, T, dk.p, ev->d_tile_ctr, ks, ev->ix->wide() ? 0 : 1));
-  STREAMED_HIP(hipMemcpyAsync(h_img, dc.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ks));
-  STREAMED_HIP(hipMemcpyAsync(h_img + words, dk.p, sizeof(double), hipMemcpyDeviceToHost, ks));
-  STREAMED_HIP(hipStreamSynchronize(ks));
-#undef STREAMED_HIP
-  double kover;
-  memcpy(&kover, h_img + words, sizeof(double));
-  if ((rc = mfx_check_seq_of_index(ev->ix, seq, "-hist (streamed)")) != MFX_OK) { cleanup(); return rc; }
-  rc = mfx_hist_result_from_counts(ev->nbins, h_img, kover, seq->ncontigs, out);
-  const uint64_t novf = h_img[mfx_histsum::novf(ev->nbins)];
-  cleanup();
-  if (rc) return rc;
-  rc = result_take_overflow(ev, novf, out);
-  if (rc) mfx_hist_result_free(out);
-  return rc;
 }
 
 int seq_alloc_planes(mfx_seq *s) {

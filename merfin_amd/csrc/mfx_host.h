@@ -1,5 +1,6 @@
 // mfx_host.h -- what the host files of the library share besides mfx_internal.h: the scoped device helpers and the pieces of
-// mfx_api.cpp that the several-slot drivers (mfx_multi.cpp) are built from.  Host only; no kernel file includes it.
+// mfx_api.cpp that the several-slot drivers (mfx_multi.cpp) and the transport of an assembly in host memory (mfx_stream.cpp)
+// are built from, and what those two hand to each other.  Host only; no kernel file includes it.
 #pragma once
 #include "mfx_internal.h"
 
@@ -24,14 +25,24 @@ struct DevBuf {   // scoped device scratch
 
 // ---- defined in mfx_api.cpp ---------------------------------------------------
 int index_canonical(const mfx_index *ix, int *canon);
+int eval_run_resources(mfx_eval *ev, size_t words);      // the evaluator's counts image, its pinned mirror, d_kover and kernel streams (mfx_eval::sr), made once
 int eval_run_enqueue(mfx_eval *ev, const mfx_seq *seq, uint32_t part_rank, uint32_t part_n);
 int result_take_overflow(mfx_eval *ev, uint64_t novf, mfx_hist_result *out);
 unsigned t_sharers_get();                // what the calling thread last passed to mfx_host_threads_share
+int ensure_tile_partials(mfx_eval *ev, uint64_t ntiles);
+int hist_launch(mfx_eval *ev, const mfx_seq *seq, uint64_t tile_begin, uint64_t tile_end, uint32_t part_rank, uint32_t part_n, uint32_t part_shift,
+                uint64_t *d_counts, double *d_kover, void *stream, uint64_t chunk_of_total = 0, int ctr_slot = 0, uint64_t partials_tile0 = 0);
+hipError_t ovf_reset_hip(mfx_eval *ev, hipStream_t st);
+void par_memcpy(uint8_t *dst, const char *src, size_t n);
+int seq_need_bases(mfx_seq *s);          // d_bases allocated and cleared, if it is not there
+void seq_digest_finish(const mfx_seq *s, uint64_t h);
 
 // a sequence's packed planes: the words each holds (a tile reads 130 words from its first one), and their allocation
 inline uint64_t seq_plane_words(const mfx_seq *s) { return s->buf_bytes / 32 + (MFX_TILE + 64) / 32 + 1; }
 int seq_alloc_planes(mfx_seq *s);
 
+// ---- defined in mfx_stream.cpp ------------------------------------------------
+int seq_upload_packed(mfx_seq *seq, const char *const *bases);      // mfx_seq_upload's packed transport
 // the streamed run over the tiles [tl, th) of an assembly in host memory (no part: all of them, and the result in `out`)
 struct StreamPart {
   uint64_t tl = 0, th = 0;

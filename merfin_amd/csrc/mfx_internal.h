@@ -143,6 +143,7 @@ struct mfx_table_view {
 };
 
 struct mfx_ingest;              // pinned staging lanes of the host -> table pipeline (mfx_api.cpp)
+struct WorkerPool;              // parked host threads (mfx_pool.h)
 
 struct mfx_index {
   int       device = 0;
@@ -323,7 +324,7 @@ struct mfx_eval {
   uint64_t *d_dbg = nullptr;         // [8] probe path counters of the DEBUG instance of the -hist kernel (mfx_eval_debug_enable); null: the measured instance runs
   uint8_t  *h_stage[2] = {nullptr, nullptr};   // pinned staging of the streamed upload (pageable sources), kept between calls
   size_t    h_stage_bytes = 0;
-  void     *pool = nullptr;                             // host threads parked between streamed runs (mfx_api.cpp: WorkerPool)
+  WorkerPool *pool = nullptr;                           // host threads parked between streamed runs (mfx_pool.h)
   // device scratch of mfx_score_paths_trv (the variant modes score ~40 batches per run, one at a time: their ~20 arrays are carved out of one
   // allocation that is kept from batch to batch)
   uint8_t  *d_var_scratch = nullptr;

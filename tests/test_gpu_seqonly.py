@@ -355,6 +355,43 @@ def test_packed_upload_equals_the_byte_upload(k, monkeypatch):
         np.testing.assert_array_equal(ea[2], asm[1])
 
 
+def test_packed_upload_over_five_chunks_equals_the_byte_upload(monkeypatch):
+    """The packed upload sends 8192 tiles per chunk through THREE staging buffers: from the fourth chunk on the host threads wait for the copy
+    that frees their buffer.  134 MB, five chunks (the fifth of two tiles): both cuts at which a buffer is taken the second time (tiles 24576
+    and 32768) lie inside the first contig, an N sits one base behind the first of them, the first contig ends five bases behind the second.
+    -hist from that upload equals -hist from the one-byte-per-base upload in every field, koverCpy bit for bit."""
+    import struct
+    m = _mfx()
+    k, peak, CH = 21, 9.0, 8192
+    r = synth.rng(5150)
+    sizes = (4 * CH * 4096 + 5, 3000)
+    contigs = [synth.random_contig(r, n) for n in sizes]
+    at = 3 * CH * 4096
+    contigs[0][at + 1] = ord("N")
+    raw = [c.tobytes() for c in contigs]
+    hists = []
+    for ascii_upload in ("0", "1"):
+        monkeypatch.setenv("MFX_UPLOAD_ASCII", ascii_upload)
+        seqs = m.Sequences(raw)
+        if not hists:
+            ix = m.Index.for_seq(k, sum(sizes) + 16)
+            ix.count_asm(seqs)
+            spots = [contigs[0][:3000], contigs[0][at - 3000:at + 3000], contigs[0][-3000:], contigs[1]]
+            rk = po.count_kmers(k, [x.tobytes() for x in spots])[0]
+            ix.add_read(rk, (1 + (rk % 50)).astype(np.uint32))
+            ev = m.Evaluator(ix, m.KParams(peak))
+        hists.append(ev.hist(seqs))
+    a, b = hists
+    assert a.kasm == b.kasm == sum(n - (k - 1) for n in sizes) - k      # one N: k k-mers lost
+    assert a.kmissing == b.kmissing and 0 < a.kmissing < a.kasm
+    assert struct.pack("<d", a.koverCpy) == struct.pack("<d", b.koverCpy)
+    np.testing.assert_array_equal(a.undr(), b.undr())
+    np.testing.assert_array_equal(a.over(), b.over())
+    np.testing.assert_array_equal(a.contig_kasm(), b.contig_kasm())
+    np.testing.assert_array_equal(a.contig_kmissing(), b.contig_kmissing())
+    assert int(a.undr().sum() + a.over().sum()) > 10000
+
+
 @pytest.mark.parametrize("k", list(range(13, 32)))
 def test_mod_minimizer_placement_every_k(k, monkeypatch):
     """the compact layout places a k-mer by the window its smallest t-mer samples (mod-minimizer: t = 4..7 by k, windows of
