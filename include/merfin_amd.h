@@ -814,6 +814,64 @@ int mfx_track_write(const mfx_track_window *w, uint64_t n, const mfx_seq *seq, c
                     const char *tsv_path, const char *bedgraph_path);
 
 /* ------------------------------------------------------------------------ */
+/* -regions: maximal runs of missing, collapsed and expanded k-mers as       */
+/* intervals, made on the device.  The evaluation is -dump's                 */
+/* (merfin-dump.C:44-67); what it replaces is the awk over the -dump text of */
+/* the reference README, "Assess collapses and duplications" (and Merqury's  */
+/* meryl-lookup -bed + bedtools merge for the missing k-mers).  Per-base     */
+/* values never leave the device; one record per interval comes back.        */
+/* ------------------------------------------------------------------------ */
+/* The class of a k-mer start position (readK, asmK = asmV, K* as -dump computes them; t = mfx_regions_opts::kstar):
+ *   MISSING    a valid k-mer with readK == 0 (merfin-dump.C:56)
+ *   COLLAPSED  readK != 0, asmV != 0, K* >= t   (double compare; equality is in)
+ *   EXPANDED   readK != 0, asmV != 0, K* <= -t
+ * A position with no valid k-mer, with |K*| < t or with a K* that is not finite (readK != 0, asmV == 0: -track's n_nonfinite)
+ * is in no class.  An elementary run is a maximal stretch of consecutive positions of one contig in one class; a region
+ * joins runs of one class and contig while at most `gap` positions (of any other class, or none) lie between one run's last
+ * position and the next run's first -- regions of different classes may overlap, none crosses a contig's end; a region
+ * of fewer than min_kmers flagged k-mers is dropped after the joining.  Records are ordered by contig, start, class.  Every
+ * field is an integer sum or a max / min: the records do not depend on the order the device met the k-mers in.  56 bytes. */
+enum { MFX_REGION_MISSING = 0, MFX_REGION_COLLAPSED = 1, MFX_REGION_EXPANDED = 2 };
+typedef struct mfx_region {
+  uint32_t contig, cls;
+  uint64_t start, end;     /* k-mer start positions [start, end): first flagged .. last flagged + 1 */
+  uint64_t n_kmers;        /* flagged k-mers in it (end - start minus bridged positions)            */
+  uint64_t sum_readK;      /* integer-valued readK summed (0 for missing)                           */
+  uint64_t sum_asmK;       /* asmV summed                                                           */
+  double   ext_kstar;      /* collapsed: largest K*; expanded: smallest K*; missing: 0.0            */
+} mfx_region;
+typedef struct { double kstar; uint64_t gap; uint64_t min_kmers; } mfx_regions_opts;     /* -kstar (finite, > 0), -gap, -minrun */
+typedef struct mfx_regions mfx_regions;                       /* the result, held by the library */
+/* The records of the whole sequence set into *out (release with mfx_regions_free); *kasm / *kmissing = the totals -hist and
+ * -dump count.  Two passes (csrc/mfx_regions.h): the evaluation writes one bit per position and class, the runs, their joining
+ * and the filter are counted, scanned and scattered from those bits, and a second evaluation of the tiles that hold a flagged
+ * position adds the sums.  MFX_E_INVAL: a null argument, kstar not finite or <= 0, a sharded index, a sequence object that
+ * holds a part only, evaluator and sequence on different devices; MFX_E_NOMEM: the planes or the runs do not fit the device. */
+int  mfx_regions_run(mfx_eval *ev, const mfx_seq *seq, const mfx_regions_opts *o, mfx_regions **out, uint64_t *kasm, uint64_t *kmissing);
+/* The result object (no reference seam: the reference writes -dump text, merfin-dump.C:70-79, and leaves the intervals to awk).  count:
+ * its records; tiles_revisited: the tiles pass 2 evaluated (0 when no record survived); copy: the records in their order into dst[cap],
+ * MFX_E_INVAL when cap is below count; free: releases it (NULL is fine). */
+uint64_t mfx_regions_count(const mfx_regions *r);
+uint64_t mfx_regions_tiles_revisited(const mfx_regions *r);
+int  mfx_regions_copy(const mfx_regions *r, mfx_region *dst, uint64_t cap);
+void mfx_regions_free(mfx_regions *r);
+/* Diagnostic (tools/regions_rate.py; not part of the stable surface, like mfx_diag_spectrum_time): ms[3] = what the run spent in pass 1,
+ * in runs / joining / filter, and in pass 2 (wall milliseconds, each waited for) */
+void mfx_diag_regions_times(const mfx_regions *r, double *ms);
+/* Host only (merfin-dump.C:70-79 writes one line per k-mer; this writes one per interval).  One header line, "#chrom start end class n_kmers mean_readK mean_asmK ext_kstar" (tab-separated), then one BED
+ * line per record: the name (up to the first blank), the BASE span [start, end - 1 + k) -- a valid k-mer fits its contig, so
+ * the span does -- the class by name, n_kmers, sum_readK / n_kmers, sum_asmK / n_kmers and ext_kstar, each "%.2f".  .gz / .bz2 /
+ * .xz names go through the compressed writers (merfin-histogram.C:151). */
+int  mfx_regions_write(const mfx_region *r, uint64_t n, const mfx_seq *seq, const char *const *names, int k, const char *bed_path);
+/* Host only (tests, tools/native/regions_sanitize.cpp): the steps between the two passes -- starts and ends per word, count,
+ * scan, scatter, joining by o->gap, filter by o->min_kmers, order -- over caller-made planes[3][ntiles * 64] of contigs of
+ * contig_len[] positions (a contig takes ceil(len / 4096) tiles of 64 words per class; bit b of word w of a tile is position
+ * 64 w + b; bits beyond a contig's end must be 0: MFX_E_INVAL).  The sums and ext_kstar of the records are 0; at most cap are
+ * stored, *n_out counts them all.  o->kstar is not looked at. */
+int  mfx_regions_from_planes_host(const uint64_t *planes, const uint64_t *contig_len, uint32_t ncontigs, const mfx_regions_opts *o,
+                                  mfx_region *out, uint64_t cap, uint64_t *n_out);
+
+/* ------------------------------------------------------------------------ */
 /* -filter / -polish / -better / -strict / -loose: replaces processVariants */
 /* + outputVariants (merfin-variants.C:131-345), vcfFile (vcf.C) and varMer  */
 /* (varMer.C).  The host enumerates the allele-combination paths of many     */

@@ -96,6 +96,8 @@ SYMBOLS = [
     "mfx_db_writer_open_streamed", "mfx_db_writer_append_sorted", "mfx_db_writer_info", "mfx_index_write_db_streamed",
     "mfx_reads_store_create", "mfx_reads_store_add", "mfx_reads_store_info", "mfx_reads_replay", "mfx_reads_store_free",
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
+    "mfx_regions_run", "mfx_regions_count", "mfx_regions_tiles_revisited", "mfx_diag_regions_times", "mfx_regions_copy", "mfx_regions_free",
+    "mfx_regions_write", "mfx_regions_from_planes_host",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
@@ -118,6 +120,16 @@ TRACK_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_missing", "<u4"), ("n_scored", "
                         ("n_nonfinite", "<u4"), ("sum_readK", "<u8"), ("sum_asmK", "<u8"), ("sum_kstar_lo", "<u8"),
                         ("sum_kstar_hi", "<i8"), ("min_kstar", "<f8"), ("max_kstar", "<f8")])
 assert TRACK_DTYPE.itemsize == 72
+
+# one record of Evaluator.regions: the layout of mfx_region (include/merfin_amd.h), 56 bytes; cls: REGION_CLASSES[cls]
+REGION_DTYPE = np.dtype([("contig", "<u4"), ("cls", "<u4"), ("start", "<u8"), ("end", "<u8"), ("n_kmers", "<u8"), ("sum_readK", "<u8"),
+                         ("sum_asmK", "<u8"), ("ext_kstar", "<f8")])
+assert REGION_DTYPE.itemsize == 56
+REGION_CLASSES = ("missing", "collapsed", "expanded")
+
+
+class _RegionsOpts(C.Structure):
+    _fields_ = [("kstar", C.c_double), ("gap", C.c_uint64), ("min_kmers", C.c_uint64)]
 
 
 def _share_hip_runtime_with_torch():
@@ -343,6 +355,18 @@ def load_library():
     L.mfx_track_num_windows.argtypes = [vp, C.c_uint64]
     L.mfx_track_run.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
     L.mfx_track_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p]
+    L.mfx_regions_run.argtypes = [vp, vp, C.POINTER(_RegionsOpts), C.POINTER(vp), u64p, u64p]
+    L.mfx_regions_count.restype = C.c_uint64
+    L.mfx_regions_count.argtypes = [vp]
+    L.mfx_regions_tiles_revisited.restype = C.c_uint64
+    L.mfx_regions_tiles_revisited.argtypes = [vp]
+    L.mfx_diag_regions_times.restype = None
+    L.mfx_diag_regions_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mfx_regions_copy.argtypes = [vp, vp, C.c_uint64]
+    L.mfx_regions_free.restype = None
+    L.mfx_regions_free.argtypes = [vp]
+    L.mfx_regions_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_int, C.c_char_p]
+    L.mfx_regions_from_planes_host.argtypes = [vp, u64p, C.c_uint32, C.POINTER(_RegionsOpts), vp, C.c_uint64, u64p]
     L.mfx_spectrum_run.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p]
     L.mfx_diag_spectrum_time.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
     L.mfx_spectrum_peak.argtypes = [u64p, C.c_uint32, C.POINTER(_SpectrumPeak)]
@@ -1243,6 +1267,38 @@ def track_write(windows, seqs, names, window, tsv_path=None, bedgraph_path=None)
                                           tsv_path.encode() if tsv_path else None, bedgraph_path.encode() if bedgraph_path else None))
 
 
+def _regions_opts(kstar, gap, min_kmers):
+    if not (0 <= int(gap) < 2**64 and 0 <= int(min_kmers) < 2**64):
+        raise MfxError(-1, "regions: gap and min_kmers are integers in [0, 2^64)")
+    return _RegionsOpts(float(kstar), int(gap), int(min_kmers))
+
+
+def regions_write(regions, seqs, names, k, bed_path):
+    """the records of Evaluator.regions as BED text (mfx_regions_write; host only): a header line, then chrom, the base span
+    [start, end - 1 + k), the class, n_kmers, mean readK, mean asmK and the extreme K*; .gz / .bz2 / .xz names are compressed"""
+    r = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    _check(load_library().mfx_regions_write(C.c_void_p(r.ctypes.data), len(r), seqs.h, nm, int(k), bed_path.encode()))
+
+
+def regions_from_planes_host(planes, contig_lens, gap=0, min_kmers=1):
+    """the steps of Evaluator.regions between its two passes, on the host, over caller-made class planes (mfx_regions_from_planes_host):
+    planes is a uint64 array [3][ntiles * 64], ntiles = sum(ceil(len / 4096)); the records come back with their sums at 0"""
+    planes = np.ascontiguousarray(planes, dtype=np.uint64)
+    lens = np.ascontiguousarray(contig_lens, dtype=np.uint64)
+    ntiles = int(sum((int(x) + 4095) // 4096 for x in lens))
+    if planes.size != 3 * 64 * ntiles:
+        raise MfxError(-1, "regions_from_planes_host: %d words for %d tiles (3 x 64 each)" % (planes.size, ntiles))
+    o = _regions_opts(1.0, gap, min_kmers)
+    L = load_library()
+    n = C.c_uint64(0)
+    lp = lens.ctypes.data_as(C.POINTER(C.c_uint64))
+    _check(L.mfx_regions_from_planes_host(C.c_void_p(planes.ctypes.data), lp, len(lens), C.byref(o), None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), dtype=REGION_DTYPE)
+    _check(L.mfx_regions_from_planes_host(C.c_void_p(planes.ctypes.data), lp, len(lens), C.byref(o), C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+    return out[:n.value]
+
+
 E_NODATA = -10
 
 
@@ -1681,6 +1737,29 @@ class Evaluator:
         got, ka, km = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(L.mfx_track_run(self.h, seqs.h, int(window), C.c_void_p(w.ctypes.data), n, C.byref(got), C.byref(ka), C.byref(km)))
         return w[:got.value], ka.value, km.value
+
+    def regions(self, seqs, kstar=1.0, gap=0, min_kmers=1, times=None):
+        """maximal runs of missing (readK == 0), collapsed (K* >= kstar) and expanded (K* <= -kstar) k-mers of every contig, runs of
+        a class joined over at most `gap` positions and regions of fewer than min_kmers flagged k-mers dropped, made on the device
+        (mfx_regions_run): a structured array of dtype REGION_DTYPE ordered by contig, start, class; the totals kasm, kmissing; and
+        the number of tiles the second pass evaluated.  times: a list that receives the milliseconds of pass 1, runs / joining, pass 2"""
+        L = load_library()
+        o = _regions_opts(kstar, gap, min_kmers)
+        h = C.c_void_p(None)
+        ka, km = C.c_uint64(0), C.c_uint64(0)
+        _check(L.mfx_regions_run(self.h, seqs.h, C.byref(o), C.byref(h), C.byref(ka), C.byref(km)))
+        try:
+            n = L.mfx_regions_count(h)
+            r = np.zeros(max(n, 1), dtype=REGION_DTYPE)
+            _check(L.mfx_regions_copy(h, C.c_void_p(r.ctypes.data), n))
+            revisited = L.mfx_regions_tiles_revisited(h)
+            if times is not None:
+                ms = (C.c_double * 3)()
+                L.mfx_diag_regions_times(h, ms)
+                times[:] = list(ms)
+        finally:
+            L.mfx_regions_free(h)
+        return r[:n], ka.value, km.value, revisited
 
     def variants(self, mode, vcf_path, names, contigs, out_path, comb=15, nosplit=False, debug_path=None, log_path=None):
         """-filter/-polish/-better/-strict/-loose over all contigs; returns clusters evaluated"""

@@ -13,7 +13,7 @@
 
 #include "../../include/merfin_amd.h"
 
-enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM };
+enum { OP_NONE, OP_HIST, OP_COMPL, OP_DUMP, OP_FILTER, OP_POLISH, OP_BETTER, OP_STRICT, OP_LOOSE, OP_TRACK, OP_SPECTRUM, OP_REGIONS };
 
 struct Globals {
   const char *seqName = nullptr, *seqDBname = nullptr, *readDBname = nullptr, *pLookupTable = nullptr;
@@ -41,6 +41,9 @@ struct Globals {
   std::vector<const char *> mergeNames;  // -merge: no report; these sorted databases combined on the GPU into -output (mfx_db_merge)
   const char *opName = nullptr;          // -op of -merge: sum (default), max, min, intersect
   int mergeOp = MFX_MERGE_SUM;
+  double regKstar = 1.0;                 // -kstar: |K*| at which -regions calls a k-mer collapsed / expanded
+  uint64_t regGap = 0, regMinrun = 1;    // -gap / -minrun of -regions
+  bool kstarGiven = false, gapGiven = false, minrunGiven = false;
   bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
 };
 
@@ -125,11 +128,26 @@ static void usage_join() {
           "\n");
 }
 
+// the entries of -regions: printed behind the text above for a command line that names one of its flags
+static void usage_regions() {
+  fprintf(stderr,
+          "  Intervals instead of windows (a report type, like -track):\n"
+          "    -regions          maximal runs of missing (readK = 0), collapsed (K* >= t) and expanded (K* <= -t) k-mers of every contig, made on\n"
+          "                      the GPU -> <output>.regions.bed: chrom, base span, class, flagged k-mers, mean readK, mean asmK, extreme K*.\n"
+          "                      An <output> ending in .gz / .bz2 / .xz compresses it (out.gz -> out.regions.bed.gz).  One device.\n"
+          "                      Takes -reads, -seqmers, -index and -peak auto as -track does.\n"
+          "    -kstar t          with -regions: the threshold t, a finite number above 0 (default 1.0)\n"
+          "    -gap g            with -regions: runs of one class and contig with at most g positions between them are one region (default 0)\n"
+          "    -minrun m         with -regions: regions of fewer than m flagged k-mers are dropped, after the joining (default 1)\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
-static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false) {
+static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false) {
   usage(argv0);
   if (merge) usage_merge();
   if (join) usage_join();
+  if (regions) usage_regions();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -259,6 +277,25 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
       if (parse_uint(v, 1, ~0ull, &x) != UINT_OK) err.push_back(std::string("Invalid -window '") + v + "': a window is an integer of at least 1.\n");
       else G.window = x;
     }
+    else if (is("-regions")) G.reportType = OP_REGIONS;
+    else if (is("-kstar")) {
+      const char *v = val();
+      char *e = nullptr;
+      G.kstarGiven = true;
+      errno = 0;
+      const double t = strtod(v, &e);
+      if (e == v || *e != 0 || isspace((unsigned char)v[0]) || !(t > 0) || !(t <= 1.7976931348623157e308))
+        err.push_back(std::string("Invalid -kstar '") + v + "': the threshold of -regions is a finite number above 0.\n");
+      else G.regKstar = t;
+    }
+    else if (is("-gap") || is("-minrun")) {
+      const bool gp = is("-gap");
+      const char *v = val();
+      (gp ? G.gapGiven : G.minrunGiven) = true;
+      if (parse_uint(v, 0, ~0ull, &x) != UINT_OK)
+        err.push_back(std::string("Invalid ") + (gp ? "-gap" : "-minrun") + " '" + v + "': " + (gp ? "a gap is a number of positions" : "-minrun is a number of k-mers") + ", an integer of at least 0.\n");
+      else (gp ? G.regGap : G.regMinrun) = x;
+    }
     else if (is("-skipMissing")) G.skipMissing = true;
     else if (is("-completeness")) G.reportType = OP_COMPL;
     else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
@@ -374,6 +411,21 @@ static void check_track_flags(const Globals &G, Errors &err) {
   if (G.vcfName) err.push_back("-track does not take -vcf (the variant modes do).\n");
 }
 
+// -regions: every check before any device is touched
+static bool regions_named(const Globals &G) { return G.reportType == OP_REGIONS || G.kstarGiven || G.gapGiven || G.minrunGiven; }
+static void check_regions_flags(const Globals &G, Errors &err) {
+  if (G.reportType != OP_REGIONS) {
+    if (G.kstarGiven) err.push_back("-kstar sets the threshold of -regions; it has no meaning without -regions.\n");
+    if (G.gapGiven) err.push_back("-gap joins the runs of -regions; it has no meaning without -regions.\n");
+    if (G.minrunGiven) err.push_back("-minrun drops short regions of -regions; it has no meaning without -regions.\n");
+    return;
+  }
+  if (G.sharded) err.push_back("-regions does not take -sharded: a k-mer's class needs its whole counts on one device.\n");
+  if (G.devices.size() > 1) err.push_back("-regions runs on one device (-device d, or -devices naming one).\n");
+  if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -regions writes the missing k-mers as intervals.\n");
+  if (G.vcfName) err.push_back("-regions does not take -vcf (the variant modes do).\n");
+}
+
 // -spectrum: every check before any device is touched
 static void check_spectrum_flags(const Globals &G, Errors &err) {
   if ((G.copiesGiven || G.maxMultGiven) && G.reportType != OP_SPECTRUM)
@@ -406,7 +458,7 @@ static void check_join_flags(const Globals &G, Errors &err) {
 static void check_peak_auto_flags(const Globals &G, Errors &err) {
   if (!G.peakAuto) return;
   if (G.peak != 0) err.push_back("-peak was given twice (a number and auto).\n");
-  if (G.reportType != OP_HIST && G.reportType != OP_DUMP && G.reportType != OP_TRACK && G.reportType != OP_SPECTRUM && G.reportType != OP_NONE)
+  if (G.reportType != OP_HIST && G.reportType != OP_DUMP && G.reportType != OP_TRACK && G.reportType != OP_SPECTRUM && G.reportType != OP_REGIONS && G.reportType != OP_NONE)
     err.push_back("-peak auto reads the peak off the table of -hist, -dump, -track or -spectrum; the variant modes and -completeness take -peak <number>.\n");
   if (G.sharded) err.push_back("-peak auto does not take -sharded: no peak is defined on a sharded table.\n");
   if (G.devices.size() > 1) err.push_back("-peak auto runs on one device (-device d, or -devices naming one).\n");

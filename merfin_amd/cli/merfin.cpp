@@ -1175,7 +1175,7 @@ static int probe_databases(Run &R) {
 // MFX_DB_STAGE=0: no stage, the build reads the database when it gets there.
 static void begin_stage(Run &R) {
   const Globals &G = R.G;
-  const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK) && !G.sharded && R.k <= 31 && G.seqName && !G.seqDBname &&
+  const bool histLike = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || G.reportType == OP_REGIONS) && !G.sharded && R.k <= 31 && G.seqName && !G.seqDBname &&
                         !G.indexName && G.devices.size() == 1 && !R.fullIndex;
   if (histLike && R.rdb.format == MFX_DB_FLAT) R.stage = mfx_db_stage_begin(G.readDBname, G.device);
 }
@@ -1237,7 +1237,7 @@ static int decide_path_only(Run &R) {
 // 2.4-3.2 s overlapped; MFX_CLI_OVERLAP=1 / 0 forces either).
 static void decide_seq_only_and_defer(Run &R, bool compressed) {
   const Globals &G = R.G;
-  R.seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || (G.reportType == OP_SPECTRUM && R.fromReads)) && !G.sharded &&
+  R.seqOnly = (G.reportType == OP_HIST || G.reportType == OP_DUMP || G.reportType == OP_TRACK || G.reportType == OP_REGIONS || (G.reportType == OP_SPECTRUM && R.fromReads)) && !G.sharded &&
               R.k <= 31 && (R.fromReads || !R.fullIndex);
   const int ov = env_flag("MFX_CLI_OVERLAP");
   const bool wantOverlap = ov >= 0 ? ov != 0 : compressed;
@@ -1717,6 +1717,45 @@ static int report_track(Run &R) {
   return 0;
 }
 
+// Runs of missing, collapsed and expanded k-mers as intervals, made on the device (mfx_regions_run): what the README's "Assess collapses and
+// duplications" makes from the -dump text with awk.  The counts on stderr are those of -dump -skipMissing.
+static int report_regions(Run &R) {
+  const Globals &G = R.G;
+  std::string stem = G.outName, zsuf;
+  if (mfx_suffix_tool(stem)) { const size_t dot = stem.rfind('.'); zsuf = stem.substr(dot); stem.resize(dot); }
+  const std::string bedName = stem + ".regions.bed" + zsuf;
+  fprintf(stderr, "-- Runs of missing k-mers and of k-mers with |k*| >= %g (gap %lu, at least %lu k-mers) to '%s'.\n", G.regKstar, (unsigned long)G.regGap,
+          (unsigned long)G.regMinrun, bedName.c_str());
+  const mfx_regions_opts o{G.regKstar, G.regGap, G.regMinrun};
+  Owned<mfx_regions, mfx_regions_free> res;
+  uint64_t kasm = 0, kmissing = 0;
+  {
+    mfx_regions *r = nullptr;
+    if (mfx_regions_run(R.ev, R.seq, &o, &r, &kasm, &kmissing)) DIE_MFX("-regions");
+    res = r;
+  }
+  std::vector<mfx_region> recs((size_t)mfx_regions_count(res));
+  if (mfx_regions_copy(res, recs.data(), recs.size())) DIE_MFX("-regions");
+  if (mfx_regions_write(recs.data(), recs.size(), R.seq, R.S.names.data(), R.k, bedName.c_str())) DIE_MFX("writing the regions");
+  // the per-contig counts: those of a -hist run, as -dump -skipMissing takes them
+  mfx_hist_result h;
+  if (mfx_hist_run(R.ev, R.seq, &h)) DIE_MFX("-regions (counts)");
+  ContigCounts counts;
+  counts.lines(R.S.recs, h);
+  mfx_hist_result_free(&h);
+  if (counts.cumAsm != kasm || counts.cumMissing != kmissing) {
+    fprintf(stderr, "ERROR: -regions: the contigs hold %lu k-mers (%lu missing), the class pass counted %lu (%lu).\n", (unsigned long)counts.cumAsm,
+            (unsigned long)counts.cumMissing, (unsigned long)kasm, (unsigned long)kmissing);
+    return 1;
+  }
+  static const char *const cls_name[3] = {"missing", "collapsed", "expanded"};
+  uint64_t nr[3] = {0, 0, 0}, nk[3] = {0, 0, 0}, nb[3] = {0, 0, 0};
+  for (const mfx_region &x : recs) { nr[x.cls]++; nk[x.cls] += x.n_kmers; nb[x.cls] += x.end - 1 + (uint64_t)R.k - x.start; }
+  for (int c = 0; c < 3; ++c)
+    fprintf(stderr, "-- %s: %lu regions, %lu flagged k-mers, %lu bases covered.\n", cls_name[c], (unsigned long)nr[c], (unsigned long)nk[c], (unsigned long)nb[c]);
+  return 0;
+}
+
 // The call set of the variant modes in several slots: one pass over the VCF gives the records per contig (for the balance), and the lines
 // themselves, so that every slot is handed a VCF of ITS contigs only (each slot parsing all 4 M records of a human call set made N slots
 // N times the host work of one; the host is what bounds these modes)
@@ -1895,11 +1934,12 @@ int main(int argc, char **argv) {
   if (G.join && !G.readsNames.empty()) return fail_usage(argv[0], err, false, true);      // (the checks of -reads open -seqmers for its k)
   if (!check_reads_flags(G, err)) return 1;
   check_track_flags(G, err);
+  check_regions_flags(G, err);
   check_spectrum_flags(G, err);
   check_peak_auto_flags(G, err);
   if (G.convertName && err.empty()) return run_convert(G);
   check_report_flags(G, err);
-  if (!err.empty()) return fail_usage(argv[0], err, false, G.join);
+  if (!err.empty()) return fail_usage(argv[0], err, false, G.join, regions_named(G));
   if (!G.devices.empty()) G.device = G.devices[0];
   else G.devices.push_back(G.device);
   // 2. load_Kmetric first (merfin-globals.C:21-62 runs before the databases are opened; host only -- a compressed table's decompressor has
@@ -1972,6 +2012,7 @@ int main(int argc, char **argv) {
   }
   // 16. the report
   const int rc = G.reportType == OP_HIST ? report_hist(R) : G.reportType == OP_DUMP ? report_dump(R) : G.reportType == OP_TRACK ? report_track(R) :
+                 G.reportType == OP_REGIONS ? report_regions(R) :
                  R.variantMode ? report_variants(R) : G.reportType == OP_COMPL ? report_completeness(R) : 0;
   if (rc) return rc;
   R.clock.lap("evaluate + write");

@@ -111,6 +111,32 @@ struct mfx_track_args {
   uint64_t       *stats;              // [0] kasm [1] kmissing
 };
 
+// -regions (csrc/mfx_regions.h).  Pass 1 (mfx_regions_class_kernel / mfx_w_regions_class_kernel) writes the class planes and the two totals;
+// pass 2 (mfx_regions_sums_kernel / mfx_w_regions_sums_kernel) evaluates the flagged positions of the flagged tiles again for the sums
+struct mfx_regions_args {
+  mfx_table_view  t;
+  int             canonical;
+  const uint8_t  *bases;
+  const uint64_t *codes = nullptr;    // non-null (k <= 31): the tiles are read from the packed planes, as -hist does
+  const uint32_t *valid = nullptr;
+  const uint64_t *contig_off, *contig_len, *tile_start;
+  const uint32_t *tile_contig;
+  uint64_t        ntiles;
+  double          peak;
+  uint32_t        n_prob;
+  const uint32_t *probK;
+  const double   *probP;
+  double          kstar;              // the threshold t: finite, > 0
+  uint64_t       *planes;             // [3][ntiles * 64]: bit b of word tile * 64 + w = position 64 w + b of the tile; every word is written by pass 1
+  uint64_t       *stats = nullptr;    // pass 1: [0] kasm [1] kmissing
+  // pass 2
+  const uint64_t *tile_flag = nullptr;   // [ntiles] != 0: one of the tile's 192 plane words is not 0
+  uint64_t       *regs = nullptr;     // the records, 7 words each (mfx_region), class after class, each class in (contig, start) order;
+                                      //   word 6 holds the largest key (collapsed) / ~key (expanded) of K* while the kernel runs
+  uint64_t       *recount = nullptr;  // [records] the flagged k-mers pass 2 found for each
+  uint64_t        reg_begin0 = 0, reg_begin1 = 0, reg_begin2 = 0, reg_begin3 = 0;   // class c's records: [reg_begin c, reg_begin c+1)
+};
+
 struct mfx_count_args {
   mfx_table_view  t;
   const uint8_t  *bases;
@@ -204,6 +230,27 @@ hipError_t mfx_kw_completeness(mfx_table_view t, double peak, uint32_t n_prob, c
 hipError_t mfx_k_dump(const mfx_dump_args &a, hipStream_t st);
 hipError_t mfx_k_track(const mfx_track_args &a, hipStream_t st);          // k <= 31
 hipError_t mfx_kw_track(const mfx_track_args &a, hipStream_t st);         // 32 <= k <= 64 (mfx_wide.hip)
+hipError_t mfx_k_regions_class(const mfx_regions_args &a, hipStream_t st);     // k <= 31
+hipError_t mfx_kw_regions_class(const mfx_regions_args &a, hipStream_t st);    // 32 <= k <= 64 (mfx_wide.hip)
+hipError_t mfx_k_regions_sums(const mfx_regions_args &a, hipStream_t st);
+hipError_t mfx_kw_regions_sums(const mfx_regions_args &a, hipStream_t st);
+// the steps between the passes (mfx_regions.hip); every array is the caller's, every count a uint64
+size_t     mfx_k_rg_temp_bytes(uint64_t n);                                        // temporary storage the scan / the sum of n counts needs
+hipError_t mfx_k_rg_scan(uint64_t *d, uint64_t n, void *tmp, size_t tmp_bytes, hipStream_t st);      // exclusive prefix sums, in place; waits for nothing
+hipError_t mfx_k_rg_sum(const uint64_t *d, uint64_t n, uint64_t *out, void *tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t mfx_k_rg_pick(const uint64_t *src, const uint64_t *idx /* host */, uint32_t n /* <= 4 */, uint64_t *dst, hipStream_t st);   // dst[i] = src[idx[i]]
+hipError_t mfx_k_rg_count(const uint64_t *planes, uint64_t ntiles, const uint32_t *tile_contig, uint64_t *cnt_s, uint64_t *cnt_e, uint64_t *tile_flag, hipStream_t st);
+hipError_t mfx_k_rg_scatter(const uint64_t *planes, uint64_t ntiles, const uint64_t *tile_start, const uint32_t *tile_contig, const uint64_t *off_s,
+                            const uint64_t *off_e, uint32_t *run_contig, uint64_t *run_start, uint64_t *run_end, hipStream_t st);
+hipError_t mfx_k_rg_heads(const uint32_t *run_contig, const uint64_t *run_start, const uint64_t *run_end, uint64_t nruns, const uint64_t *cls_run /* [4], host */,
+                          uint64_t gap, uint64_t *head, uint64_t *len, hipStream_t st);
+hipError_t mfx_k_rg_bounds(const uint64_t *head_x /* exclusive scan of head, nruns + 1 */, uint64_t nruns, uint64_t *reg_first, uint64_t *reg_last, hipStream_t st);
+hipError_t mfx_k_rg_keep(const uint64_t *reg_first, const uint64_t *reg_last, const uint64_t *len_x /* exclusive scan of len, nruns + 1 */, uint64_t nraw,
+                         uint64_t min_kmers, uint64_t *keep, hipStream_t st);
+hipError_t mfx_k_rg_emit(const uint64_t *reg_first, const uint64_t *reg_last, const uint64_t *len_x, const uint64_t *keep_x /* exclusive scan of keep, nraw + 1 */,
+                         uint64_t nraw, const uint64_t *cls_run /* [4], host */, const uint32_t *run_contig, const uint64_t *run_start, const uint64_t *run_end,
+                         uint64_t *regs, hipStream_t st);
+hipError_t mfx_k_rg_finish(uint64_t *regs, uint64_t nreg, hipStream_t st);        // word 6: key -> ext_kstar
 hipError_t mfx_k_track_finish(uint64_t *recs, uint64_t nrec, hipStream_t st);   // the min / max keys of the records -> doubles (+inf / -inf where nothing was scored)
 // *out += the content digest of nwords 32-base words (codes != nullptr: from the packed planes, else from the bytes)
 hipError_t mfx_k_seq_digest(const uint8_t *bases, const uint64_t *codes, const uint32_t *valid, uint64_t nwords, uint64_t *out, hipStream_t st);

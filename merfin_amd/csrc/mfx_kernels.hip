@@ -16,6 +16,8 @@
 #include "mfx_device.h"
 #include "mfx_place.h"
 #include "mfx_track.h"
+#define MFX_REGIONS_DEVICE
+#include "mfx_regions.h"
 #include "mfx_spectrum.h"
 
 #include <stdlib.h>
@@ -3244,6 +3246,114 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_track_finish_kernel(uint64_t *r
 }
 
 // ===========================================================================
+// -regions (csrc/mfx_regions.h): the evaluation of mfx_track_kernel -- its tile loop, its lookups -- twice.  Pass 1 (SUMS = false) turns
+// every position's class into one bit of the wave's three ballots and stores the 64-bit masks: no per-position value, no atomic but the
+// two totals.  Pass 2 (SUMS = true) goes over the tiles that hold a flagged position only, looks up the flagged positions only, and
+// adds each to the record of its region.
+// ===========================================================================
+static_assert(MFX_RG_TILE == MFX_TILE && MFX_RG_WORDS * 64 == MFX_TILE && MFX_BLOCK == 256, "mfx_regions.h: a wave of a round holds one word of the tile");
+
+template <bool CANON, bool COMPACT, bool SUMS>
+__device__ __forceinline__ void mfx_regions_tiles(const mfx_regions_args &a, mfx_tile_lds &L, mfx_mailbox &MB, uint64_t &n_valid, uint64_t &n_missing) {
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t nwords = a.ntiles * MFX_RG_WORDS;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    if (SUMS && a.tile_flag[tile] == 0ull) continue;           // block-uniform: nothing of this tile is in a class
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    if (a.codes) {                                             // block-uniform
+      const uint64_t w0 = (a.contig_off[c] + pos0) >> 5;
+      mfx_tile_fill_packed(L, a.codes + w0, a.valid + w0);
+    } else {
+      mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    }
+    __syncthreads();                                           // the tile is in LDS
+    uint32_t b = 0;
+    for (; b < MFX_TILE / MFX_BLOCK; b += MFX_BATCH) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      uint64_t key[MFX_BATCH], key2[MFX_BATCH];
+      uint32_t rv[MFX_BATCH], av[MFX_BATCH];
+      bool     ok[MFX_BATCH];
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;          // lane-consecutive positions: a wave holds word p / 64 of the tile
+        uint64_t f;
+        ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
+        if (SUMS) {                                            // only what pass 1 flagged is looked up again
+          const uint64_t word = tile * MFX_RG_WORDS + (p >> 6);
+          const uint64_t m = a.planes[word] | a.planes[nwords + word] | a.planes[2 * nwords + word];
+          ok[j] = ok[j] && ((m >> (tid & 63u)) & 1ull);
+        }
+        const uint64_t r = mfx_revcomp(f, k);
+        if (CANON) { key[j] = f < r ? f : r; key2[j] = f < r ? r : f; }
+        else { key[j] = f; key2[j] = r; }
+      }
+      if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key, key2, ok, rv, av);
+      else mfx_group_lookup<MFX_BATCH>(a.t, MB, key, key2, ok, rv, av);
+      if (!CANON) {                                            // value(fmer) + value(rmer), uint32 arithmetic (merfin-globals.C:107-108)
+        uint32_t rv2[MFX_BATCH], av2[MFX_BATCH];
+        if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key2, key, ok, rv2, av2);
+        else mfx_group_lookup<MFX_BATCH>(a.t, MB, key2, key, ok, rv2, av2);
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) { rv[j] += rv2[j]; av[j] += av2[j]; }
+      } else if ((k & 1) == 0) {                               // even k: a palindromic k-mer is value(fmer) + value(rmer) of ONE slot
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) if (key[j] == key2[j]) { rv[j] += rv[j]; av[j] += av[j]; }
+      }
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;
+        if (SUMS) {
+          mfx_rg_visit(a, c, pos0 + p, ok[j], rv[j], av[j]);
+        } else {
+          uint32_t cls = MFX_RG_NONE;
+          if (ok[j]) {
+            double readK, x;
+            n_valid++;                                         // merfin-dump.C:48
+            cls = mfx_rg_classify(a.peak, a.n_prob, a.probK, a.probP, a.kstar, rv[j], av[j], readK, x);
+            if (cls == MFX_REGION_MISSING) n_missing++;        // :56-58
+          }
+          mfx_rg_store_masks(a.planes, nwords, tile * MFX_RG_WORDS + (p >> 6), cls);
+        }
+      }
+    }
+    if (!SUMS)                                                 // the rounds beyond a contig's end: their words are 0
+      for (uint32_t w = b * (MFX_BLOCK / 64) + tid; w < MFX_RG_WORDS; w += MFX_BLOCK) {
+        const uint64_t word = tile * MFX_RG_WORDS + w;
+        a.planes[word] = 0ull;
+        a.planes[nwords + word] = 0ull;
+        a.planes[2 * nwords + word] = 0ull;
+      }
+    __syncthreads();                                           // the tile is consumed
+  }
+}
+
+template <bool CANON, bool COMPACT>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_regions_class_kernel(mfx_regions_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_mailbox MB;
+  __shared__ uint64_t s_red[MFX_BLOCK / 64][3];
+  uint64_t n_valid = 0, n_missing = 0, zz = 0;
+  mfx_regions_tiles<CANON, COMPACT, false>(a, L, MB, n_valid, n_missing);
+  mfx_block_sum3(n_valid, n_missing, zz, s_red);
+  if (threadIdx.x == 0 && (n_valid | n_missing)) {
+    atomicAdd((unsigned long long *)&a.stats[0], n_valid);
+    atomicAdd((unsigned long long *)&a.stats[1], n_missing);
+  }
+}
+
+template <bool CANON, bool COMPACT>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_regions_sums_kernel(mfx_regions_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_mailbox MB;
+  uint64_t n_valid = 0, n_missing = 0;
+  mfx_regions_tiles<CANON, COMPACT, true>(a, L, MB, n_valid, n_missing);
+}
+
+// ===========================================================================
 // varMer::score on the device (varMer.C:66-144): one lane per alternative PATH of a batch of variant clusters.  The paths'
 // k-mers have been looked up by mfx_dump_kernel over the packed path text (readV / asmV per start position); this walks a
 // path's bases in order exactly as the reference does -- run length of valid bases, the k-mer ENDING at idx, readK / prob by
@@ -4149,6 +4259,24 @@ hipError_t mfx_k_track(const mfx_track_args &a, hipStream_t st) {
   else if (a.canonical)           mfx_track_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else if (a.t.compact)           mfx_track_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else                            mfx_track_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_regions_class(const mfx_regions_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical && a.t.compact) mfx_regions_class_kernel<true, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.canonical)           mfx_regions_class_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.t.compact)           mfx_regions_class_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else                            mfx_regions_class_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_regions_sums(const mfx_regions_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical && a.t.compact) mfx_regions_sums_kernel<true, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.canonical)           mfx_regions_sums_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.t.compact)           mfx_regions_sums_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else                            mfx_regions_sums_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_k_track_finish(uint64_t *recs, uint64_t nrec, hipStream_t st) {

@@ -15,6 +15,8 @@
 // of that order.
 #include "mfx_device.h"
 #include "mfx_track.h"
+#define MFX_REGIONS_DEVICE
+#include "mfx_regions.h"
 #include "mfx_spectrum.h"
 
 typedef unsigned __int128 mfx_u128;
@@ -384,6 +386,80 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_track_kernel(mfx_track_args a
   }
 }
 
+// -regions (csrc/mfx_regions.h): the evaluation of mfx_w_track_kernel twice, as the k <= 31 kernels do it (mfx_kernels.hip: mfx_regions_tiles) -- the
+// planes and the records are the same whichever kernel made them
+static_assert(MFX_RG_TILE == MFX_TILE && MFX_BLOCK == 256, "mfx_regions.h: a wave of a round holds one word of the tile");
+
+template <bool CANON, bool SUMS>
+__device__ __forceinline__ void mfx_w_regions_tiles(const mfx_regions_args &a, mfx_tile_lds &L, uint64_t &n_valid, uint64_t &n_missing) {
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t nwords = a.ntiles * MFX_RG_WORDS;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    if (SUMS && a.tile_flag[tile] == 0ull) continue;           // block-uniform: nothing of this tile is in a class
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    __syncthreads();
+    uint32_t b = 0;
+    for (; b < MFX_TILE / MFX_BLOCK; ++b) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      const uint32_t p = b * MFX_BLOCK + tid;
+      const uint64_t word = tile * MFX_RG_WORDS + (p >> 6);
+      mfx_u128 f;
+      bool ok = mfx_w_tile_kmer(L, k, p, f) && p < n;
+      if (SUMS) {                                              // only what pass 1 flagged is looked up again
+        const uint64_t m = a.planes[word] | a.planes[nwords + word] | a.planes[2 * nwords + word];
+        ok = ok && ((m >> (tid & 63u)) & 1ull);
+      }
+      uint2 v = make_uint2(0u, 0u);
+      if (ok) v = mfx_w_getV<CANON>(a.t, f, k);
+      if (SUMS) {
+        mfx_rg_visit(a, c, pos0 + p, ok, v.x, v.y);
+      } else {
+        uint32_t cls = MFX_RG_NONE;
+        if (ok) {
+          double readK, x;
+          n_valid++;                                           // merfin-dump.C:48
+          cls = mfx_rg_classify(a.peak, a.n_prob, a.probK, a.probP, a.kstar, v.x, v.y, readK, x);
+          if (cls == MFX_REGION_MISSING) n_missing++;          // :56-58
+        }
+        mfx_rg_store_masks(a.planes, nwords, word, cls);
+      }
+    }
+    if (!SUMS)                                                 // the rounds beyond a contig's end: their words are 0
+      for (uint32_t w = b * (MFX_BLOCK / 64) + tid; w < MFX_RG_WORDS; w += MFX_BLOCK) {
+        const uint64_t word = tile * MFX_RG_WORDS + w;
+        a.planes[word] = 0ull;
+        a.planes[nwords + word] = 0ull;
+        a.planes[2 * nwords + word] = 0ull;
+      }
+    __syncthreads();                                           // the tile is consumed
+  }
+}
+
+template <bool CANON>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_regions_class_kernel(mfx_regions_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ uint64_t s_red[MFX_BLOCK / 64][3];
+  uint64_t n_valid = 0, n_missing = 0, zz = 0;
+  mfx_w_regions_tiles<CANON, false>(a, L, n_valid, n_missing);
+  mfx_block_sum3(n_valid, n_missing, zz, s_red);
+  if (threadIdx.x == 0 && (n_valid | n_missing)) {
+    atomicAdd((unsigned long long *)&a.stats[0], n_valid);
+    atomicAdd((unsigned long long *)&a.stats[1], n_missing);
+  }
+}
+
+template <bool CANON>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_regions_sums_kernel(mfx_regions_args a) {
+  __shared__ mfx_tile_lds L;
+  uint64_t n_valid = 0, n_missing = 0;
+  mfx_w_regions_tiles<CANON, true>(a, L, n_valid, n_missing);
+}
+
 // `meryl count` of the assembly (merfin-globals.C:182-186)
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_count_kernel(mfx_count_args a) {
   __shared__ mfx_tile_lds L;
@@ -564,6 +640,20 @@ hipError_t mfx_kw_track(const mfx_track_args &a, hipStream_t st) {
   const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
   if (a.canonical) mfx_w_track_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else             mfx_w_track_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_kw_regions_class(const mfx_regions_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical) mfx_w_regions_class_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_w_regions_class_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_kw_regions_sums(const mfx_regions_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical) mfx_w_regions_sums_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_w_regions_sums_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_kw_count(const mfx_count_args &a, hipStream_t st) {
