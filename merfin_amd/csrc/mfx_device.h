@@ -173,6 +173,7 @@ struct mfx_hist_lds {
   uint32_t wl_n;                          // mfx_hist_kernel: entries this block has put on its segment of the worklist
   uint64_t next[2];                       // dynamic tile scheduler: the tile fetched for the next iteration
   uint64_t tot[2];                        // mfx_hist_kernel: valid / missing k-mers of the contigs this block already flushed (thread 0)
+  unsigned long long kfx_slot[MFX_BLOCK / 64];   // mfx_hist_kernel: the koverCpy sums of the tile's four slots (units of 2^-52), slot of position p: (p >> 6) & 3
   uint64_t red[MFX_BLOCK / 64][3];
   double   dred[MFX_BLOCK];
 };

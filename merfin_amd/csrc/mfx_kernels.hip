@@ -1964,9 +1964,10 @@ __device__ __forceinline__ uint32_t mfx_lane_probe_defer(const mfx_table_view &c
   return defer;
 }
 
-// phase B: the wave's parked queries (nq <= 64 of them) answered and handed to eval(readV, asmV), one entry per lane.
+// phase B: the wave's parked queries (nq <= 64 of them) answered and handed to eval(readV, asmV, p), one entry per lane; p: the
+// entry's parked tile position (its koverCpy term belongs to the slot of p, whichever lane evaluates it).
 // kmer_at(p): the canonical k-mer at tile position p (quotient form: the side table is keyed by the k-mer itself).
-// push1(want, kmer): the worklist again (one query per lane here)
+// push1(want, kmer, aux, mode, p): the worklist again (one query per lane here)
 template <class KmerAt, class Eval, class Push1>
 __device__ __forceinline__ void mfx_lane_flush(const mfx_table_view &c, mfx_mailbox &M, uint32_t &nq, KmerAt kmer_at, Eval eval, Push1 push1, unsigned long long *dbg = nullptr) {
   const uint32_t tid = threadIdx.x, sub16 = (tid & 7u) << 4, lane = tid & 63u, wbase = tid & ~63u;
@@ -2043,7 +2044,7 @@ __device__ __forceinline__ void mfx_lane_flush(const mfx_table_view &c, mfx_mail
   bool listed = false;
   if (__any(scan || satd)) {                                     // wave-uniform
     if (dbg && (scan || satd)) atomicAdd(&dbg[scan ? 3 : 2], 1ull);
-    listed = push1(scan || satd, (scan || satd) ? (c.quot ? kmer_at(r.w >> 4) : fk) : 0ull, scan ? r.z : lo, scan ? 1u : 2u) && (scan || satd);      // (scan: r.z is still the HOME line)
+    listed = push1(scan || satd, (scan || satd) ? (c.quot ? kmer_at(r.w >> 4) : fk) : 0ull, scan ? r.z : lo, scan ? 1u : 2u, r.w >> 4) && (scan || satd);      // (scan: r.z is still the HOME line)
   }
   if (mine && !listed) {
     bool beyond = false;
@@ -2062,7 +2063,7 @@ __device__ __forceinline__ void mfx_lane_flush(const mfx_table_view &c, mfx_mail
     }
     uint32_t o_rv = 0u, o_av = 0u;
     if (have) { o_rv = (r_rv < c.minV || r_rv > c.maxV) ? 0u : r_rv; o_av = r_av; }      // -min / -max (merfin.C:199-200)
-    eval(o_rv, o_av);
+    eval(o_rv, o_av, r.w >> 4);
   }
   mfx_wave_handoff();                                            // the mailbox is free again
 }
@@ -2122,7 +2123,7 @@ __device__ __forceinline__ bool mfx_tile_kmer(const mfx_tile_lds &L, int k, uint
 // q), high half: ties to the rightmost (127 - q) -- and v_pk_min_u16 takes both minima at once; a k-mer whose canonical form
 // is the reverse strand reads the high half (the leftmost t-mer of the canonical k-mer is the rightmost of the forward one).
 // The up to 15 positions behind the wave's 64 are computed once for all B batch elements: lane 15 * j + i takes the t-mer at
-// position 64 + i of element j (mfx_wave_mod_halo).
+// position 64 + i of element j (mfx_wave_mod_halo; the elements of a lane lie `stride` positions apart).
 // f, r: the forward k-mer at the lane's position and its reverse complement (whatever their validity: a valid k-mer only
 // ever looks at t-mers inside itself).  p0: the tile position of the lane's first batch element.  Every lane of the wave
 // takes part (the calls are wave-uniform).
@@ -2137,9 +2138,10 @@ __device__ __forceinline__ uint32_t mfx_pk_min_u16(uint32_t a, uint32_t b) {
 __device__ __forceinline__ uint32_t mfx_mod_pack(uint32_t order, uint32_t q) { return ((order << 7) | q) | (((order << 7) | (127u - q)) << 16); }
 
 // the order values of the H = npos - 1 positions behind the wave (H <= 27), for all B batch elements: lane H * jj + i takes the
-// t-mer at position 64 + i of element jj; 64 / H elements fit one pass (all four for k = 21: H = 15), the rest a second one
+// t-mer at position 64 + i of element jj; 64 / H elements fit one pass (all four for k = 21: H = 15), the rest a second one.
+// stride: the distance of a lane's consecutive elements in the tile (the -hist kernel: 64, a wave's elements are adjacent stretches)
 template <int B>
-__device__ __forceinline__ void mfx_wave_mod_halo(const mfx_table_view &c, const mfx_tile_lds &L, uint32_t p0, uint32_t (&halo)[2]) {
+__device__ __forceinline__ void mfx_wave_mod_halo(const mfx_table_view &c, const mfx_tile_lds &L, uint32_t p0, uint32_t stride, uint32_t (&halo)[2]) {
   const int t = c.mz_t;
   const uint32_t H = (uint32_t)(c.k - t), per = 64u / H;
   const uint32_t lane = threadIdx.x & 63u;
@@ -2149,7 +2151,7 @@ __device__ __forceinline__ void mfx_wave_mod_halo(const mfx_table_view &c, const
     halo[ps] = 0xffffffffu;
     const uint32_t el = ps * per + jj;
     if (ps * per < (uint32_t)B && jj < per && el < (uint32_t)B) {     // (wave-uniform first test: no second pass when one holds all B)
-      const uint32_t q = p0 - lane + el * MFX_BLOCK + 64u + ii, wd = q >> 5, o = q & 31u, sh = 2u * o;
+      const uint32_t q = p0 - lane + el * stride + 64u + ii, wd = q >> 5, o = q & 31u, sh = 2u * o;
       const uint64_t w0 = L.codes[wd], w1 = L.codes[wd + 1];
       const uint32_t a = (uint32_t)(((w0 << sh) | ((w1 >> 1) >> (63u - sh))) >> (64 - 2 * t));
       const uint32_t b = (uint32_t)mfx_revcomp((uint64_t)a, t);
@@ -2171,7 +2173,8 @@ __device__ __forceinline__ uint32_t mfx_wave_mod_line(const mfx_table_view &c, u
   const uint64_t mmask = (~0ULL) >> (64 - 2 * m);
   const uint32_t a = (uint32_t)(f >> (2 * (k - t))) & tmask, b = (uint32_t)r & tmask;     // the t-mer at this position, and its reverse complement
   const uint32_t hsrc = (uint32_t)j < per ? halo[0] : halo[1];
-  const uint32_t hv = (uint32_t)__shfl((int)hsrc, (int)(H * ((uint32_t)j < per ? (uint32_t)j : (uint32_t)j - per) + lane), 64);
+  // (lane H jj + i's halo value to lane i: the permute takes its source lane modulo 64 by itself, and what lanes >= H receive is not used)
+  const uint32_t hv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((H * ((uint32_t)j < per ? (uint32_t)j : (uint32_t)j - per) + lane) << 2), (int)hsrc);
   mfx_wave_handoff();                                          // the previous element's reads are done
   mw[lane] = mfx_mod_pack(mfx_tmer_order(a < b ? a : b), lane);
   if (lane <= H) mw[64u + lane] = lane < H ? hv : 0xffffffffu;
@@ -2278,18 +2281,21 @@ constexpr int MFX_BATCH = MFX_V_BATCH;          // queries per lane and cooperat
 #ifndef MFX_V_DEFER_K31
 #define MFX_V_DEFER_K31 1
 #endif
-// kfxlds: the lane's koverCpy sum of the tile lives in LDS -- the upper half of the wave's mailbox, whose passes then have 32 entries
-// (MFX_KFX_BASE) -- instead of a register pair: at 72 VGPRs the allocator kept that pair, live across the whole tile and touched by
-// one k-mer in fifty, in SCRATCH, and every evaluation that met an `asmK > readK` k-mer paid a scratch load and store behind a
-// full vmcnt wait (107 G k-mers/s against 150 G; profiles/r06_pmc_compare.txt: 16 M scratch stores per 10^9 k-mers).  A ds_add_u64
-// without return costs one issue slot and nothing waits for it.
+// The koverCpy sums of a tile live in LDS, one 64-bit word per SLOT of the tile (mfx_hist_lds::kfx_slot; the slot of position p is
+// (p >> 6) & 3, mfx_hist_pos): every `asmK > readK` term is one ds_add_u64 without return to its slot's word -- one issue slot, and
+// nothing waits for it.  A register pair per lane, live across the whole tile and touched by one k-mer in fifty, was kept in SCRATCH
+// at 72 VGPRs, and every evaluation that met such a k-mer paid a scratch load and store behind a full vmcnt wait (107 G k-mers/s
+// against 150 G; profiles/r06_pmc_compare.txt: 16 M scratch stores per 10^9 k-mers); and a lane feeds BT different slots, so that a sum per
+// lane would not be a slot's.  A slot has 1024 positions of a tile: 2^10 terms of at most 2^52 units: at most 2^62.
+// kfxlds: the lane's count of the dominant bin lives in LDS as well -- a word per lane in the upper half of the wave's mailbox, whose
+// passes then have 32 entries (MFX_KFX_BASE) --, bumped where the bin is met instead of a register touched in the batch loop.
 #ifndef MFX_V_KFXLDS_K21
 #define MFX_V_KFXLDS_K21 1
 #endif
-// THE RULE the shared word rests on: a lane evaluates at most 16 k-mers of a tile (MFX_TILE / MFX_BLOCK positions, its own).  Sixteen
-// terms of at most 2^52 units stay below 2^56, sixteen bumps of the dominant-bin count fit the 8 bits above.  The deferred probe
-// (mfx_lane_flush) hands parked queries to OTHER lanes of the wave, which breaks the rule: an instance takes kfxlds or defer, never
-// both (static_assert in mfx_hist_kernel; tests/test_gpu_kstar_grid.py: test_saturation_tiles_of_the_packed_word fills both fields).
+// THE RULE the lane's word rests on: a lane evaluates at most 16 k-mers of a tile (MFX_TILE / MFX_BLOCK positions, its own): sixteen
+// bumps of the dominant-bin count fit the 8 bits the word keeps for them (its top byte).  The deferred probe (mfx_lane_flush) hands
+// parked queries to OTHER lanes of the wave, which breaks the rule: an instance takes kfxlds or defer, never both (static_assert in
+// mfx_hist_kernel; tests/test_gpu_kstar_grid.py: test_saturation_tiles_of_the_packed_word fills the count and the slot sums).
 constexpr uint32_t MFX_KFX_BASE = 32u;
 // bucket2: the per-lane second mini-bucket step of the probe (mfx_lane_front).  It ends 47 % of the displaced queries of the 3 Gb i.i.d. world
 // (32.4 M of 69.7 M) with one more 16-byte load of a line the lane already has -- not the nine in ten it would take to keep most batches of
@@ -2311,6 +2317,19 @@ template <> struct mfx_hist_tune<true, true, 21> { static constexpr int blocks =
 #endif
 template <> struct mfx_hist_tune<true, true, 31> { static constexpr int blocks = MFX_V_MINBLOCKS_K31, batch = MFX_V_BATCH_K31, defer = MFX_V_DEFER_K31, kfxlds = MFX_V_KFXLDS_K31, bucket2 = MFX_V_BUCKET2_K31; };
 template <> struct mfx_hist_tune<true, true, 0> { static constexpr int blocks = MFX_V_MINBLOCKS_GEN, batch = MFX_V_BATCH_GEN, defer = 0, kfxlds = 0, bucket2 = 0; };
+// Who takes which position of a tile.  A batch of BT elements covers the 4 BT cells of 64 positions from b * MFX_BLOCK on, in position
+// order, and wave v takes the BT ADJACENT cells v BT .. v BT + BT - 1: 128 contiguous positions (BT = 2) or 256 (BT = 4), so that the
+// 16-byte loads a lane issues back to back (mfx_lane_front) go to neighbouring stretches -- the table line that lies across the seam
+// between two of a wave's cells is asked for twice within a few cycles, not by two waves that run whenever they run.  The SLOT of a
+// position -- the (tile, slot) word its koverCpy term is summed in, and the worklist's -- stays (p >> 6) & 3, whichever wave holds it.
+// wv: the wave's number in the block, as a SCALAR (mfx_hist_kernel reads it off lane 0): a slot's word is then a scalar address -- held
+// per lane, the allocator kept it in scratch and reloaded it, behind a full vmcnt wait, wherever a term was added.
+template <int BT>
+__device__ __forceinline__ uint32_t mfx_hist_cell(uint32_t wv, uint32_t j) { return wv * (uint32_t)BT + j; }
+template <int BT>
+__device__ __forceinline__ uint32_t mfx_hist_pos(uint32_t b, uint32_t wv, uint32_t tid, uint32_t j) { return b * MFX_BLOCK + (mfx_hist_cell<BT>(wv, j) << 6) + (tid & 63u); }
+template <int BT>
+__device__ __forceinline__ uint32_t mfx_hist_slot(uint32_t wv, uint32_t j) { return mfx_hist_cell<BT>(wv, j) & (MFX_BLOCK / 64 - 1u); }
 template <bool CANON, bool COMPACT, int KF, int WF, int TF, bool DBG = false>
 __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::blocks)) void mfx_hist_kernel(mfx_hist_args a) {
   constexpr int BT = mfx_hist_tune<CANON, COMPACT, KF>::batch;                  // queries per lane and probe sequence of this instance
@@ -2319,6 +2338,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
   __shared__ mfx_hist_lds H;
 
   const uint32_t tid = threadIdx.x;
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));      // (mfx_hist_cell)
   if (KF) { a.t.k = KF; a.t.mz_w = WF; a.t.mz_t = TF; a.t.quot = KF > MFX_MAX_K_DIRECT ? 1 : 0; }   // (the launcher checked that they are the table's)
   const int k = KF ? KF : a.t.k;
   const mfx_kstar_args &ka = a.ks;
@@ -2329,13 +2349,14 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
   // widened when they leave the lane.  The block's running totals live in LDS (only thread 0 touches them).
   uint32_t n_valid = 0, n_missing = 0, n_over0 = 0;
   if (tid == 0) { H.tot[0] = H.tot[1] = 0; H.wl_n = 0u; }
+  if (tid < MFX_BLOCK / 64) H.kfx_slot[tid] = 0ull;      // (the first tile's barrier stands between this and the first add)
   uint64_t *c_glob = ka.counts + 2ull * ka.nbins;        // kasm, kmissing, novf
   uint64_t *c_kasm = c_glob + 3, *c_kmis = c_kasm + ka.ncontigs;
 
   // Persistent block, tiles handed out dynamically: block b starts on tile_begin + b and
   // draws every further tile from one global counter (the draw for the NEXT tile is issued
   // before the current one is processed, so its latency is never waited on).  The k-mer
-  // counters are integers and koverCpy is kept per (tile, wave), so the result does not
+  // counters are integers and koverCpy is kept per (tile, slot), so the result does not
   // depend on which block evaluated which tile.
   const uint32_t none = 0xffffffffu;
   uint32_t c = none;
@@ -2374,28 +2395,30 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
     }
     __syncthreads();
 
-    // This lane's koverCpy terms of this tile, in units of 2^-52 (a term is (1 - readK/asmK) * prob in [0, 1]: at most 16 of them per lane
-    // and tile).  An INTEGER sum: the value of a (tile, wave) does not depend on the order its terms were added in, nor on which lane
-    // evaluated which k-mer (the deferred tail of the probe hands parked queries to other lanes of the wave, mfx_lane_flush).
-    uint64_t kfx = 0;
+    // The koverCpy terms of this tile, in units of 2^-52 (a term is (1 - readK/asmK) * prob in [0, 1]), are added to the word of their
+    // position's slot (H.kfx_slot: zero here -- made so before the first tile and behind every tile's closing barrier).  An INTEGER sum:
+    // the value of a (tile, slot) does not depend on the order its terms were added in, nor on which lane or wave evaluated which k-mer
+    // (the deferred tail of the probe hands parked queries to other lanes of the wave, mfx_lane_flush).
     constexpr bool kfx_lds = mfx_hist_tune<CANON, COMPACT, KF>::kfxlds != 0 && COMPACT && CANON && KF != 0 && TF != 0;
     constexpr uint32_t mb_cap = kfx_lds ? MFX_KFX_BASE : 64u;      // mailbox entries the probe has
     static_assert(!(mfx_hist_tune<CANON, COMPACT, KF>::kfxlds != 0 && mfx_hist_tune<CANON, COMPACT, KF>::defer != 0),
-                  "kfxlds packs 16 terms and a count of at most 16 into one LDS word per lane: the deferred probe lets a lane evaluate more than its own 16 k-mers of a tile");
-    static_assert(MFX_TILE / MFX_BLOCK <= 16, "the packed koverCpy word (56-bit sum, 8-bit count) holds 16 evaluations per lane and tile");
+                  "kfxlds keeps a count of at most 16 in 8 bits of one LDS word per lane: the deferred probe lets a lane evaluate more than its own 16 k-mers of a tile");
+    static_assert(MFX_TILE / MFX_BLOCK <= 16, "the lane's word (an 8-bit count of the dominant bin) holds 16 evaluations per lane and tile");
+    static_assert(MFX_TILE / (MFX_BLOCK / 64) <= 1024, "a slot's word holds the terms (at most 2^52 units each) of 1024 positions of a tile");
     unsigned long long *const kfxw = reinterpret_cast<unsigned long long *>(&MB.rec[(tid & ~63u) + MFX_KFX_BASE]) + (tid & 63u);   // (kfx_lds) this lane's word
     if (kfx_lds) *kfxw = 0ull;                                   // (the mailbox was handed back at the end of the tile before)
-    // ... and so does the count of the dominant bin (`over` 0: nine k-mers in ten), in the same word above the 56 bits of the sum (a lane
-    // evaluates at most 16 k-mers of a tile: 16 terms below 2^52 each, a count of at most 16)
+    // (kfx_lds) the lane's count of the dominant bin (`over` 0: nine k-mers in ten) in the top byte of its word (a lane evaluates at most
+    // 16 k-mers of a tile)
     // (a 32-bit add to the word's high half: the 64-bit constant 1 << 56 was hoisted out of the loop as a register pair -- and spilled)
     struct lds_bump { unsigned long long *w; __device__ __forceinline__ void operator++(int) { (void)__hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(w) + 1, 1u << 24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } };
     struct lds_sum { unsigned long long *w; __device__ __forceinline__ void operator+=(uint64_t v) { (void)__hip_atomic_fetch_add(w, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } };
-    auto eval1 = [&](uint32_t rvv, uint32_t avv) {
+    // slot: the slot of the k-mer's position
+    auto eval1 = [&](uint32_t rvv, uint32_t avv, uint32_t slot) {
+      lds_sum sum{&H.kfx_slot[slot]};                            // (added where the term is made: the `asmK > readK` branch)
       if (kfx_lds) {
         lds_bump bump{kfxw};
-        lds_sum sum{kfxw};                                       // (added where the term is made: the `asmK > readK` branch)
         if (mfx_hist_eval_fx(H, ka, lut_ok, rvv, avv, bump, sum)) n_missing++;
-      } else if (mfx_hist_eval_fx(H, ka, lut_ok, rvv, avv, n_over0, kfx)) n_missing++;
+      } else if (mfx_hist_eval_fx(H, ka, lut_ok, rvv, avv, n_over0, sum)) n_missing++;
     };
     // mod-minimizer placement: the wave finds its home lines together (mfx_wave_mod_line)
     const bool wave_lines = COMPACT && CANON && (KF ? TF != 0 : a.t.mz_t != 0);
@@ -2405,12 +2428,12 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
     const bool quotf = KF ? KF > MFX_MAX_K_DIRECT : a.t.quot != 0;
     constexpr bool bucket2 = MFX_V_BUCKET2 != 0 && mfx_hist_tune<CANON, COMPACT, KF>::bucket2 != 0;      // the probe's second mini-bucket step (mfx_lane_front)
     // The worklist of mfx_hist_rest_kernel: a query whose probe did not end in its two cooperative passes is LISTED -- {canonical
-    // k-mer, aux, the (tile, wave) slot its koverCpy term belongs to, mode, "an even-k palindrome: both counts twice"} -- instead of
+    // k-mer, aux, the (tile, slot) word its koverCpy term belongs to (slot: that of its POSITION, not the wave that holds it), mode, "an even-k palindrome: both counts twice"} -- instead of
     // being scanned for by its lane while 63 others wait.  mode 0: aux = its home line; 1 (deep): ... and that line and the next are
     // known to be full of other k-mers; 2 (saturated): aux = the low word of its slot, only the side table is left to read.  The whole wave calls; the lanes that want are given consecutive entries
     // of this BLOCK's segment of the list (one LDS atomic per call); false: no list (a.wl == nullptr) or no room left in the segment,
     // the lane then scans.  kasm is counted here either way.
-    auto push_wave = [&](bool want, uint64_t kmer, uint32_t aux, uint32_t mode, bool dbl) -> bool {
+    auto push_wave = [&](bool want, uint64_t kmer, uint32_t aux, uint32_t mode, bool dbl, uint32_t slot) -> bool {
       if (!a.wl) return false;                                     // (kernel-uniform)
       const uint64_t m = __ballot(want);
       if (!m) return false;
@@ -2421,7 +2444,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
       const uint32_t at = base + (uint32_t)__popcll(m & ((1ULL << ln) - 1ULL));
       const bool fits = want && at < a.wl_segcap;
       if (fits) reinterpret_cast<uint4 *>(a.wl + MFX_WL_HEADER)[(uint64_t)blockIdx.x * a.wl_segcap + at] =
-                  make_uint4((uint32_t)kmer, (uint32_t)(kmer >> 32), aux, ((uint32_t)li * (MFX_BLOCK / 64) + (tid >> 6)) | (dbl ? 0x80000000u : 0u) | (mode << 29));
+                  make_uint4((uint32_t)kmer, (uint32_t)(kmer >> 32), aux, ((uint32_t)li * (MFX_BLOCK / 64) + slot) | (dbl ? 0x80000000u : 0u) | (mode << 29));
       return fits;
     };
     uint32_t nq = 0;                         // queries parked in this wave's mailbox (wave-uniform)
@@ -2436,7 +2459,8 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
           const uint64_t r = mfx_revcomp(f, k);
           return f < r ? f : r;
         };
-        mfx_lane_flush(a.t, MB, nq, kmer_at, eval1, [&](bool want, uint64_t km, uint32_t aux, uint32_t mode) { return push_wave(want, km, aux, mode, false); }, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr);
+        auto eval_at = [&](uint32_t rvv, uint32_t avv, uint32_t p) { eval1(rvv, avv, (p >> 6) & (MFX_BLOCK / 64 - 1u)); };      // (a parked query: the slot from its parked position)
+        mfx_lane_flush(a.t, MB, nq, kmer_at, eval_at, [&](bool want, uint64_t km, uint32_t aux, uint32_t mode, uint32_t p) { return push_wave(want, km, aux, mode, false, (p >> 6) & (MFX_BLOCK / 64 - 1u)); }, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr);
       }
       if (last) break;
       uint32_t rv[BT], av[BT];
@@ -2447,10 +2471,10 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
         uint64_t fkey[BT];
         uint32_t line[BT], b0[BT];
         uint32_t halo[2], pal = 0u;
-        mfx_wave_mod_halo<BT>(a.t, L, b * MFX_BLOCK + tid, halo);
+        mfx_wave_mod_halo<BT>(a.t, L, mfx_hist_pos<BT>(b, wv, tid, 0u), 64u, halo);
 #pragma unroll
         for (int j = 0; j < BT; ++j) {
-          const uint32_t p = (b + j) * MFX_BLOCK + tid;     // lane-consecutive positions
+          const uint32_t p = mfx_hist_pos<BT>(b, wv, tid, (uint32_t)j);     // lane-consecutive positions, the wave's elements side by side
           uint64_t f;
           ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
           const uint64_t r = mfx_revcomp(f, k);
@@ -2467,7 +2491,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
             for (int j = 0; j < BT; ++j) if (j == sj) kk = fkey[j];
           } else {
             uint64_t f;
-            (void)mfx_tile_kmer(L, k, (b + (uint32_t)sj) * MFX_BLOCK + tid, f);
+            (void)mfx_tile_kmer(L, k, mfx_hist_pos<BT>(b, wv, tid, (uint32_t)sj), f);
             const uint64_t r = mfx_revcomp(f, k);
             kk = f < r ? f : r;
           }
@@ -2476,12 +2500,12 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
         if (defer_tail) {
           uint32_t posn[BT];
 #pragma unroll
-          for (int j = 0; j < BT; ++j) posn[j] = (b + (uint32_t)j) * MFX_BLOCK + tid;
-          auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { (void)jj; return push_wave(want, km, aux, mode, false); };     // (odd k: no palindromes)
+          for (int j = 0; j < BT; ++j) posn[j] = mfx_hist_pos<BT>(b, wv, tid, (uint32_t)j);
+          auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { return push_wave(want, km, aux, mode, false, mfx_hist_slot<BT>(wv, (uint32_t)jj)); };     // (odd k: no palindromes)
           parked = mfx_lane_probe_defer<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap, bucket2>(
                        a.t, MB, nq, fkey, ok, rv, av, line, b0, posn, keyof, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr, mfx_push_fn<decltype(pj)>{pj});
         } else {
-          auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { return push_wave(want, km, aux, mode, ((pal >> jj) & 1u) != 0u); };
+          auto pj = [&](int jj, bool want, uint64_t km, uint32_t aux, uint32_t mode) { return push_wave(want, km, aux, mode, ((pal >> jj) & 1u) != 0u, mfx_hist_slot<BT>(wv, (uint32_t)jj)); };
           parked = mfx_lane_lookup8<BT, decltype(keyof), mfx_push_fn<decltype(pj)>, mb_cap, bucket2>(
                        a.t, MB, fkey, ok, rv, av, line, b0, keyof, DBG ? reinterpret_cast<unsigned long long *>(a.dbg) : nullptr, mfx_push_fn<decltype(pj)>{pj});
         }
@@ -2496,7 +2520,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
         uint64_t key[BT], key2[BT];
 #pragma unroll
         for (int j = 0; j < BT; ++j) {
-          const uint32_t p = (b + j) * MFX_BLOCK + tid;     // lane-consecutive positions
+          const uint32_t p = mfx_hist_pos<BT>(b, wv, tid, (uint32_t)j);     // lane-consecutive positions, the wave's elements side by side
           uint64_t f;
           ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
           const uint64_t r = mfx_revcomp(f, k);
@@ -2525,18 +2549,19 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
       for (int j = 0; j < BT; ++j) {
         if (!ok[j]) continue;
         n_valid++;                                                   // merfin-histogram.C:58
-        if (!((parked >> j) & 1u)) eval1(rv[j], av[j]);             // (a parked query is evaluated when the mailbox is flushed)
+        if (!((parked >> j) & 1u)) eval1(rv[j], av[j], mfx_hist_slot<BT>(wv, (uint32_t)j));   // (a parked query is evaluated when the mailbox is flushed)
       }
     }
-    // koverCpy of this (tile, wave): the integer sum over the 64 lanes (< 2^62)
-    if (kfx_lds) { mfx_wave_handoff(); const unsigned long long w = *kfxw; kfx = w & ((1ull << 56) - 1ull); n_over0 += (uint32_t)(w >> 56); }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kfx += __shfl_down(kfx, off, 64);
-    // (stored as the INTEGER: mfx_hist_rest_kernel adds the terms of the k-mers it ends to the same word; the summing kernels
-    // convert, mfx_sum_chunks_kernel<true>)
-    if ((tid & 63u) == 0) reinterpret_cast<uint64_t *>(a.tile_partials)[li * (MFX_BLOCK / 64) + (tid >> 6)] = kfx;
+    if (kfx_lds) { mfx_wave_handoff(); n_over0 += (uint32_t)(*kfxw >> 56); }
 
     __syncthreads();                         // tile consumed; H.next[it & 1] written
+    // koverCpy of this tile's four slots: the integer sums (<= 2^62), read and zeroed again between this barrier and the next tile's first
+    // one -- nobody adds there.  (Stored as the INTEGER: mfx_hist_rest_kernel adds the terms of the k-mers it ends to the same word; the
+    // summing kernels convert, mfx_sum_chunks_kernel<true>)
+    if (tid < MFX_BLOCK / 64) {
+      reinterpret_cast<uint64_t *>(a.tile_partials)[li * (MFX_BLOCK / 64) + tid] = H.kfx_slot[tid];
+      H.kfx_slot[tid] = 0ull;
+    }
     const uint64_t nx = H.next[it & 1];
     li = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(nx >> 32)) << 32) |
          (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)nx);
@@ -2564,7 +2589,7 @@ __global__ __launch_bounds__(MFX_BLOCK, (mfx_hist_tune<CANON, COMPACT, KF>::bloc
 // scanning further candidate lines or the side table holds the other 63 -- here EVERY lane has an entry of its own, so the plain
 // per-lane lookup (mfx_c_lookup: whole lines, all candidate lines, the side table, the read filter) runs with the wave full.
 // Each entry is evaluated like a position of the sequence (merfin-histogram.C:63-90): bins and counters into the same image, the
-// koverCpy term -- an integer, units of 2^-52 -- added to the word of its own (tile, wave), so that the launch's result is the one
+// koverCpy term -- an integer, units of 2^-52 -- added to the word of its own (tile, slot), so that the launch's result is the one
 // the main kernel alone would have produced, bit for bit, whatever was listed.  kasm was counted where the position was seen.
 // Launched behind every launch of the main kernel on the same stream.  The list is cut into one segment per block of the main kernel
 // (a block appends to its own segment through a counter in LDS: one shared counter would be a single-address atomic per listed wave,

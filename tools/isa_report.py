@@ -20,7 +20,7 @@ def main():
     cmd += [a for a in sys.argv[1:] if a.startswith("-D")]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")
-    print("# %s" % " ".join(cmd[:-2]))
+    print("# %s" % " ".join(os.path.relpath(a, ROOT) if a == SRC else a for a in cmd[:-2]))      # (the source as the repository names it)
     i = 0
     while i < len(lines):
         m = re.match(r"^(_Z15mfx_hist_kernelI\S+):", lines[i])
@@ -28,10 +28,12 @@ def main():
             i += 1
             continue
         name = m.group(1)
+        # up to the function's end label, not its first s_endpgm: an instance may place the block that ends the program (a block with no
+        # tile to evaluate) in front of its loops
         j = i
-        while "s_endpgm" not in lines[j]:
+        while not lines[j].startswith(".Lfunc_end"):
             j += 1
-        body = lines[i:j + 1]
+        body = lines[i:j]
         i = j + 1
         demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
         # Blocks and the loops they belong to, from the compiler's own annotations ("in Loop: Header=BBf_n Depth=d", "Parent Loop BBf_n
