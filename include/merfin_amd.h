@@ -323,6 +323,14 @@ int  mfx_index_write_db_streamed(const mfx_index *ix, int side, const char *path
 typedef struct { int op; uint64_t minV, maxV; int device; } mfx_db_merge_opts;
 typedef struct { uint64_t n_in, n_out, n_filtered, n_saturated, windows; } mfx_db_merge_stats;
 int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st /* may be NULL */);
+/* Set difference (`meryl difference` and what follows it): mfx_db_merge over in_paths, without the k-mers that a file of not_paths holds,
+ * whatever its count there.  A k-mer is written iff the operation over in_paths yields it, no file of not_paths holds it, and
+ * minV <= combined count <= maxV; the count written is the operation's over in_paths alone.  n_not == 0 is mfx_db_merge byte for byte.
+ * The same input forms, refusals and "nothing at out_path on failure"; also refused: n_in + n_not > 64, a subtracted file that is the
+ * output, a subtracted file of another k.  st as for mfx_db_merge (n_in: the k-mers of in_paths; n_filtered keeps its meaning);
+ * *n_subtracted (may be NULL): the k-mers the operation yields and a subtracted file holds. */
+int mfx_db_merge_except(const char *const *in_paths, uint32_t n_in, const char *const *not_paths, uint32_t n_not, const char *out_path,
+                        const mfx_db_merge_opts *o, mfx_db_merge_stats *st /* may be NULL */, uint64_t *n_subtracted /* may be NULL */);
 /* the window plan of mfx_db_merge alone (host only; tests): input i has n[i] k-mers in ceil(n[i] / 4096) blocks whose first k-mers are
  * first[i][..], ascending.  Row w of out (3 + 2 n_in words, at most cap rows are written): lo, hi, the pairs of its blocks, then per input
  * the blocks [b0, b1).  *n_windows: the windows of the plan. */
@@ -870,6 +878,58 @@ int  mfx_regions_write(const mfx_region *r, uint64_t n, const mfx_seq *seq, cons
  * stored, *n_out counts them all.  o->kstar is not looked at. */
 int  mfx_regions_from_planes_host(const uint64_t *planes, const uint64_t *contig_len, uint32_t ncontigs, const mfx_regions_opts *o,
                                   mfx_region *out, uint64_t cap, uint64_t *n_out);
+
+/* ------------------------------------------------------------------------ */
+/* -phase: hap-mer markers of two parents, their phase blocks and switch     */
+/* errors, made on the device.  No reference counterpart: merfin has no trio */
+/* mode.  The block rule is this project's own, in the spirit of Merqury's   */
+/* phase blocks (its defaults, 100 switches within 20000 bases, are kept),   */
+/* and is NOT validated against Merqury.                                     */
+/* ------------------------------------------------------------------------ */
+/* The index holds set A on its read side and set B on its assembly side (the sequence-only index: the k-mers of the sequence
+ * claimed, A and B loaded update-only; any other index whose two values are > 0 exactly for A and for B gives the same records).
+ * A k-mer start position is a MARKER of haplotype 0 when its k-mer is in A and not in B, of haplotype 1 when in B and not in A;
+ * a k-mer in both is shared and no marker.  The markers of a contig in ascending order form RUNS: maximal stretches of
+ * consecutive markers of one haplotype (positions without a marker are transparent).  A run of n markers whose first and last
+ * lie at `first` and `last` spans last - first + k bases; it is SHORT iff n <= switches and span <= range, else LONG (with
+ * switches = 0 every run is long).  A BLOCK opens at a contig's first run and at every long run whose nearest earlier long run
+ * of the contig has the other haplotype; every other run joins the open block.  A block's haplotype is that of its long runs;
+ * a block without a long run (then the contig's only block) takes the haplotype with more markers, a tie goes to 0.
+ * Records are ordered by contig, start; every field is an integer.  48 bytes. */
+typedef struct mfx_phase_block {
+  uint32_t contig, hap;
+  uint64_t start, end;       /* k-mer start positions: first marker, last marker + 1; the base span is [start, end - 1 + k) */
+  uint64_t n_hap, n_switch;  /* markers of the block's own and of the other haplotype                                       */
+  uint64_t n_switch_runs;    /* runs of the other haplotype in the block                                                     */
+} mfx_phase_block;
+typedef struct { uint64_t switches, range; } mfx_phase_opts;  /* -switches (100), -range (20000): any values are valid */
+typedef struct mfx_phase mfx_phase;                           /* the result, held by the library */
+/* The blocks of the whole sequence set into *out (release with mfx_phase_free).  Two passes (csrc/mfx_phase.h): the evaluation
+ * writes one bit per position and haplotype and the per-contig totals; runs and blocks are counted, scanned and scattered from
+ * those bits -- no atomic orders anything, a second run gives the same bytes.  The evaluator's K* parameters are not read.
+ * MFX_E_INVAL: a null argument, a sharded index, a sequence object that holds a part only, evaluator and sequence on different
+ * devices; MFX_E_NOMEM: the planes or the runs do not fit the device. */
+int  mfx_phase_run(mfx_eval *ev, const mfx_seq *seq, const mfx_phase_opts *o, mfx_phase **out);
+uint64_t mfx_phase_count(const mfx_phase *p);
+int  mfx_phase_copy(const mfx_phase *p, mfx_phase_block *dst, uint64_t cap);
+/* dst[ncontigs][4]: valid k-mers, A markers, B markers, shared k-mers of every contig; MFX_E_INVAL when cap (in contigs) is too small */
+int  mfx_phase_contig_counts(const mfx_phase *p, uint64_t *dst, uint64_t cap);
+void mfx_phase_free(mfx_phase *p);
+/* Diagnostic (tools/phase_rate.py; not part of the stable surface): ms[2] = what the run spent in pass 1 and in runs / blocks */
+void mfx_diag_phase_times(const mfx_phase *p, double *ms);
+/* Host only.  Three texts (.gz / .bz2 / .xz stems compress each; the suffix stays last):
+ *   <stem>.phased_block.bed    "#chrom start end hap n_hap n_switch n_switch_runs" (tab-separated), hap as A / B, the BASE span
+ *   <stem>.hapmers.count       "#chrom A B shared kmers": one line per contig of contig_counts[ncontigs][4]
+ *   <stem>.phased_block.stats  for A, B and all: blocks, sum / min / mean / max of the base spans, N50 (the largest L such that
+ *                              blocks of span >= L hold at least half the sum), markers, switch markers, switch rate "%.6f"
+ * names[c]: the contig names (up to the first blank). */
+int  mfx_phase_write(const mfx_phase_block *b, uint64_t n, const uint64_t *contig_counts, const mfx_seq *seq, const char *const *names, int k,
+                     const mfx_phase_opts *o, const char *stem);
+/* Host only (tests, tools/native/phase_sanitize.cpp): pass 2 over caller-made planes[2][ntiles * 64] of contigs of contig_len[]
+ * positions, laid out as for mfx_regions_from_planes_host; bits beyond a contig's end and a position in both planes: MFX_E_INVAL.
+ * At most cap records are stored, *n_out counts them all. */
+int  mfx_phase_from_planes_host(const uint64_t *planes, const uint64_t *contig_len, uint32_t ncontigs, int k, const mfx_phase_opts *o,
+                                mfx_phase_block *out, uint64_t cap, uint64_t *n_out);
 
 /* ------------------------------------------------------------------------ */
 /* -filter / -polish / -better / -strict / -loose: replaces processVariants */

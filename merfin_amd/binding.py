@@ -98,6 +98,8 @@ SYMBOLS = [
     "mfx_track_num_windows", "mfx_track_run", "mfx_track_write",
     "mfx_regions_run", "mfx_regions_count", "mfx_regions_tiles_revisited", "mfx_diag_regions_times", "mfx_regions_copy", "mfx_regions_free",
     "mfx_regions_write", "mfx_regions_from_planes_host",
+    "mfx_db_merge_except", "mfx_phase_run", "mfx_phase_count", "mfx_phase_copy", "mfx_phase_contig_counts", "mfx_phase_free", "mfx_diag_phase_times", "mfx_phase_write",
+    "mfx_phase_from_planes_host",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
@@ -130,6 +132,16 @@ REGION_CLASSES = ("missing", "collapsed", "expanded")
 
 class _RegionsOpts(C.Structure):
     _fields_ = [("kstar", C.c_double), ("gap", C.c_uint64), ("min_kmers", C.c_uint64)]
+
+
+# one block of Evaluator.phase: the layout of mfx_phase_block (include/merfin_amd.h), 48 bytes; hap: 0 = A (the read side), 1 = B
+PHASE_DTYPE = np.dtype([("contig", "<u4"), ("hap", "<u4"), ("start", "<u8"), ("end", "<u8"), ("n_hap", "<u8"), ("n_switch", "<u8"),
+                        ("n_switch_runs", "<u8")])
+assert PHASE_DTYPE.itemsize == 48
+
+
+class _PhaseOpts(C.Structure):
+    _fields_ = [("switches", C.c_uint64), ("range", C.c_uint64)]
 
 
 def _share_hip_runtime_with_torch():
@@ -204,6 +216,8 @@ def load_library():
     L.mfx_db_convert.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
     L.mfx_db_convert_placed.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
     L.mfx_db_merge.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(DbMergeOpts), C.POINTER(DbMergeStats)]
+    L.mfx_db_merge_except.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(DbMergeOpts), C.POINTER(DbMergeStats),
+                                      u64p]
     L.mfx_db_merge_plan.argtypes = [C.POINTER(u64p), u64p, C.c_uint32, C.c_int, C.c_uint64, u64p, C.c_uint64, u64p]
     L.mfx_db_join_completeness.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(DbJoinOpts), f64p, f64p, C.POINTER(DbJoinStats)]
     L.mfx_db_join_spectrum.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(DbJoinOpts), u64p, u64p, C.POINTER(DbJoinStats)]
@@ -367,6 +381,17 @@ def load_library():
     L.mfx_regions_free.argtypes = [vp]
     L.mfx_regions_write.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), C.c_int, C.c_char_p]
     L.mfx_regions_from_planes_host.argtypes = [vp, u64p, C.c_uint32, C.POINTER(_RegionsOpts), vp, C.c_uint64, u64p]
+    L.mfx_phase_run.argtypes = [vp, vp, C.POINTER(_PhaseOpts), C.POINTER(vp)]
+    L.mfx_phase_count.restype = C.c_uint64
+    L.mfx_phase_count.argtypes = [vp]
+    L.mfx_phase_copy.argtypes = [vp, vp, C.c_uint64]
+    L.mfx_phase_contig_counts.argtypes = [vp, vp, C.c_uint64]
+    L.mfx_phase_free.restype = None
+    L.mfx_phase_free.argtypes = [vp]
+    L.mfx_diag_phase_times.restype = None
+    L.mfx_diag_phase_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mfx_phase_write.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(_PhaseOpts), C.c_char_p]
+    L.mfx_phase_from_planes_host.argtypes = [vp, u64p, C.c_uint32, C.c_int, C.POINTER(_PhaseOpts), vp, C.c_uint64, u64p]
     L.mfx_spectrum_run.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p]
     L.mfx_diag_spectrum_time.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
     L.mfx_spectrum_peak.argtypes = [u64p, C.c_uint32, C.POINTER(_SpectrumPeak)]
@@ -496,6 +521,22 @@ def db_merge(paths, out_path, op="sum", min_count=0, max_count=2**32 - 1, device
     st = DbMergeStats()
     _check(load_library().mfx_db_merge(arr, len(paths), out_path.encode(), C.byref(o), C.byref(st)))
     return {name: int(getattr(st, name)) for name, _ in DbMergeStats._fields_}
+
+
+def db_merge_except(paths, not_paths, out_path, op="sum", min_count=0, max_count=2**32 - 1, device=0):
+    """db_merge over `paths` without the k-mers that a database of `not_paths` holds, whatever its count there (mfx_db_merge_except: set
+    difference); the count written is the operation's over `paths` alone, the filter acts on it.  No not_paths: db_merge, byte for byte.
+    Returns db_merge's stats and n_subtracted: the k-mers the operation yields and a database of not_paths holds."""
+    paths = [paths] if isinstance(paths, (str, bytes)) else list(paths)
+    not_paths = [not_paths] if isinstance(not_paths, (str, bytes)) else list(not_paths)
+    enc = lambda ps: (C.c_char_p * max(1, len(ps)))(*[p.encode() if isinstance(p, str) else p for p in ps])
+    o = DbMergeOpts(MERGE_OPS[op] if isinstance(op, str) else int(op), int(min_count), int(max_count), int(device))
+    st = DbMergeStats()
+    sub = C.c_uint64(0)
+    _check(load_library().mfx_db_merge_except(enc(paths), len(paths), enc(not_paths), len(not_paths), out_path.encode(), C.byref(o), C.byref(st), C.byref(sub)))
+    out = {name: int(getattr(st, name)) for name, _ in DbMergeStats._fields_}
+    out["n_subtracted"] = sub.value
+    return out
 
 
 class DbJoinOpts(C.Structure):
@@ -1299,6 +1340,40 @@ def regions_from_planes_host(planes, contig_lens, gap=0, min_kmers=1):
     return out[:n.value]
 
 
+def _phase_opts(switches, range_):
+    if not (0 <= int(switches) < 2**64 and 0 <= int(range_) < 2**64):
+        raise MfxError(-1, "phase: switches and range are integers in [0, 2^64)")
+    return _PhaseOpts(int(switches), int(range_))
+
+
+def phase_write(blocks, contig_counts, seqs, names, k, stem, switches=100, range_=20000):
+    """the records and per-contig counts of Evaluator.phase as text (mfx_phase_write; host only): <stem>.phased_block.bed,
+    <stem>.hapmers.count and <stem>.phased_block.stats; a stem ending in .gz / .bz2 / .xz compresses them (the suffix stays last)"""
+    b = np.ascontiguousarray(blocks, dtype=PHASE_DTYPE)
+    cc = np.ascontiguousarray(contig_counts, dtype=np.uint64)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    o = _phase_opts(switches, range_)
+    _check(load_library().mfx_phase_write(C.c_void_p(b.ctypes.data), len(b), C.c_void_p(cc.ctypes.data), seqs.h, nm, int(k), C.byref(o), stem.encode()))
+
+
+def phase_from_planes_host(planes, contig_lens, k, switches=100, range_=20000):
+    """pass 2 of Evaluator.phase on the host over caller-made haplotype planes (mfx_phase_from_planes_host): planes is a uint64 array
+    [2][ntiles * 64], ntiles = sum(ceil(len / 4096)); plane 0 flags the markers of A, plane 1 those of B"""
+    planes = np.ascontiguousarray(planes, dtype=np.uint64)
+    lens = np.ascontiguousarray(contig_lens, dtype=np.uint64)
+    ntiles = int(sum((int(x) + 4095) // 4096 for x in lens))
+    if planes.size != 2 * 64 * ntiles:
+        raise MfxError(-1, "phase_from_planes_host: %d words for %d tiles (2 x 64 each)" % (planes.size, ntiles))
+    o = _phase_opts(switches, range_)
+    L = load_library()
+    n = C.c_uint64(0)
+    lp = lens.ctypes.data_as(C.POINTER(C.c_uint64))
+    _check(L.mfx_phase_from_planes_host(C.c_void_p(planes.ctypes.data), lp, len(lens), int(k), C.byref(o), None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), dtype=PHASE_DTYPE)
+    _check(L.mfx_phase_from_planes_host(C.c_void_p(planes.ctypes.data), lp, len(lens), int(k), C.byref(o), C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+    return out[:n.value]
+
+
 E_NODATA = -10
 
 
@@ -1760,6 +1835,31 @@ class Evaluator:
         finally:
             L.mfx_regions_free(h)
         return r[:n], ka.value, km.value, revisited
+
+    def phase(self, seqs, switches=100, range_=20000, times=None):
+        """hap-mer phase blocks of every contig (mfx_phase_run): the index holds set A on its read side and set B on its assembly side;
+        a position whose k-mer is in exactly one set is a marker, runs of at most `switches` markers within `range_` bases are short
+        and do not break a block.  Returns (blocks, contig_counts): a structured array of dtype PHASE_DTYPE ordered by contig, start,
+        and a uint64 array [ncontigs, 4] of valid k-mers, A markers, B markers and shared k-mers.  The K* parameters are not read.
+        times: a list that receives the milliseconds of pass 1 and of runs / blocks"""
+        L = load_library()
+        o = _phase_opts(switches, range_)
+        h = C.c_void_p(None)
+        _check(L.mfx_phase_run(self.h, seqs.h, C.byref(o), C.byref(h)))
+        try:
+            n = L.mfx_phase_count(h)
+            r = np.zeros(max(n, 1), dtype=PHASE_DTYPE)
+            _check(L.mfx_phase_copy(h, C.c_void_p(r.ctypes.data), n))
+            nc = seqs.ncontigs
+            cc = np.zeros((max(nc, 1), 4), dtype=np.uint64)
+            _check(L.mfx_phase_contig_counts(h, C.c_void_p(cc.ctypes.data), nc))
+            if times is not None:
+                ms = (C.c_double * 2)()
+                L.mfx_diag_phase_times(h, ms)
+                times[:] = list(ms)
+        finally:
+            L.mfx_phase_free(h)
+        return r[:n], cc[:nc]
 
     def variants(self, mode, vcf_path, names, contigs, out_path, comb=15, nosplit=False, debug_path=None, log_path=None):
         """-filter/-polish/-better/-strict/-loose over all contigs; returns clusters evaluated"""

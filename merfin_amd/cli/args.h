@@ -39,11 +39,16 @@ struct Globals {
   bool passesGiven = false, passesAuto = false;   // -count -passes P|auto: the k-mers counted in passes over key ranges
   uint32_t passes = 1;
   std::vector<const char *> mergeNames;  // -merge: no report; these sorted databases combined on the GPU into -output (mfx_db_merge)
+  std::vector<const char *> notNames;    // -not of -merge: databases whose k-mers are not written (mfx_db_merge_except)
   const char *opName = nullptr;          // -op of -merge: sum (default), max, min, intersect
   int mergeOp = MFX_MERGE_SUM;
   double regKstar = 1.0;                 // -kstar: |K*| at which -regions calls a k-mer collapsed / expanded
   uint64_t regGap = 0, regMinrun = 1;    // -gap / -minrun of -regions
   bool kstarGiven = false, gapGiven = false, minrunGiven = false;
+  bool phase = false;                    // -phase: no K* report; hap-mer markers, phase blocks and switch errors of -sequence (mfx_phase_run)
+  std::vector<const char *> hapmers;     // -hapmers: the two sets of haplotype-specific k-mers (A, then B)
+  uint64_t phSwitches = 100, phRange = 20000;   // -switches / -range of -phase
+  bool switchesGiven = false, rangeGiven = false;
   bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
 };
 
@@ -118,6 +123,14 @@ static void usage_merge() {
           "\n");
 }
 
+// the entry of -not: printed behind the text above for a command line that names it
+static void usage_not() {
+  fprintf(stderr,
+          "    -not db           with -merge: the k-mers of this sorted flat database are not written, whatever their counts there (`meryl\n"
+          "                      difference`; hap-mers: -merge mat.mfxk -not pat.mfxk); repeatable; the -merge and -not databases are 64 at the most\n"
+          "\n");
+}
+
 // the entry of -join: printed behind the text above for a command line that names it
 static void usage_join() {
   fprintf(stderr,
@@ -142,12 +155,30 @@ static void usage_regions() {
           "\n");
 }
 
+// the entries of -phase: printed behind the text above for a command line that names one of its flags
+static void usage_phase() {
+  fprintf(stderr,
+          "  Trio phasing (an operation of its own: no -readmers, no -peak):\n"
+          "    -phase            hap-mer markers of two parents on every contig of -sequence, their phase blocks and switch errors, made on the\n"
+          "                      GPU -> <output>.phased_block.bed (chrom, base span, hap A / B, markers of the block's own and of the other\n"
+          "                      haplotype, runs of the other), <output>.hapmers.count (per contig: A markers, B markers, shared, k-mers) and\n"
+          "                      <output>.phased_block.stats.  An <output> ending in .gz / .bz2 / .xz compresses them.  One device.\n"
+          "                      The block rule is this program's own, in the spirit of Merqury's phase blocks; it is not validated against Merqury.\n"
+          "    -hapmers db       with -phase, exactly twice: the k-mers specific to haplotype A, then to B (any database form; one k).\n"
+          "                      -min / -max apply to the counts of both.\n"
+          "    -switches S       with -phase: a run of the other haplotype of at most S markers ... (default 100)\n"
+          "    -range R          ... that spans at most R bases is a switch error inside a block; a longer one ends the block (default 20000)\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
-static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false) {
+static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false, bool phase = false, bool nots = false) {
   usage(argv0);
   if (merge) usage_merge();
+  if (nots) usage_not();
   if (join) usage_join();
   if (regions) usage_regions();
+  if (phase) usage_phase();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -242,6 +273,7 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
     else if (is("-convert")) G.convertName = val();
     else if (is("-count")) G.count = true;
     else if (is("-merge")) G.mergeNames.push_back(val());
+    else if (is("-not")) G.notNames.push_back(val());
     else if (is("-join")) G.join = true;
     else if (is("-op")) {
       G.opName = val();
@@ -296,6 +328,16 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
         err.push_back(std::string("Invalid ") + (gp ? "-gap" : "-minrun") + " '" + v + "': " + (gp ? "a gap is a number of positions" : "-minrun is a number of k-mers") + ", an integer of at least 0.\n");
       else (gp ? G.regGap : G.regMinrun) = x;
     }
+    else if (is("-phase")) G.phase = true;
+    else if (is("-hapmers")) G.hapmers.push_back(val());
+    else if (is("-switches") || is("-range")) {
+      const bool sw = is("-switches");
+      const char *v = val();
+      (sw ? G.switchesGiven : G.rangeGiven) = true;
+      if (parse_uint(v, 0, ~0ull, &x) != UINT_OK)
+        err.push_back(std::string("Invalid ") + (sw ? "-switches" : "-range") + " '" + v + "': " + (sw ? "-switches is a number of markers" : "-range is a number of bases") + ", an integer of at least 0.\n");
+      else (sw ? G.phSwitches : G.phRange) = x;
+    }
     else if (is("-skipMissing")) G.skipMissing = true;
     else if (is("-completeness")) G.reportType = OP_COMPL;
     else if (is("-comb")) G.comb = (unsigned)strtoul(val(), nullptr, 10);
@@ -328,6 +370,7 @@ static bool devices_available(const std::vector<int> &devs) {
 static void check_merge_flags(const Globals &G, Errors &err) {
   if (G.mergeNames.empty()) {
     if (G.opName) err.push_back("-op names the operation of -merge: it has no meaning without -merge.\n");
+    if (!G.notNames.empty()) err.push_back("-not names a database to subtract in -merge: it has no meaning without -merge.\n");
     return;
   }
   if (G.reportType != OP_NONE) err.push_back("-merge is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
@@ -349,6 +392,12 @@ static void check_merge_flags(const Globals &G, Errors &err) {
   for (const char *f : G.mergeNames) {
     struct stat mst;
     if (stat(f, &mst) != 0 || access(f, R_OK) != 0) err.push_back(std::string("Cannot read the -merge database '") + f + "'.\n");
+  }
+  if (!G.notNames.empty() && G.mergeNames.size() <= 64 && G.mergeNames.size() + G.notNames.size() > 64)
+    err.push_back("-merge and -not take 64 databases at the most (here " + std::to_string(G.mergeNames.size()) + " and " + std::to_string(G.notNames.size()) + ").\n");
+  for (const char *f : G.notNames) {
+    struct stat mst;
+    if (stat(f, &mst) != 0 || access(f, R_OK) != 0) err.push_back(std::string("Cannot read the -not database '") + f + "'.\n");
   }
 }
 
@@ -424,6 +473,45 @@ static void check_regions_flags(const Globals &G, Errors &err) {
   if (G.devices.size() > 1) err.push_back("-regions runs on one device (-device d, or -devices naming one).\n");
   if (G.skipMissing) err.push_back("-skipMissing belongs to -dump; -regions writes the missing k-mers as intervals.\n");
   if (G.vcfName) err.push_back("-regions does not take -vcf (the variant modes do).\n");
+}
+
+// -phase: every check before any device is touched (the two databases are probed on the host for their k)
+static bool phase_named(const Globals &G) { return G.phase || !G.hapmers.empty() || G.switchesGiven || G.rangeGiven; }
+static void check_phase_flags(const Globals &G, Errors &err) {
+  if (!G.phase) {
+    if (!G.hapmers.empty()) err.push_back("-hapmers names a hap-mer database of -phase; it has no meaning without -phase.\n");
+    if (G.switchesGiven) err.push_back("-switches bounds the switch errors of -phase; it has no meaning without -phase.\n");
+    if (G.rangeGiven) err.push_back("-range bounds the switch errors of -phase; it has no meaning without -phase.\n");
+    return;
+  }
+  if (G.hapmers.size() != 2) err.push_back("-phase takes exactly two -hapmers databases, haplotype A then B (here " + std::to_string(G.hapmers.size()) + ").\n");
+  if (G.reportType != OP_NONE) err.push_back("-phase is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
+  if (G.count || G.convertName || !G.mergeNames.empty()) err.push_back("-phase, -count, -convert and -merge are separate operations: give one of them.\n");
+  if (G.readDBname) err.push_back("-phase takes its k-mers as -hapmers <file>: it does not take -readmers.\n");
+  if (G.seqDBname) err.push_back("-phase does not count the assembly's k-mers: it does not take -seqmers.\n");
+  if (!G.readsNames.empty()) err.push_back("-phase takes databases of hap-mers: it does not take -reads (count them first: -count).\n");
+  if (G.peakGiven) err.push_back("-phase evaluates no K*: it does not take -peak.\n");
+  if (G.pLookupTable) err.push_back("-phase evaluates no K*: it does not take -prob.\n");
+  if (G.vcfName) err.push_back("-phase does not take -vcf (the variant modes do).\n");
+  if (G.sharded) err.push_back("-phase does not take -sharded: a marker needs both sets' whole membership on one device.\n");
+  if (G.devices.size() > 1) err.push_back("-phase runs on one device (-device d, or -devices naming one).\n");
+  if (G.indexName) err.push_back("-phase does not take -index: its table holds the two hap-mer sets, not a run's counts.\n");
+  if (G.join) err.push_back("-join is a way to run -completeness and -spectrum: -phase does not take it.\n");
+  if (!G.seqName) err.push_back("No input sequences (-sequence) supplied.\n");
+  if (!G.outName) err.push_back("No output (-output) supplied.\n");
+  if (G.hapmers.size() == 2) {
+    if (strcmp(G.hapmers[0], G.hapmers[1]) == 0) {
+      err.push_back(std::string("-phase needs two different hap-mer sets: both -hapmers name '") + G.hapmers[0] + "'.\n");
+    } else {
+      mfx_db_info a, b;
+      const bool oka = mfx_db_probe(G.hapmers[0], &a) == MFX_OK;
+      if (!oka) err.push_back(std::string("Cannot open the -hapmers database '") + G.hapmers[0] + "': " + mfx_last_error() + "\n");
+      const bool okb = mfx_db_probe(G.hapmers[1], &b) == MFX_OK;
+      if (!okb) err.push_back(std::string("Cannot open the -hapmers database '") + G.hapmers[1] + "': " + mfx_last_error() + "\n");
+      if (oka && okb && a.k != b.k)
+        err.push_back("The two -hapmers databases hold different k-mers: " + std::to_string(a.k) + "-mers and " + std::to_string(b.k) + "-mers.\n");
+    }
+  }
 }
 
 // -spectrum: every check before any device is touched

@@ -1041,9 +1041,17 @@ static int run_merge(Globals &G) {
   o.maxV = G.maxV;
   o.device = G.device;
   mfx_db_merge_stats st;
-  if (mfx_db_merge(G.mergeNames.data(), (uint32_t)G.mergeNames.size(), G.outName, &o, &st)) DIE_MFX("-merge");
+  uint64_t subtracted = 0;
+  if (G.notNames.empty()) {
+    if (mfx_db_merge(G.mergeNames.data(), (uint32_t)G.mergeNames.size(), G.outName, &o, &st)) DIE_MFX("-merge");
+  } else {
+    fprintf(stderr, "-- Without the k-mers of %lu database%s (-not).\n", (unsigned long)G.notNames.size(), G.notNames.size() == 1 ? "" : "s");
+    if (mfx_db_merge_except(G.mergeNames.data(), (uint32_t)G.mergeNames.size(), G.notNames.data(), (uint32_t)G.notNames.size(), G.outName, &o, &st, &subtracted))
+      DIE_MFX("-merge -not");
+  }
   fprintf(stderr, "-- Merged: %lu k-mers read, %lu written, %lu filtered, %lu saturated, %lu window%s.\n", (unsigned long)st.n_in, (unsigned long)st.n_out,
           (unsigned long)st.n_filtered, (unsigned long)st.n_saturated, (unsigned long)st.windows, st.windows == 1 ? "" : "s");
+  if (!G.notNames.empty()) fprintf(stderr, "-- Subtracted: %lu k-mers that a -not database holds.\n", (unsigned long)subtracted);
   print_wrote(G.outName, st.n_out);
   fprintf(stderr, "Bye!\n");
   return 0;
@@ -1603,6 +1611,78 @@ static int run_join(const Globals &G) {
   return 0;
 }
 
+// merfin -phase: hap-mer markers, phase blocks and switch errors (mfx_phase_run).  The table is the sequence-only index -- the k-mers of
+// -sequence claimed, set A loaded update-only on the read side, set B on the assembly side; the assembly's own counts are not needed and
+// are not counted -- or, for k > 31 and for a database that is not canonical, the full tables of the two sets.
+static int run_phase(Globals &G) {
+  mfx_db_info adb, bdb;
+  if (mfx_db_probe(G.hapmers[0], &adb) || mfx_db_probe(G.hapmers[1], &bdb)) DIE_MFX("opening -hapmers");
+  const int k = adb.k;
+  fprintf(stderr, "-- Opening sequences in '%s'.\n", G.seqName);
+  Sequences S;
+  if (!S.start(G.seqName)) { fprintf(stderr, "ERROR: cannot open '%s'.\n", G.seqName); return 1; }
+  if (!S.finish()) {
+    fprintf(stderr, "ERROR: reading '%s' failed (read error, or the decompressor exited with an error: truncated or corrupt file?).\n", G.seqName);
+    return 1;
+  }
+  Owned<mfx_seq, mfx_seq_free> seq;
+  seq = mfx_seq_upload(G.device, S.bases.data(), S.lens.data(), S.size());
+  if (!seq) DIE_MFX("uploading sequences");
+  Owned<mfx_index, mfx_index_free> ix;
+  int lrc = MFX_E_NONCANON;
+  if (k <= 31) {
+    const uint64_t capacity = S.totalBases + 1024;
+    memory_banner(G, mfx_index_estimate_gb_for_seq(k, capacity));
+    ix = mfx_index_create_for_seq_lf(k, capacity, G.maxMemory, G.device, 0.4);
+    if (!ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+    fprintf(stderr, "-- Claiming the %d-mers of '%s' on the GPU.\n", k, G.seqName);
+    if (mfx_index_claim_seq(ix, seq, nullptr)) DIE_MFX("claiming sequence k-mers");
+    for (int side = 0; side < 2; ++side) {
+      fprintf(stderr, "-- Loading hap-mers %c from '%s' into lookup table.\n", "AB"[side], G.hapmers[side]);
+      lrc = mfx_index_load_db(ix, G.hapmers[side], side, G.minV, G.maxV);
+      if (lrc && lrc != MFX_E_NONCANON) DIE_MFX("loading -hapmers");
+      if (lrc) break;
+    }
+    if (lrc) fprintf(stderr, "-- A k-mer database is not canonical; building the full lookup tables instead.\n");
+  }
+  if (lrc) {
+    const uint64_t capacity = adb.n_kmers + bdb.n_kmers + 1024;
+    memory_banner(G, mfx_index_estimate_gb(k, capacity));
+    ix = mfx_index_create_lf(k, capacity, G.maxMemory, G.device, 0.7);
+    if (!ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+    for (int side = 0; side < 2; ++side) {
+      fprintf(stderr, "-- Loading hap-mers %c from '%s' into lookup table.\n", "AB"[side], G.hapmers[side]);
+      if (mfx_index_load_db(ix, G.hapmers[side], side, G.minV, G.maxV)) DIE_MFX("loading -hapmers");
+    }
+  }
+  const mfx_kparams kp{1.0, 0, nullptr, nullptr};                 // (no K* is evaluated: mfx_phase_run does not read them)
+  Owned<mfx_eval, mfx_eval_free> ev;
+  ev = mfx_eval_create(ix, &kp, 0);
+  if (!ev) DIE_MFX("creating evaluator");
+  const mfx_phase_opts o{G.phSwitches, G.phRange};
+  fprintf(stderr, "-- Phase blocks of the hap-mers (at most %lu switch markers within %lu bases stay inside a block) to '%s'.\n", (unsigned long)o.switches,
+          (unsigned long)o.range, G.outName);
+  Owned<mfx_phase, mfx_phase_free> res;
+  {
+    mfx_phase *r = nullptr;
+    if (mfx_phase_run(ev, seq, &o, &r)) DIE_MFX("-phase");
+    res = r;
+  }
+  std::vector<mfx_phase_block> recs((size_t)mfx_phase_count(res));
+  std::vector<uint64_t> counts((size_t)S.size() * 4);
+  if (mfx_phase_copy(res, recs.data(), recs.size()) || mfx_phase_contig_counts(res, counts.data(), S.size())) DIE_MFX("-phase");
+  if (mfx_phase_write(recs.data(), recs.size(), counts.data(), seq, S.names.data(), k, &o, G.outName)) DIE_MFX("writing the phase blocks");
+  uint64_t nb[2] = {0, 0}, nm[2] = {0, 0}, ns[2] = {0, 0}, span[2] = {0, 0};
+  for (const mfx_phase_block &x : recs) { nb[x.hap]++; nm[x.hap] += x.n_hap + x.n_switch; ns[x.hap] += x.n_switch; span[x.hap] += x.end - 1 + (uint64_t)k - x.start; }
+  for (int h = 0; h < 2; ++h)
+    fprintf(stderr, "-- %c: %lu blocks, %lu bases, %lu markers, %lu switch markers.\n", "AB"[h], (unsigned long)nb[h], (unsigned long)span[h], (unsigned long)nm[h],
+            (unsigned long)ns[h]);
+  fprintf(stderr, "-- all: %lu blocks, %lu bases, %lu markers, %lu switch markers (switch rate %.6f).\n", (unsigned long)(nb[0] + nb[1]), (unsigned long)(span[0] + span[1]),
+          (unsigned long)(nm[0] + nm[1]), (unsigned long)(ns[0] + ns[1]), nm[0] + nm[1] ? (double)(ns[0] + ns[1]) / (double)(nm[0] + nm[1]) : 0.0);
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
 static int report_hist(Run &R) {
   const Globals &G = R.G;
   fprintf(stderr, "-- Generate histogram of the k* metric to '%s'.\n", G.outName);
@@ -1926,8 +2006,15 @@ int main(int argc, char **argv) {
   Errors err;
   // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
   parse_args(argc, argv, G, err);
+  check_phase_flags(G, err);
+  if (phase_named(G)) {
+    if (!err.empty()) return fail_usage(argv[0], err, false, false, false, true);
+    if (!G.devices.empty()) G.device = G.devices[0];
+    return devices_available({G.device}) ? run_phase(G) : 1;
+  }
   check_merge_flags(G, err);
-  if (!G.mergeNames.empty() || G.opName) return err.empty() ? run_merge(G) : fail_usage(argv[0], err, true);
+  if (!G.mergeNames.empty() || G.opName || !G.notNames.empty())
+    return err.empty() ? run_merge(G) : fail_usage(argv[0], err, true, false, false, false, !G.notNames.empty());
   check_count_flags(G, err);
   if (G.count) return err.empty() ? run_count(G) : fail_usage(argv[0], err);
   check_join_flags(G, err);

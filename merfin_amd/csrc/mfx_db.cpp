@@ -2210,6 +2210,7 @@ struct MergeDecoder {                                          // a window's way
   std::vector<uint32_t> hev, cnt, errs;
   std::vector<MergeRun> runs;                                  // per input: its dense run of the window in the decoded buffer
   double t_read = 0, t_decode = 0;                             // of the last window
+  uint32_t zero_from = ~0u;                                    // mfx_db_merge_except: the inputs from this one on are subtracted
   MergeDecoder() = default;
   MergeDecoder(const MergeDecoder &) = delete;
   MergeDecoder &operator=(const MergeDecoder &) = delete;
@@ -2310,7 +2311,7 @@ static int merge_decode_window(const std::vector<std::unique_ptr<MergeIn>> &ins,
   double t1 = db_now();
   D.t_read = t1 - t0;
   // ---- decode: one ascending run per input
-  MFX_HIP(mfx_k_delta_decode(D.d_tasks, nt, (const uint64_t *)D.d_words, D.d_ek, D.d_ev, lo, hi, keys, vals, D.d_below, D.d_above, D.d_err, nullptr));
+  MFX_HIP(mfx_k_delta_decode(D.d_tasks, nt, (const uint64_t *)D.d_words, D.d_ek, D.d_ev, lo, hi, keys, vals, D.d_below, D.d_above, D.d_err, nullptr, D.zero_from));
   D.cnt.resize(2 * (size_t)nt);
   MFX_HIP(hipMemcpyAsync(D.cnt.data(), D.d_below, nt * 4, hipMemcpyDeviceToHost, nullptr));
   MFX_HIP(hipMemcpyAsync(D.cnt.data() + nt, D.d_above, nt * 4, hipMemcpyDeviceToHost, nullptr));
@@ -2334,17 +2335,38 @@ static int merge_decode_window(const std::vector<std::unique_ptr<MergeIn>> &ins,
   return MFX_OK;
 }
 
-static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
-  const char *who = "mfx_db_merge";
+// not_paths: the databases whose k-mers are not written (mfx_db_merge_except); they are opened behind the inputs, share their windows and are
+// decoded with counts of 0, which the combine kernel takes as "this k-mer is barred".  n_not == 0: mfx_db_merge.
+static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const char *const *not_paths, uint32_t n_not, const char *out_path, const mfx_db_merge_opts *o,
+                             mfx_db_merge_stats *st, uint64_t *n_subtracted) {
+  const char *who = n_not ? "mfx_db_merge_except" : "mfx_db_merge";
   if (st) memset(st, 0, sizeof(*st));
+  if (n_subtracted) *n_subtracted = 0;
   std::vector<std::unique_ptr<MergeIn>> ins;
+  if (n_not && (!not_paths || (uint64_t)n_in + n_not > MFX_MERGE_MAX_INPUTS))
+    return not_paths ? mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: %u inputs and %u to subtract (%u files at the most)", n_in, n_not, MFX_MERGE_MAX_INPUTS)
+                     : mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: null argument");
   if (int rc = merge_check(in_paths, n_in, out_path, o, ins)) return rc;
   const int k = (int)ins[0]->h.k;
+  uint64_t n_read = 0;
+  for (uint32_t i = 0; i < n_in; ++i) n_read += ins[i]->h.n;
+  for (uint32_t j = 0; j < n_not; ++j) {
+    if (!not_paths[j]) return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: null argument");
+    ins.emplace_back(new MergeIn);
+    if (int rc = merge_open_input(not_paths[j], *ins.back(), who)) return rc;
+    if ((int)ins.back()->h.k != k)
+      return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: '%s' holds %u-mers, '%s' %u-mers: the inputs and what is subtracted are of one k", not_paths[j], ins.back()->h.k,
+                      in_paths[0], ins[0]->h.k);
+    struct stat so, si;
+    if (stat(out_path, &so) == 0 && fstat(ins.back()->fd, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)
+      return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: the output '%s' is the subtracted database '%s'", out_path, not_paths[j]);
+  }
+  const uint32_t n_all_in = n_in + n_not;
   // ---- the windows, and what the largest of them takes
   MergeWindows P;
   if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
   const std::vector<mfx_merge_window> &win = P.win;
-  const uint64_t n_all = P.n_all, max_pairs = P.max_pairs, max_bytes = P.max_bytes, max_tasks = P.max_tasks, max_esc = P.max_esc;
+  const uint64_t n_all = n_read, max_pairs = P.max_pairs, max_bytes = P.max_bytes, max_tasks = P.max_tasks, max_esc = P.max_esc;
   mfx_db_writer *w = nullptr;
   if (int rc = db_open_streamed(out_path, k, &w)) return rc;
   WriterAbort guard{w};
@@ -2356,7 +2378,7 @@ static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const c
     // and the packed words of the one that is free by then.  p[2]: the window's blocks.  p[3]: tasks, their below / above, the inputs' error words,
     // the stats, the combine's tile offsets.  p[4], p[5]: the window's escapes.
     const uint64_t cap = max_pairs + MFX_DELTA_BLOCK, tiles = mfx_combine_tiles(max_pairs);
-    const uint64_t small = max_tasks * (sizeof(mfx_merge_task) + 8) + (tiles + 1 + 2) * 8 + n_in * 4 + 64;
+    const uint64_t small = max_tasks * (sizeof(mfx_merge_task) + 8) + (tiles + 1 + 3) * 8 + n_all_in * 4 + 64;
     DbDev D;
     hipError_t e = hipMalloc(&D.p[0], cap * 12);
     if (e == hipSuccess) e = hipMalloc(&D.p[1], cap * 12);
@@ -2372,13 +2394,14 @@ static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const c
     uint64_t *bk[2] = {(uint64_t *)D.p[0], (uint64_t *)D.p[1]};
     uint32_t *bv[2] = {(uint32_t *)((char *)D.p[0] + cap * 8), (uint32_t *)((char *)D.p[1] + cap * 8)};
     uint64_t *d_tile = (uint64_t *)D.p[3], *d_stats = d_tile + tiles + 1;
-    mfx_merge_task *d_tasks = (mfx_merge_task *)(d_stats + 2);
+    mfx_merge_task *d_tasks = (mfx_merge_task *)(d_stats + 3);
     uint32_t *d_below = (uint32_t *)(d_tasks + max_tasks), *d_above = d_below + max_tasks, *d_err = d_above + max_tasks;
-    MFX_HIP(mfx_memset_now(d_stats, 0, 16));
+    MFX_HIP(mfx_memset_now(d_stats, 0, 24));
     StreamDev S;
     if (int rc = stream_dev_init(S, w, cap, who, "MFX_MERGE_RANGE")) return rc;
     const bool timing = getenv("MFX_DB_TIMING") != nullptr;
     MergeDecoder dec;
+    if (n_not) dec.zero_from = n_in;
     dec.d_words = D.p[2]; dec.d_tasks = d_tasks; dec.d_below = d_below; dec.d_above = d_above; dec.d_err = d_err;
     dec.d_ek = (uint64_t *)D.p[4]; dec.d_ev = (uint32_t *)D.p[5];
     MFX_HIP(hipHostMalloc(&dec.pinned, max_bytes + 8, hipHostMallocDefault));
@@ -2423,9 +2446,10 @@ static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const c
       if (n_out)
         if (int rc = stream_append_device(w, S, bk[cur ^ 1], bv[cur ^ 1], n_out, bk[cur], cap * 12, who, "MFX_MERGE_RANGE")) return rc;
     }
-    uint64_t stats[2] = {0, 0};
-    MFX_HIP(hipMemcpy(stats, d_stats, 16, hipMemcpyDeviceToHost));
+    uint64_t stats[3] = {0, 0, 0};
+    MFX_HIP(hipMemcpy(stats, d_stats, 24, hipMemcpyDeviceToHost));
     if (st) { st->n_saturated = stats[0]; st->n_filtered = stats[1]; }
+    if (n_subtracted) *n_subtracted = stats[2];
   }
   guard.w = nullptr;
   uint64_t n = 0;
@@ -2435,9 +2459,16 @@ static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const c
 }
 
 extern "C" int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
-  try { return mfx_db_merge_impl(in_paths, n_in, out_path, o, st); }                   // (nothing leaves the C ABI as an exception)
+  try { return mfx_db_merge_impl(in_paths, n_in, nullptr, 0, out_path, o, st, nullptr); }      // (nothing leaves the C ABI as an exception)
   catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge: out of memory"); }
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge: %s", e.what()); }
+}
+
+extern "C" int mfx_db_merge_except(const char *const *in_paths, uint32_t n_in, const char *const *not_paths, uint32_t n_not, const char *out_path,
+                                   const mfx_db_merge_opts *o, mfx_db_merge_stats *st, uint64_t *n_subtracted) {
+  try { return mfx_db_merge_impl(in_paths, n_in, not_paths, n_not, out_path, o, st, n_subtracted); }
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge_except: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge_except: %s", e.what()); }
 }
 
 // ---------------------------------------------------------------------------

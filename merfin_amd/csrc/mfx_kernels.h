@@ -137,6 +137,20 @@ struct mfx_regions_args {
   uint64_t        reg_begin0 = 0, reg_begin1 = 0, reg_begin2 = 0, reg_begin3 = 0;   // class c's records: [reg_begin c, reg_begin c+1)
 };
 
+// -phase (csrc/mfx_phase.h).  Pass 1 (mfx_phase_mark_kernel / mfx_w_phase_mark_kernel) writes the two haplotype planes and the per-contig totals
+struct mfx_phase_args {
+  mfx_table_view  t;
+  int             canonical;
+  const uint8_t  *bases;
+  const uint64_t *codes = nullptr;    // non-null (k <= 31): the tiles are read from the packed planes, as -hist does
+  const uint32_t *valid = nullptr;
+  const uint64_t *contig_off, *contig_len, *tile_start;
+  const uint32_t *tile_contig;
+  uint64_t        ntiles;
+  uint64_t       *planes;             // [2][ntiles * 64]: plane 0 in A and not in B, plane 1 in B and not in A; every word is written
+  uint64_t       *counts;             // [ncontigs][4] += valid k-mers, A markers, B markers, shared; zero at launch
+};
+
 struct mfx_count_args {
   mfx_table_view  t;
   const uint8_t  *bases;
@@ -251,6 +265,23 @@ hipError_t mfx_k_rg_emit(const uint64_t *reg_first, const uint64_t *reg_last, co
                          uint64_t nraw, const uint64_t *cls_run /* [4], host */, const uint32_t *run_contig, const uint64_t *run_start, const uint64_t *run_end,
                          uint64_t *regs, hipStream_t st);
 hipError_t mfx_k_rg_finish(uint64_t *regs, uint64_t nreg, hipStream_t st);        // word 6: key -> ext_kstar
+hipError_t mfx_k_phase_mark(const mfx_phase_args &a, hipStream_t st);          // k <= 31
+hipError_t mfx_kw_phase_mark(const mfx_phase_args &a, hipStream_t st);         // 32 <= k <= 64 (mfx_wide.hip)
+// pass 2 of -phase (mfx_phase.hip); the sums are mfx_k_rg_scan's, the bounds mfx_k_rg_bounds'
+size_t     mfx_k_ph_temp_bytes(uint64_t n);                                        // temporary storage any scan of n entries needs
+hipError_t mfx_k_ph_join_scan(const uint64_t *in, uint64_t *out, uint64_t n, void *tmp, size_t tmp_bytes, hipStream_t st);   // inclusive, by mfx_ph_join
+hipError_t mfx_k_ph_tile(const uint64_t *planes, uint64_t ntiles, const uint64_t *tile_start, const uint32_t *tile_contig, uint64_t *cnt /* ntiles + 1 */,
+                         uint64_t *car /* ntiles */, hipStream_t st);
+hipError_t mfx_k_ph_count(const uint64_t *planes, uint64_t ntiles, const uint64_t *tile_start, const uint32_t *tile_contig, const uint64_t *car /* scanned */,
+                          uint64_t *cnt_run /* ntiles + 1 */, hipStream_t st);
+hipError_t mfx_k_ph_scatter(const uint64_t *planes, uint64_t ntiles, const uint64_t *tile_start, const uint32_t *tile_contig, const uint64_t *car, const uint64_t *rank0,
+                            const uint64_t *off, uint32_t *run_contig, uint32_t *run_hap, uint64_t *run_start, uint64_t *run_end, uint64_t *run_rank, hipStream_t st);
+hipError_t mfx_k_ph_runs(const uint32_t *run_contig, const uint32_t *run_hap, const uint64_t *run_start, const uint64_t *run_end, const uint64_t *run_rank, uint64_t nruns,
+                         uint64_t nmarkers, uint64_t k, uint64_t S, uint64_t R, uint64_t *lng /* nruns */, uint64_t *cnt_a /* nruns + 1 */, uint64_t *cnt_b, hipStream_t st);
+hipError_t mfx_k_ph_heads(const uint32_t *run_contig, const uint32_t *run_hap, const uint64_t *lng, const uint64_t *lng_x, uint64_t nruns, uint64_t *head /* nruns + 1 */,
+                          hipStream_t st);
+hipError_t mfx_k_ph_emit(const uint64_t *blk_first, const uint64_t *blk_last, uint64_t nblocks, const uint32_t *run_contig, const uint32_t *run_hap,
+                         const uint64_t *run_start, const uint64_t *run_end, const uint64_t *lng_x, const uint64_t *a_x, const uint64_t *b_x, uint64_t *recs, hipStream_t st);
 hipError_t mfx_k_track_finish(uint64_t *recs, uint64_t nrec, hipStream_t st);   // the min / max keys of the records -> doubles (+inf / -inf where nothing was scored)
 // *out += the content digest of nwords 32-base words (codes != nullptr: from the packed planes, else from the bytes)
 hipError_t mfx_k_seq_digest(const uint8_t *bases, const uint64_t *codes, const uint32_t *valid, uint64_t nwords, uint64_t *out, hipStream_t st);
@@ -286,7 +317,8 @@ struct mfx_merge_task { uint64_t word_off, first, limit, out; uint32_t kb, vb, c
 constexpr uint32_t MFX_MERGE_ERR_ORDER = 1u, MFX_MERGE_ERR_ESCAPE = 2u, MFX_MERGE_ERR_ZERO = 4u;      // err[input] of the decode: what no writer makes
 // below[t] / above[t]: the records of task t under lo / at or above hi
 hipError_t mfx_k_delta_decode(const mfx_merge_task *tasks, uint32_t ntasks, const uint64_t *payload, const uint64_t *esc_keys, const uint32_t *esc_vals, uint64_t lo,
-                              uint64_t hi, uint64_t *keys, uint32_t *vals, uint32_t *below, uint32_t *above, uint32_t *err, hipStream_t st);
+                              uint64_t hi, uint64_t *keys, uint32_t *vals, uint32_t *below, uint32_t *above, uint32_t *err, hipStream_t st,
+                              uint32_t zero_from = ~0u /* the inputs from this one on leave with a count of 0: mfx_db_merge_except */);
 // two ascending runs into one of la + lb pairs; equal k-mers stay, a's first
 hipError_t mfx_k_merge_pairs(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, uint64_t *ko, uint32_t *vo,
                              hipStream_t st);

@@ -18,6 +18,8 @@
 #include "mfx_track.h"
 #define MFX_REGIONS_DEVICE
 #include "mfx_regions.h"
+#define MFX_PHASE_DEVICE
+#include "mfx_phase.h"
 #include "mfx_spectrum.h"
 
 #include <stdlib.h>
@@ -3379,6 +3381,72 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_regions_sums_kernel(mfx_regions
 }
 
 // ===========================================================================
+// -phase (csrc/mfx_phase.h), pass 1: a sibling of mfx_regions_class_kernel -- its tiles, its lookups, its canonical / non-canonical /
+// even-k rules.  The read side of the index holds set A, the assembly side set B; membership is "value > 0".  A position in A and not in
+// B is one bit of plane 0, in B and not in A of plane 1; a wave's ballots are stored by one lane, and the wave's popcounts of a tile
+// go to the tile's contig as integer sums.
+// ===========================================================================
+template <bool CANON, bool COMPACT>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_phase_mark_kernel(mfx_phase_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_mailbox MB;
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t nwords = a.ntiles * MFX_RG_WORDS;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    if (a.codes) {                                             // block-uniform
+      const uint64_t w0 = (a.contig_off[c] + pos0) >> 5;
+      mfx_tile_fill_packed(L, a.codes + w0, a.valid + w0);
+    } else {
+      mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    }
+    __syncthreads();                                           // the tile is in LDS
+    mfx_ph_acc acc = {0u, 0u, 0u, 0u};
+    uint32_t b = 0;
+    for (; b < MFX_TILE / MFX_BLOCK; b += MFX_BATCH) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      uint64_t key[MFX_BATCH], key2[MFX_BATCH];
+      uint32_t rv[MFX_BATCH], av[MFX_BATCH];
+      bool     ok[MFX_BATCH];
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;          // lane-consecutive positions: a wave holds word p / 64 of the tile
+        uint64_t f;
+        ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
+        const uint64_t r = mfx_revcomp(f, k);
+        if (CANON) { key[j] = f < r ? f : r; key2[j] = f < r ? r : f; }
+        else { key[j] = f; key2[j] = r; }
+      }
+      if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key, key2, ok, rv, av);
+      else mfx_group_lookup<MFX_BATCH>(a.t, MB, key, key2, ok, rv, av);
+      if (!CANON) {                                            // value(fmer) + value(rmer), uint32 arithmetic (merfin-globals.C:107-108)
+        uint32_t rv2[MFX_BATCH], av2[MFX_BATCH];
+        if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key2, key, ok, rv2, av2);
+        else mfx_group_lookup<MFX_BATCH>(a.t, MB, key2, key, ok, rv2, av2);
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) { rv[j] |= rv2[j]; av[j] |= av2[j]; }      // (membership: "a sum > 0" without the sum's wrap)
+      }                                                        // (even k: a palindromic k-mer's doubled value is > 0 when the value is)
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;
+        mfx_ph_store_masks(a.planes, nwords, tile * MFX_RG_WORDS + (p >> 6), ok[j], rv[j], av[j], acc);
+      }
+    }
+    for (uint32_t w = b * (MFX_BLOCK / 64) + tid; w < MFX_RG_WORDS; w += MFX_BLOCK) {      // the rounds beyond a contig's end: their words are 0
+      const uint64_t word = tile * MFX_RG_WORDS + w;
+      a.planes[word] = 0ull;
+      a.planes[nwords + word] = 0ull;
+    }
+    mfx_ph_add_counts(a.counts, c, acc);
+    __syncthreads();                                           // the tile is consumed
+  }
+}
+
+// ===========================================================================
 // varMer::score on the device (varMer.C:66-144): one lane per alternative PATH of a batch of variant clusters.  The paths'
 // k-mers have been looked up by mfx_dump_kernel over the packed path text (readV / asmV per start position); this walks a
 // path's bases in order exactly as the reference does -- run length of valid bases, the k-mer ENDING at idx, readK / prob by
@@ -4293,6 +4361,15 @@ hipError_t mfx_k_regions_class(const mfx_regions_args &a, hipStream_t st) {
   else if (a.canonical)           mfx_regions_class_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else if (a.t.compact)           mfx_regions_class_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else                            mfx_regions_class_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_phase_mark(const mfx_phase_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical && a.t.compact) mfx_phase_mark_kernel<true, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.canonical)           mfx_phase_mark_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.t.compact)           mfx_phase_mark_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else                            mfx_phase_mark_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_k_regions_sums(const mfx_regions_args &a, hipStream_t st) {

@@ -14,10 +14,11 @@
 // A count field of all ones is an escape: the count stands in the input's escape list, whose slice for this window [esc_lo, esc_hi) is
 // ascending.  What no writer makes is reported in err[input] and nothing of the window is written to the output file: k-mers that do not ascend
 // strictly or reach the next block's first (MFX_MERGE_ERR_ORDER), an escape that is not in the list (.._ESCAPE), a count of zero (.._ZERO).
+// The inputs from zero_from on are decoded and checked like the others and then leave with a count of 0: the mark of a k-mer to subtract.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mfx_delta_decode_kernel(const mfx_merge_task *tasks, uint32_t ntasks, const uint64_t *payload, const uint64_t *esc_keys,
                                                                const uint32_t *esc_vals, uint64_t lo, uint64_t hi, uint64_t *keys, uint32_t *vals,
-                                                               uint32_t *below, uint32_t *above, uint32_t *err) {
+                                                               uint32_t *below, uint32_t *above, uint32_t *err, uint32_t zero_from) {
   __shared__ uint64_t wsum[4];
   __shared__ uint32_t s_cnt[4][2];
   if (blockIdx.x >= ntasks) return;                            // (uniform)
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(256) void mfx_delta_decode_kernel(const mfx_merge_t
       else bad |= MFX_MERGE_ERR_ESCAPE;
     }
     if (v == 0u) bad |= MFX_MERGE_ERR_ZERO;
+    if (t.input >= zero_from) v = 0u;                          // an input that is subtracted (mfx_db_merge_except): its k-mers, whatever their counts
     nb += run < lo ? 1u : 0u;
     na += run >= hi ? 1u : 0u;
     keys[t.out + e] = run;
@@ -121,7 +123,8 @@ __global__ __launch_bounds__(256) void mfx_merge_pairs_kernel(const uint64_t *ka
 // count.  The survivors are compacted in order without an atomic that could reorder them: the kernel runs twice over tiles of MFX_COMB_TILE
 // positions -- the first run leaves every tile's number of survivors, a one-workgroup scan turns them into offsets, the second run computes
 // the same again and stores.  Within a tile: rounds of 256 positions, a ballot per wave and the waves' counts in front of it.
-// stats (second run): [0] sums clamped to 2^32 - 1, [1] k-mers the operation yields and the filter drops.
+// stats (second run): [0] sums clamped to 2^32 - 1, [1] k-mers the operation yields and the filter drops, [2] k-mers the operation yields and a
+// subtracted input holds.  n_in: the inputs of the operation, the subtracted ones not counted.
 // ---------------------------------------------------------------------------
 constexpr uint32_t MFX_COMB_ROUNDS = 8;
 constexpr uint32_t MFX_COMB_TILE = 256u * MFX_COMB_ROUNDS;
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(256) void mfx_combine_kernel(const uint64_t *keys, 
   __shared__ uint32_t s_cnt[4];
   const uint32_t tid = threadIdx.x, wv = tid >> 6, ln = tid & 63u;
   uint64_t base = SCATTER ? tile_off[blockIdx.x] : 0ull;
-  uint32_t nsat = 0u, nfilt = 0u;
+  uint32_t nsat = 0u, nfilt = 0u, nbar = 0u;
   for (uint32_t r = 0; r < MFX_COMB_ROUNDS; ++r) {             // (uniform)
     const uint64_t i = (uint64_t)blockIdx.x * MFX_COMB_TILE + (uint64_t)r * 256u + tid;
     bool take = false;
@@ -141,16 +144,19 @@ __global__ __launch_bounds__(256) void mfx_combine_kernel(const uint64_t *keys, 
     if (i < n) {
       key = keys[i];
       if (i == 0 || keys[i - 1] != key) {
-        uint32_t v = vals[i], mn = v, mx = v, len = 1u;
+        // (a count of 0 is a subtracted input's: it is no member of the operation, and its k-mer is not written)
+        uint32_t v = vals[i], mn = v ? v : 0xffffffffu, mx = v, len = v ? 1u : 0u;
         uint64_t sum = v;
+        bool barred = v == 0u;
         for (uint64_t j = i + 1; j < n && keys[j] == key; ++j) {
           v = vals[j];
+          if (v == 0u) { barred = true; continue; }
           sum += v;
           mn = v < mn ? v : mn;
           mx = v > mx ? v : mx;
           ++len;
         }
-        bool yields = true;
+        bool yields = len != 0u;
         if (op == MFX_MERGE_SUM) {
           if (sum > 0xffffffffull) { sum = 0xffffffffull; ++nsat; }
           c = (uint32_t)sum;
@@ -159,6 +165,7 @@ __global__ __launch_bounds__(256) void mfx_combine_kernel(const uint64_t *keys, 
           c = mn;
           if (op == MFX_MERGE_INTERSECT) yields = len == n_in;
         }
+        if (yields && barred) { yields = false; ++nbar; }
         if (yields) {
           take = (uint64_t)c >= minV && (uint64_t)c <= maxV;
           if (!take) ++nfilt;
@@ -182,10 +189,11 @@ __global__ __launch_bounds__(256) void mfx_combine_kernel(const uint64_t *keys, 
     if (tid == 0u) tile_off[blockIdx.x] = base;
     return;
   }
-  for (int o = 32; o; o >>= 1) { nsat += __shfl_xor(nsat, o, 64); nfilt += __shfl_xor(nfilt, o, 64); }
+  for (int o = 32; o; o >>= 1) { nsat += __shfl_xor(nsat, o, 64); nfilt += __shfl_xor(nfilt, o, 64); nbar += __shfl_xor(nbar, o, 64); }
   if (ln == 0u) {
     if (nsat) atomicAdd(&stats[0], (unsigned long long)nsat);
     if (nfilt) atomicAdd(&stats[1], (unsigned long long)nfilt);
+    if (nbar) atomicAdd(&stats[2], (unsigned long long)nbar);
   }
 }
 
@@ -215,9 +223,9 @@ __global__ __launch_bounds__(256) void mfx_tile_scan_kernel(uint64_t *t, uint32_
 }
 
 hipError_t mfx_k_delta_decode(const mfx_merge_task *tasks, uint32_t ntasks, const uint64_t *payload, const uint64_t *esc_keys, const uint32_t *esc_vals, uint64_t lo,
-                              uint64_t hi, uint64_t *keys, uint32_t *vals, uint32_t *below, uint32_t *above, uint32_t *err, hipStream_t st) {
+                              uint64_t hi, uint64_t *keys, uint32_t *vals, uint32_t *below, uint32_t *above, uint32_t *err, hipStream_t st, uint32_t zero_from) {
   if (ntasks == 0) return hipSuccess;
-  mfx_delta_decode_kernel<<<ntasks, 256, 0, st>>>(tasks, ntasks, payload, esc_keys, esc_vals, lo, hi, keys, vals, below, above, err);
+  mfx_delta_decode_kernel<<<ntasks, 256, 0, st>>>(tasks, ntasks, payload, esc_keys, esc_vals, lo, hi, keys, vals, below, above, err, zero_from);
   return hipGetLastError();
 }
 

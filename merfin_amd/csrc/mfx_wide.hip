@@ -17,6 +17,8 @@
 #include "mfx_track.h"
 #define MFX_REGIONS_DEVICE
 #include "mfx_regions.h"
+#define MFX_PHASE_DEVICE
+#include "mfx_phase.h"
 #include "mfx_spectrum.h"
 
 typedef unsigned __int128 mfx_u128;
@@ -460,6 +462,42 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_regions_sums_kernel(mfx_regio
   mfx_w_regions_tiles<CANON, true>(a, L, n_valid, n_missing);
 }
 
+// -phase (csrc/mfx_phase.h), pass 1: the twin of mfx_phase_mark_kernel (mfx_kernels.hip) -- the planes and the totals are the same whichever
+// kernel made them
+template <bool CANON>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_w_phase_mark_kernel(mfx_phase_args a) {
+  __shared__ mfx_tile_lds L;
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t nwords = a.ntiles * MFX_RG_WORDS;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const uint32_t c = a.tile_contig[tile];
+    const uint64_t pos0 = (tile - a.tile_start[c]) * MFX_TILE;
+    const uint64_t clen = a.contig_len[c];
+    const uint32_t n = (clen - pos0 < MFX_TILE) ? (uint32_t)(clen - pos0) : MFX_TILE;
+    mfx_tile_fill(L, a.bases + a.contig_off[c] + pos0);
+    __syncthreads();
+    mfx_ph_acc acc = {0u, 0u, 0u, 0u};
+    uint32_t b = 0;
+    for (; b < MFX_TILE / MFX_BLOCK; ++b) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile of a contig (block-uniform)
+      const uint32_t p = b * MFX_BLOCK + tid;
+      mfx_u128 f;
+      const bool ok = mfx_w_tile_kmer(L, k, p, f) && p < n;
+      uint2 v = make_uint2(0u, 0u);
+      if (ok) v = mfx_w_getV<CANON>(a.t, f, k);
+      mfx_ph_store_masks(a.planes, nwords, tile * MFX_RG_WORDS + (p >> 6), ok, v.x, v.y, acc);
+    }
+    for (uint32_t w = b * (MFX_BLOCK / 64) + tid; w < MFX_RG_WORDS; w += MFX_BLOCK) {      // the rounds beyond a contig's end: their words are 0
+      const uint64_t word = tile * MFX_RG_WORDS + w;
+      a.planes[word] = 0ull;
+      a.planes[nwords + word] = 0ull;
+    }
+    mfx_ph_add_counts(a.counts, c, acc);
+    __syncthreads();                                           // the tile is consumed
+  }
+}
+
 // `meryl count` of the assembly (merfin-globals.C:182-186)
 __global__ __launch_bounds__(MFX_BLOCK) void mfx_w_count_kernel(mfx_count_args a) {
   __shared__ mfx_tile_lds L;
@@ -647,6 +685,13 @@ hipError_t mfx_kw_regions_class(const mfx_regions_args &a, hipStream_t st) {
   const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
   if (a.canonical) mfx_w_regions_class_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else             mfx_w_regions_class_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_kw_phase_mark(const mfx_phase_args &a, hipStream_t st) {
+  if (a.ntiles == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(a.ntiles < 8192 ? a.ntiles : 8192);
+  if (a.canonical) mfx_w_phase_mark_kernel<true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else             mfx_w_phase_mark_kernel<false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_kw_regions_sums(const mfx_regions_args &a, hipStream_t st) {
