@@ -932,6 +932,46 @@ int  mfx_phase_from_planes_host(const uint64_t *planes, const uint64_t *contig_l
                                 mfx_phase_block *out, uint64_t cap, uint64_t *n_out);
 
 /* ------------------------------------------------------------------------ */
+/* -bin: per-read hap-mer counts on the device, reads sorted by parent (trio */
+/* binning).  No reference counterpart: merfin has no trio mode.  The class  */
+/* rule is this project's own, in the spirit of Canu's haplotype split, and  */
+/* is NOT validated against Canu.                                            */
+/* ------------------------------------------------------------------------ */
+/* The index behind the evaluator holds set A on its read side and set B on its assembly side, as for -phase; membership is
+ * "value > 0".  Every record (read) gets the number of its valid k-mers, of those in A only, in B only and in both:
+ * kmers = a + b + shared + in neither.  16 bytes. */
+typedef struct mfx_bin_record { uint32_t kmers, a, b, shared; } mfx_bin_record;
+typedef struct { uint64_t reads, bases, kmers, a, b, shared; double seconds_kernel, seconds_copy; } mfx_bin_stats;
+typedef struct mfx_bin mfx_bin;
+/* Records are batched as the read counters batch them (batch_bases per batch, 0: the library's; a record longer than the room left
+ * is cut with a k - 1 overlap), packed into one of two pinned stages and counted on that stage's stream; the counts of the batch's
+ * pieces of records come back on the same stream and are folded into the records in input order.  Integer sums only: a second run
+ * gives the same bytes.  The evaluator's K* parameters are not read.  MFX_E_INVAL: a null argument, k > 31, a sharded index, a
+ * batch below 2k + 2 bases. */
+mfx_bin *mfx_bin_begin(mfx_eval *ev, uint64_t batch_bases);
+/* n records; returns once bases / lens may be reused.  MFX_E_INVAL: a null argument, a record of 2^32 bases or more (nothing of the
+ * call is taken then). */
+int  mfx_bin_add(mfx_bin *b, const char *const *bases, const uint64_t *lens, uint64_t n);
+/* sends the open batch and waits for every stage: every record added is final afterwards */
+int  mfx_bin_flush(mfx_bin *b);
+/* records whose counts are final and not yet taken.  A record is final when the stage that holds its last piece has settled (stages
+ * settle inside add, flush and end); one shorter than k is final with zeros but keeps its place in the order. */
+uint64_t mfx_bin_ready(const mfx_bin *b);
+/* the next min(cap, ready) records, in input order */
+int  mfx_bin_take(mfx_bin *b, mfx_bin_record *dst, uint64_t cap, uint64_t *n_out);
+/* flushes and frees b whatever the result; records not taken are lost (the statistics count them) */
+int  mfx_bin_end(mfx_bin *b, mfx_bin_stats *out);
+/* The class rule, host only, integers only.  With NA = norm_a ? norm_a : 1 and NB likewise, a record is class 0 (A) iff
+ * a + b >= min_hits and a * NB * 1000 > b * NA * ratio_milli, class 1 (B) iff the same holds with the roles swapped, else class 2
+ * (unknown: ties, a = b = 0); the products in 128 bits.  MFX_E_INVAL: a null argument, ratio_milli < 1000 (both could hold). */
+typedef struct { uint64_t norm_a, norm_b; uint32_t ratio_milli; uint32_t min_hits; } mfx_bin_opts;
+int  mfx_bin_classify(const mfx_bin_record *r, uint64_t n, const mfx_bin_opts *o, uint8_t *cls);
+/* Host only (tests, tools/native/bin_sanitize.cpp): the pieces n records of lens[] bases are cut into, batch after batch, by the
+ * code the device path cuts with (csrc/mfx_bin.h) -- pieces[i] = batch, record, first position in the batch, length.  At most cap
+ * are stored, *n_pieces counts them all.  batch_bases 0: the library's. */
+int  mfx_bin_plan_host(const uint64_t *lens, uint64_t n, int k, uint64_t batch_bases, uint64_t *pieces, uint64_t cap, uint64_t *n_pieces);
+
+/* ------------------------------------------------------------------------ */
 /* -filter / -polish / -better / -strict / -loose: replaces processVariants */
 /* + outputVariants (merfin-variants.C:131-345), vcfFile (vcf.C) and varMer  */
 /* (varMer.C).  The host enumerates the allele-combination paths of many     */

@@ -100,6 +100,7 @@ SYMBOLS = [
     "mfx_regions_write", "mfx_regions_from_planes_host",
     "mfx_db_merge_except", "mfx_phase_run", "mfx_phase_count", "mfx_phase_copy", "mfx_phase_contig_counts", "mfx_phase_free", "mfx_diag_phase_times", "mfx_phase_write",
     "mfx_phase_from_planes_host",
+    "mfx_bin_begin", "mfx_bin_add", "mfx_bin_flush", "mfx_bin_ready", "mfx_bin_take", "mfx_bin_end", "mfx_bin_classify", "mfx_bin_plan_host",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
@@ -142,6 +143,19 @@ assert PHASE_DTYPE.itemsize == 48
 
 class _PhaseOpts(C.Structure):
     _fields_ = [("switches", C.c_uint64), ("range", C.c_uint64)]
+
+
+# the counts of one read of Evaluator.bin_reads: mfx_bin_record (include/merfin_amd.h) is four uint32 -- k-mers, A only, B only, shared
+BIN_CLASSES = ("A", "B", "U")
+
+
+class _BinStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64), ("a", C.c_uint64), ("b", C.c_uint64),
+                ("shared", C.c_uint64), ("seconds_kernel", C.c_double), ("seconds_copy", C.c_double)]
+
+
+class _BinOpts(C.Structure):
+    _fields_ = [("norm_a", C.c_uint64), ("norm_b", C.c_uint64), ("ratio_milli", C.c_uint32), ("min_hits", C.c_uint32)]
 
 
 def _share_hip_runtime_with_torch():
@@ -392,6 +406,16 @@ def load_library():
     L.mfx_diag_phase_times.argtypes = [vp, C.POINTER(C.c_double)]
     L.mfx_phase_write.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(_PhaseOpts), C.c_char_p]
     L.mfx_phase_from_planes_host.argtypes = [vp, u64p, C.c_uint32, C.c_int, C.POINTER(_PhaseOpts), vp, C.c_uint64, u64p]
+    L.mfx_bin_begin.restype = vp
+    L.mfx_bin_begin.argtypes = [vp, C.c_uint64]
+    L.mfx_bin_add.argtypes = [vp, C.POINTER(C.c_char_p), u64p, C.c_uint64]
+    L.mfx_bin_flush.argtypes = [vp]
+    L.mfx_bin_ready.restype = C.c_uint64
+    L.mfx_bin_ready.argtypes = [vp]
+    L.mfx_bin_take.argtypes = [vp, vp, C.c_uint64, u64p]
+    L.mfx_bin_end.argtypes = [vp, C.POINTER(_BinStats)]
+    L.mfx_bin_classify.argtypes = [vp, C.c_uint64, C.POINTER(_BinOpts), vp]
+    L.mfx_bin_plan_host.argtypes = [u64p, C.c_uint64, C.c_int, C.c_uint64, vp, C.c_uint64, u64p]
     L.mfx_spectrum_run.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p]
     L.mfx_diag_spectrum_time.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
     L.mfx_spectrum_peak.argtypes = [u64p, C.c_uint32, C.POINTER(_SpectrumPeak)]
@@ -1377,6 +1401,75 @@ def phase_from_planes_host(planes, contig_lens, k, switches=100, range_=20000):
 E_NODATA = -10
 
 
+class Binner:
+    """the per-read hap-mer counter of -bin (mfx_bin_*): records go in with add(), their counts come out of take() in input order.  The
+    index behind the evaluator holds set A on its read side and set B on its assembly side, as for Evaluator.phase."""
+
+    def __init__(self, evaluator, batch_bases=0):
+        self.h = _need(load_library().mfx_bin_begin(evaluator.h if evaluator is not None else None, int(batch_bases)))
+        self._ev = evaluator                                         # (the index must outlive the binner)
+
+    def add(self, reads):
+        recs = [x.encode() if isinstance(x, str) else bytes(x) for x in reads]
+        ptrs = (C.c_char_p * len(recs))(*recs)
+        lens = (C.c_uint64 * len(recs))(*[len(x) for x in recs])
+        _check(load_library().mfx_bin_add(self.h, ptrs, lens, len(recs)))
+
+    def flush(self):
+        _check(load_library().mfx_bin_flush(self.h))
+
+    def ready(self):
+        return load_library().mfx_bin_ready(self.h)
+
+    def take(self, cap):
+        """the next min(cap, ready()) records: a uint32 array [n, 4] of k-mers, A only, B only, shared"""
+        out = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+        n = C.c_uint64(0)
+        _check(load_library().mfx_bin_take(self.h, C.c_void_p(out.ctypes.data), int(cap), C.byref(n)))
+        return out[:n.value]
+
+    def end(self):
+        """flushes and frees the binner; the statistics as a dict"""
+        h, self.h = self.h, None
+        st = _BinStats()
+        _check(load_library().mfx_bin_end(h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _BinStats._fields_}
+
+    def close(self):
+        if getattr(self, "h", None):
+            h, self.h = self.h, None
+            load_library().mfx_bin_end(h, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bin_classify(records, norm_a, norm_b, ratio_milli=1000, min_hits=1):
+    """the class rule of -bin over the records of Evaluator.bin_reads (mfx_bin_classify; host only, integers only): a uint8 array of
+    0 (A), 1 (B), 2 (unknown).  The rule is this project's own, in the spirit of Canu's haplotype split; not validated against Canu."""
+    r = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 4)
+    cls = np.zeros(max(len(r), 1), dtype=np.uint8)
+    o = _BinOpts(int(norm_a), int(norm_b), int(ratio_milli), int(min_hits))
+    _check(load_library().mfx_bin_classify(C.c_void_p(r.ctypes.data), len(r), C.byref(o), C.c_void_p(cls.ctypes.data)))
+    return cls[:len(r)]
+
+
+def bin_plan_host(lens, k, batch_bases=0):
+    """the pieces records of these lengths are cut into by the batcher of -bin and the read counters (mfx_bin_plan_host; host only): a
+    uint64 array [n_pieces, 4] of batch, record, first position in the batch, length"""
+    L = load_library()
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    lp = lens.ctypes.data_as(C.POINTER(C.c_uint64))
+    n = C.c_uint64(0)
+    _check(L.mfx_bin_plan_host(lp, len(lens), int(k), int(batch_bases), None, 0, C.byref(n)))
+    out = np.zeros((max(n.value, 1), 4), dtype=np.uint64)
+    _check(L.mfx_bin_plan_host(lp, len(lens), int(k), int(batch_bases), C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+    return out[:n.value]
+
+
 def spectrum_peak(row):
     """the haploid peak of one spectrum row of max_mult + 1 cells (mfx_spectrum_peak; host only, exact): a dict of valley,
     main_peak, haploid_peak and count_at_peak, or None when the rule finds no peak"""
@@ -1860,6 +1953,31 @@ class Evaluator:
         finally:
             L.mfx_phase_free(h)
         return r[:n], cc[:nc]
+
+    def bin_reads(self, reads, batch_bases=0, with_stats=False, chunk=4096):
+        """per-read hap-mer counts (mfx_bin_*): the index holds set A on its read side and set B on its assembly side, as for phase().
+        Returns a uint32 array [n, 4] of valid k-mers, k-mers in A only, in B only and in both, one row per read in input order; with
+        with_stats also the statistics of the run as a dict.  The K* parameters are not read."""
+        reads = list(reads)
+        b = Binner(self, batch_bases)
+        out = np.zeros((len(reads), 4), dtype=np.uint32)
+        got = 0
+        try:
+            for o in range(0, len(reads), chunk):
+                b.add(reads[o:o + chunk])
+                r = b.take(b.ready())
+                out[got:got + len(r)] = r
+                got += len(r)
+            b.flush()
+            r = b.take(b.ready())
+            out[got:got + len(r)] = r
+            got += len(r)
+            st = b.end()
+        finally:
+            b.close()
+        if got != len(reads):
+            raise MfxError(-3, "bin_reads: %d records in, %d out" % (len(reads), got))
+        return (out, st) if with_stats else out
 
     def variants(self, mode, vcf_path, names, contigs, out_path, comb=15, nosplit=False, debug_path=None, log_path=None):
         """-filter/-polish/-better/-strict/-loose over all contigs; returns clusters evaluated"""

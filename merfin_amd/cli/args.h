@@ -49,6 +49,9 @@ struct Globals {
   std::vector<const char *> hapmers;     // -hapmers: the two sets of haplotype-specific k-mers (A, then B)
   uint64_t phSwitches = 100, phRange = 20000;   // -switches / -range of -phase
   bool switchesGiven = false, rangeGiven = false;
+  bool bin = false;                      // -bin: no K* report; per-read hap-mer counts of -reads, the reads sorted by parent (mfx_bin_*)
+  uint32_t binRatioMilli = 1000, binMinHits = 1;   // -ratio (in thousandths) / -minhits of -bin
+  bool ratioGiven = false, minhitsGiven = false, binSplit = false;      // -split: the reads themselves written per class
   bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
 };
 
@@ -171,14 +174,36 @@ static void usage_phase() {
           "\n");
 }
 
+// the entries of -bin: printed behind the text above for a command line that names one of its flags
+static void usage_bin() {
+  fprintf(stderr,
+          "  Trio binning (an operation of its own: no -sequence, no -readmers, no -peak):\n"
+          "    -bin              per read of the -reads files (FASTA / FASTQ, plain or .gz / .bz2 / .xz; repeatable) the k-mers found in hap-mer\n"
+          "                      set A only, in B only and in both, counted on the GPU (k <= 31), and the read's class -> <output>.bin.tsv\n"
+          "                      (read, length, kmers, A, B, shared, class A / B / U; one line per read in input order) and\n"
+          "                      <output>.bin.stats (reads, bases and hits per class).  An <output> ending in .gz / .bz2 / .xz compresses\n"
+          "                      them.  One device.  With NA, NB the k-mers of the two sets a read is A iff A + B >= m and\n"
+          "                      A / NA > r * B / NB, B iff the same holds with the roles swapped, else U (unknown).  The rule is this\n"
+          "                      program's own, in the spirit of Canu's haplotype split; it is not validated against Canu.\n"
+          "    -hapmers db       with -bin, exactly twice: the k-mers specific to haplotype A, then to B (any database form; one k).\n"
+          "                      -min / -max apply to the counts of both.\n"
+          "    -ratio r          with -bin: the factor r, a decimal of at most three places, at least 1 (default 1.0)\n"
+          "    -minhits m        with -bin: reads with fewer than m hits of either set are unknown (default 1)\n"
+          "    -split            with -bin: the reads are written to <output>.hapA.fasta, <output>.hapB.fasta and <output>.unknown.fasta,\n"
+          "                      name and bases as read; the reader drops the qualities of a FASTQ\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
-static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false, bool phase = false, bool nots = false) {
+static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false, bool phase = false, bool nots = false,
+                      bool bin = false) {
   usage(argv0);
   if (merge) usage_merge();
   if (nots) usage_not();
   if (join) usage_join();
   if (regions) usage_regions();
   if (phase) usage_phase();
+  if (bin) usage_bin();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -203,6 +228,27 @@ static int parse_uint(const char *v, unsigned long long lo, unsigned long long h
   if (x > hi) return UINT_ABOVE;
   *out = x;
   return UINT_OK;
+}
+
+// -ratio: digits, then at most a point and one to three digits; thousandths, 1000 to 4 000 000 000
+static bool parse_milli(const char *v, uint32_t *out) {
+  size_t i = 0;
+  unsigned long long ip = 0;
+  if (!isdigit((unsigned char)v[0])) return false;
+  for (; isdigit((unsigned char)v[i]); ++i) {
+    ip = ip * 10 + (unsigned long long)(v[i] - '0');
+    if (ip > 4000000ull) return false;
+  }
+  unsigned long long fr = 0;
+  if (v[i] == '.') {
+    size_t d = 0;
+    for (++i; isdigit((unsigned char)v[i]); ++i, ++d) fr = fr * 10 + (unsigned long long)(v[i] - '0');
+    if (d == 0 || d > 3) return false;
+    for (; d < 3; ++d) fr *= 10;
+  }
+  if (v[i] != 0 || ip < 1) return false;
+  *out = (uint32_t)(ip * 1000 + fr);
+  return true;
 }
 
 // -devices "0-7", "0,2,5", "0-3,6": a device may be named twice (two evaluation contexts on one GPU)
@@ -337,6 +383,20 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
       if (parse_uint(v, 0, ~0ull, &x) != UINT_OK)
         err.push_back(std::string("Invalid ") + (sw ? "-switches" : "-range") + " '" + v + "': " + (sw ? "-switches is a number of markers" : "-range is a number of bases") + ", an integer of at least 0.\n");
       else (sw ? G.phSwitches : G.phRange) = x;
+    }
+    else if (is("-bin")) G.bin = true;
+    else if (is("-split")) G.binSplit = true;
+    else if (is("-ratio")) {
+      const char *v = val();
+      G.ratioGiven = true;
+      if (!parse_milli(v, &G.binRatioMilli))
+        err.push_back(std::string("Invalid -ratio '") + v + "': the ratio of -bin is a decimal of at most three places, 1 to 4000000.\n");
+    }
+    else if (is("-minhits")) {
+      const char *v = val();
+      G.minhitsGiven = true;
+      if (parse_uint(v, 0, 0xffffffffull, &x) != UINT_OK) err.push_back(std::string("Invalid -minhits '") + v + "': -minhits is a number of k-mers, an integer from 0 to 4294967295.\n");
+      else G.binMinHits = (uint32_t)x;
     }
     else if (is("-skipMissing")) G.skipMissing = true;
     else if (is("-completeness")) G.reportType = OP_COMPL;
@@ -510,6 +570,50 @@ static void check_phase_flags(const Globals &G, Errors &err) {
       if (!okb) err.push_back(std::string("Cannot open the -hapmers database '") + G.hapmers[1] + "': " + mfx_last_error() + "\n");
       if (oka && okb && a.k != b.k)
         err.push_back("The two -hapmers databases hold different k-mers: " + std::to_string(a.k) + "-mers and " + std::to_string(b.k) + "-mers.\n");
+    }
+  }
+}
+
+// -bin: every check before any device is touched (the two databases are probed on the host for their k)
+static bool bin_named(const Globals &G) { return G.bin || G.ratioGiven || G.minhitsGiven || G.binSplit; }
+static void check_bin_flags(const Globals &G, Errors &err) {
+  if (!G.bin) {
+    if (G.ratioGiven) err.push_back("-ratio sets the class rule of -bin; it has no meaning without -bin.\n");
+    if (G.minhitsGiven) err.push_back("-minhits sets the class rule of -bin; it has no meaning without -bin.\n");
+    if (G.binSplit) err.push_back("-split writes the reads of -bin per class; it has no meaning without -bin.\n");
+    return;
+  }
+  if (G.hapmers.size() != 2) err.push_back("-bin takes exactly two -hapmers databases, haplotype A then B (here " + std::to_string(G.hapmers.size()) + ").\n");
+  if (G.reportType != OP_NONE) err.push_back("-bin is an operation of its own: it does not take a report type (-hist, -dump, -completeness, ...).\n");
+  if (G.count || G.convertName || !G.mergeNames.empty() || G.phase) err.push_back("-bin, -phase, -count, -convert and -merge are separate operations: give one of them.\n");
+  if (G.readsNames.empty()) err.push_back("-bin needs the reads it sorts: give -reads <file> (repeatable).\n");
+  if (G.seqName) err.push_back("-bin sorts reads, it evaluates no assembly: it does not take -sequence (-phase does).\n");
+  if (G.readDBname) err.push_back("-bin takes its k-mers as -hapmers <file>: it does not take -readmers.\n");
+  if (G.seqDBname) err.push_back("-bin takes its k-mers as -hapmers <file>: it does not take -seqmers.\n");
+  if (G.peakGiven) err.push_back("-bin evaluates no K*: it does not take -peak.\n");
+  if (G.pLookupTable) err.push_back("-bin evaluates no K*: it does not take -prob.\n");
+  if (G.vcfName) err.push_back("-bin does not take -vcf (the variant modes do).\n");
+  if (G.sharded) err.push_back("-bin does not take -sharded: a read's counts need both sets' whole membership on one device.\n");
+  if (G.devices.size() > 1) err.push_back("-bin runs on one device (-device d, or -devices naming one).\n");
+  if (G.indexName) err.push_back("-bin does not take -index: its table holds the two hap-mer sets, not a run's counts.\n");
+  if (G.join) err.push_back("-join is a way to run -completeness and -spectrum: -bin does not take it.\n");
+  if (G.switchesGiven || G.rangeGiven) err.push_back("-switches and -range bound the switch errors of -phase: -bin does not take them.\n");
+  if (!G.outName) err.push_back("No output (-output) supplied.\n");
+  reads_files_readable(G, err);
+  if (G.hapmers.size() == 2) {
+    if (strcmp(G.hapmers[0], G.hapmers[1]) == 0) {
+      err.push_back(std::string("-bin needs two different hap-mer sets: both -hapmers name '") + G.hapmers[0] + "'.\n");
+    } else {
+      mfx_db_info a, b;
+      const bool oka = mfx_db_probe(G.hapmers[0], &a) == MFX_OK;
+      if (!oka) err.push_back(std::string("Cannot open the -hapmers database '") + G.hapmers[0] + "': " + mfx_last_error() + "\n");
+      const bool okb = mfx_db_probe(G.hapmers[1], &b) == MFX_OK;
+      if (!okb) err.push_back(std::string("Cannot open the -hapmers database '") + G.hapmers[1] + "': " + mfx_last_error() + "\n");
+      if (oka && okb && a.k != b.k)
+        err.push_back("The two -hapmers databases hold different k-mers: " + std::to_string(a.k) + "-mers and " + std::to_string(b.k) + "-mers.\n");
+      else if (oka && okb && a.k > 31)
+        err.push_back("-bin holds k <= 31 (here k = " + std::to_string(a.k) + "): hap-mer databases of larger k-mers are not binned.\n");
+      if (oka && okb && G.kArg > 0 && G.kArg != a.k) err.push_back("-k " + std::to_string(G.kArg) + " disagrees with -hapmers, which hold " + std::to_string(a.k) + "-mers.\n");
     }
   }
 }

@@ -1683,6 +1683,174 @@ static int run_phase(Globals &G) {
   return 0;
 }
 
+// merfin -bin: per-read hap-mer counts and the reads sorted by parent (mfx_bin_*).  The table is the full table of the two sets, A on the
+// read side and B on the assembly side, as in the second branch of run_phase.  The reads are parsed in chunks, added, taken and written:
+// the host keeps only the records in flight -- under -split their bases, until their class is known.
+static int run_bin(Globals &G) {
+  mfx_db_info adb, bdb;
+  if (mfx_db_probe(G.hapmers[0], &adb) || mfx_db_probe(G.hapmers[1], &bdb)) DIE_MFX("opening -hapmers");
+  const int k = adb.k;
+  const uint64_t capacity = adb.n_kmers + bdb.n_kmers + 1024;
+  memory_banner(G, mfx_index_estimate_gb(k, capacity));
+  Owned<mfx_index, mfx_index_free> ix;
+  ix = mfx_index_create_lf(k, capacity, G.maxMemory, G.device, 0.7);
+  if (!ix) { fprintf(stderr, "\n%s\n\n", mfx_last_error()); return 1; }
+  // the norms of the class rule: the distinct k-mers each load puts into the table (a k-mer of B that A holds is a shared one: it is a hit
+  // of neither set and adds to neither norm_b nor the classes)
+  uint64_t norm[2] = {0, 0}, held = 0;
+  for (int side = 0; side < 2; ++side) {
+    fprintf(stderr, "-- Loading hap-mers %c from '%s' into lookup table.\n", "AB"[side], G.hapmers[side]);
+    if (mfx_index_load_db(ix, G.hapmers[side], side, G.minV, G.maxV)) DIE_MFX("loading -hapmers");
+    mfx_index_info info;
+    if (mfx_index_get_info(ix, &info)) DIE_MFX("loading -hapmers");
+    norm[side] = info.distinct - held;
+    held = info.distinct;
+  }
+  const mfx_kparams kp{1.0, 0, nullptr, nullptr};                 // (no K* is evaluated: mfx_bin_* do not read them)
+  Owned<mfx_eval, mfx_eval_free> ev;
+  ev = mfx_eval_create(ix, &kp, 0);
+  if (!ev) DIE_MFX("creating evaluator");
+  const mfx_bin_opts o{norm[0], norm[1], G.binRatioMilli, G.binMinHits};
+  std::string stem = G.outName, zsuf;                           // out.gz -> out.bin.tsv.gz
+  if (mfx_suffix_tool(stem)) { const size_t dot = stem.rfind('.'); zsuf = stem.substr(dot); stem.resize(dot); }
+  fprintf(stderr, "-- Hap-mer counts of every read (A: %lu k-mers, B: %lu; ratio %u.%03u, at least %u hits) to '%s.bin.tsv%s'.\n", (unsigned long)norm[0],
+          (unsigned long)norm[1], G.binRatioMilli / 1000, G.binRatioMilli % 1000, G.binMinHits, stem.c_str(), zsuf.c_str());
+  static const char *const splitNames[3] = {".hapA.fasta", ".hapB.fasta", ".unknown.fasta"};
+  mfx_file tsv, split[3];
+  std::vector<std::string> outNames;
+  auto open_out = [&](mfx_file &fh, const std::string &name) {
+    outNames.push_back(name);
+    fh = mfx_open_writer(name.c_str(), false);
+    if (!fh.f) fprintf(stderr, "ERROR: cannot open '%s' for writing.\n", name.c_str());
+    return fh.f != nullptr;
+  };
+  bool ok = open_out(tsv, stem + ".bin.tsv" + zsuf);
+  for (int c = 0; ok && G.binSplit && c < 3; ++c) ok = open_out(split[c], stem + splitNames[c] + zsuf);
+  mfx_bin *bn = ok ? mfx_bin_begin(ev, (uint64_t)std::max(0, env_flag("MFX_BIN_BATCH"))) : nullptr;
+  if (ok && !bn) { fprintf(stderr, "ERROR: -bin: %s\n", mfx_last_error()); ok = false; }
+  if (ok) fprintf(tsv.f, "#read\tlength\tkmers\tA\tB\tshared\tclass\n");
+  struct Pending { std::string name, bases; uint64_t len; };
+  std::deque<Pending> pending;                                   // the records added and not yet taken, in input order
+  uint64_t cls_reads[3] = {0, 0, 0}, cls_bases[3] = {0, 0, 0}, cls_hits[3][4] = {{0}};
+  std::vector<mfx_bin_record> recs;
+  std::vector<uint8_t> cls;
+  double t_parse = 0, t_add = 0, t_write = 0;
+  auto now = []() { return std::chrono::steady_clock::now(); };
+  auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); };
+  auto drain = [&]() {                                           // what is final is taken, classified and written
+    const auto t0 = now();
+    uint64_t n = mfx_bin_ready(bn);
+    recs.resize((size_t)n);
+    cls.resize((size_t)n);
+    if (n && (mfx_bin_take(bn, recs.data(), n, &n) || mfx_bin_classify(recs.data(), n, &o, cls.data()))) {
+      fprintf(stderr, "ERROR: -bin: %s\n", mfx_last_error());
+      return false;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+      const Pending &p = pending.front();
+      const mfx_bin_record &r = recs[(size_t)i];
+      const int c = cls[(size_t)i];
+      fprintf(tsv.f, "%s\t%lu\t%u\t%u\t%u\t%u\t%c\n", p.name.c_str(), (unsigned long)p.len, r.kmers, r.a, r.b, r.shared, "ABU"[c]);
+      if (G.binSplit) {
+        fputc('>', split[c].f);
+        fwrite(p.name.data(), 1, p.name.size(), split[c].f);
+        fputc('\n', split[c].f);
+        fwrite(p.bases.data(), 1, p.bases.size(), split[c].f);
+        fputc('\n', split[c].f);
+      }
+      cls_reads[c]++;
+      cls_bases[c] += p.len;
+      cls_hits[c][0] += r.kmers; cls_hits[c][1] += r.a; cls_hits[c][2] += r.b; cls_hits[c][3] += r.shared;
+      pending.pop_front();
+    }
+    t_write += since(t0);
+    return true;
+  };
+  const uint64_t CHUNK_BASES = 32ull << 20, CHUNK_RECORDS = 1u << 16;
+  std::vector<SeqRecord> chunk;
+  std::vector<const char *> ptrs;
+  std::vector<uint64_t> lens;
+  auto submit = [&]() {
+    const auto t0 = now();
+    ptrs.resize(chunk.size());
+    lens.resize(chunk.size());
+    for (size_t i = 0; i < chunk.size(); ++i) { ptrs[i] = chunk[i].data(); lens[i] = chunk[i].size(); }
+    const int rc = mfx_bin_add(bn, ptrs.data(), lens.data(), (uint64_t)chunk.size());
+    t_add += since(t0);
+    if (rc) { fprintf(stderr, "ERROR: -bin: %s\n", mfx_last_error()); return false; }
+    for (SeqRecord &r : chunk) {
+      Pending p;
+      p.len = r.size();
+      p.name = std::move(r.name);
+      if (G.binSplit) p.bases.assign(r.data(), r.size());
+      pending.push_back(std::move(p));
+    }
+    chunk.clear();
+    return drain();
+  };
+  for (size_t f = 0; ok && f < G.readsNames.size(); ++f) {
+    fprintf(stderr, "-- Reading '%s'.\n", G.readsNames[f]);
+    SeqFile sf(G.readsNames[f]);
+    if (!sf.ok()) { fprintf(stderr, "ERROR: cannot open '%s'.\n", G.readsNames[f]); ok = false; break; }
+    uint64_t held_bases = 0;
+    auto t0 = now();
+    for (SeqRecord r; ok && sf.next(r); r = SeqRecord()) {
+      held_bases += r.size();
+      chunk.push_back(std::move(r));
+      if (held_bases >= CHUNK_BASES || chunk.size() >= CHUNK_RECORDS) {
+        t_parse += since(t0);
+        ok = submit();
+        held_bases = 0;
+        t0 = now();
+      }
+    }
+    t_parse += since(t0);
+    if (ok && sf.finish() != 0) {
+      fprintf(stderr, "ERROR: reading '%s' failed (read error, or the decompressor exited with an error: truncated or corrupt file?).\n", G.readsNames[f]);
+      ok = false;
+    }
+    if (ok) ok = submit();
+  }
+  if (ok && mfx_bin_flush(bn)) { fprintf(stderr, "ERROR: -bin: %s\n", mfx_last_error()); ok = false; }
+  if (ok) ok = drain();
+  mfx_bin_stats st{};
+  if (bn && mfx_bin_end(bn, &st) && ok) { fprintf(stderr, "ERROR: -bin: %s\n", mfx_last_error()); ok = false; }
+  if (ok && !pending.empty()) { fprintf(stderr, "ERROR: -bin: internal error: %zu records were never final.\n", pending.size()); ok = false; }
+  if (tsv.f && mfx_close(tsv) && ok) { fprintf(stderr, "ERROR: writing '%s' failed (stream error or the compressor exited with an error).\n", outNames[0].c_str()); ok = false; }
+  for (int c = 0; c < 3; ++c)
+    if (split[c].f && mfx_close(split[c]) && ok) {
+      fprintf(stderr, "ERROR: writing '%s' failed (stream error or the compressor exited with an error).\n", outNames[1 + c].c_str());
+      ok = false;
+    }
+  if (!ok) return 1;
+  {
+    const std::string name = stem + ".bin.stats" + zsuf;
+    mfx_file fh = mfx_open_writer(name.c_str(), false);
+    if (!fh.f) { fprintf(stderr, "ERROR: cannot open '%s' for writing.\n", name.c_str()); return 1; }
+    fprintf(fh.f, "#ratio\t%u.%03u\tminhits\t%u\tk\t%d\tnorm_A\t%lu\tnorm_B\t%lu\n", G.binRatioMilli / 1000, G.binRatioMilli % 1000, G.binMinHits, k, (unsigned long)norm[0],
+            (unsigned long)norm[1]);
+    fprintf(fh.f, "#class\treads\tbases\tkmers\tA\tB\tshared\n");
+    uint64_t all[6] = {0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 3; ++c) {
+      fprintf(fh.f, "%c\t%lu\t%lu\t%lu\t%lu\t%lu\t%lu\n", "ABU"[c], (unsigned long)cls_reads[c], (unsigned long)cls_bases[c], (unsigned long)cls_hits[c][0],
+              (unsigned long)cls_hits[c][1], (unsigned long)cls_hits[c][2], (unsigned long)cls_hits[c][3]);
+      all[0] += cls_reads[c]; all[1] += cls_bases[c];
+      for (int j = 0; j < 4; ++j) all[2 + j] += cls_hits[c][j];
+    }
+    fprintf(fh.f, "all\t%lu\t%lu\t%lu\t%lu\t%lu\t%lu\n", (unsigned long)all[0], (unsigned long)all[1], (unsigned long)all[2], (unsigned long)all[3], (unsigned long)all[4],
+            (unsigned long)all[5]);
+    if (mfx_close(fh)) { fprintf(stderr, "ERROR: writing '%s' failed (stream error or the compressor exited with an error).\n", name.c_str()); return 1; }
+  }
+  for (int c = 0; c < 3; ++c)
+    fprintf(stderr, "-- %s: %lu reads, %lu bases, %lu hits of A, %lu of B.\n", c == 0 ? "A" : c == 1 ? "B" : "unknown", (unsigned long)cls_reads[c], (unsigned long)cls_bases[c],
+            (unsigned long)cls_hits[c][1], (unsigned long)cls_hits[c][2]);
+  if (env_flag("MFX_CLI_TIMING") > 0)
+    fprintf(stderr, "-- bin: %.3f s parsing, %.3f s batching / packing / waiting for a stage, %.3f s classifying and writing; device %.3f s kernel + %.3f s copy\n", t_parse,
+            t_add, t_write, st.seconds_kernel, st.seconds_copy);
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
 static int report_hist(Run &R) {
   const Globals &G = R.G;
   fprintf(stderr, "-- Generate histogram of the k* metric to '%s'.\n", G.outName);
@@ -2006,6 +2174,12 @@ int main(int argc, char **argv) {
   Errors err;
   // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
   parse_args(argc, argv, G, err);
+  check_bin_flags(G, err);
+  if (bin_named(G)) {
+    if (!err.empty()) return fail_usage(argv[0], err, false, false, false, false, false, true);
+    if (!G.devices.empty()) G.device = G.devices[0];
+    return devices_available({G.device}) ? run_bin(G) : 1;
+  }
   check_phase_flags(G, err);
   if (phase_named(G)) {
     if (!err.empty()) return fail_usage(argv[0], err, false, false, false, true);

@@ -151,6 +151,19 @@ struct mfx_phase_args {
   uint64_t       *counts;             // [ncontigs][4] += valid k-mers, A markers, B markers, shared; zero at launch
 };
 
+// -bin (csrc/mfx_bin.h; mfx_bin_kernel, k <= 31): one batch of reads as mfx_reads_args has it, and the batch's pieces
+struct mfx_bin_args {
+  mfx_table_view  t;
+  int             canonical;
+  const uint64_t *codes;
+  const uint32_t *valid;
+  uint64_t        npos;               // base positions of the batch (separators included)
+  const uint64_t *piece_start;        // [npieces] first position of every piece, ascending
+  const uint64_t *tile_first;         // [tiles] the first piece that touches the tile (npieces: none)
+  uint64_t        npieces;
+  uint64_t       *out;                // [npieces][2] += k-mers | A only << 32, B only | shared << 32 (mfx_bin_record as two words); zero at launch
+};
+
 struct mfx_count_args {
   mfx_table_view  t;
   const uint8_t  *bases;
@@ -266,6 +279,7 @@ hipError_t mfx_k_rg_emit(const uint64_t *reg_first, const uint64_t *reg_last, co
                          uint64_t *regs, hipStream_t st);
 hipError_t mfx_k_rg_finish(uint64_t *regs, uint64_t nreg, hipStream_t st);        // word 6: key -> ext_kstar
 hipError_t mfx_k_phase_mark(const mfx_phase_args &a, hipStream_t st);          // k <= 31
+hipError_t mfx_k_bin(const mfx_bin_args &a, hipStream_t st);                   // k <= 31
 hipError_t mfx_kw_phase_mark(const mfx_phase_args &a, hipStream_t st);         // 32 <= k <= 64 (mfx_wide.hip)
 // pass 2 of -phase (mfx_phase.hip); the sums are mfx_k_rg_scan's, the bounds mfx_k_rg_bounds'
 size_t     mfx_k_ph_temp_bytes(uint64_t n);                                        // temporary storage any scan of n entries needs

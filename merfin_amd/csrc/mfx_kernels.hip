@@ -3447,6 +3447,150 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_phase_mark_kernel(mfx_phase_arg
 }
 
 // ===========================================================================
+// -bin (csrc/mfx_bin.h): a sibling of mfx_phase_mark_kernel -- its lookups, its canonical / non-canonical / even-k membership rule -- over
+// the tiles of one BATCH of reads (the planes of mfx_reads_kernel).  Every valid k-mer adds to the four counts of its PIECE (the part of
+// one read inside this batch): k-mers, in A only, in B only, in both.
+//
+// THE PIECE OF A POSITION.  The pieces ascend with the position and two of them are separated by an invalid base, so a valid k-mer lies
+// in the last piece that starts at or before it.  Per tile the block marks the starts of the pieces that start inside the tile as bits
+// of 64 words in LDS (s_bits) and one wave turns the words' popcounts into their exclusive prefix sums (s_pre); the piece of position p,
+// counted from the tile's first piece, is then  base + s_pre[p / 64] + popcount(s_bits[p / 64] up to bit p % 64) - 1  (base: the first
+// piece began in an earlier tile), two LDS reads.  It does not decrease with p, whether a tile holds one piece or MFX_TILE / (k + 1).
+//
+// THE REDUCTION is that of csrc/mfx_track.h: a lane sums in one register pair (four 16-bit fields: a lane sees 16 positions of a tile, a
+// wave 1024) while its piece stays the same; when a lane's piece changes the wave reduces by segments; the segments' head lanes add into
+// an LDS table when the tile touches at most MFX_BIN_LDS_PIECES pieces, and after the tile's last round one lane per (tile, piece) sends
+// two packed 64-bit adds to the batch's output; a tile of more pieces sends its heads' shares there directly.  Relaxed integer atomics
+// only: the sums are the same in any order.
+// ===========================================================================
+constexpr uint32_t MFX_BIN_LDS_PIECES = 64;
+static_assert(MFX_TILE == 64 * 64 && MFX_BLOCK == 256, "mfx_bin_kernel: a tile's piece starts are 64 words of 64 bits, one wave scans them");
+
+// the segmented reduction of mfx_trk_wave_reduce for one packed word: afterwards the first lane of every run of equal `win` holds the run's sum
+__device__ __forceinline__ bool mfx_bin_wave_reduce(uint64_t &acc, uint32_t win) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t off = 1; off < 64u; off <<= 1) {
+    const uint32_t ow = (uint32_t)__shfl_down((int)win, off, 64);
+    const uint64_t oa = __shfl_down(acc, off, 64);
+    if (lane + off < 64u && ow == win) acc += oa;
+  }
+  const uint32_t pw = (uint32_t)__shfl_up((int)win, 1, 64);
+  return lane == 0u || pw != win;
+}
+
+// the wave sends what its lanes hold for their pieces `win` (wave-wide call; lanes holding nothing take part with empty shares)
+__device__ __forceinline__ void mfx_bin_flush(uint64_t *out, uint64_t piece0, uint64_t npieces, bool use_lds, uint64_t (*T)[2], uint64_t &acc, uint32_t win) {
+  const bool head = mfx_bin_wave_reduce(acc, win);
+  if (head && (acc & 0xffffull)) {
+    const uint64_t w0 = (acc & 0xffffull) | (((acc >> 16) & 0xffffull) << 32), w1 = ((acc >> 32) & 0xffffull) | ((acc >> 48) << 32);
+    if (use_lds) {
+      unsigned long long *r = reinterpret_cast<unsigned long long *>(T[win]);
+      (void)__hip_atomic_fetch_add(r + 0, (unsigned long long)w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (w1) (void)__hip_atomic_fetch_add(r + 1, (unsigned long long)w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else if (piece0 + win < npieces) {                       // (always: a valid k-mer lies in a piece of the batch)
+      unsigned long long *r = reinterpret_cast<unsigned long long *>(out + 2ull * (piece0 + win));
+      (void)__hip_atomic_fetch_add(r + 0, (unsigned long long)w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (w1) (void)__hip_atomic_fetch_add(r + 1, (unsigned long long)w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  acc = 0ull;
+}
+
+template <bool CANON, bool COMPACT>
+__global__ __launch_bounds__(MFX_BLOCK) void mfx_bin_kernel(mfx_bin_args a) {
+  __shared__ mfx_tile_lds L;
+  __shared__ mfx_mailbox MB;
+  __shared__ uint64_t s_bits[64];                              // bit b of word w: a piece starts at position 64 w + b of the tile
+  __shared__ uint32_t s_pre[65];                               // pieces that start in the words before w; [64]: in the tile
+  __shared__ uint64_t T[MFX_BIN_LDS_PIECES][2];
+  const uint32_t tid = threadIdx.x;
+  const int k = a.t.k;
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (tid < MFX_BIN_LDS_PIECES) { T[tid][0] = 0ull; T[tid][1] = 0ull; }
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t pos0 = tile * MFX_TILE;
+    const uint32_t n = a.npos - pos0 < MFX_TILE ? (uint32_t)(a.npos - pos0) : MFX_TILE;
+    const uint64_t piece0 = a.tile_first[tile];                // block-uniform
+    const uint32_t base = (piece0 < a.npieces && a.piece_start[piece0] < pos0) ? 1u : 0u;
+    mfx_tile_fill_packed(L, a.codes + (pos0 >> 5), a.valid + (pos0 >> 5));
+    if (tid < 64u) s_bits[tid] = 0ull;
+    __syncthreads();                                           // the tile is in LDS, s_bits is clear; T is clear (kernel start / the tile before)
+    for (uint64_t q = piece0 + base + tid; q < a.npieces; q += MFX_BLOCK) {      // the pieces that start inside the tile
+      const uint64_t s = a.piece_start[q];
+      if (s >= pos0 + MFX_TILE) break;                         // (ascending: none of this lane's later pieces does)
+      if (s < pos0) continue;                                  // (never: piece0 is the first piece that ends behind pos0, the ones after it start behind it)
+      const uint32_t p = (uint32_t)(s - pos0);
+      (void)__hip_atomic_fetch_or(reinterpret_cast<unsigned long long *>(&s_bits[p >> 6]), 1ull << (p & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    if (tid < 64u) {                                           // one wave: exclusive prefix sums of the words' popcounts
+      const uint32_t c = (uint32_t)__popcll(s_bits[tid]);
+      uint32_t inc = c;
+#pragma unroll
+      for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
+        if (tid >= off) inc += o;
+      }
+      s_pre[tid] = inc - c;
+      if (tid == 63u) s_pre[64] = inc;
+    }
+    __syncthreads();
+    const bool use_lds = base + s_pre[64] <= MFX_BIN_LDS_PIECES;      // block-uniform
+    uint64_t acc = 0ull;
+    uint32_t cur = 0u;
+    for (uint32_t b = 0; b < MFX_TILE / MFX_BLOCK; b += MFX_BATCH) {
+      if (b * MFX_BLOCK >= n) break;                           // short last tile (block-uniform)
+      uint64_t key[MFX_BATCH], key2[MFX_BATCH];
+      uint32_t rv[MFX_BATCH], av[MFX_BATCH];
+      bool     ok[MFX_BATCH];
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;          // lane-consecutive positions
+        uint64_t f;
+        ok[j] = mfx_tile_kmer(L, k, p, f) && (p < n);
+        const uint64_t r = mfx_revcomp(f, k);
+        if (CANON) { key[j] = f < r ? f : r; key2[j] = f < r ? r : f; }
+        else { key[j] = f; key2[j] = r; }
+      }
+      if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key, key2, ok, rv, av);
+      else mfx_group_lookup<MFX_BATCH>(a.t, MB, key, key2, ok, rv, av);
+      if (!CANON) {
+        uint32_t rv2[MFX_BATCH], av2[MFX_BATCH];
+        if (COMPACT) MFX_COMPACT_LOOKUP(a.t, MB, key2, key, ok, rv2, av2);
+        else mfx_group_lookup<MFX_BATCH>(a.t, MB, key2, key, ok, rv2, av2);
+#pragma unroll
+        for (int j = 0; j < MFX_BATCH; ++j) { rv[j] |= rv2[j]; av[j] |= av2[j]; }      // (membership: "a sum > 0" without the sum's wrap)
+      }                                                        // (even k: a palindromic k-mer's doubled value is > 0 when the value is)
+#pragma unroll
+      for (int j = 0; j < MFX_BATCH; ++j) {
+        const uint32_t p = (b + j) * MFX_BLOCK + tid;
+        const uint64_t upto = s_bits[p >> 6] & (~0ull >> (63u - (p & 63u)));
+        const uint32_t started = base + s_pre[p >> 6] + (uint32_t)__popcll(upto);
+        const uint32_t win = started ? started - 1u : 0u;      // (no piece yet: the separator in front of the tile's first piece; it holds no k-mer)
+        if (__any(acc != 0ull && win != cur)) mfx_bin_flush(a.out, piece0, a.npieces, use_lds, T, acc, cur);
+        cur = win;
+        if (ok[j]) {
+          const bool inA = rv[j] != 0u, inB = av[j] != 0u;
+          acc += 1ull | (inA && !inB ? 1ull << 16 : 0ull) | (inB && !inA ? 1ull << 32 : 0ull) | (inA && inB ? 1ull << 48 : 0ull);
+        }
+      }
+    }
+    if (__any(acc != 0ull)) mfx_bin_flush(a.out, piece0, a.npieces, use_lds, T, acc, cur);
+    __syncthreads();                                           // every wave's shares of this tile are in T; the tile and its bits are consumed
+    if (use_lds && tid < MFX_BIN_LDS_PIECES && T[tid][0] != 0ull) {
+      if (piece0 + tid < a.npieces) {
+        unsigned long long *r = reinterpret_cast<unsigned long long *>(a.out + 2ull * (piece0 + tid));
+        (void)__hip_atomic_fetch_add(r + 0, (unsigned long long)T[tid][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (T[tid][1]) (void)__hip_atomic_fetch_add(r + 1, (unsigned long long)T[tid][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      T[tid][0] = 0ull;
+      T[tid][1] = 0ull;
+    }
+  }
+}
+
+// ===========================================================================
 // varMer::score on the device (varMer.C:66-144): one lane per alternative PATH of a batch of variant clusters.  The paths'
 // k-mers have been looked up by mfx_dump_kernel over the packed path text (readV / asmV per start position); this walks a
 // path's bases in order exactly as the reference does -- run length of valid bases, the k-mer ENDING at idx, readK / prob by
@@ -4370,6 +4514,16 @@ hipError_t mfx_k_phase_mark(const mfx_phase_args &a, hipStream_t st) {
   else if (a.canonical)           mfx_phase_mark_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else if (a.t.compact)           mfx_phase_mark_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
   else                            mfx_phase_mark_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  return hipGetLastError();
+}
+hipError_t mfx_k_bin(const mfx_bin_args &a, hipStream_t st) {
+  const uint64_t ntiles = (a.npos + MFX_TILE - 1) / MFX_TILE;
+  if (ntiles == 0 || a.npieces == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(ntiles < 8192 ? ntiles : 8192);
+  if (a.canonical && a.t.compact) mfx_bin_kernel<true, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.canonical)           mfx_bin_kernel<true, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else if (a.t.compact)           mfx_bin_kernel<false, true><<<blocks, MFX_BLOCK, 0, st>>>(a);
+  else                            mfx_bin_kernel<false, false><<<blocks, MFX_BLOCK, 0, st>>>(a);
   return hipGetLastError();
 }
 hipError_t mfx_k_regions_sums(const mfx_regions_args &a, hipStream_t st) {

@@ -18,6 +18,7 @@
 #include "mfx_internal.h"
 #include "mfx_kernels.h"
 #include "mfx_grow.h"
+#include "mfx_bin.h"
 
 #include <chrono>
 
@@ -29,7 +30,7 @@
 extern "C" void mfx_pack_bases(const uint8_t *src, uint64_t n, uint64_t *codes, uint32_t *valid);      // mfx_pack.cpp
 
 namespace {
-constexpr uint64_t MFX_READS_BATCH_DEFAULT = 1ull << 26;     // bases per batch: 24 MB of planes per stage
+constexpr uint64_t MFX_READS_BATCH_DEFAULT = MFX_BATCH_BASES_DEFAULT;
 constexpr int MFX_READS_STAGES = 2;
 constexpr uint64_t MFX_TILE_WORDS_HOST = (MFX_TILE + 64) / 32;        // words a tile reads (mfx_device.h: MFX_TILE_WORDS)
 
@@ -47,11 +48,7 @@ struct DeviceScope {
 // The bytes of the batch being filled.  batch_records copies records in, one 'N' between two; a record longer than the room left is cut and
 // its rest starts the next batch k-1 bases before the cut.  Whenever a batch is complete `flush` is called (it sends or keeps b.bytes[0, b.used)
 // and sets b.used = 0; non-zero: its error, passed on).  batch_pack turns such a batch into the planes a launch reads.
-struct Batch {
-  uint64_t cap = 0;                  // bases per batch
-  std::vector<uint8_t> bytes;
-  uint64_t used = 0;
-};
+typedef mfx_batch Batch;             // (csrc/mfx_bin.h: the cut is shared with -bin, which also asks for the pieces)
 
 // planes of npos bases in nw words each (nw >= (npos + 31) / 32): the words beyond the bases are invalid (the halo of the last tile)
 void batch_pack(const uint8_t *bytes, uint64_t npos, uint64_t nw, uint64_t *codes, uint32_t *valid) {
@@ -66,30 +63,9 @@ void batch_pack(const uint8_t *bytes, uint64_t npos, uint64_t nw, uint64_t *code
 template <class Flush>
 int batch_records(Batch &b, uint64_t k, const char *const *bases, const uint64_t *lens, uint64_t n, uint64_t &n_reads, uint64_t &n_bases, const char *who,
                   Flush &&flush) {
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t len = lens[i];
-    n_reads += 1;
-    n_bases += len;
-    if (len < k) continue;                                     // no k-mer
-    if (!bases[i]) return mfx_fail(MFX_E_INVAL, "%s: record %llu has no bases", who, (unsigned long long)i);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(bases[i]);
-    uint64_t at = 0;
-    while (true) {
-      if (b.cap - b.used < k) {                                // no whole k-mer fits: the batch goes
-        if (int rc = flush()) return rc;
-      }
-      const uint64_t take = std::min(len - at, b.cap - b.used);
-      memcpy(b.bytes.data() + b.used, src + at, take);
-      b.used += take;
-      if (at + take == len) {
-        if (b.used < b.cap) b.bytes[b.used++] = 'N';           // (a read that ends the batch needs no separator)
-        break;
-      }
-      at += take - (k - 1);                                    // the rest, from the first k-mer this batch does not hold
-      if (int rc = flush()) return rc;
-    }
-  }
-  return MFX_OK;
+  return mfx_batch_records(b, k, bases, lens, n, n_reads, n_bases,
+                           [&](uint64_t i) { return mfx_fail(MFX_E_INVAL, "%s: record %llu has no bases", who, (unsigned long long)i); }, flush,
+                           [](uint64_t, uint64_t, uint64_t, bool) {});
 }
 
 // the batch size both the counters and the store take; 0: refused (the text is set)
