@@ -371,6 +371,58 @@ void mfx_db_join_grain(uint32_t *per_lane, uint32_t *tile);
 int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *asm_keys, const uint32_t *asm_vals, uint64_t n_asm,
                      uint64_t *keys, uint32_t *readV, uint32_t *asmV, uint64_t cap, uint64_t *n_pairs);
 
+/* mfx_db_trio: the two hap-mer databases of a trio from the parents' databases, and optionally the child's, in one windowed pass with no
+ * intermediate file (what -phase and -bin take as -hapmers A B).  The inputs are what mfx_db_merge takes -- sorted, delta-coded flat files of
+ * one k <= 31 -- and share its windows (MFX_MERGE_RANGE), its pread loop, its block decode and its pairwise merge; the record's input travels
+ * through the merge in the two low bits of the key (csrc/mfx_trio.h).  With cm, cp, cc a k-mer's counts in mat, pat and child (0: absent) and
+ * the cutoffs tm, tp, tc >= 1:
+ *   set A (maternal):  cm >= tm and cp == 0 and (no child given or cc >= tc); the count written is min(cm, cc), cm without a child
+ *   set B (paternal):  cp >= tp and cm == 0 and (no child given or cc >= tc); min(cp, cc), or cp
+ * so out_a is byte for byte the file of mfx_db_merge_except([mat], [pat], X, minV = tm), mfx_db_merge([child], Y, minV = tc),
+ * mfx_db_merge([X, Y], out_a, INTERSECT), and out_b the same with the parents swapped.  Both outputs go through a streamed writer each;
+ * a second run gives the same bytes; on any failure neither out_a nor out_b exists and no spool stays.
+ * The histogram image: 3 rows of max_mult + 1 cells (max_mult as for mfx_spectrum_run: 4 to 65536), column m < max_mult the count m, the last
+ * column the counts >= max_mult.  Row 0: the k-mers with cp == 0, by cm; row 1: the k-mers with cm == 0, by cp; row 2: every child k-mer, by
+ * cc (all zero without a child).  It is made on the device with mfx_spectrum.h's bins (exact integer adds).
+ * A cutoff of 0 is automatic: mfx_spectrum_peak(row).valley of its row (mat: row 0, pat: row 1, child: row 2), after a first pass over the
+ * inputs that makes the image.  A row without a valley ends the call in MFX_E_NODATA, the text names the database and the cutoff to give
+ * instead, and nothing is written.  This rule -- parent-specific k-mers above the error valley of their own histogram, kept where the child
+ * holds them above its valley -- is this library's own, in the spirit of Merqury's hapmers.sh; it is UNVALIDATED against Merqury.
+ * Refused before any device is touched (MFX_E_INVAL / MFX_E_FORMAT, the text names the file): a null argument, an input form mfx_db_merge
+ * refuses, inputs of different k, an output that is an input, out_a and out_b the same file, cut_child != 0 without a child, max_mult out of
+ * bounds.  mat and pat may be the same file: two databases of no k-mers.  MFX_E_NOMEM names the buffers of a window and of both writers.
+ * img (may be NULL): filled when the first pass ran (stats->hist_pass), else left as it was.
+ * stats (may be NULL), all exact: the k-mers of each input, of both parents, of one parent alone, of one parent alone at or above its cutoff,
+ * the child's at or above tc, the k-mers written to A and to B, the windows that held blocks, the cutoffs used and whether each was
+ * automatic; seconds in pread + copy, decode, tag + merge, the histogram kernel, the classify kernels, the writers' appends, their close and
+ * the call (the kernels' own time only with MFX_DB_TIMING set, which waits for them per window). */
+typedef struct { uint32_t cut_mat, cut_pat, cut_child; /* 0: automatic */ uint32_t max_mult; int device; } mfx_db_trio_opts;
+typedef struct {
+  uint64_t n_mat, n_pat, n_child, n_both, n_mat_only, n_pat_only, n_mat_only_cut, n_pat_only_cut, n_child_cut, n_a, n_b, windows;
+  uint32_t cut_mat, cut_pat, cut_child, auto_mat, auto_pat, auto_child, hist_pass, reserved;
+  double   t_read, t_decode, t_merge, t_hist, t_classify, t_write, t_close, t_total;
+} mfx_db_trio_stats;
+int mfx_db_trio(const char *mat_path, const char *pat_path, const char *child_path /* may be NULL */, const char *out_a, const char *out_b, const mfx_db_trio_opts *o,
+                uint64_t *img /* may be NULL */, mfx_db_trio_stats *st /* may be NULL */);
+/* The image of the first pass alone: img[3 * (max_mult + 1)].  stats (may be NULL): the k-mers of the inputs, of both parents, of one alone,
+ * the windows and the times; the cutoffs and what depends on them stay 0.  The same inputs and refusals; nothing is written. */
+int mfx_db_trio_hist(const char *mat_path, const char *pat_path, const char *child_path /* may be NULL */, uint32_t max_mult, uint64_t *img, mfx_db_trio_stats *st, int device);
+/* `meryl histogram` of one sorted flat database (k <= 31), by the same pass with the file in the child's role: row[max_mult + 1], column
+ * m < max_mult the k-mers of count m, the last column those of max_mult and more; *n_kmers (may be NULL) = the sum of the row = the k-mers
+ * of the file.  The input forms and refusals of mfx_db_merge. */
+int mfx_db_histogram(const char *path, uint32_t max_mult, uint64_t *row, uint64_t *n_kmers, int device);
+/* Host only.  "count<TAB>k-mers", one line per non-zero cell, ascending; the overflow column is written as max_mult.  .gz / .bz2 / .xz
+ * names go through the compressed writers.  This is the two-column k-mer histogram GenomeScope reads (what `meryl histogram` prints);
+ * the layout is written from that description and UNVALIDATED against `meryl histogram`. */
+int mfx_db_histogram_write(const uint64_t *row, uint32_t max_mult, const char *path);
+/* Host only (tests, tools/native/trio_sanitize.cpp): the rule of csrc/mfx_trio.h -- tag, merge, head walk, class -- over three strictly
+ * ascending host runs, as the kernels run it.  has_child == 0: no child (n_child must be 0).  cut_* >= 1.  a_keys / a_vals hold n_mat,
+ * b_keys / b_vals n_pat records at the most; img[3 * (max_mult + 1)]; st: the counters (no times, no windows). */
+int mfx_db_trio_host(const uint64_t *mat_keys, const uint32_t *mat_vals, uint64_t n_mat, const uint64_t *pat_keys, const uint32_t *pat_vals, uint64_t n_pat,
+                     const uint64_t *child_keys, const uint32_t *child_vals, uint64_t n_child, int has_child, uint32_t cut_mat, uint32_t cut_pat, uint32_t cut_child,
+                     uint32_t max_mult, uint64_t *a_keys, uint32_t *a_vals, uint64_t *n_a, uint64_t *b_keys, uint32_t *b_vals, uint64_t *n_b, uint64_t *img,
+                     mfx_db_trio_stats *st);
+
 /* ------------------------------------------------------------------------ */
 /* Read k-mer counting: the read counts of a run straight from its reads     */
 /* (FASTA / FASTQ records), no k-mer database in between.                   */

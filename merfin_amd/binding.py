@@ -102,6 +102,7 @@ SYMBOLS = [
     "mfx_phase_from_planes_host",
     "mfx_bin_begin", "mfx_bin_add", "mfx_bin_flush", "mfx_bin_ready", "mfx_bin_take", "mfx_bin_end", "mfx_bin_classify", "mfx_bin_plan_host",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
+    "mfx_db_trio", "mfx_db_trio_hist", "mfx_db_histogram", "mfx_db_histogram_write", "mfx_db_trio_host",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
 
@@ -239,6 +240,13 @@ def load_library():
     L.mfx_db_join_grain.restype = None
     L.mfx_db_join_host.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                    C.c_uint64, u64p]
+    L.mfx_db_trio.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(DbTrioOpts), u64p, C.POINTER(DbTrioStats)]
+    L.mfx_db_trio_hist.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, u64p, C.POINTER(DbTrioStats), C.c_int]
+    L.mfx_db_histogram.argtypes = [C.c_char_p, C.c_uint32, u64p, u64p, C.c_int]
+    L.mfx_db_histogram_write.argtypes = [u64p, C.c_uint32, C.c_char_p]
+    L.mfx_db_trio_host.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, C.c_int,
+                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.POINTER(C.c_uint32), u64p, u64p, C.POINTER(C.c_uint32), u64p, u64p,
+                                   C.POINTER(DbTrioStats)]
     L.mfx_db_write_flat_placed.argtypes = [C.c_char_p, C.c_int, u64p, u32p, C.c_uint64]
     L.mfx_db_place_keys.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_int, C.c_int]
     L.mfx_index_load_db_multi.argtypes = [C.POINTER(vp), C.c_uint32, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64]
@@ -628,6 +636,87 @@ def db_join_host(read_keys, read_vals, asm_keys, asm_vals):
                                            keys.ctypes.data_as(u64p), orv.ctypes.data_as(u32p), oav.ctypes.data_as(u32p), cap, C.byref(n)))
     assert n.value <= cap
     return keys[:n.value], orv[:n.value], oav[:n.value]
+
+
+class DbTrioOpts(C.Structure):
+    _fields_ = [("cut_mat", C.c_uint32), ("cut_pat", C.c_uint32), ("cut_child", C.c_uint32), ("max_mult", C.c_uint32), ("device", C.c_int)]
+
+
+class DbTrioStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_mat", "n_pat", "n_child", "n_both", "n_mat_only", "n_pat_only", "n_mat_only_cut", "n_pat_only_cut", "n_child_cut", "n_a",
+                                          "n_b", "windows")] + \
+               [(n, C.c_uint32) for n in ("cut_mat", "cut_pat", "cut_child", "auto_mat", "auto_pat", "auto_child", "hist_pass", "reserved")] + \
+               [(n, C.c_double) for n in ("t_read", "t_decode", "t_merge", "t_hist", "t_classify", "t_write", "t_close", "t_total")]
+
+
+def _trio_stats(st):
+    return {name: (float if name.startswith("t_") else int)(getattr(st, name)) for name, _ in DbTrioStats._fields_ if name != "reserved"}
+
+
+def _enc(p):
+    return None if p is None else p.encode() if isinstance(p, str) else p
+
+
+def db_trio(mat, pat, child, out_a, out_b, cut_mat=0, cut_pat=0, cut_child=0, max_mult=10000, device=0, with_image=False):
+    """the two hap-mer databases of a trio (mfx_db_trio): out_a holds the k-mers of `mat` with a count of cut_mat or more that `pat` does not
+    hold -- and, with a child database, that the child holds cut_child times or more, with the smaller of the two counts --, out_b the same
+    with the parents swapped.  child None: parents alone.  A cutoff of 0 is read off the valley of its histogram row (spectrum_peak); a row
+    without one raises MfxError (E_NODATA).  The rule is this library's own and unvalidated against Merqury.  Returns the stats (k-mers of
+    the inputs, of both parents, of one alone, at or above the cutoffs, written to A and B, windows, the cutoffs used and whether each was
+    automatic, the time split); with_image: also the (3, max_mult + 1) histogram image, or None when no cutoff was automatic."""
+    o = DbTrioOpts(int(cut_mat), int(cut_pat), int(cut_child), int(max_mult), int(device))
+    st = DbTrioStats()
+    img = np.zeros((3, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    _check(load_library().mfx_db_trio(_enc(mat), _enc(pat), _enc(child), _enc(out_a), _enc(out_b), C.byref(o), img.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st)))
+    out = _trio_stats(st)
+    return (out, img if st.hist_pass else None) if with_image else out
+
+
+def db_trio_hist(mat, pat, child=None, max_mult=10000, device=0, with_stats=False):
+    """the histogram image of db_trio's first pass (mfx_db_trio_hist): (3, max_mult + 1) uint64 -- row 0 the k-mers `pat` does not hold by
+    their count in `mat`, row 1 the k-mers `mat` does not hold by their count in `pat`, row 2 every k-mer of `child` by its count (zeros
+    without one); the last column takes the counts of max_mult and more"""
+    st = DbTrioStats()
+    img = np.zeros((3, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    _check(load_library().mfx_db_trio_hist(_enc(mat), _enc(pat), _enc(child), int(max_mult), img.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st), int(device)))
+    return (img, _trio_stats(st)) if with_stats else img
+
+
+def db_histogram(path, max_mult=10000, device=0, with_count=False):
+    """the k-mer histogram of one sorted flat database (mfx_db_histogram; `meryl histogram`): max_mult + 1 uint64 cells, cell m the
+    k-mers of count m, the last those of max_mult and more; with_count: also the k-mers of the file"""
+    row = np.zeros(max(int(max_mult), 0) + 1, dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(load_library().mfx_db_histogram(_enc(path), int(max_mult), row.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), int(device)))
+    return (row, n.value) if with_count else row
+
+
+def db_histogram_write(row, path):
+    """a histogram row as text (mfx_db_histogram_write; host only): count, k-mers per non-zero cell -- the two columns GenomeScope reads;
+    .gz / .bz2 / .xz names are compressed.  Unvalidated against `meryl histogram`."""
+    row = np.ascontiguousarray(row, dtype=np.uint64)
+    _check(load_library().mfx_db_histogram_write(row.ctypes.data_as(C.POINTER(C.c_uint64)), len(row) - 1, _enc(path)))
+
+
+def db_trio_host(mat, pat, child, cut_mat, cut_pat, cut_child=1, max_mult=10000):
+    """db_trio's rule on the host (mfx_db_trio_host; csrc/mfx_trio.h as the kernels run it) over (k-mers, counts) pairs of ascending arrays;
+    child None: no child.  Returns ((A k-mers, A counts), (B k-mers, B counts), image, stats)."""
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    has_child = child is not None
+    arrs = []
+    for pair in (mat, pat, child if has_child else (np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint32))):
+        arrs.append((np.ascontiguousarray(pair[0], dtype=np.uint64), np.ascontiguousarray(pair[1], dtype=np.uint32)))
+    ak, av = np.zeros(max(len(arrs[0][0]), 1), dtype=np.uint64), np.zeros(max(len(arrs[0][0]), 1), dtype=np.uint32)
+    bk, bv = np.zeros(max(len(arrs[1][0]), 1), dtype=np.uint64), np.zeros(max(len(arrs[1][0]), 1), dtype=np.uint32)
+    img = np.zeros((3, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    na, nb, st = C.c_uint64(0), C.c_uint64(0), DbTrioStats()
+    args = []
+    for k_, v_ in arrs:
+        args += [k_.ctypes.data_as(u64p), v_.ctypes.data_as(u32p), len(k_)]
+    _check(load_library().mfx_db_trio_host(*args, 1 if has_child else 0, int(cut_mat), int(cut_pat), int(cut_child), int(max_mult), ak.ctypes.data_as(u64p),
+                                           av.ctypes.data_as(u32p), C.byref(na), bk.ctypes.data_as(u64p), bv.ctypes.data_as(u32p), C.byref(nb),
+                                           img.ctypes.data_as(u64p), C.byref(st)))
+    return (ak[:na.value], av[:na.value]), (bk[:nb.value], bv[:nb.value]), img, _trio_stats(st)
 
 
 def db_merge_plan(firsts, counts, k, R):

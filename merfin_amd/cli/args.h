@@ -53,6 +53,11 @@ struct Globals {
   uint32_t binRatioMilli = 1000, binMinHits = 1;   // -ratio (in thousandths) / -minhits of -bin
   bool ratioGiven = false, minhitsGiven = false, binSplit = false;      // -split: the reads themselves written per class
   bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
+  bool trio = false;                     // -trio: no report; the two hap-mer databases of -mat / -pat [/ -child] in one pass (mfx_db_trio)
+  const char *matName = nullptr, *patName = nullptr, *childName = nullptr;
+  uint32_t cutMat = 0, cutPat = 0, cutChild = 0;      // -cutmat / -cutpat / -cutchild of -trio; 0: auto (the valley of the k-mer histogram)
+  bool cutMatGiven = false, cutPatGiven = false, cutChildGiven = false;
+  const char *histName = nullptr;        // -histogram db: no report; the k-mer histogram of a sorted database (mfx_db_histogram)
 };
 
 typedef std::vector<std::string> Errors;
@@ -194,9 +199,30 @@ static void usage_bin() {
           "\n");
 }
 
+// the entries of -trio and -histogram: printed behind the text above for a command line that names one of their flags
+static void usage_trio() {
+  fprintf(stderr,
+          "  Hap-mer databases of a trio, and k-mer histograms (operations of their own: no -sequence, no -readmers, no -peak):\n"
+          "    -trio             the k-mers of -mat that -pat does not hold -> <output>.hapA.mfxk, those of -pat that -mat does not hold ->\n"
+          "                      <output>.hapB.mfxk (what -phase and -bin take as -hapmers), each k-mer with a count of its cutoff or more;\n"
+          "                      with -child only the k-mers the child holds, with the smaller of the two counts.  One windowed pass over the\n"
+          "                      sorted flat databases (what -count and -convert write; one k <= 31) on the GPU, no intermediate file; the\n"
+          "                      counters -> <output>.trio.stats.  One device.  The rule is this program's own, in the spirit of Merqury's\n"
+          "                      hapmers.sh; it is not validated against Merqury.\n"
+          "    -mat db / -pat db the parents' databases;  -child db  the child's (optional)\n"
+          "    -cutmat n|auto    -cutpat, -cutchild likewise: the smallest count kept, 1 or more (k-mers below it are taken for sequencing\n"
+          "                      errors); auto (the default): the first valley of the database's k-mer histogram, made on the GPU in a pass\n"
+          "                      before -- of the k-mers the other parent does not hold for -mat and -pat -- and written to\n"
+          "                      <output>.mat_only.hist, <output>.pat_only.hist and <output>.child.hist\n"
+          "    -histogram db     the k-mer histogram of a sorted flat database (`meryl histogram`) -> -output <file>: count, k-mers per line,\n"
+          "                      the form GenomeScope reads; valley and peaks on stderr.  An <output> ending in .gz / .bz2 / .xz is compressed.\n"
+          "    -maxmult M        with -trio and -histogram: counts of M and more share the last line (4 to 65536, default 10000)\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
 static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false, bool phase = false, bool nots = false,
-                      bool bin = false) {
+                      bool bin = false, bool trio = false) {
   usage(argv0);
   if (merge) usage_merge();
   if (nots) usage_not();
@@ -204,6 +230,7 @@ static int fail_usage(const char *argv0, const Errors &err, bool merge = false, 
   if (regions) usage_regions();
   if (phase) usage_phase();
   if (bin) usage_bin();
+  if (trio) usage_trio();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -397,6 +424,22 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
       G.minhitsGiven = true;
       if (parse_uint(v, 0, 0xffffffffull, &x) != UINT_OK) err.push_back(std::string("Invalid -minhits '") + v + "': -minhits is a number of k-mers, an integer from 0 to 4294967295.\n");
       else G.binMinHits = (uint32_t)x;
+    }
+    else if (is("-trio")) G.trio = true;
+    else if (is("-mat")) G.matName = val();
+    else if (is("-pat")) G.patName = val();
+    else if (is("-child")) G.childName = val();
+    else if (is("-histogram")) G.histName = val();
+    else if (is("-cutmat") || is("-cutpat") || is("-cutchild")) {
+      const std::string flag = argv[arg];
+      const int which = flag == "-cutmat" ? 0 : flag == "-cutpat" ? 1 : 2;
+      const char *v = val();
+      (which == 0 ? G.cutMatGiven : which == 1 ? G.cutPatGiven : G.cutChildGiven) = true;
+      uint32_t &cut = which == 0 ? G.cutMat : which == 1 ? G.cutPat : G.cutChild;
+      if (strcmp(v, "auto") == 0) cut = 0;
+      else if (parse_uint(v, 1, 0xffffffffull, &x) != UINT_OK)
+        err.push_back("Invalid " + flag + " '" + v + "': a cutoff of -trio is a count from 1 to 4294967295, or auto.\n");
+      else cut = (uint32_t)x;
     }
     else if (is("-skipMissing")) G.skipMissing = true;
     else if (is("-completeness")) G.reportType = OP_COMPL;
@@ -615,6 +658,56 @@ static void check_bin_flags(const Globals &G, Errors &err) {
         err.push_back("-bin holds k <= 31 (here k = " + std::to_string(a.k) + "): hap-mer databases of larger k-mers are not binned.\n");
       if (oka && okb && G.kArg > 0 && G.kArg != a.k) err.push_back("-k " + std::to_string(G.kArg) + " disagrees with -hapmers, which hold " + std::to_string(a.k) + "-mers.\n");
     }
+  }
+}
+
+// -trio and -histogram: every check before any device is touched (what the databases hold is checked by mfx_db_trio / mfx_db_histogram,
+// before they touch one)
+static bool trio_named(const Globals &G) {
+  return G.trio || G.matName || G.patName || G.childName || G.cutMatGiven || G.cutPatGiven || G.cutChildGiven || G.histName;
+}
+static void check_trio_flags(const Globals &G, Errors &err) {
+  if (!trio_named(G)) return;
+  const char *me = G.trio || !G.histName ? "-trio" : "-histogram";
+  if (G.trio && G.histName) err.push_back("-trio and -histogram are two operations: give one of them.\n");
+  if (!G.trio && !G.histName) {
+    if (G.matName) err.push_back("-mat names the maternal database of -trio; it has no meaning without -trio.\n");
+    if (G.patName) err.push_back("-pat names the paternal database of -trio; it has no meaning without -trio.\n");
+    if (G.childName) err.push_back("-child names the child's database of -trio; it has no meaning without -trio.\n");
+    if (G.cutMatGiven || G.cutPatGiven || G.cutChildGiven) err.push_back("-cutmat, -cutpat and -cutchild set the cutoffs of -trio; they have no meaning without -trio.\n");
+    return;
+  }
+  if (G.reportType != OP_NONE) err.push_back(std::string(me) + " is an operation of its own: it does not take a report type (-hist, -dump, -completeness, -spectrum, ...).\n");
+  if (G.count || G.convertName || !G.mergeNames.empty() || G.phase || G.bin)
+    err.push_back(std::string(me) + ", -bin, -phase, -count, -convert and -merge are separate operations: give one of them.\n");
+  if (G.join) err.push_back(std::string("-join is a way to run -completeness and -spectrum: ") + me + " does not take it.\n");
+  if (G.readDBname) err.push_back(std::string(me) + " takes its databases by flags of its own: it does not take -readmers.\n");
+  if (G.seqDBname) err.push_back(std::string(me) + " takes its databases by flags of its own: it does not take -seqmers.\n");
+  if (G.seqName) err.push_back(std::string(me) + " evaluates nothing: it does not take -sequence.\n");
+  if (!G.readsNames.empty()) err.push_back(std::string(me) + " reads databases: it does not take -reads (count them first: -count).\n");
+  if (G.peakGiven) err.push_back(std::string(me) + " evaluates no K*: it does not take -peak.\n");
+  if (G.vcfName) err.push_back(std::string(me) + " does not take -vcf (the variant modes do).\n");
+  if (G.sharded) err.push_back(std::string(me) + " does not take -sharded: the windows it reads live on one device.\n");
+  if (G.indexName) err.push_back(std::string(me) + " does not take -index: it builds no table.\n");
+  if (G.copiesGiven) err.push_back(std::string("-copies shapes the image of -spectrum: ") + me + " does not take it.\n");
+  if (G.devices.size() > 1) err.push_back(std::string(me) + " runs on one device (-device d, or -devices naming one).\n");
+  if (G.trio) {
+    if (!G.matName) err.push_back("-trio needs the maternal database: give -mat <file>.\n");
+    if (!G.patName) err.push_back("-trio needs the paternal database: give -pat <file>.\n");
+    if (!G.outName) err.push_back("-trio writes <output>.hapA.mfxk and <output>.hapB.mfxk: give -output <stem>.\n");
+    if (G.cutChildGiven && !G.childName) err.push_back("-cutchild sets the cutoff of the child's database: it has no meaning without -child.\n");
+    const char *const names[3] = {G.matName, G.patName, G.childName};
+    const char *const flags[3] = {"-mat", "-pat", "-child"};
+    for (int i = 0; i < 3; ++i) {
+      struct stat mst;
+      if (names[i] && (stat(names[i], &mst) != 0 || access(names[i], R_OK) != 0)) err.push_back(std::string("Cannot read the ") + flags[i] + " database '" + names[i] + "'.\n");
+    }
+  } else {
+    if (G.matName || G.patName || G.childName || G.cutMatGiven || G.cutPatGiven || G.cutChildGiven)
+      err.push_back("-mat, -pat, -child and the cutoffs belong to -trio: -histogram takes one database, -histogram <file>.\n");
+    if (!G.outName) err.push_back("-histogram writes a k-mer histogram: give -output <file>.\n");
+    struct stat mst;
+    if (stat(G.histName, &mst) != 0 || access(G.histName, R_OK) != 0) err.push_back(std::string("Cannot read the -histogram database '") + G.histName + "'.\n");
   }
 }
 

@@ -1057,6 +1057,62 @@ static int run_merge(Globals &G) {
   return 0;
 }
 
+// merfin -trio -mat m -pat p [-child c] -output stem: the two hap-mer databases in one windowed pass on the GPU (mfx_db_trio); a cutoff that
+// is not given is read off the valley of its k-mer histogram, which is then written beside the databases
+static int run_trio(Globals &G) {
+  const std::string stem = G.outName, out_a = stem + ".hapA.mfxk", out_b = stem + ".hapB.mfxk";
+  fprintf(stderr, "-- Hap-mers of '%s' (A) and '%s' (B)%s%s%s into '%s' and '%s'.\n", G.matName, G.patName, G.childName ? ", kept where '" : "", G.childName ? G.childName : "",
+          G.childName ? "' holds them," : "", out_a.c_str(), out_b.c_str());
+  mfx_db_trio_opts o;
+  o.cut_mat = G.cutMat; o.cut_pat = G.cutPat; o.cut_child = G.childName ? G.cutChild : 0;
+  o.max_mult = G.maxMult;
+  o.device = G.device;
+  const size_t W = (size_t)G.maxMult + 1;
+  std::vector<uint64_t> img(3 * W, 0);
+  mfx_db_trio_stats st;
+  if (mfx_db_trio(G.matName, G.patName, G.childName, out_a.c_str(), out_b.c_str(), &o, img.data(), &st)) DIE_MFX("-trio");
+  if (st.hist_pass) {
+    static const char *const rows[3] = {".mat_only.hist", ".pat_only.hist", ".child.hist"};
+    for (int r = 0; r < (G.childName ? 3 : 2); ++r)
+      if (mfx_db_histogram_write(img.data() + r * W, G.maxMult, (stem + rows[r]).c_str())) DIE_MFX("-trio");
+  }
+  const std::string sname = stem + ".trio.stats";
+  FILE *f = fopen(sname.c_str(), "w");
+  if (!f) { fprintf(stderr, "ERROR: -trio: cannot open '%s' for writing\n", sname.c_str()); return 1; }
+  const std::pair<const char *, unsigned long long> lines[] = {
+      {"mat_kmers", st.n_mat}, {"pat_kmers", st.n_pat}, {"child_kmers", st.n_child}, {"both_parents", st.n_both}, {"mat_only", st.n_mat_only}, {"pat_only", st.n_pat_only},
+      {"mat_only_at_cutoff", st.n_mat_only_cut}, {"pat_only_at_cutoff", st.n_pat_only_cut}, {"child_at_cutoff", st.n_child_cut}, {"hapA_kmers", st.n_a},
+      {"hapB_kmers", st.n_b}, {"windows", st.windows}, {"cut_mat", st.cut_mat}, {"cut_mat_auto", st.auto_mat}, {"cut_pat", st.cut_pat}, {"cut_pat_auto", st.auto_pat},
+      {"cut_child", st.cut_child}, {"cut_child_auto", st.auto_child}};
+  for (const auto &l : lines) fprintf(f, "%s\t%llu\n", l.first, l.second);
+  if (fclose(f) != 0) { fprintf(stderr, "ERROR: -trio: writing '%s' failed\n", sname.c_str()); return 1; }
+  fprintf(stderr, "-- Cutoffs: mat %u%s, pat %u%s", st.cut_mat, st.auto_mat ? " (auto)" : "", st.cut_pat, st.auto_pat ? " (auto)" : "");
+  if (G.childName) fprintf(stderr, ", child %u%s", st.cut_child, st.auto_child ? " (auto)" : "");
+  fprintf(stderr, ".\n-- %lu k-mers of both parents, %lu of mat alone (%lu at the cutoff), %lu of pat alone (%lu), %lu window%s.\n", (unsigned long)st.n_both,
+          (unsigned long)st.n_mat_only, (unsigned long)st.n_mat_only_cut, (unsigned long)st.n_pat_only, (unsigned long)st.n_pat_only_cut, (unsigned long)st.windows,
+          st.windows == 1 ? "" : "s");
+  print_wrote(out_a.c_str(), st.n_a);
+  print_wrote(out_b.c_str(), st.n_b);
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
+// merfin -histogram db -output file: `meryl histogram` of a sorted flat database on the GPU (mfx_db_histogram), and what mfx_spectrum_peak reads off it
+static int run_histogram(Globals &G) {
+  fprintf(stderr, "-- K-mer histogram of '%s' into '%s'.\n", G.histName, G.outName);
+  std::vector<uint64_t> row((size_t)G.maxMult + 1, 0);
+  uint64_t n = 0;
+  if (mfx_db_histogram(G.histName, G.maxMult, row.data(), &n, G.device)) DIE_MFX("-histogram");
+  if (mfx_db_histogram_write(row.data(), G.maxMult, G.outName)) DIE_MFX("-histogram");
+  mfx_spectrum_peak_t pk;
+  const int rc = mfx_spectrum_peak(row.data(), G.maxMult, &pk);
+  if (rc == MFX_OK) fprintf(stderr, "-- %lu k-mers; valley %u, main_peak %u, haploid_peak %u.\n", (unsigned long)n, pk.valley, pk.main_peak, pk.haploid_peak);
+  else if (rc == MFX_E_NODATA) fprintf(stderr, "-- %lu k-mers; no peak found.\n", (unsigned long)n);
+  else DIE_MFX("-histogram");
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
 // ---- the run of a report: what its steps share ------------------------------------------------------------------------------------------
 static double epoch() { return std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count(); }
 
@@ -2174,6 +2230,13 @@ int main(int argc, char **argv) {
   Errors err;
   // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
   parse_args(argc, argv, G, err);
+  check_trio_flags(G, err);
+  if (trio_named(G)) {
+    if (!err.empty()) return fail_usage(argv[0], err, false, false, false, false, false, false, true);
+    if (!G.devices.empty()) G.device = G.devices[0];
+    if (!devices_available({G.device})) return 1;
+    return G.trio ? run_trio(G) : run_histogram(G);
+  }
   check_bin_flags(G, err);
   if (bin_named(G)) {
     if (!err.empty()) return fail_usage(argv[0], err, false, false, false, false, false, true);

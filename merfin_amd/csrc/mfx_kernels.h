@@ -349,5 +349,15 @@ hipError_t mfx_k_join_completeness(const uint64_t *ka, const uint32_t *va, uint6
                                    uint32_t n_prob, const uint32_t *probK, const double *probP, double *pieces, uint64_t *stats, int grid, hipStream_t st);
 hipError_t mfx_k_join_spectrum(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, const mfx_spectrum_args &a,
                                uint64_t minV, uint64_t maxV, uint64_t *stats, int grid, hipStream_t st);
+// mfx_db_trio, mfx_db_trio_hist, mfx_db_histogram (mfx_trio.hip; the rule: mfx_trio.h).  tag: the role into the two low bits of an input's decoded
+// k-mers, in place.  hist: the three rows of a tagged merged run into a.img (a.copies == 1: 3 rows and the counter word, added to).  classify: the
+// two hap-mer sets of a tagged merged run, ascending and dense, behind a_keys / b_keys; tile_off: 2 * (mfx_trio_tiles(n) + 1) words, the last two
+// end as the k-mers written to A and to B; stats: MFX_TRIO_STAT_WORDS words (copies of the MFX_TRIO_S_* counters, mfx_trio.h), added to.
+struct mfx_trio_cuts;
+hipError_t mfx_k_trio_tag(uint64_t *keys, uint64_t n, uint32_t role, hipStream_t st);
+hipError_t mfx_k_trio_hist(const uint64_t *keys, const uint32_t *vals, uint64_t n, const mfx_spectrum_args &a, int grid, hipStream_t st);
+uint64_t mfx_trio_tiles(uint64_t n);
+hipError_t mfx_k_trio_classify(const uint64_t *keys, const uint32_t *vals, uint64_t n, const mfx_trio_cuts &cuts, uint64_t *tile_off, uint64_t *a_keys, uint32_t *a_vals,
+                               uint64_t *b_keys, uint32_t *b_vals, uint64_t *stats, hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);
