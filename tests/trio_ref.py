@@ -44,10 +44,10 @@ def reference(mat, pat, child, tm, tp, tc=1, max_mult=10000):
     return (u[in_a], va), (u[in_b], vb), image(cm, cp, cc, max_mult), st
 
 
-def sets(k, sizes, seed, lo=1, hi=5):
-    """databases of these sizes drawn from one pool of 30 000 k-mers, so that every membership pattern occurs; counts lo .. hi - 1"""
+def sets(k, sizes, seed, lo=1, hi=5, pool=30000):
+    """databases of these sizes drawn from one pool of `pool` k-mers, so that every membership pattern occurs; counts lo .. hi - 1"""
     rng = np.random.default_rng(seed)
-    pool = sw.random_keys(k, 30000, seed)
+    pool = sw.random_keys(k, pool, seed)
     out = []
     for n in sizes:
         keys = np.sort(rng.choice(pool, size=n, replace=False)) if n else np.zeros(0, dtype=np.uint64)
