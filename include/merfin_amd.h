@@ -371,6 +371,52 @@ void mfx_db_join_grain(uint32_t *per_lane, uint32_t *tile);
 int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *asm_keys, const uint32_t *asm_vals, uint64_t n_asm,
                      uint64_t *keys, uint32_t *readV, uint32_t *asmV, uint64_t cap, uint64_t *n_pairs);
 
+/* mfx_db_diploid: TWO haplotype assemblies against the reads in one windowed pass over three sorted flat databases, ending in reductions
+ * only: no table, no sort, no intermediate file, device memory holds one window (MFX_MERGE_RANGE).  It replaces the chain mfx_db_merge
+ * ([hap1, hap2]) + three mfx_db_join_completeness + one mfx_db_join_spectrum, which reads the read database four times, and adds what that
+ * chain cannot give: the class of a k-mer by which assembly holds it.  The rule is csrc/mfx_diploid.h, the kernels csrc/mfx_diploid.hip: the
+ * two assemblies' runs are tagged, merged and compacted into one run of (k-mer, c1, c2), against which the read run is joined by
+ * mfx_join_kernel; the read run is read once.
+ * For every distinct k-mer of the union: r its raw read count (0: absent), rf = r where minV <= r <= maxV and else 0, c1 / c2 its counts in
+ * hap1 / hap2, cb = min(c1 + c2, 2^32 - 1) (what mfx_db_merge writes with MFX_MERGE_SUM).
+ *   asm_img   the class image (spectra-asm): 4 rows of max_mult + 1 cells, column min(rf, max_mult); row 0 read-only (c1 == c2 == 0), row 1
+ *             hap1-only, row 2 hap2-only, row 3 shared; a k-mer with rf == 0 and cb == 0 is no entry
+ *   cn_img    (copies + 2) rows of max_mult + 1 cells and *n_entries: cell for cell what mfx_db_join_spectrum(reads, M) gives for
+ *             M = mfx_db_merge([hap1, hap2], SUM); the column sums of the two images are equal
+ *   stats     per X in hap1, hap2, both (cX = c1, c2, cb): distinct = the k-mers with cX > 0, total = the sum of cX, only_distinct /
+ *             only_total = the same over the k-mers with r == 0 (the RAW count: minV / maxV do not apply), found = the k-mers with rf > 0
+ *             and cX > 0; solid = the k-mers with rf > 0; n_read, n_hap1, n_hap2 the k-mers of the inputs, n_shared those of both
+ *             assemblies, windows; seconds in pread + copy, decode, tag + merge + pair run, launching the join (the kernels' own time only
+ *             with MFX_DB_TIMING set, which waits per window) and in the call.  All counters are exact.
+ *   total64[64], undrcpy64[3 * 64] (computed iff both are given): merfin's completeness sums as mfx_db_join_completeness defines them, for
+ *             hap1, hap2 and M -- the same doubles as three calls of it (the total does not depend on the assembly); peak, n_prob, probK,
+ *             probP as there.
+ * QV of X: mfx_histoQV(only_total, total) (merfin-histogram.C:22-31); k-mer completeness of X: found / solid.  Both follow Merqury's QV and
+ * completeness in spirit and are UNVALIDATED against Merqury; the distinct and the total counts are both given, so that a reader can apply
+ * the other convention.
+ * The inputs and refusals are mfx_db_merge's (sorted delta-coded flat files of one k <= 31), all before any device is touched; also refused:
+ * copies / max_mult outside mfx_spectrum_run's bounds, null outputs, exactly one of total64 / undrcpy64.  hap1 and hap2 may be the same
+ * file; a file of no k-mers is valid in any role.  distinct of hap1 / hap2 is checked against n_hap1 / n_hap2, the images against their
+ * entry counters (MFX_E_HIP).  On every failure the outputs are left as they were. */
+typedef struct { uint64_t distinct, total, only_distinct, only_total, found; } mfx_diploid_counts;
+typedef struct {
+  mfx_diploid_counts hap1, hap2, both;
+  uint64_t solid, n_read, n_hap1, n_hap2, n_shared, windows;
+  double   t_read, t_decode, t_pair, t_join, t_total;
+} mfx_db_diploid_stats;
+int mfx_db_diploid(const char *read_path, const char *hap1_path, const char *hap2_path, const mfx_db_join_opts *o, uint64_t *asm_img, uint64_t *cn_img,
+                   uint64_t *n_entries, mfx_db_diploid_stats *st, double *total64 /* may be NULL */, double *undrcpy64 /* [3 * 64], may be NULL */);
+/* Host only (tests, tools/native/diploid_sanitize.cpp): the text the kernels run -- tag, merge, head compaction, the tiled lane walk, the
+ * rule -- over three strictly ascending host runs of k-mers of length k.  One (k-mer, r, c1, c2) per distinct k-mer in the order the lanes
+ * meet them: at most cap are stored, *n_kmers counts them all.  Images, counters (no times; windows 0) and piece sums as above. */
+int mfx_db_diploid_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *hap1_keys, const uint32_t *hap1_vals, uint64_t n_hap1,
+                        const uint64_t *hap2_keys, const uint32_t *hap2_vals, uint64_t n_hap2, int k, const mfx_db_join_opts *o, uint64_t *keys, uint32_t *readV,
+                        uint32_t *c1V, uint32_t *c2V, uint64_t cap, uint64_t *n_kmers, uint64_t *asm_img, uint64_t *cn_img, uint64_t *n_entries,
+                        mfx_db_diploid_stats *st, double *total64 /* may be NULL */, double *undrcpy64 /* may be NULL */);
+/* Host only.  The class image as text: "Assembly<TAB>kmer_multiplicity<TAB>Count", the rows labelled read-only, hap1-only, hap2-only,
+ * shared, one line per non-zero cell; .gz / .bz2 / .xz names go through the compressed writers (as mfx_spectrum_write). */
+int mfx_diploid_write_asm(const uint64_t *img, uint32_t max_mult, const char *path);
+
 /* mfx_db_trio: the two hap-mer databases of a trio from the parents' databases, and optionally the child's, in one windowed pass with no
  * intermediate file (what -phase and -bin take as -hapmers A B).  The inputs are what mfx_db_merge takes -- sorted, delta-coded flat files of
  * one k <= 31 -- and share its windows (MFX_MERGE_RANGE), its pread loop, its block decode and its pairwise merge; the record's input travels

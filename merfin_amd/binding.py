@@ -103,6 +103,7 @@ SYMBOLS = [
     "mfx_bin_begin", "mfx_bin_add", "mfx_bin_flush", "mfx_bin_ready", "mfx_bin_take", "mfx_bin_end", "mfx_bin_classify", "mfx_bin_plan_host",
     "mfx_spectrum_run", "mfx_spectrum_peak", "mfx_spectrum_write", "mfx_diag_spectrum_time",
     "mfx_db_trio", "mfx_db_trio_hist", "mfx_db_histogram", "mfx_db_histogram_write", "mfx_db_trio_host",
+    "mfx_db_diploid", "mfx_db_diploid_host", "mfx_diploid_write_asm",
     "mfx_debug_traverse_host", "mfx_debug_score_paths", "mfx_debug_score_paths_trv",
 ]
 
@@ -247,6 +248,11 @@ def load_library():
     L.mfx_db_trio_host.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, C.c_int,
                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.POINTER(C.c_uint32), u64p, u64p, C.POINTER(C.c_uint32), u64p, u64p,
                                    C.POINTER(DbTrioStats)]
+    L.mfx_db_diploid.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(DbJoinOpts), u64p, u64p, u64p, C.POINTER(DbDiploidStats), f64p, f64p]
+    L.mfx_db_diploid_host.argtypes = [u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint64, C.c_int,
+                                      C.POINTER(DbJoinOpts), u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, u64p, u64p, u64p, u64p,
+                                      C.POINTER(DbDiploidStats), f64p, f64p]
+    L.mfx_diploid_write_asm.argtypes = [u64p, C.c_uint32, C.c_char_p]
     L.mfx_db_write_flat_placed.argtypes = [C.c_char_p, C.c_int, u64p, u32p, C.c_uint64]
     L.mfx_db_place_keys.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_int, C.c_int]
     L.mfx_index_load_db_multi.argtypes = [C.POINTER(vp), C.c_uint32, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64]
@@ -636,6 +642,96 @@ def db_join_host(read_keys, read_vals, asm_keys, asm_vals):
                                            keys.ctypes.data_as(u64p), orv.ctypes.data_as(u32p), oav.ctypes.data_as(u32p), cap, C.byref(n)))
     assert n.value <= cap
     return keys[:n.value], orv[:n.value], oav[:n.value]
+
+
+class DiploidCounts(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("distinct", "total", "only_distinct", "only_total", "found")]
+
+
+class DbDiploidStats(C.Structure):
+    _fields_ = [(n, DiploidCounts) for n in ("hap1", "hap2", "both")] + [(n, C.c_uint64) for n in ("solid", "n_read", "n_hap1", "n_hap2", "n_shared", "windows")] + \
+               [(n, C.c_double) for n in ("t_read", "t_decode", "t_pair", "t_join", "t_total")]
+
+
+DIPLOID_CLASSES = ("read-only", "hap1-only", "hap2-only", "shared")      # the rows of the class image
+
+
+def _diploid_stats(st):
+    out = {}
+    for name, typ in DbDiploidStats._fields_:
+        v = getattr(st, name)
+        out[name] = {f: int(getattr(v, f)) for f, _ in DiploidCounts._fields_} if typ is DiploidCounts else (float if name.startswith("t_") else int)(v)
+    return out
+
+
+def _diploid_opts(kparams, copies, max_mult, min_count, max_count, device):
+    kp = None if kparams is None else kparams if isinstance(kparams, KParams) else KParams(kparams)
+    if kp is None:
+        return DbJoinOpts(int(device), int(min_count), int(max_count), 0.0, 0, None, None, int(copies), int(max_mult)), None
+    return DbJoinOpts(int(device), int(min_count), int(max_count), kp.peak, len(kp.probK), kp.probK.ctypes.data_as(C.POINTER(C.c_uint32)),
+                      kp.probP.ctypes.data_as(C.POINTER(C.c_double)), int(copies), int(max_mult)), kp
+
+
+def _diploid_result(asm_img, cn_img, n, st, t, u):
+    out = {"asm_img": asm_img, "cn_img": cn_img, "n_entries": int(n.value), "stats": _diploid_stats(st)}
+    if t is not None:
+        out["total"], out["undrcpy"] = t, u
+    return out
+
+
+def db_diploid(read_path, hap1_path, hap2_path, copies=4, max_mult=10000, min_count=0, max_count=2**32 - 1, kparams=None, device=0):
+    """two haplotype assemblies against the reads in one windowed join of three sorted flat databases (mfx_db_diploid; the rule:
+    csrc/mfx_diploid.h).  Returns a dict: asm_img, the (4, max_mult + 1) class image (rows DIPLOID_CLASSES, column the read count through
+    min_count / max_count); cn_img, the (copies + 2, max_mult + 1) copy-number image db_join_spectrum gives for the reads and
+    db_merge([hap1, hap2]); n_entries; stats (hap1 / hap2 / both: distinct, total, only_distinct, only_total, found; solid, n_read, n_hap1,
+    n_hap2, n_shared, windows, the time split); with kparams also total (64) and undrcpy (3, 64), db_join_completeness' sums for hap1,
+    hap2 and the merged database.  QV and completeness derived from the counters are unvalidated against Merqury."""
+    o, kp = _diploid_opts(kparams, copies, max_mult, min_count, max_count, device)
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    asm_img = np.zeros((4, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    cn_img = np.zeros((max(int(copies), 0) + 2, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    t = np.zeros(64, dtype=np.float64) if kp is not None else None
+    u = np.zeros((3, 64), dtype=np.float64) if kp is not None else None
+    n, st = C.c_uint64(0), DbDiploidStats()
+    _check(load_library().mfx_db_diploid(_enc(read_path), _enc(hap1_path), _enc(hap2_path), C.byref(o), asm_img.ctypes.data_as(u64p), cn_img.ctypes.data_as(u64p),
+                                         C.byref(n), C.byref(st), None if t is None else t.ctypes.data_as(f64p), None if u is None else u.ctypes.data_as(f64p)))
+    return _diploid_result(asm_img, cn_img, n, st, t, u)
+
+
+def db_diploid_host(reads, hap1, hap2, k, copies=4, max_mult=10000, min_count=0, max_count=2**32 - 1, kparams=None):
+    """db_diploid on the host (mfx_db_diploid_host: the text the kernels run) over three (k-mers, counts) pairs of strictly ascending arrays
+    of k-mers of length k.  Returns db_diploid's dict and "kmers": (k-mers, read counts, hap1 counts, hap2 counts), one per distinct k-mer in
+    the order the lanes meet them."""
+    o, kp = _diploid_opts(kparams, copies, max_mult, min_count, max_count, 0)
+    u64p, u32p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    arrs, args = [], []
+    for pair in (reads, hap1, hap2):
+        arrs.append((np.ascontiguousarray(pair[0], dtype=np.uint64), np.ascontiguousarray(pair[1], dtype=np.uint32)))
+        args += [arrs[-1][0].ctypes.data_as(u64p), arrs[-1][1].ctypes.data_as(u32p), len(arrs[-1][0])]
+    cap = sum(len(a[0]) for a in arrs)
+    keys = np.zeros(max(cap, 1), dtype=np.uint64)
+    rv, c1, c2 = (np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(3))
+    asm_img = np.zeros((4, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    cn_img = np.zeros((max(int(copies), 0) + 2, max(int(max_mult), 0) + 1), dtype=np.uint64)
+    t = np.zeros(64, dtype=np.float64) if kp is not None else None
+    u = np.zeros((3, 64), dtype=np.float64) if kp is not None else None
+    nk, n, st = C.c_uint64(0), C.c_uint64(0), DbDiploidStats()
+    _check(load_library().mfx_db_diploid_host(*args, int(k), C.byref(o), keys.ctypes.data_as(u64p), rv.ctypes.data_as(u32p), c1.ctypes.data_as(u32p), c2.ctypes.data_as(u32p),
+                                              cap, C.byref(nk), asm_img.ctypes.data_as(u64p), cn_img.ctypes.data_as(u64p), C.byref(n), C.byref(st),
+                                              None if t is None else t.ctypes.data_as(f64p), None if u is None else u.ctypes.data_as(f64p)))
+    assert nk.value <= cap
+    out = _diploid_result(asm_img, cn_img, n, st, t, u)
+    out["kmers"] = (keys[:nk.value], rv[:nk.value], c1[:nk.value], c2[:nk.value])
+    return out
+
+
+def diploid_write_asm(img, path):
+    """the class image as text (mfx_diploid_write_asm; host only): Assembly, kmer_multiplicity, Count per non-zero cell, the rows labelled
+    DIPLOID_CLASSES; .gz / .bz2 / .xz names are compressed"""
+    img = np.ascontiguousarray(img, dtype=np.uint64)
+    if img.ndim != 2 or img.shape[0] != 4:
+        raise ValueError("diploid_write_asm: the class image has 4 rows")
+    _check(load_library().mfx_diploid_write_asm(img.ctypes.data_as(C.POINTER(C.c_uint64)), img.shape[1] - 1, _enc(path)))
 
 
 class DbTrioOpts(C.Structure):

@@ -53,6 +53,9 @@ struct Globals {
   uint32_t binRatioMilli = 1000, binMinHits = 1;   // -ratio (in thousandths) / -minhits of -bin
   bool ratioGiven = false, minhitsGiven = false, binSplit = false;      // -split: the reads themselves written per class
   bool join = false;                     // -join: -completeness / -spectrum as the sorted join of two sorted databases, no table (mfx_db_join_*)
+  bool diploid = false;                  // -diploid: two haplotype assemblies (-hap1 / -hap2) against -readmers in one join (mfx_db_diploid)
+  std::vector<const char *> hap1Names, hap2Names;      // every -hap1 / -hap2 given (exactly one each is taken)
+  int readmersGiven = 0;                 // how often -readmers was named
   bool trio = false;                     // -trio: no report; the two hap-mer databases of -mat / -pat [/ -child] in one pass (mfx_db_trio)
   const char *matName = nullptr, *patName = nullptr, *childName = nullptr;
   uint32_t cutMat = 0, cutPat = 0, cutChild = 0;      // -cutmat / -cutpat / -cutchild of -trio; 0: auto (the valley of the k-mer histogram)
@@ -220,9 +223,28 @@ static void usage_trio() {
           "\n");
 }
 
+// the entry of -diploid: printed behind the text above for a command line that names it or one of its flags
+static void usage_diploid() {
+  fprintf(stderr,
+          "  Two haplotype assemblies against the reads (an operation of its own: no -sequence, no -seqmers):\n"
+          "    -diploid          -readmers reads.mfxk -hap1 h1.mfxk -hap2 h2.mfxk -output stem: one windowed join of the three sorted flat\n"
+          "                      databases (what -count and -convert write; one k <= 31) on the GPU, no table, no intermediate file; the read\n"
+          "                      database is read once.  It writes <output>.spectra-asm.hist (the k-mers of the reads alone, of hap1 alone, of\n"
+          "                      hap2 alone and of both, by read count), <output>.spectra-cn.hist (the file -spectrum -join writes for\n"
+          "                      -merge hap1 hap2), <output>.qv (per hap1 / hap2 / both: the assembly's k-mers the reads do not hold, all of\n"
+          "                      them, QV and error rate; a second block with the distinct counts) and <output>.completeness.stats (the solid\n"
+          "                      read k-mers an assembly holds).  One device.  QV and completeness follow Merqury's in spirit; they are\n"
+          "                      unvalidated against Merqury.\n"
+          "    -hap1 db / -hap2 db  the assemblies' databases (merfin -count -reads hap1.fasta -k K -output h1.mfxk); they may be one file\n"
+          "    -copies C / -maxmult M  the rows and columns of the two images (as -spectrum);  -min m / -max m  the read counts that count as\n"
+          "                      present in the images and the completeness (the QV uses the raw read count)\n"
+          "    -peak P [-prob t] also print merfin's -completeness report of hap1, of hap2 and of both (-peak auto is not taken: no table)\n"
+          "\n");
+}
+
 // the usage text, then what is wrong with this command line; the exit code of a refused run
 static int fail_usage(const char *argv0, const Errors &err, bool merge = false, bool join = false, bool regions = false, bool phase = false, bool nots = false,
-                      bool bin = false, bool trio = false) {
+                      bool bin = false, bool trio = false, bool diploid = false) {
   usage(argv0);
   if (merge) usage_merge();
   if (nots) usage_not();
@@ -231,6 +253,7 @@ static int fail_usage(const char *argv0, const Errors &err, bool merge = false, 
   if (phase) usage_phase();
   if (bin) usage_bin();
   if (trio) usage_trio();
+  if (diploid) usage_diploid();
   for (auto &e : err) fputs(e.c_str(), stderr);
   return 1;
 }
@@ -306,7 +329,10 @@ static void parse_args(int argc, char **argv, Globals &G, Errors &err) {
     unsigned long long x = 0;
     if (is("-sequence")) G.seqName = val();
     else if (is("-seqmers")) G.seqDBname = val();
-    else if (is("-readmers")) G.readDBname = val();
+    else if (is("-readmers")) { G.readDBname = val(); ++G.readmersGiven; }
+    else if (is("-diploid")) G.diploid = true;
+    else if (is("-hap1")) G.hap1Names.push_back(val());
+    else if (is("-hap2")) G.hap2Names.push_back(val());
     else if (is("-reads")) G.readsNames.push_back(val());
     else if (is("-k")) {
       const char *v = val();
@@ -708,6 +734,40 @@ static void check_trio_flags(const Globals &G, Errors &err) {
     if (!G.outName) err.push_back("-histogram writes a k-mer histogram: give -output <file>.\n");
     struct stat mst;
     if (stat(G.histName, &mst) != 0 || access(G.histName, R_OK) != 0) err.push_back(std::string("Cannot read the -histogram database '") + G.histName + "'.\n");
+  }
+}
+
+// -diploid: every check before any device is touched (what the databases hold is checked by mfx_db_diploid, before it touches one)
+static bool diploid_named(const Globals &G) { return G.diploid || !G.hap1Names.empty() || !G.hap2Names.empty(); }
+static void check_diploid_flags(const Globals &G, Errors &err) {
+  if (!diploid_named(G)) return;
+  if (!G.diploid) {
+    err.push_back("-hap1 and -hap2 name the assemblies of -diploid; they have no meaning without -diploid.\n");
+    return;
+  }
+  if (G.reportType != OP_NONE) err.push_back("-diploid is an operation of its own: it does not take a report type (-hist, -dump, -completeness, -spectrum, ...).\n");
+  if (G.count || G.convertName || !G.mergeNames.empty() || G.phase || G.bin || G.trio || G.histName)
+    err.push_back("-diploid, -trio, -histogram, -bin, -phase, -count, -convert and -merge are separate operations: give one of them.\n");
+  if (G.join) err.push_back("-join is a way to run -completeness and -spectrum: -diploid is a join already and does not take it.\n");
+  if (G.readmersGiven != 1) err.push_back(G.readmersGiven ? "-diploid takes one read database: -readmers was given more than once.\n" : "-diploid needs the read database: give -readmers <file>.\n");
+  if (G.hap1Names.size() != 1) err.push_back(G.hap1Names.empty() ? "-diploid needs the first assembly's database: give -hap1 <file>.\n" : "-diploid takes two assemblies: -hap1 was given more than once.\n");
+  if (G.hap2Names.size() != 1) err.push_back(G.hap2Names.empty() ? "-diploid needs the second assembly's database: give -hap2 <file>.\n" : "-diploid takes two assemblies: -hap2 was given more than once.\n");
+  if (!G.outName) err.push_back("-diploid writes <output>.spectra-asm.hist, .spectra-cn.hist, .qv and .completeness.stats: give -output <stem>.\n");
+  if (G.seqName) err.push_back("-diploid joins databases: it does not take -sequence (merfin -count -reads hap1.fasta -k K -output h1.mfxk, then -hap1 h1.mfxk).\n");
+  if (G.seqDBname) err.push_back("-diploid takes its assemblies as -hap1 and -hap2: it does not take -seqmers.\n");
+  if (!G.readsNames.empty()) err.push_back("-diploid joins databases: it does not take -reads (count them first: -count).\n");
+  if (!G.hapmers.empty()) err.push_back("-diploid compares assemblies with the reads: it does not take -hapmers (-phase and -bin do).\n");
+  if (!G.devices.empty()) err.push_back("-diploid runs on one device: it does not take -devices (-device d).\n");
+  if (G.peakAuto) err.push_back("-diploid does not take -peak auto: the peak is read off a table, and -diploid builds none; give -peak <number>.\n");
+  if (G.pLookupTable && !G.peakGiven) err.push_back("-prob belongs to the completeness report of -peak: give -peak <number> with it.\n");
+  if (G.vcfName) err.push_back("-diploid does not take -vcf (the variant modes do).\n");
+  if (G.sharded) err.push_back("-diploid does not take -sharded: the windows it joins live on one device, and no table is built.\n");
+  if (G.indexName) err.push_back("-diploid does not take -index: it builds no table.\n");
+  const char *const names[3] = {G.readmersGiven == 1 ? G.readDBname : nullptr, G.hap1Names.size() == 1 ? G.hap1Names[0] : nullptr, G.hap2Names.size() == 1 ? G.hap2Names[0] : nullptr};
+  const char *const flags[3] = {"-readmers", "-hap1", "-hap2"};
+  for (int i = 0; i < 3; ++i) {
+    struct stat mst;
+    if (names[i] && (stat(names[i], &mst) != 0 || access(names[i], R_OK) != 0)) err.push_back(std::string("Cannot read the ") + flags[i] + " database '" + names[i] + "'.\n");
   }
 }
 

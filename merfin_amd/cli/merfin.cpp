@@ -7,6 +7,7 @@
 // -polish / -better / -strict / -loose (paths enumerated on the host, every
 // path k-mer scored on the GPU).
 #include <libgen.h>
+#include <math.h>
 #include <dirent.h>
 
 #include <algorithm>
@@ -1667,6 +1668,71 @@ static int run_join(const Globals &G) {
   return 0;
 }
 
+// merfin -diploid -readmers r -hap1 a -hap2 b -output stem: two haplotype assemblies against the reads in one join (mfx_db_diploid), no table.
+// The QV is mfx_histoQV over the assembly's k-mers the reads do not hold; it and the completeness follow Merqury's in spirit and are not
+// validated against Merqury.
+static bool write_diploid_text(const std::string &name, const std::string &text) {
+  FILE *f = fopen(name.c_str(), "w");
+  if (!f) { fprintf(stderr, "ERROR: -diploid: cannot open '%s' for writing\n", name.c_str()); return false; }
+  const bool ok = fputs(text.c_str(), f) >= 0;
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "ERROR: -diploid: writing '%s' failed\n", name.c_str()); return false; }
+  return true;
+}
+
+static int run_diploid(Globals &G) {
+  const char *h1 = G.hap1Names[0], *h2 = G.hap2Names[0];
+  mfx_db_join_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = G.device;
+  o.minV = G.minV; o.maxV = G.maxV;
+  o.peak = G.peak;
+  o.n_prob = (uint32_t)G.copyKmerK.size(); o.probK = G.copyKmerK.data(); o.probP = G.copyKmerP.data();
+  o.copies = G.copies; o.max_mult = G.maxMult;
+  mfx_db_info rdb;
+  if (mfx_db_probe(G.readDBname, &rdb)) DIE_MFX("opening -readmers");
+  const size_t W = (size_t)G.maxMult + 1;
+  std::vector<uint64_t> cls(4 * W), cn((size_t)(G.copies + 2) * W);
+  uint64_t entries = 0;
+  mfx_db_diploid_stats st;
+  double t64[64], u64[3 * 64];
+  const bool peak = G.peakGiven;
+  fprintf(stderr, "-- Joining '%s' with '%s' and '%s' window by window.\n", G.readDBname, h1, h2);
+  if (mfx_db_diploid(G.readDBname, h1, h2, &o, cls.data(), cn.data(), &entries, &st, peak ? t64 : nullptr, peak ? u64 : nullptr)) DIE_MFX("-diploid");
+  const std::string stem = G.outName;
+  fprintf(stderr, "-- Spectrum of the %d-mers by assembly to '%s'.\n", rdb.k, (stem + ".spectra-asm.hist").c_str());
+  if (mfx_diploid_write_asm(cls.data(), G.maxMult, (stem + ".spectra-asm.hist").c_str())) DIE_MFX("writing the spectrum");
+  if (write_spectrum_report(G, rdb.k, cn, entries, true)) return 1;
+  const char *const names[3] = {"hap1", "hap2", "both"};
+  const mfx_diploid_counts *const x[3] = {&st.hap1, &st.hap2, &st.both};
+  char line[512];
+  std::string qv = "# QV = -10 log10(1 - (1 - only / all)^(1 / k)): Merqury's in spirit, unvalidated against Merqury\n#name\tonly_total\ttotal\tQV\terror\n";
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) qv += "#name\tonly_distinct\tdistinct\tQV\terror\n";
+    for (int i = 0; i < 3; ++i) {
+      const uint64_t only = pass ? x[i]->only_distinct : x[i]->only_total, all = pass ? x[i]->distinct : x[i]->total;
+      const double q = mfx_histoQV((double)only, (double)all, rdb.k);
+      snprintf(line, sizeof line, "%s\t%lu\t%lu\t%.4f\t%.6g\n", names[i], (unsigned long)only, (unsigned long)all, q, pow(10.0, q / -10.0));
+      qv += line;
+    }
+  }
+  if (!write_diploid_text(stem + ".qv", qv)) return 1;
+  std::string cs = "# the solid read k-mers (-min <= count <= -max) an assembly holds: Merqury's k-mer completeness in spirit, unvalidated against Merqury\n#name\tall\tfound\tsolid\tpercent\n";
+  for (int i = 0; i < 3; ++i) {
+    snprintf(line, sizeof line, "%s\tall\t%lu\t%lu\t%.4f\n", names[i], (unsigned long)x[i]->found, (unsigned long)st.solid, st.solid ? 100.0 * (double)x[i]->found / (double)st.solid : 0.0);
+    cs += line;
+  }
+  if (!write_diploid_text(stem + ".completeness.stats", cs)) return 1;
+  if (peak)
+    for (int i = 0; i < 3; ++i) {
+      fprintf(stderr, "-- Compute completeness: %s.\n", names[i]);
+      print_completeness(t64, u64 + 64 * i);
+    }
+  fprintf(stderr, "-- Joined: %lu read k-mers, %lu and %lu assembly k-mers, %lu in both assemblies, %lu window%s.\n", (unsigned long)st.n_read, (unsigned long)st.n_hap1,
+          (unsigned long)st.n_hap2, (unsigned long)st.n_shared, (unsigned long)st.windows, st.windows == 1 ? "" : "s");
+  fprintf(stderr, "Bye!\n");
+  return 0;
+}
+
 // merfin -phase: hap-mer markers, phase blocks and switch errors (mfx_phase_run).  The table is the sequence-only index -- the k-mers of
 // -sequence claimed, set A loaded update-only on the read side, set B on the assembly side; the assembly's own counts are not needed and
 // are not counted -- or, for k > 31 and for a database that is not canonical, the full tables of the two sets.
@@ -2230,6 +2296,12 @@ int main(int argc, char **argv) {
   Errors err;
   // 1. parse, check (every refusal before a device is touched), dispatch the operations that are not reports
   parse_args(argc, argv, G, err);
+  check_diploid_flags(G, err);
+  if (diploid_named(G)) {
+    if (!err.empty()) return fail_usage(argv[0], err, false, false, false, false, false, false, false, true);
+    if (G.peakGiven && !load_Kmetric(G)) return 1;             // (host only, before the HIP runtime starts: see below)
+    return devices_available({G.device}) ? run_diploid(G) : 1;
+  }
   check_trio_flags(G, err);
   if (trio_named(G)) {
     if (!err.empty()) return fail_usage(argv[0], err, false, false, false, false, false, false, true);

@@ -21,6 +21,8 @@
 #include "mfx_join.h"
 #include "mfx_spectrum.h"
 #include "mfx_trio.h"
+#include "mfx_diploid.h"
+#include "mfx_kstar.h"
 #include "mfx_pipe.h"
 #include "mfx_place.h"
 
@@ -2636,6 +2638,247 @@ extern "C" int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_
     });
   } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_host: out of memory"); }
   *n_pairs = n;
+  return MFX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// mfx_db_diploid: two haplotype assemblies against the reads, window by window (include/merfin_amd.h; the rule: mfx_diploid.h; the kernels:
+// mfx_diploid.hip).  mfx_db_merge's windows and decode over the three files; hap1's and hap2's runs are tagged, merged (mfx_merge_pairs_kernel)
+// and compacted into the pair run; the read run stays where the decode left it and is joined against the pair run by mfx_join_kernel.
+// ---------------------------------------------------------------------------
+static void diploid_fill_stats(const uint64_t *c, mfx_db_diploid_stats *st) {
+  mfx_diploid_counts *x[3] = {&st->hap1, &st->hap2, &st->both};
+  for (int i = 0; i < 3; ++i) {
+    const uint64_t *s = c + i * MFX_DIP_PER_X;
+    x[i]->distinct = s[MFX_DIP_DISTINCT]; x[i]->total = s[MFX_DIP_TOTAL]; x[i]->only_distinct = s[MFX_DIP_ONLY_DISTINCT];
+    x[i]->only_total = s[MFX_DIP_ONLY_TOTAL]; x[i]->found = s[MFX_DIP_FOUND];
+  }
+  st->solid = c[MFX_DIP_SOLID]; st->n_read = c[MFX_DIP_N_READ]; st->n_shared = c[MFX_DIP_N_SHARED];
+}
+
+static int diploid_check_opts(const char *who, const mfx_db_join_opts *o, const uint64_t *asm_img, const uint64_t *cn_img, const uint64_t *n_entries,
+                              const mfx_db_diploid_stats *st, const double *total64, const double *undrcpy64) {
+  if (!o || !asm_img || !cn_img || !n_entries || !st) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if ((total64 != nullptr) != (undrcpy64 != nullptr)) return mfx_fail(MFX_E_INVAL, "%s: total64 and undrcpy64 are given together or not at all", who);
+  if (total64 && o->n_prob && (!o->probK || !o->probP)) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if (o->copies < MFX_SPEC_MIN_COPIES || o->copies > MFX_SPEC_MAX_COPIES)      // (mfx_spectrum_run's bounds and texts)
+    return mfx_fail(MFX_E_INVAL, "%s: copies = %u is outside [%u, %u]", who, o->copies, MFX_SPEC_MIN_COPIES, MFX_SPEC_MAX_COPIES);
+  if (o->max_mult < MFX_SPEC_MIN_MULT || o->max_mult > MFX_SPEC_MAX_MULT)
+    return mfx_fail(MFX_E_INVAL, "%s: max_mult = %u is outside [%u, %u]", who, o->max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
+  return MFX_OK;
+}
+
+static int db_diploid_impl(const char *read_path, const char *hap1_path, const char *hap2_path, const mfx_db_join_opts *o, uint64_t *asm_img, uint64_t *cn_img,
+                           uint64_t *n_entries, mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
+  const char *who = "mfx_db_diploid";
+  const double t_begin = db_now();
+  // ---- every check that needs no device
+  if (!read_path || !hap1_path || !hap2_path) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if (int rc = diploid_check_opts(who, o, asm_img, cn_img, n_entries, st, total64, undrcpy64)) return rc;
+  const bool pieces = total64 != nullptr;
+  std::vector<std::unique_ptr<MergeIn>> ins;
+  const char *paths[3] = {read_path, hap1_path, hap2_path};
+  for (int i = 0; i < 3; ++i) {
+    ins.emplace_back(new MergeIn);
+    mfx_db_info info;                                            // (k > 31 has no sorted form: said as that, not as "a plain flat file")
+    if (detect(paths[i]) == MFX_DB_FLAT && mfx_db_probe_impl(paths[i], &info) == MFX_OK && info.k > MFX_MAX_K_NARROW)
+      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %d-mers: the sorted join takes k <= %d", who, paths[i], info.k, MFX_MAX_K_NARROW);
+    if (int rc = merge_open_input(paths[i], *ins.back(), who)) return rc;
+    if (ins[i]->h.k != ins[0]->h.k)
+      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", who, paths[i], ins[i]->h.k, paths[0], ins[0]->h.k);
+  }
+  const int k = (int)ins[0]->h.k;
+  MergeWindows P;
+  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
+  uint64_t max_asm = 0;                                        // the most a window's blocks hold of the two assemblies together
+  for (size_t w = 0; w < P.win.size(); ++w) {
+    uint64_t a = 0;
+    for (uint32_t i = 1; i < 3; ++i) a += mfx_merge_block_pairs(P.pin[i], P.blk[2 * (w * 3 + i)], P.blk[2 * (w * 3 + i) + 1]);
+    max_asm = std::max(max_asm, a);
+  }
+  const uint64_t W = (uint64_t)o->max_mult + 1, cls_cells = MFX_DIP_ROWS * W, cn_cells = (uint64_t)(o->copies + 2u) * W;
+  // res: [0] the k-mers of the reads and of an assembly, [1] spare; the class image and its counter word; the cn image and its counter word;
+  // the 256 piece sums; the copies of the counters
+  const size_t off_cls = 2, off_cn = off_cls + cls_cells + 1, off_sums = off_cn + cn_cells + 1, off_cnt = off_sums + 256, res_words = off_cnt + MFX_DIP_STAT_WORDS;
+  std::vector<uint64_t> res(res_words, 0);
+  uint64_t got[3] = {0, 0, 0}, windows = 0;
+  double t_read = 0, t_decode = 0, t_pair = 0, t_join = 0;
+  if (P.max_pairs) {
+    DeviceBack back;
+    MFX_HIP(hipSetDevice(o->device));
+    // p[0]: one buffer of cap pairs, the k-mers in front of the counts: the decoded runs of the three inputs.  p[1]: the window's blocks.  p[2]: tasks,
+    // their below / above, the inputs' error words, the pair kernel's tile offsets.  p[3], p[4]: the window's escapes.  p[5]: the result.  p[6], p[7]: the
+    // -prob table.  E.p[0]: the tagged merged run of the two assemblies (acap pairs).  E.p[1]: the pair run (acap k-mers, acap words).
+    const uint64_t cap = P.max_pairs + 1, acap = max_asm + 1, tiles = mfx_dip_tiles(max_asm);
+    const uint64_t small = P.max_tasks * (sizeof(mfx_merge_task) + 8) + 3 * 4 + 64 + (tiles + 1) * 8;
+    const size_t np = o->n_prob && pieces ? o->n_prob : 1;
+    DbDev D, E;
+    hipError_t e = hipMalloc(&D.p[0], cap * 12);
+    if (e == hipSuccess) e = hipMalloc(&D.p[1], P.max_bytes + 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[2], small);
+    if (e == hipSuccess) e = hipMalloc(&D.p[3], (P.max_esc + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[4], (P.max_esc + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc(&D.p[5], res_words * 8);
+    if (e == hipSuccess) e = hipMalloc(&D.p[6], np * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&D.p[7], np * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&E.p[0], acap * 12);
+    if (e == hipSuccess) e = hipMalloc(&E.p[1], acap * 16);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs, %lu of them the assemblies' (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who,
+                      (unsigned long)P.max_pairs, (unsigned long)max_asm,
+                      ((double)cap * 12 + (double)acap * 28 + (double)P.max_bytes + (double)P.max_esc * 12 + (double)small + (double)res_words * 8) / 1e9, hipGetErrorString(e));
+    }
+    uint64_t *d_keys = (uint64_t *)D.p[0], *d_res = (uint64_t *)D.p[5];
+    uint32_t *d_vals = (uint32_t *)((char *)D.p[0] + cap * 8);
+    uint64_t *m_keys = (uint64_t *)E.p[0], *p_keys = (uint64_t *)E.p[1], *p_vals = p_keys + acap;
+    uint32_t *m_vals = (uint32_t *)((char *)E.p[0] + acap * 8);
+    MergeDecoder dec;
+    dec.d_words = D.p[1];
+    uint64_t *d_tile = (uint64_t *)D.p[2];
+    dec.d_tasks = (mfx_merge_task *)(d_tile + tiles + 1);
+    dec.d_below = (uint32_t *)(dec.d_tasks + P.max_tasks); dec.d_above = dec.d_below + P.max_tasks; dec.d_err = dec.d_above + P.max_tasks;
+    dec.d_ek = (uint64_t *)D.p[3]; dec.d_ev = (uint32_t *)D.p[4];
+    MFX_HIP(hipHostMalloc(&dec.pinned, P.max_bytes + 8, hipHostMallocDefault));
+    MFX_HIP(mfx_memset_now(d_res, 0, res_words * 8));
+    if (pieces && o->n_prob) {
+      MFX_HIP(hipMemcpy(D.p[6], o->probK, o->n_prob * sizeof(uint32_t), hipMemcpyHostToDevice));
+      MFX_HIP(hipMemcpy(D.p[7], o->probP, o->n_prob * sizeof(double), hipMemcpyHostToDevice));
+    }
+    int cus = 0;
+    MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
+    const int grid = (cus > 0 ? cus : 256) * 2;                  // the workgroups a CU holds at once (mfx_diploid.hip: LDS)
+    mfx_spectrum_args cls{}, cn{};
+    const char *ag = getenv("MFX_SPECTRUM_AGG");                 // as mfx_spectrum_run reads it (docs/KNOBS.md)
+    cls.copies = MFX_DIP_ROWS - 2u; cn.copies = o->copies;
+    cls.max_mult = cn.max_mult = o->max_mult;
+    cls.lds_cols = cn.lds_cols = mfx_dip_lds_cols(o->copies, o->max_mult);
+    cls.aggregate = cn.aggregate = ag ? (atoi(ag) != 0) : MFX_SPEC_AGG_DEFAULT;
+    cls.img = d_res + off_cls; cn.img = d_res + off_cn;
+    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
+    for (size_t wi = 0; wi < P.win.size(); ++wi) {
+      if (P.win[wi].pairs == 0) continue;
+      const int rc = merge_decode_window(ins, P, wi, k, who, dec, d_keys, d_vals);
+      t_read += dec.t_read; t_decode += dec.t_decode;
+      if (rc) return rc;
+      double t0 = db_now();
+      const MergeRun a = dec.runs[0], h1 = dec.runs[1], h2 = dec.runs[2];
+      got[0] += a.len; got[1] += h1.len; got[2] += h2.len;
+      // ---- a. the pair run: the role into the two low bits of the assemblies' k-mers, one merge, the head positions compacted
+      const uint64_t M = h1.len + h2.len;
+      uint64_t n_pairs = 0;
+      if (M > max_asm) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is merged beyond the buffers)
+      if (M) {
+        MFX_HIP(mfx_k_trio_tag(d_keys + h1.off, h1.len, MFX_DIP_HAP1, nullptr));
+        MFX_HIP(mfx_k_trio_tag(d_keys + h2.off, h2.len, MFX_DIP_HAP2, nullptr));
+        MFX_HIP(mfx_k_merge_pairs(d_keys + h1.off, d_vals + h1.off, h1.len, d_keys + h2.off, d_vals + h2.off, h2.len, m_keys, m_vals, nullptr));
+        MFX_HIP(mfx_k_dip_pairs(m_keys, m_vals, M, d_tile, p_keys, p_vals, nullptr));
+        MFX_HIP(hipMemcpyAsync(&n_pairs, d_tile + mfx_dip_tiles(M), 8, hipMemcpyDeviceToHost, nullptr));
+        MFX_HIP(hipStreamSynchronize(nullptr));
+      }
+      if (n_pairs > M || 2 * n_pairs < M) return mfx_fail(MFX_E_HIP, "%s: the pair run of a window is damaged", who);
+      double t1 = db_now();
+      t_pair += t1 - t0;
+      // ---- b. the join of the read run against it
+      MFX_HIP(mfx_k_dip_join(d_keys + a.off, d_vals + a.off, a.len, p_keys, p_vals, n_pairs, cls, cn, o->minV, o->maxV, k, pieces ? 1 : 0, o->peak,
+                             pieces ? o->n_prob : 0u, (const uint32_t *)D.p[6], (const double *)D.p[7], reinterpret_cast<double *>(d_res + off_sums), d_res + off_cnt,
+                             d_res, grid, nullptr));
+      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
+      t_join += db_now() - t1;
+      ++windows;
+    }
+    MFX_HIP(hipMemcpy(res.data(), d_res, res_words * 8, hipMemcpyDeviceToHost));
+  }
+  // ---- what the windows held against what the files say, the counters against the files, the images against their counters: no partial result
+  for (int i = 0; i < 3; ++i)
+    if (got[i] != ins[i]->h.n)
+      return mfx_fail(MFX_E_FORMAT, "'%s': the windows hold %lu of its %lu k-mers: the directory does not describe the blocks", paths[i], (unsigned long)got[i], (unsigned long)ins[i]->h.n);
+  uint64_t c[MFX_DIP_NSTATS];
+  for (uint32_t s = 0; s < MFX_DIP_NSTATS; ++s) {
+    c[s] = 0;
+    for (uint32_t j = 0; j < MFX_DIP_STAT_SHARDS; ++j) c[s] += res[off_cnt + j * MFX_DIP_STAT_STRIDE + s];
+  }
+  const uint64_t d1 = c[MFX_DIP_DISTINCT], d2 = c[MFX_DIP_PER_X + MFX_DIP_DISTINCT], db = c[2 * MFX_DIP_PER_X + MFX_DIP_DISTINCT];
+  if (d1 != got[1] || d2 != got[2] || c[MFX_DIP_N_READ] != got[0] || d1 + d2 - c[MFX_DIP_N_SHARED] != db ||
+      res[0] != db - c[2 * MFX_DIP_PER_X + MFX_DIP_ONLY_DISTINCT])
+    return mfx_fail(MFX_E_HIP, "%s: the join counted %lu, %lu and %lu k-mers of the reads, hap1 and hap2 (%lu shared, %lu of either, %lu of the reads and an assembly): "
+                    "not what databases of %lu, %lu and %lu k-mers give", who, (unsigned long)c[MFX_DIP_N_READ], (unsigned long)d1, (unsigned long)d2,
+                    (unsigned long)c[MFX_DIP_N_SHARED], (unsigned long)db, (unsigned long)res[0], (unsigned long)got[0], (unsigned long)got[1], (unsigned long)got[2]);
+  uint64_t sum_cls = 0, sum_cn = 0;
+  for (size_t i = 0; i < cls_cells; ++i) sum_cls += res[off_cls + i];
+  for (size_t i = 0; i < cn_cells; ++i) sum_cn += res[off_cn + i];
+  if (sum_cls != res[off_cls + cls_cells] || sum_cn != res[off_cn + cn_cells] || sum_cls != sum_cn)
+    return mfx_fail(MFX_E_HIP, "%s: the images sum to %lu and %lu, the join counted %lu and %lu entries", who, (unsigned long)sum_cls, (unsigned long)sum_cn,
+                    (unsigned long)res[off_cls + cls_cells], (unsigned long)res[off_cn + cn_cells]);
+  const bool filtered = o->minV > 1 || o->maxV < 0xffffffffull;      // (a count is 1 at the least: no other filter makes an entry vanish)
+  if (!filtered && sum_cn != got[0] + db - res[0])
+    return mfx_fail(MFX_E_HIP, "%s: the join counted %lu entries, the inputs hold %lu distinct k-mers", who, (unsigned long)sum_cn, (unsigned long)(got[0] + db - res[0]));
+  memcpy(asm_img, res.data() + off_cls, cls_cells * 8);
+  memcpy(cn_img, res.data() + off_cn, cn_cells * 8);
+  *n_entries = sum_cn;
+  if (pieces) {
+    memcpy(total64, res.data() + off_sums, 64 * sizeof(double));
+    memcpy(undrcpy64, res.data() + off_sums + 64, 3 * 64 * sizeof(double));
+  }
+  memset(st, 0, sizeof(*st));
+  diploid_fill_stats(c, st);
+  st->n_hap1 = got[1]; st->n_hap2 = got[2]; st->windows = windows;
+  st->t_read = t_read; st->t_decode = t_decode; st->t_pair = t_pair; st->t_join = t_join; st->t_total = db_now() - t_begin;
+  return MFX_OK;
+}
+
+extern "C" int mfx_db_diploid(const char *read_path, const char *hap1_path, const char *hap2_path, const mfx_db_join_opts *o, uint64_t *asm_img, uint64_t *cn_img,
+                              uint64_t *n_entries, mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
+  try { return db_diploid_impl(read_path, hap1_path, hap2_path, o, asm_img, cn_img, n_entries, st, total64, undrcpy64); }      // (nothing leaves the C ABI as an exception)
+  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_diploid: out of memory"); }
+  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_diploid: %s", e.what()); }
+}
+
+extern "C" int mfx_db_diploid_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *hap1_keys, const uint32_t *hap1_vals,
+                                   uint64_t n_hap1, const uint64_t *hap2_keys, const uint32_t *hap2_vals, uint64_t n_hap2, int k, const mfx_db_join_opts *o, uint64_t *keys,
+                                   uint32_t *readV, uint32_t *c1V, uint32_t *c2V, uint64_t cap, uint64_t *n_kmers, uint64_t *asm_img, uint64_t *cn_img, uint64_t *n_entries,
+                                   mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
+  const char *who = "mfx_db_diploid_host";
+  if ((n_read && (!read_keys || !read_vals)) || (n_hap1 && (!hap1_keys || !hap1_vals)) || (n_hap2 && (!hap2_keys || !hap2_vals)) || !n_kmers ||
+      (cap && (!keys || !readV || !c1V || !c2V)))
+    return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
+  if (int rc = diploid_check_opts(who, o, asm_img, cn_img, n_entries, st, total64, undrcpy64)) return rc;
+  if (k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "%s: k = %d is outside [1, %d]", who, k, MFX_MAX_K_NARROW);
+  try {
+    mfx_dip_host_result R;
+    uint64_t n = 0;
+    mfx_dip_host(read_keys, read_vals, n_read, hap1_keys, hap1_vals, n_hap1, hap2_keys, hap2_vals, n_hap2, k, o->minV, o->maxV, o->copies, o->max_mult, total64 != nullptr,
+                 [&](uint32_t r) { double rk, pr; mfx_getK_core(o->peak, o->n_prob, o->probK, o->probP, r, rk, pr); return rk; },
+                 [&](uint64_t key, uint32_t r, uint32_t c1, uint32_t c2) {
+                   if (n < cap) { keys[n] = key; readV[n] = r; c1V[n] = c1; c2V[n] = c2; }
+                   ++n;
+                 }, R);
+    if (R.stats[MFX_DIP_DISTINCT] != n_hap1 || R.stats[MFX_DIP_PER_X + MFX_DIP_DISTINCT] != n_hap2 || R.stats[MFX_DIP_N_READ] != n_read)
+      return mfx_fail(MFX_E_INVAL, "%s: the runs do not ascend strictly, or hold a count of 0", who);
+    *n_kmers = n;
+    memcpy(asm_img, R.asm_img.data(), R.asm_img.size() * 8);
+    memcpy(cn_img, R.cn_img.data(), R.cn_img.size() * 8);
+    *n_entries = R.n_entries;
+    if (total64) { memcpy(total64, R.tot, sizeof(R.tot)); memcpy(undrcpy64, R.und, sizeof(R.und)); }
+    memset(st, 0, sizeof(*st));
+    diploid_fill_stats(R.stats, st);
+    st->n_hap1 = n_hap1; st->n_hap2 = n_hap2;
+    return MFX_OK;
+  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "%s: out of memory", who); }
+}
+
+extern "C" int mfx_diploid_write_asm(const uint64_t *img, uint32_t max_mult, const char *path) {
+  if (!img || !path) return mfx_fail(MFX_E_INVAL, "mfx_diploid_write_asm: null argument");
+  if (max_mult < MFX_SPEC_MIN_MULT || max_mult > MFX_SPEC_MAX_MULT)
+    return mfx_fail(MFX_E_INVAL, "mfx_diploid_write_asm: max_mult = %u is outside [%u, %u]", max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
+  static const char *const label[MFX_DIP_ROWS] = {"read-only", "hap1-only", "hap2-only", "shared"};
+  mfx_file fh = mfx_open_writer(path, false);                    // compressor chosen by suffix (mfx_pipe.h)
+  if (!fh.f) return mfx_fail(MFX_E_IO, "mfx_diploid_write_asm: cannot open '%s' for writing", path);
+  fprintf(fh.f, "Assembly\tkmer_multiplicity\tCount\n");
+  for (uint32_t r = 0; r < MFX_DIP_ROWS; ++r)
+    for (uint32_t m = 0; m <= max_mult; ++m)
+      if (img[(size_t)r * (max_mult + 1u) + m]) fprintf(fh.f, "%s\t%u\t%llu\n", label[r], m, (unsigned long long)img[(size_t)r * (max_mult + 1u) + m]);
+  if (mfx_close(fh)) return mfx_fail(MFX_E_IO, "mfx_diploid_write_asm: writing '%s' failed", path);
   return MFX_OK;
 }
 

@@ -23,33 +23,39 @@ constexpr uint32_t MFX_JOIN_TILE = MFX_JOIN_LANES * MFX_JOIN_PER;      // merged
 constexpr uint64_t MFX_JOIN_NONE = ~0ull;                      // no record across the boundary (a k-mer is below 2^62)
 
 // A tile as a lane sees it: k[0 .. na) the tile's read k-mers, k[na .. na + nb) its asm k-mers, v their counts; prev_a the read k-mer in
-// front of the tile, next_bk / next_bv the asm record behind it (MFX_JOIN_NONE where the run has none).
-struct mfx_join_tile {
+// front of the tile, next_bk / next_bv the asm record behind it (MFX_JOIN_NONE where the run has none).  V: the asm run's value -- a count
+// (uint32_t: mfx_db_join_*) or the two counts of a pair run in one word (uint64_t: mfx_db_diploid, mfx_diploid.h); a read count staged in v
+// is widened to V and is a uint32_t again where the walk hands it on.
+template <class V>
+struct mfx_join_tile_t {
   const uint64_t *k;
-  const uint32_t *v;
+  const V *v;
   uint32_t na, nb;
   uint64_t prev_a, next_bk;
-  uint32_t next_bv;
+  V next_bv;
 };
+using mfx_join_tile = mfx_join_tile_t<uint32_t>;
 
 // The share [t0, t1) of the tile's merged positions, t1 - t0 <= MFX_JOIN_PER: sink(have, k-mer, read count, asm count) is called
 // MFX_JOIN_PER times whatever the share holds (a consumer may vote across the wave), `have` for the pairs the lane owns; a count of 0
 // stands for "not in that run".
-template <class Sink>
-MFX_MERGE_HD void mfx_join_lane(const mfx_join_tile &T, uint32_t t0, uint32_t t1, Sink &&sink) {
+template <class V, class Sink>
+MFX_MERGE_HD void mfx_join_lane(const mfx_join_tile_t<V> &T, uint32_t t0, uint32_t t1, Sink &&sink) {
   uint32_t i = mfx_merge_cut<uint32_t>(T.k, T.na, T.k + T.na, T.nb, t0), j = t0 - i;
   uint64_t last_a = i ? T.k[i - 1] : T.prev_a;
+#if defined(__HIPCC__)                                         // (g++ builds this text as well: tools/native/diploid_sanitize.cpp)
 #pragma unroll
+#endif
   for (uint32_t r = 0; r < MFX_JOIN_PER; ++r) {
     const bool on = t0 + r < t1, ha = on && i < T.na, hb = j < T.nb;
     const uint64_t xa = ha ? T.k[i] : MFX_JOIN_NONE;
     const uint64_t xb = hb ? T.k[T.na + j] : T.next_bk;          // the next asm record of the merged order, the tile's or the one behind it
-    const uint32_t vb = hb ? T.v[T.na + j] : T.next_bv;
+    const V vb = hb ? T.v[T.na + j] : T.next_bv;
     const bool from_a = ha && xa <= xb;                          // (the tile's cut: no read k-mer of the tile is above next_bk)
     const bool twin = xb == (from_a ? xa : last_a);
     const bool have = on && (from_a || !twin);
-    const uint32_t rv = from_a ? T.v[i] : 0u;
-    sink(have, from_a ? xa : xb, rv, (from_a && !twin) ? 0u : vb);
+    const uint32_t rv = from_a ? (uint32_t)T.v[i] : 0u;
+    sink(have, from_a ? xa : xb, rv, (from_a && !twin) ? (V)0 : vb);
     if (from_a) { last_a = xa; ++i; }
     else if (on) ++j;
   }
@@ -64,10 +70,10 @@ inline mfx_join_cuts mfx_join_tile_cuts(const uint64_t *ka, uint64_t la, const u
 inline uint64_t mfx_join_tiles(uint64_t la, uint64_t lb) { return (la + lb + MFX_JOIN_TILE - 1) / MFX_JOIN_TILE; }
 
 // The kernel's walk on the host: every tile staged as the kernel stages it, every lane's share walked by mfx_join_lane.
-template <class Sink>
-inline void mfx_join_host(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const uint32_t *vb, uint64_t lb, Sink &&sink) {
+template <class V, class Sink>
+inline void mfx_join_host(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *kb, const V *vb, uint64_t lb, Sink &&sink) {
   std::vector<uint64_t> sk(MFX_JOIN_TILE);
-  std::vector<uint32_t> sv(MFX_JOIN_TILE);
+  std::vector<V> sv(MFX_JOIN_TILE);
   const uint64_t total = la + lb;
   for (uint64_t d0 = 0; d0 < total; d0 += MFX_JOIN_TILE) {
     const uint64_t d1 = std::min<uint64_t>(d0 + MFX_JOIN_TILE, total);
@@ -75,11 +81,11 @@ inline void mfx_join_host(const uint64_t *ka, const uint32_t *va, uint64_t la, c
     const uint32_t n = c.na + c.nb;
     for (uint32_t x = 0; x < n; ++x) {
       sk[x] = x < c.na ? ka[c.a0 + x] : kb[c.b0 + (x - c.na)];
-      sv[x] = x < c.na ? va[c.a0 + x] : vb[c.b0 + (x - c.na)];
+      sv[x] = x < c.na ? (V)va[c.a0 + x] : vb[c.b0 + (x - c.na)];
     }
     const bool more_b = c.b0 + c.nb < lb;
-    const mfx_join_tile T{sk.data(), sv.data(), c.na, c.nb, c.a0 ? ka[c.a0 - 1] : MFX_JOIN_NONE, more_b ? kb[c.b0 + c.nb] : MFX_JOIN_NONE,
-                          more_b ? vb[c.b0 + c.nb] : 0u};
+    const mfx_join_tile_t<V> T{sk.data(), sv.data(), c.na, c.nb, c.a0 ? ka[c.a0 - 1] : MFX_JOIN_NONE, more_b ? kb[c.b0 + c.nb] : MFX_JOIN_NONE,
+                               more_b ? vb[c.b0 + c.nb] : (V)0};
     for (uint32_t lane = 0; lane < MFX_JOIN_LANES; ++lane) {
       const uint32_t t0 = std::min(lane * MFX_JOIN_PER, n), t1 = std::min(t0 + MFX_JOIN_PER, n);
       mfx_join_lane(T, t0, t1, sink);

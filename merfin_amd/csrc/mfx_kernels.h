@@ -359,5 +359,14 @@ hipError_t mfx_k_trio_hist(const uint64_t *keys, const uint32_t *vals, uint64_t 
 uint64_t mfx_trio_tiles(uint64_t n);
 hipError_t mfx_k_trio_classify(const uint64_t *keys, const uint32_t *vals, uint64_t n, const mfx_trio_cuts &cuts, uint64_t *tile_off, uint64_t *a_keys, uint32_t *a_vals,
                                uint64_t *b_keys, uint32_t *b_vals, uint64_t *stats, hipStream_t st);
+// mfx_db_diploid (mfx_diploid.hip; the rule: mfx_diploid.h).  pairs: the tagged merged run of hap1 and hap2 into the pair run -- one record
+// (k-mer, c1 | c2 << 32) per k-mer, ascending and dense, room for n; tile_off: mfx_dip_tiles(n) + 1 words, the last ends as the records written.
+// join: the read run a against the pair run; cls / cn: the class image (copies == 2) and the cn image, one lds_cols, each with its counter word
+// behind it, added to; sums[256] (tot[64], und[3][64]; pieces != 0) and counters[MFX_DIP_STAT_WORDS] added to; stats[0] += the k-mers both hold.
+uint64_t mfx_dip_tiles(uint64_t n);
+hipError_t mfx_k_dip_pairs(const uint64_t *keys, const uint32_t *vals, uint64_t n, uint64_t *tile_off, uint64_t *pk, uint64_t *pv, hipStream_t st);
+hipError_t mfx_k_dip_join(const uint64_t *ka, const uint32_t *va, uint64_t la, const uint64_t *pk, const uint64_t *pv, uint64_t lb, const mfx_spectrum_args &cls,
+                          const mfx_spectrum_args &cn, uint64_t minV, uint64_t maxV, int k, int pieces, double peak, uint32_t n_prob, const uint32_t *probK,
+                          const double *probP, double *sums, uint64_t *counters, uint64_t *stats, int grid, hipStream_t st);
 hipError_t mfx_k_completeness(mfx_table_view t, double peak, uint32_t n_prob, const uint32_t *probK, const double *probP,
                               double *partials, int grid, hipStream_t st);
