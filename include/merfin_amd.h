@@ -856,7 +856,10 @@ int mfx_hist_run_sharded(mfx_eval *const *evs, mfx_router *const *routers, const
 /* ------------------------------------------------------------------------ */
 /* Raw per-position values: for k-mer start positions [pos_begin,pos_end) of
  * contig `contig`, readV[i]/asmV[i] = summed read / asm counts of the k-mer
- * starting there (0,0 where no valid k-mer starts).  Host output arrays. */
+ * starting there (0,0 where no valid k-mer starts).  Host output arrays.
+ * The counters are those of the range: kasm is the number of positions in
+ * [pos_begin,pos_end) where a valid k-mer starts; kmissing is those of them
+ * whose readK == 0 by getK (merfin-globals.C:66-98). */
 int mfx_dump_values(mfx_eval *ev, const mfx_seq *seq, uint32_t contig, uint64_t pos_begin, uint64_t pos_end,
                     uint32_t *readV, uint32_t *asmV, uint64_t *kasm, uint64_t *kmissing);
 /* The complete -dump of one contig appended to `path` in the reference's text

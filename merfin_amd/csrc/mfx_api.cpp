@@ -2851,6 +2851,19 @@ static void dump_format_range(const mfx_kparams &kp, const char *name, size_t na
   used = (size_t)(w - out.data());
 }
 
+// positions per chunk: MFX_DUMP_CHUNK from 1 to 1 << 24 as given (the tests bring the chunk seam within reach of a small
+// contig); unset, 0, malformed or larger: 1 << 24
+static uint64_t dump_chunk() {
+  const uint64_t dflt = 1ull << 24;
+  const char *e = getenv("MFX_DUMP_CHUNK");
+  if (!e || *e < '0' || *e > '9') return dflt;
+  char *end = nullptr;
+  errno = 0;
+  const unsigned long long v = strtoull(e, &end, 10);
+  if (errno || *end || v < 1 || v > dflt) return dflt;
+  return (uint64_t)v;
+}
+
 // outputDump, merfin-dump.C:87-93: a line for every position where any of
 // readK, asmK, K* is non-zero.  Values come from the GPU in 16 M-position
 // chunks -- chunk i + 1 is looked up while chunk i is formatted and written --; host threads format disjoint sub-ranges and,
@@ -2878,7 +2891,7 @@ static int dump_contig_impl(const mfx_eval *ev, const mfx_seq *seq, uint32_t con
     if (!f) return mfx_fail(MFX_E_IO, "cannot open '%s' for writing", path);
   }
   const uint64_t len = seq->len[contig];
-  const uint64_t CH = 1ull << 24;
+  const uint64_t CH = dump_chunk();
   struct U32Buf { std::unique_ptr<uint32_t[]> p; uint32_t *data() { return p.get(); } } rvb[2], avb[2];     // (not value-initialised)
   for (int b = 0; b < 2; ++b) { rvb[b].p.reset(new uint32_t[std::min(len, CH) + 1]); avb[b].p.reset(new uint32_t[std::min(len, CH) + 1]); }
   mfx_kparams kp{ev->peak, ev->n_prob, ev->probK.data(), ev->probP.data()};
