@@ -14,14 +14,8 @@
 //                 own writer of the same layout (tests/meryl_layout.py).  It
 //                 refuses anything whose magic numbers / sizes do not match
 //                 rather than guessing.
-#include "mfx_internal.h"
-#include "mfx_kernels.h"
+#include "mfx_db_internal.h"
 #include "mfx_grow.h"
-#include "mfx_merge.h"
-#include "mfx_join.h"
-#include "mfx_spectrum.h"
-#include "mfx_trio.h"
-#include "mfx_diploid.h"
 #include "mfx_kstar.h"
 #include "mfx_pipe.h"
 #include "mfx_place.h"
@@ -70,14 +64,7 @@ int base_code(unsigned char c) {
   }
 }
 
-// ---- flat binary ------------------------------------------------------------
-struct FlatHeader {
-  char     magic[8];     // "MFXKMER1"
-  uint32_t k;
-  uint32_t flags;        // bit 0: canonical; bit 1: PACKED records (k <= 21); bit 2: DELTA-coded blocks (sorted k-mers, k <= 31)
-  uint64_t n;
-  uint64_t n_escape;     // packed: records whose count did not fit the record (was: reserved, 0)
-};
+// ---- flat binary: FlatHeader (mfx_db_internal.h), then ------------------------
 // Payload, plain : n k-mers (8 bytes; 16 for k > 31), then n uint32 counts.
 // Payload, packed: n records {k-mer << 22 | count} (mfx_internal.h MFX_PACKED_*: 8 bytes per k-mer instead of 12 on disk, in
 //                  the staging lanes and over PCIe; a count field of all ones = escape), then the n_escape escaped k-mers
@@ -91,21 +78,19 @@ struct FlatHeader {
 //                  makes block + escapes smallest): 2.5-3 bytes per k-mer of a 30x human read set.  Blocks are decoded by the
 //                  kernel that inserts them (mfx_table_add_delta_kernel): on disk, in the staging lanes and over PCIe the
 //                  database is a third of its packed size.
-constexpr uint32_t FLAT_PACKED = 2u;
-constexpr uint32_t FLAT_DELTA = 4u;
 // Payload, placed: a delta-coded file whose records are not the k-mers but the numbers P of mfx_place.h -- one to one with the canonical
 //                  k-mers, ascending P = ascending LINE of the compact table, for a table of any size (13 <= k <= 30) -- in ascending
 //                  order: what `merfin -convert -placed` makes.  The table's update kernel then walks the table line after line instead
 //                  of reading a random line per record (mfx_table_add_placed_kernel).  Directory and blocks as in the delta form with P
 //                  in the k-mer's place (2k + 3 bits); the escape list holds k-mers.  Bits 8-15 of `flags`: MFX_PLACE_VERSION of the
 //                  functions that made P (another version is refused: convert again).
-constexpr uint32_t FLAT_PLACED = 8u;
 inline uint32_t flat_place_version(const FlatHeader &h) { return (h.flags >> 8) & 0xffu; }
 
 // The header's counts are bounded by the file's size BEFORE any arithmetic uses them (a damaged or crafted header must end in
 // MFX_E_FORMAT, never in a wrapped size check, a std::length_error through the C ABI or an out-of-bounds scatter): every
 // escape takes 12 bytes; a k-mer takes 8 (16) + 4 bytes plain, 8 packed, and at least 2 bits delta-coded (vbits >= 2).
 // nullptr = acceptable, else what is wrong.
+}  // namespace
 const char *flat_header_problem(const FlatHeader &h, uint64_t fsize) {
   if (memcmp(h.magic, "MFXKMER1", 8) != 0) return "bad magic (not a flat k-mer file)";
   if (h.k < 1 || h.k > (uint32_t)MFX_MAX_K) return "k out of range";
@@ -131,8 +116,7 @@ const char *flat_header_problem(const FlatHeader &h, uint64_t fsize) {
   if (h.n_escape > h.n) return "more escapes than k-mers";
   return nullptr;
 }
-// a k-mer of k <= 31 bases has no bit at or above 2k
-inline bool flat_key_fits(uint64_t key, uint32_t k) { return k >= 32 || (key >> (2 * k)) == 0; }
+namespace {
 // bits of a record's key: the k-mer's 2k, or the 2k + 3 of a placed record
 inline uint32_t flat_rec_bits(const FlatHeader &h) { return (h.flags & FLAT_PLACED) ? (uint32_t)mfx_p_bits((int)h.k) : 2u * h.k; }
 inline bool flat_rec_fits(uint64_t key, const FlatHeader &h) { const uint32_t b = flat_rec_bits(h); return b >= 64 || (key >> b) == 0; }
@@ -440,6 +424,7 @@ int for_each_meryl_file(F &&fn) {
   return bad_rc == MFX_OK ? MFX_OK : mfx_fail(bad_rc, "%s", bad_msg.c_str());
 }
 
+}  // namespace
 int detect(const std::string &path) {
   if (is_dir(path)) return MFX_DB_MERYL;
   if (!is_file(path)) return 0;
@@ -451,6 +436,7 @@ int detect(const std::string &path) {
   if (r == 8 && memcmp(m, "MFXKMER1", 8) == 0) return MFX_DB_FLAT;
   return MFX_DB_TEXT;
 }
+namespace {
 
 // batches (kmer,value) pairs into the index
 struct Feeder {
@@ -772,6 +758,7 @@ int load_flat_escapes(mfx_index *const *ixs, uint32_t nix, int fd, const char *p
 }
 
 // the block directory of a delta-coded file, read and checked; *expect_out: where the blocks end (the escape list follows)
+}  // namespace
 int read_delta_directory(int fd, const char *path, const FlatHeader &h, uint64_t fsize, std::vector<uint64_t> &dir, uint64_t *nblocks_out,
                          uint64_t *expect_out) {
   auto bad = [&](const char *what) { return mfx_fail(MFX_E_FORMAT, "'%s': %s", path, what); };
@@ -807,6 +794,7 @@ int read_delta_directory(int fd, const char *path, const FlatHeader &h, uint64_t
   *expect_out = expect;
   return MFX_OK;
 }
+namespace {
 
 int load_flat_delta(mfx_index *const *ixs, uint32_t nix, int fd, const char *path, const FlatHeader &h, uint64_t fsize, int side,
                     uint64_t minV, uint64_t maxV) {
@@ -849,7 +837,7 @@ int mfx_flat_delta_open(const char *path, int *fd_out, mfx_flat_delta_info *info
 
 // merylFileReader(path): opens the DB and reveals k (merfin-globals.C:118-119:
 // "Make readDB first so we know the k size").
-static int mfx_db_probe_impl(const char *path, mfx_db_info *out) {
+int mfx_db_probe_impl(const char *path, mfx_db_info *out) {
   if (!path || !out) return mfx_fail(MFX_E_INVAL, "mfx_db_probe: null argument");
   memset(out, 0, sizeof(*out));
   std::string p(path);
@@ -895,9 +883,7 @@ static int mfx_db_probe_impl(const char *path, mfx_db_info *out) {
 }
 
 extern "C" int mfx_db_probe(const char *path, mfx_db_info *out) {
-  try { return mfx_db_probe_impl(path, out); }                       // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_probe: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_probe: %s", e.what()); }
+  return db_guard("mfx_db_probe", [&] { return mfx_db_probe_impl(path, out); });
 }
 
 
@@ -1002,9 +988,7 @@ static int mfx_index_load_db_multi_impl(mfx_index *const *ixs, uint32_t nix, con
 }
 
 extern "C" int mfx_index_load_db_multi(mfx_index *const *ixs, uint32_t nix, const char *path, int side, uint64_t minV, uint64_t maxV) {
-  try { return mfx_index_load_db_multi_impl(ixs, nix, path, side, minV, maxV); }                       // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_index_load_db_multi: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_index_load_db_multi: %s", e.what()); }
+  return db_guard("mfx_index_load_db_multi", [&] { return mfx_index_load_db_multi_impl(ixs, nix, path, side, minV, maxV); });
 }
 
 
@@ -1054,9 +1038,7 @@ static int mfx_db_write_flat_impl(const char *path, int k, const uint64_t *kmers
 }
 
 extern "C" int mfx_db_write_flat(const char *path, int k, const uint64_t *kmers, const uint32_t *values, uint64_t n) {
-  try { return mfx_db_write_flat_impl(path, k, kmers, values, n); }                       // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_write_flat: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_write_flat: %s", e.what()); }
+  return db_guard("mfx_db_write_flat", [&] { return mfx_db_write_flat_impl(path, k, kmers, values, n); });
 }
 
 
@@ -1357,9 +1339,7 @@ static int mfx_db_write_flat_placed_impl(const char *path, int k, const uint64_t
   return rc;
 }
 extern "C" int mfx_db_write_flat_placed(const char *path, int k, const uint64_t *pkeys, const uint32_t *values, uint64_t n) {
-  try { return mfx_db_write_flat_placed_impl(path, k, pkeys, values, n); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_write_flat_placed: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_write_flat_placed: %s", e.what()); }
+  return db_guard("mfx_db_write_flat_placed", [&] { return mfx_db_write_flat_placed_impl(path, k, pkeys, values, n); });
 }
 
 // P of n canonical k-mers, on the host (mfx_place.h; the device form: mfx_db_place_keys in mfx_api.cpp)
@@ -1431,15 +1411,11 @@ static int mfx_db_convert_placed_impl(const char *in_path, const char *out_path,
   return mfx_db_write_flat_placed_impl(out_path, k, mk.data(), mv.data(), N, sb.data());
 }
 extern "C" int mfx_db_convert_placed(const char *in_path, const char *out_path, uint64_t *n_out) {
-  try { return mfx_db_convert_placed_impl(in_path, out_path, n_out); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_convert_placed: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_convert_placed: %s", e.what()); }
+  return db_guard("mfx_db_convert_placed", [&] { return mfx_db_convert_placed_impl(in_path, out_path, n_out); });
 }
 
 extern "C" int mfx_db_convert(const char *in_path, const char *out_path, uint64_t *n_out) {
-  try { return mfx_db_convert_impl(in_path, out_path, n_out); }                       // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_convert: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_convert: %s", e.what()); }
+  return db_guard("mfx_db_convert", [&] { return mfx_db_convert_impl(in_path, out_path, n_out); });
 }
 
 
@@ -1453,13 +1429,6 @@ extern "C" int mfx_db_convert(const char *in_path, const char *out_path, uint64_
 constexpr int MFX_DB_BIN_BITS = 12;
 constexpr uint64_t MFX_DB_RANGE_DEFAULT = 1ull << 28;        // entries per range: 2 x 12 bytes x 2^28 = 6 GB of device buffers + the sort's
 
-namespace {
-struct DbDev {                                                 // device buffers of one call, freed on every way out
-  void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~DbDev() { for (void *x : p) if (x) (void)hipFree(x); }
-};
-}  // namespace
-
 // the refusals of mfx_index_write_db, for everything that reads a side of a full table by key bins; `who`: the entry point, for the texts
 static int db_side_checks(const mfx_index *ix, int side, const char *who) {
   if (side != 0 && side != 1) return mfx_fail(MFX_E_INVAL, "%s: side %d (0: the read counts, 1: the assembly counts)", who, side);
@@ -1468,14 +1437,6 @@ static int db_side_checks(const mfx_index *ix, int side, const char *who) {
   if (ix->shard_n > 1) return mfx_fail(MFX_E_INVAL, "%s: a sharded index holds part of a database only", who);
   return MFX_OK;
 }
-
-namespace {
-struct DeviceBack {                                            // the caller's device again on every way out
-  int d = -1;
-  DeviceBack() { if (hipGetDevice(&d) != hipSuccess) d = -1; }
-  ~DeviceBack() { if (d >= 0) (void)hipSetDevice(d); }
-};
-}  // namespace
 
 // bins[key >> shift] of the side's entries, on the host (nbins = 2^min(2k, 12)); d_bins: nbins + 1 device words, the last left zero
 static int db_side_bins(const mfx_index *ix, int side, uint64_t *d_bins, std::vector<uint64_t> &bins) {
@@ -1508,37 +1469,6 @@ extern "C" int mfx_index_key_bins(const mfx_index *ix, int side, uint64_t *bins,
   try { return mfx_index_key_bins_impl(ix, side, bins, nbins); }
   catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_index_key_bins: out of memory"); }
 }
-
-// the writer that takes several tables (mfx_db_writer_*): the host arrays of the database so far, ascending
-struct mfx_db_writer {
-  std::string path;
-  int k = 0;
-  std::vector<uint64_t> keys;
-  std::vector<uint32_t> vals;
-  // the streamed kind (mfx_db_writer_open_streamed): the blocks go to the spool <path>.blocks as they are made.  What stays on the host is
-  // the directory (16 bytes per MFX_DELTA_BLOCK k-mers), the escapes and the carry: the fewer than MFX_DELTA_BLOCK pairs behind the last
-  // full block.  close writes header and directory, puts the spool behind them, then the escapes: the bytes of write_flat_delta.
-  bool streamed = false;
-  std::string spool;
-  int fd = -1;
-  uint64_t n = 0, spool_bytes = 0;                             // k-mers appended (those of the carry too); bytes of the spool
-  std::vector<uint64_t> dir;                                   // per block written: its first k-mer, its spool offset | kb << 48 | vb << 56
-  std::vector<uint64_t> ek;                                    // the escapes, in the file's order
-  std::vector<uint32_t> ev;
-  std::vector<uint64_t> ck;                                    // the carry
-  std::vector<uint32_t> cv;
-  uint64_t last = 0;                                           // the last k-mer appended (n > 0)
-  size_t bounce = 16u << 20;                                   // bytes of one pinned bounce buffer (MFX_DB_BOUNCE, read at open)
-  double t_export = 0, t_sort = 0, t_plan = 0, t_pack = 0, t_copy = 0, t_spool = 0;      // MFX_DB_TIMING
-  bool merging = false;                                        // mfx_db_merge's writer: its split has these in the place of export and sort
-  double t_read = 0, t_decode = 0, t_merge = 0, t_combine = 0;
-  ~mfx_db_writer() {
-    if (fd >= 0) close(fd);
-    if (streamed && !spool.empty()) unlink(spool.c_str());
-  }
-};
-
-static double db_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static int spool_write(mfx_db_writer *w, const void *p, uint64_t bytes) {         // behind the spool's end
   const char *c = (const char *)p;
@@ -1627,17 +1557,6 @@ static int stream_append_host(mfx_db_writer *w, const uint64_t *kmers, const uin
 }
 
 // the device part: the side's entries, by key ranges compacted out of the table, sorted and copied behind what the writer holds
-namespace {
-struct DbBounce {                                              // two pinned buffers and their events: the packed bytes' way to the spool
-  void *pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~DbBounce() {
-    for (void *x : pin) if (x) (void)hipHostFree(x);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
-
 // `bytes` of device memory behind the spool's end: the copy of piece i + 1 runs while piece i is written
 static int spool_from_device(mfx_db_writer *w, DbBounce &B, const char *src, uint64_t bytes, double &t_copy, double &t_write) {
   const uint64_t piece = w->bounce;
@@ -1660,20 +1579,7 @@ static int spool_from_device(mfx_db_writer *w, DbBounce &B, const char *src, uin
   return MFX_OK;
 }
 
-namespace {
-// what stream_append_device needs beside the pairs, for appends of at most `cap` pairs (the carry in front of them counted): plan and offsets
-// of the blocks on the device and on the host, the escapes' buffers (grown to what an append escapes), the bounce buffers
-struct StreamDev {
-  DbDev D;                                                     // p[0]: plan and offsets of the blocks; p[1], p[2]: the escapes' k-mers and counts
-  DbBounce B;
-  uint64_t cap = 0, maxb = 0, esc_cap = 0;
-  std::vector<mfx_delta_plan> plan;
-  std::vector<uint64_t> woff;
-  std::vector<uint32_t> eoff;
-};
-}  // namespace
-
-static int stream_dev_init(StreamDev &S, const mfx_db_writer *w, uint64_t cap, const char *who, const char *knob) {
+int stream_dev_init(StreamDev &S, const mfx_db_writer *w, uint64_t cap, const char *who, const char *knob) {
   S.cap = cap;
   S.maxb = cap / MFX_DELTA_BLOCK;
   if (hipMalloc(&S.D.p[0], (S.maxb ? S.maxb : 1) * (sizeof(mfx_delta_plan) + 8 + 4)) != hipSuccess) {
@@ -1691,7 +1597,7 @@ static int stream_dev_init(StreamDev &S, const mfx_db_writer *w, uint64_t cap, c
 // writer's carry (w->ck.size() when the arrays were filled), c + rn <= S.cap.  The carry is uploaded in front of them, the full blocks are
 // planned and packed on the device (mfx_sort.hip) into d_out (out_bytes of it; 12 bytes a pair hold any block) and reach the spool through
 // the bounce buffers; what is left is the next carry.  The first k-mer must lie above the writer's last.  A failure adds nothing.
-static int stream_append_device(mfx_db_writer *w, StreamDev &S, uint64_t *s_keys, uint32_t *s_vals, uint64_t rn, uint64_t *d_out, uint64_t out_bytes,
+int stream_append_device(mfx_db_writer *w, StreamDev &S, uint64_t *s_keys, uint32_t *s_vals, uint64_t rn, uint64_t *d_out, uint64_t out_bytes,
                                 const char *who, const char *knob) {
   StreamUndo undo(w);
   const uint64_t c = w->ck.size(), m = c + rn, nb = m / MFX_DELTA_BLOCK, rem = m % MFX_DELTA_BLOCK;
@@ -1931,7 +1837,7 @@ extern "C" int mfx_db_writer_append_index(mfx_db_writer *w, const mfx_index *ix,
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_writer_append_index: %s", e.what()); }
 }
 
-static int db_open_streamed(const char *path, int k, mfx_db_writer **out) {
+int db_open_streamed(const char *path, int k, mfx_db_writer **out) {
   *out = nullptr;
   if (!path) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_open_streamed: null argument");
   if (k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_open_streamed: the sorted form holds 1 <= k <= %d; k = %d", MFX_MAX_K_NARROW, k);
@@ -1983,9 +1889,7 @@ static int db_append_sorted(mfx_db_writer *w, const uint64_t *kmers, const uint3
 
 extern "C" int mfx_db_writer_append_sorted(mfx_db_writer *w, const uint64_t *kmers, const uint32_t *values, uint64_t n) {
   if (!w || (n && (!kmers || !values))) return mfx_fail(MFX_E_INVAL, "mfx_db_writer_append_sorted: null argument");
-  try { return db_append_sorted(w, kmers, values, n); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_writer_append_sorted: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_writer_append_sorted: %s", e.what()); }
+  return db_guard("mfx_db_writer_append_sorted", [&] { return db_append_sorted(w, kmers, values, n); });
 }
 
 extern "C" int mfx_db_writer_info(const mfx_db_writer *w, uint64_t *kmers, uint64_t *blocks, uint64_t *escapes, uint64_t *spool_bytes, uint64_t *held_bytes) {
@@ -2095,9 +1999,7 @@ extern "C" int mfx_index_write_db_streamed(const mfx_index *ix, int side, const 
   mfx_db_writer *w = nullptr;
   if (int rc = db_open_streamed(path, ix->k, &w)) return rc;
   int rc;
-  try { rc = db_append_index(w, ix, side, nullptr, "mfx_index_write_db_streamed"); }
-  catch (const std::bad_alloc &) { rc = mfx_fail(MFX_E_NOMEM, "mfx_index_write_db_streamed: out of memory"); }
-  catch (const std::exception &e) { rc = mfx_fail(MFX_E_IO, "mfx_index_write_db_streamed: %s", e.what()); }
+  rc = db_guard("mfx_index_write_db_streamed", [&] { return db_append_index(w, ix, side, nullptr, "mfx_index_write_db_streamed"); });
   if (rc) { mfx_db_writer_abort(w); return rc; }
   return mfx_db_writer_close(w, n_kmers);
 }
@@ -2108,1138 +2010,6 @@ extern "C" int mfx_index_write_db(const mfx_index *ix, int side, const char *pat
   catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_index_write_db: %s", e.what()); }
 }
 
-
-// ---------------------------------------------------------------------------
-// mfx_db_merge: sorted, delta-coded databases combined window by window (include/merfin_amd.h; the windows: mfx_merge.h; the kernels:
-// mfx_merge.hip).  file blocks -> ascending runs on the device -> merged and combined -> stream_append_device; no table in between.
-// ---------------------------------------------------------------------------
-static_assert(MFX_MERGE_BLOCK == MFX_DELTA_BLOCK, "mfx_merge.h plans in blocks of the delta form");
-
-namespace {
-struct MergeIn {                                               // one input: header, directory and escapes on the host, the blocks in the file
-  std::string path;
-  int fd = -1;
-  FlatHeader h;
-  std::vector<uint64_t> dir;
-  uint64_t nblocks = 0;
-  std::vector<uint64_t> ek;
-  std::vector<uint32_t> ev;
-  MergeIn() = default;
-  MergeIn(const MergeIn &) = delete;
-  MergeIn &operator=(const MergeIn &) = delete;
-  ~MergeIn() { if (fd >= 0) close(fd); }
-  uint64_t off(uint64_t b) const { return dir[2 * b + 1] & 0xffffffffffffull; }
-};
-struct WriterAbort {                                           // the writer of a call that does not reach close: the spool goes with it
-  mfx_db_writer *w = nullptr;
-  ~WriterAbort() { if (w) mfx_db_writer_abort(w); }
-};
-}  // namespace
-
-// header, directory and escape list of an input, by the loader's checks; every refusal names the file
-static int merge_open_input(const char *path, MergeIn &in, const char *who = "mfx_db_merge") {
-  in.path = path;
-  const int fmt = detect(in.path);
-  if (!fmt) return mfx_fail(MFX_E_IO, "%s: the input '%s' does not exist", who, path);
-  if (fmt == MFX_DB_MERYL) return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a meryl directory; the inputs are sorted flat databases: run `merfin -convert` first", who, path);
-  if (fmt == MFX_DB_TEXT) return mfx_fail(MFX_E_FORMAT, "%s: '%s' is not a flat k-mer file (`meryl print` text?); the inputs are sorted flat databases: run `merfin -convert` first", who, path);
-  in.fd = open(path, O_RDONLY | O_CLOEXEC);
-  struct stat st;
-  if (in.fd < 0 || fstat(in.fd, &st) != 0) return mfx_fail(MFX_E_IO, "cannot open '%s'", path);
-  const uint64_t fsize = (uint64_t)st.st_size;
-  if (fsize < sizeof(in.h) || pread(in.fd, &in.h, sizeof(in.h), 0) != (ssize_t)sizeof(in.h)) return mfx_fail(MFX_E_FORMAT, "'%s': truncated header", path);
-  if (const char *why = flat_header_problem(in.h, fsize)) return mfx_fail(MFX_E_FORMAT, "'%s': %s", path, why);
-  if (in.h.flags & FLAT_PLACED)
-    return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a placed database; the inputs are sorted by k-mer: merge those, then place the result (merfin -convert -placed)", who, path);
-  if (in.h.n == 0) return MFX_OK;                               // (no k-mers: what mfx_db_write_flat writes for none has no blocks in any form)
-  if (!(in.h.flags & FLAT_DELTA))
-    return mfx_fail(MFX_E_FORMAT, "%s: '%s' is a %s flat file, not a sorted one: run `merfin -convert` first", who, path, (in.h.flags & FLAT_PACKED) ? "packed" : "plain");
-  uint64_t expect = 0;
-  if (int rc = read_delta_directory(in.fd, path, in.h, fsize, in.dir, &in.nblocks, &expect)) return rc;
-  const uint64_t ne = in.h.n_escape;
-  try { in.ek.resize(ne); in.ev.resize(ne); }
-  catch (const std::exception &) { return mfx_fail(MFX_E_NOMEM, "'%s': no memory for %lu escapes", path, (unsigned long)ne); }
-  if (ne && (pread(in.fd, in.ek.data(), ne * 8, (off_t)expect) != (ssize_t)(ne * 8) || pread(in.fd, in.ev.data(), ne * 4, (off_t)(expect + ne * 8)) != (ssize_t)(ne * 4)))
-    return mfx_fail(MFX_E_IO, "reading '%s' failed", path);
-  for (uint64_t i = 0; i < ne; ++i) {
-    if (!flat_key_fits(in.ek[i], in.h.k)) return mfx_fail(MFX_E_FORMAT, "'%s': an escaped k-mer is wider than 2k bits", path);
-    if (i && in.ek[i] <= in.ek[i - 1]) return mfx_fail(MFX_E_FORMAT, "'%s': the escape list of a sorted database does not ascend", path);
-  }
-  return MFX_OK;
-}
-
-// every check of mfx_db_merge that needs no device: the arguments, the inputs (opened into `ins`), their k, the output's identity
-static int merge_check(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, std::vector<std::unique_ptr<MergeIn>> &ins) {
-  if (!in_paths || !out_path || !o) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: null argument");
-  if (n_in == 0 || n_in > MFX_MERGE_MAX_INPUTS) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: %u inputs (1 to %u)", n_in, MFX_MERGE_MAX_INPUTS);
-  if (o->op != MFX_MERGE_SUM && o->op != MFX_MERGE_MAX && o->op != MFX_MERGE_MIN && o->op != MFX_MERGE_INTERSECT)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_merge: unknown operation %d (MFX_MERGE_SUM, _MAX, _MIN, _INTERSECT)", o->op);
-  if (o->minV > o->maxV) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: the filter keeps nothing (min %llu > max %llu)", (unsigned long long)o->minV, (unsigned long long)o->maxV);
-  for (uint32_t i = 0; i < n_in; ++i) {
-    if (!in_paths[i]) return mfx_fail(MFX_E_INVAL, "mfx_db_merge: null argument");
-    ins.emplace_back(new MergeIn);
-    if (int rc = merge_open_input(in_paths[i], *ins.back())) return rc;
-    if (ins[i]->h.k != ins[0]->h.k)
-      return mfx_fail(MFX_E_INVAL, "mfx_db_merge: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", in_paths[i], ins[i]->h.k, in_paths[0], ins[0]->h.k);
-  }
-  struct stat so;
-  if (stat(out_path, &so) == 0)
-    for (uint32_t i = 0; i < n_in; ++i) {
-      struct stat si;
-      if (fstat(ins[i]->fd, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)
-        return mfx_fail(MFX_E_INVAL, "mfx_db_merge: the output '%s' is the input '%s'", out_path, in_paths[i]);
-    }
-  return MFX_OK;
-}
-
-// ---- what mfx_db_merge and mfx_db_join_* share: the windows of the opened inputs, and a window's blocks decoded into one dense run per input
-namespace {
-struct MergeWindows {                                          // the plan (mfx_merge.h) and what the largest window takes
-  std::vector<mfx_merge_input> pin;
-  std::vector<mfx_merge_window> win;
-  std::vector<uint64_t> blk;
-  uint64_t n_all = 0, max_pairs = 0, max_bytes = 0, max_tasks = 0, max_esc = 0;
-};
-struct MergeRun { uint64_t off, len; };
-struct MergeDecoder {                                          // a window's way from the files to the runs; the caller owns the device buffers
-  void *d_words = nullptr;                                     // max_bytes + 8: the window's blocks
-  mfx_merge_task *d_tasks = nullptr;                           // max_tasks
-  uint32_t *d_below = nullptr, *d_above = nullptr, *d_err = nullptr;      // max_tasks, max_tasks, one per input
-  uint64_t *d_ek = nullptr;                                    // max_esc + 1: the window's escapes
-  uint32_t *d_ev = nullptr;
-  void *pinned = nullptr;                                      // max_bytes + 8 on the host: the blocks on their way to the device
-  std::vector<mfx_merge_task> tasks;
-  std::vector<uint64_t> hek, run_off, run_len, first_task;
-  std::vector<uint32_t> hev, cnt, errs;
-  std::vector<MergeRun> runs;                                  // per input: its dense run of the window in the decoded buffer
-  double t_read = 0, t_decode = 0;                             // of the last window
-  uint32_t zero_from = ~0u;                                    // mfx_db_merge_except: the inputs from this one on are subtracted
-  MergeDecoder() = default;
-  MergeDecoder(const MergeDecoder &) = delete;
-  MergeDecoder &operator=(const MergeDecoder &) = delete;
-  ~MergeDecoder() { if (pinned) (void)hipHostFree(pinned); }
-};
-}  // namespace
-
-static uint64_t merge_range_knob() {
-  uint64_t R = MFX_MERGE_RANGE_DEFAULT;
-  if (const char *e = getenv("MFX_MERGE_RANGE")) {             // read per call: tests reach many windows on small files
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < R) R = (uint64_t)v;
-  }
-  return R;
-}
-
-static int merge_plan_windows(const std::vector<std::unique_ptr<MergeIn>> &ins, int k, const char *who, MergeWindows &P) {
-  const uint32_t n_in = (uint32_t)ins.size();
-  P.pin.resize(n_in);
-  for (uint32_t i = 0; i < n_in; ++i) { P.pin[i] = mfx_merge_input{ins[i]->dir.data(), 2u, ins[i]->nblocks, ins[i]->h.n}; P.n_all += ins[i]->h.n; }
-  mfx_merge_plan(P.pin.data(), n_in, k, merge_range_knob(), P.win, P.blk);
-  for (size_t w = 0; w < P.win.size(); ++w) {
-    uint64_t bytes = 0, tasks = 0, esc = 0;
-    for (uint32_t i = 0; i < n_in; ++i) {
-      const uint64_t b0 = P.blk[2 * (w * n_in + i)], b1 = P.blk[2 * (w * n_in + i) + 1];
-      if (b1 <= b0) continue;
-      bytes += ins[i]->off(b1) - ins[i]->off(b0);
-      tasks += b1 - b0;
-      uint64_t e0, e1;
-      mfx_merge_escape_slice(ins[i]->ek.data(), ins[i]->ek.size(), P.win[w].lo, P.win[w].hi, &e0, &e1);
-      esc += e1 - e0;
-    }
-    P.max_pairs = std::max(P.max_pairs, P.win[w].pairs); P.max_bytes = std::max(P.max_bytes, bytes);
-    P.max_tasks = std::max(P.max_tasks, tasks); P.max_esc = std::max(P.max_esc, esc);
-  }
-  if (P.max_pairs > 0x7fffffffull || P.max_esc > 0x7fffffffull)
-    return mfx_fail(MFX_E_INVAL, "%s: a window of %lu pairs (at most 2^31 - 1); lower MFX_MERGE_RANGE", who, (unsigned long)P.max_pairs);
-  return MFX_OK;
-}
-
-// window wi: its blocks read (pread) and decoded on the device into keys / vals, D.runs the inputs' dense runs in them.  A block that decodes
-// what no writer makes ends in MFX_E_FORMAT, naming the file.
-static int merge_decode_window(const std::vector<std::unique_ptr<MergeIn>> &ins, const MergeWindows &P, size_t wi, int k, const char *who, MergeDecoder &D,
-                               uint64_t *keys, uint32_t *vals) {
-  const uint32_t n_in = (uint32_t)ins.size();
-  const uint64_t lo = P.win[wi].lo, hi = P.win[wi].hi, END = mfx_merge_end(k);
-  uint64_t *words = (uint64_t *)D.pinned;
-  D.run_off.resize(n_in); D.run_len.resize(n_in); D.first_task.resize(n_in); D.errs.resize(n_in);
-  D.t_read = D.t_decode = 0;
-  double t0 = db_now();
-  // ---- the window's blocks and escapes, input after input
-  D.tasks.clear(); D.hek.clear(); D.hev.clear();
-  uint64_t nwords = 0, npairs = 0;
-  for (uint32_t i = 0; i < n_in; ++i) {
-    const MergeIn &in = *ins[i];
-    const uint64_t b0 = P.blk[2 * (wi * n_in + i)], b1 = P.blk[2 * (wi * n_in + i) + 1];
-    D.run_off[i] = npairs; D.run_len[i] = 0; D.first_task[i] = D.tasks.size();
-    if (b1 <= b0) continue;
-    const uint64_t from = in.off(b0), bytes = in.off(b1) - from;
-    if ((nwords * 8 + bytes) > P.max_bytes) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is read beyond the buffer)
-    for (uint64_t got = 0; got < bytes;) {
-      const ssize_t r = pread(in.fd, (char *)(words + nwords) + got, bytes - got, (off_t)(from + got));
-      if (r <= 0) return mfx_fail(MFX_E_IO, "reading '%s' failed", in.path.c_str());
-      got += (uint64_t)r;
-    }
-    uint64_t e0, e1;
-    mfx_merge_escape_slice(in.ek.data(), in.ek.size(), lo, hi, &e0, &e1);
-    const uint32_t esc_lo = (uint32_t)D.hek.size(), esc_hi = esc_lo + (uint32_t)(e1 - e0);
-    D.hek.insert(D.hek.end(), in.ek.begin() + e0, in.ek.begin() + e1);
-    D.hev.insert(D.hev.end(), in.ev.begin() + e0, in.ev.begin() + e1);
-    for (uint64_t b = b0; b < b1; ++b) {
-      mfx_merge_task t;
-      t.word_off = nwords + (in.off(b) - from) / 8;
-      t.first = in.dir[2 * b];
-      t.limit = b + 1 < in.nblocks ? in.dir[2 * (b + 1)] : END;
-      t.out = npairs + (b - b0) * MFX_DELTA_BLOCK;
-      t.kb = (uint32_t)(in.dir[2 * b + 1] >> 48) & 0xffu;
-      t.vb = (uint32_t)(in.dir[2 * b + 1] >> 56) & 0xffu;
-      t.cnt = (uint32_t)std::min<uint64_t>(MFX_DELTA_BLOCK, in.h.n - b * MFX_DELTA_BLOCK);
-      t.esc_lo = esc_lo; t.esc_hi = esc_hi; t.input = i;
-      D.tasks.push_back(t);
-    }
-    D.run_len[i] = mfx_merge_block_pairs(P.pin[i], b0, b1);
-    npairs += D.run_len[i];
-    nwords += bytes / 8;
-  }
-  const uint32_t nt = (uint32_t)D.tasks.size();
-  if (npairs != P.win[wi].pairs || npairs > P.max_pairs || nwords * 8 > P.max_bytes || nt > P.max_tasks || D.hek.size() > P.max_esc)
-    return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is decoded beyond the buffers)
-  MFX_HIP(hipMemcpyAsync(D.d_words, words, nwords * 8, hipMemcpyHostToDevice, nullptr));
-  MFX_HIP(hipMemcpyAsync(D.d_tasks, D.tasks.data(), nt * sizeof(mfx_merge_task), hipMemcpyHostToDevice, nullptr));
-  if (!D.hek.empty()) {
-    MFX_HIP(hipMemcpyAsync(D.d_ek, D.hek.data(), D.hek.size() * 8, hipMemcpyHostToDevice, nullptr));
-    MFX_HIP(hipMemcpyAsync(D.d_ev, D.hev.data(), D.hev.size() * 4, hipMemcpyHostToDevice, nullptr));
-  }
-  MFX_HIP(hipMemsetAsync(D.d_err, 0, n_in * 4, nullptr));
-  MFX_HIP(hipStreamSynchronize(nullptr));                      // (the host arrays are filled again for the next window)
-  double t1 = db_now();
-  D.t_read = t1 - t0;
-  // ---- decode: one ascending run per input
-  MFX_HIP(mfx_k_delta_decode(D.d_tasks, nt, (const uint64_t *)D.d_words, D.d_ek, D.d_ev, lo, hi, keys, vals, D.d_below, D.d_above, D.d_err, nullptr, D.zero_from));
-  D.cnt.resize(2 * (size_t)nt);
-  MFX_HIP(hipMemcpyAsync(D.cnt.data(), D.d_below, nt * 4, hipMemcpyDeviceToHost, nullptr));
-  MFX_HIP(hipMemcpyAsync(D.cnt.data() + nt, D.d_above, nt * 4, hipMemcpyDeviceToHost, nullptr));
-  MFX_HIP(hipMemcpyAsync(D.errs.data(), D.d_err, n_in * 4, hipMemcpyDeviceToHost, nullptr));
-  MFX_HIP(hipStreamSynchronize(nullptr));
-  D.t_decode = db_now() - t1;
-  for (uint32_t i = 0; i < n_in; ++i)
-    if (D.errs[i])
-      return mfx_fail(MFX_E_FORMAT, "'%s': a block holds what no writer makes (%s%s%s): the file is damaged", ins[i]->path.c_str(),
-                      (D.errs[i] & MFX_MERGE_ERR_ORDER) ? "k-mers that do not ascend below the next block's first; " : "",
-                      (D.errs[i] & MFX_MERGE_ERR_ESCAPE) ? "an escaped count that is not in the escape list; " : "", (D.errs[i] & MFX_MERGE_ERR_ZERO) ? "a count of zero; " : "");
-  D.runs.clear();
-  for (uint32_t i = 0; i < n_in; ++i) {
-    const uint64_t f = D.first_task[i], l = (i + 1 < n_in ? D.first_task[i + 1] : nt);
-    MergeRun r{0, 0};
-    // (ascending k-mers below every block's limit: only an input's first block reaches under lo, only its last to hi and beyond)
-    if (!mfx_join_trim(D.run_off[i], D.run_len[i], D.cnt.data() + f, D.cnt.data() + nt + f, l - f, &r.off, &r.len))
-      return mfx_fail(MFX_E_FORMAT, "'%s': the k-mers of a block lie outside its place in the directory", ins[i]->path.c_str());
-    D.runs.push_back(r);
-  }
-  return MFX_OK;
-}
-
-// not_paths: the databases whose k-mers are not written (mfx_db_merge_except); they are opened behind the inputs, share their windows and are
-// decoded with counts of 0, which the combine kernel takes as "this k-mer is barred".  n_not == 0: mfx_db_merge.
-static int mfx_db_merge_impl(const char *const *in_paths, uint32_t n_in, const char *const *not_paths, uint32_t n_not, const char *out_path, const mfx_db_merge_opts *o,
-                             mfx_db_merge_stats *st, uint64_t *n_subtracted) {
-  const char *who = n_not ? "mfx_db_merge_except" : "mfx_db_merge";
-  if (st) memset(st, 0, sizeof(*st));
-  if (n_subtracted) *n_subtracted = 0;
-  std::vector<std::unique_ptr<MergeIn>> ins;
-  if (n_not && (!not_paths || (uint64_t)n_in + n_not > MFX_MERGE_MAX_INPUTS))
-    return not_paths ? mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: %u inputs and %u to subtract (%u files at the most)", n_in, n_not, MFX_MERGE_MAX_INPUTS)
-                     : mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: null argument");
-  if (int rc = merge_check(in_paths, n_in, out_path, o, ins)) return rc;
-  const int k = (int)ins[0]->h.k;
-  uint64_t n_read = 0;
-  for (uint32_t i = 0; i < n_in; ++i) n_read += ins[i]->h.n;
-  for (uint32_t j = 0; j < n_not; ++j) {
-    if (!not_paths[j]) return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: null argument");
-    ins.emplace_back(new MergeIn);
-    if (int rc = merge_open_input(not_paths[j], *ins.back(), who)) return rc;
-    if ((int)ins.back()->h.k != k)
-      return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: '%s' holds %u-mers, '%s' %u-mers: the inputs and what is subtracted are of one k", not_paths[j], ins.back()->h.k,
-                      in_paths[0], ins[0]->h.k);
-    struct stat so, si;
-    if (stat(out_path, &so) == 0 && fstat(ins.back()->fd, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)
-      return mfx_fail(MFX_E_INVAL, "mfx_db_merge_except: the output '%s' is the subtracted database '%s'", out_path, not_paths[j]);
-  }
-  const uint32_t n_all_in = n_in + n_not;
-  // ---- the windows, and what the largest of them takes
-  MergeWindows P;
-  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
-  const std::vector<mfx_merge_window> &win = P.win;
-  const uint64_t n_all = n_read, max_pairs = P.max_pairs, max_bytes = P.max_bytes, max_tasks = P.max_tasks, max_esc = P.max_esc;
-  mfx_db_writer *w = nullptr;
-  if (int rc = db_open_streamed(out_path, k, &w)) return rc;
-  WriterAbort guard{w};
-  w->merging = true;
-  if (max_pairs) {
-    DeviceBack back;
-    MFX_HIP(hipSetDevice(o->device));
-    // p[0], p[1]: two buffers of cap pairs, the k-mers in front of the counts: decoded runs, merge levels, combined pairs behind the writer's carry,
-    // and the packed words of the one that is free by then.  p[2]: the window's blocks.  p[3]: tasks, their below / above, the inputs' error words,
-    // the stats, the combine's tile offsets.  p[4], p[5]: the window's escapes.
-    const uint64_t cap = max_pairs + MFX_DELTA_BLOCK, tiles = mfx_combine_tiles(max_pairs);
-    const uint64_t small = max_tasks * (sizeof(mfx_merge_task) + 8) + (tiles + 1 + 3) * 8 + n_all_in * 4 + 64;
-    DbDev D;
-    hipError_t e = hipMalloc(&D.p[0], cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&D.p[1], cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&D.p[2], max_bytes + 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[3], small);
-    if (e == hipSuccess) e = hipMalloc(&D.p[4], (max_esc + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[5], (max_esc + 1) * 4);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who, (unsigned long)max_pairs,
-                      ((double)cap * 24 + (double)max_bytes + (double)max_esc * 12 + (double)small) / 1e9, hipGetErrorString(e));
-    }
-    uint64_t *bk[2] = {(uint64_t *)D.p[0], (uint64_t *)D.p[1]};
-    uint32_t *bv[2] = {(uint32_t *)((char *)D.p[0] + cap * 8), (uint32_t *)((char *)D.p[1] + cap * 8)};
-    uint64_t *d_tile = (uint64_t *)D.p[3], *d_stats = d_tile + tiles + 1;
-    mfx_merge_task *d_tasks = (mfx_merge_task *)(d_stats + 3);
-    uint32_t *d_below = (uint32_t *)(d_tasks + max_tasks), *d_above = d_below + max_tasks, *d_err = d_above + max_tasks;
-    MFX_HIP(mfx_memset_now(d_stats, 0, 24));
-    StreamDev S;
-    if (int rc = stream_dev_init(S, w, cap, who, "MFX_MERGE_RANGE")) return rc;
-    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
-    MergeDecoder dec;
-    if (n_not) dec.zero_from = n_in;
-    dec.d_words = D.p[2]; dec.d_tasks = d_tasks; dec.d_below = d_below; dec.d_above = d_above; dec.d_err = d_err;
-    dec.d_ek = (uint64_t *)D.p[4]; dec.d_ev = (uint32_t *)D.p[5];
-    MFX_HIP(hipHostMalloc(&dec.pinned, max_bytes + 8, hipHostMallocDefault));
-    typedef MergeRun Run;
-    std::vector<Run> &runs = dec.runs, next;
-    for (size_t wi = 0; wi < win.size(); ++wi) {
-      if (win[wi].pairs == 0) continue;
-      // ---- read and decode: one ascending run per input in buffer 0
-      const int rc_dec = merge_decode_window(ins, P, wi, k, who, dec, bk[0], bv[0]);
-      w->t_read += dec.t_read; w->t_decode += dec.t_decode;
-      if (rc_dec) return rc_dec;
-      double t0 = db_now(), t1;
-      // ---- merge: a pairwise tree, from one buffer to the other
-      int cur = 0;
-      while (runs.size() > 1) {
-        next.clear();
-        uint64_t at = 0;
-        for (size_t j = 0; j < runs.size(); j += 2) {
-          const Run a = runs[j], b = j + 1 < runs.size() ? runs[j + 1] : Run{0, 0};
-          MFX_HIP(mfx_k_merge_pairs(bk[cur] + a.off, bv[cur] + a.off, a.len, bk[cur] + b.off, bv[cur] + b.off, b.len, bk[cur ^ 1] + at, bv[cur ^ 1] + at, nullptr));
-          next.push_back(Run{at, a.len + b.len});
-          at += a.len + b.len;
-        }
-        runs.swap(next);
-        cur ^= 1;
-      }
-      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
-      t1 = db_now();
-      w->t_merge += t1 - t0;
-      // ---- combine and filter: behind the place of the writer's carry in the other buffer
-      const uint64_t M = runs[0].len, c = w->ck.size();
-      uint64_t n_out = 0;
-      if (M) {
-        const uint64_t mt = mfx_combine_tiles(M);
-        MFX_HIP(mfx_k_combine(bk[cur] + runs[0].off, bv[cur] + runs[0].off, M, n_in, o->op, o->minV, o->maxV, d_tile, bk[cur ^ 1] + c, bv[cur ^ 1] + c, d_stats, nullptr));
-        MFX_HIP(hipMemcpyAsync(&n_out, d_tile + mt, 8, hipMemcpyDeviceToHost, nullptr));
-        MFX_HIP(hipStreamSynchronize(nullptr));
-      }
-      w->t_combine += db_now() - t1;
-      if (st) ++st->windows;
-      if (n_out > M) return mfx_fail(MFX_E_HIP, "%s: the combined pairs of a window are damaged", who);
-      if (n_out)
-        if (int rc = stream_append_device(w, S, bk[cur ^ 1], bv[cur ^ 1], n_out, bk[cur], cap * 12, who, "MFX_MERGE_RANGE")) return rc;
-    }
-    uint64_t stats[3] = {0, 0, 0};
-    MFX_HIP(hipMemcpy(stats, d_stats, 24, hipMemcpyDeviceToHost));
-    if (st) { st->n_saturated = stats[0]; st->n_filtered = stats[1]; }
-    if (n_subtracted) *n_subtracted = stats[2];
-  }
-  guard.w = nullptr;
-  uint64_t n = 0;
-  if (int rc = mfx_db_writer_close(w, &n)) return rc;
-  if (st) { st->n_in = n_all; st->n_out = n; }
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_merge(const char *const *in_paths, uint32_t n_in, const char *out_path, const mfx_db_merge_opts *o, mfx_db_merge_stats *st) {
-  try { return mfx_db_merge_impl(in_paths, n_in, nullptr, 0, out_path, o, st, nullptr); }      // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge: %s", e.what()); }
-}
-
-extern "C" int mfx_db_merge_except(const char *const *in_paths, uint32_t n_in, const char *const *not_paths, uint32_t n_not, const char *out_path,
-                                   const mfx_db_merge_opts *o, mfx_db_merge_stats *st, uint64_t *n_subtracted) {
-  try { return mfx_db_merge_impl(in_paths, n_in, not_paths, n_not, out_path, o, st, n_subtracted); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge_except: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_merge_except: %s", e.what()); }
-}
-
-// ---------------------------------------------------------------------------
-// mfx_db_join_*: -completeness and -spectrum from two sorted databases, window by window (include/merfin_amd.h).  mfx_db_merge's windows and
-// decode, then mfx_join_kernel (mfx_join.hip): the join ends in the piece sums or in the image, nothing is merged into memory or written.
-// ---------------------------------------------------------------------------
-namespace { enum JoinKind { JOIN_COMPLETENESS, JOIN_SPECTRUM }; }
-
-static int db_join_impl(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, JoinKind kind, double *total64, double *undrcpy64, uint64_t *img,
-                        uint64_t *n_entries, mfx_db_join_stats *st) {
-  const char *who = kind == JOIN_COMPLETENESS ? "mfx_db_join_completeness" : "mfx_db_join_spectrum";
-  const double t_begin = db_now();
-  if (st) memset(st, 0, sizeof(*st));
-  // ---- every check that needs no device
-  if (!read_path || !asm_path || !o || (kind == JOIN_COMPLETENESS ? (!total64 || !undrcpy64) : (!img || !n_entries))) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (kind == JOIN_COMPLETENESS && o->n_prob && (!o->probK || !o->probP)) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (kind == JOIN_SPECTRUM) {                                 // (mfx_spectrum_run's bounds and texts)
-    if (o->copies < MFX_SPEC_MIN_COPIES || o->copies > MFX_SPEC_MAX_COPIES)
-      return mfx_fail(MFX_E_INVAL, "%s: copies = %u is outside [%u, %u]", who, o->copies, MFX_SPEC_MIN_COPIES, MFX_SPEC_MAX_COPIES);
-    if (o->max_mult < MFX_SPEC_MIN_MULT || o->max_mult > MFX_SPEC_MAX_MULT)
-      return mfx_fail(MFX_E_INVAL, "%s: max_mult = %u is outside [%u, %u]", who, o->max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  }
-  std::vector<std::unique_ptr<MergeIn>> ins;
-  const char *paths[2] = {read_path, asm_path};
-  for (int i = 0; i < 2; ++i) {
-    ins.emplace_back(new MergeIn);
-    mfx_db_info info;                                            // (k > 31 has no sorted form: said as that, not as "a plain flat file")
-    if (detect(paths[i]) == MFX_DB_FLAT && mfx_db_probe_impl(paths[i], &info) == MFX_OK && info.k > MFX_MAX_K_NARROW)
-      return mfx_fail(MFX_E_INVAL, "mfx_db_join: '%s' holds %d-mers: the sorted join takes k <= %d", paths[i], info.k, MFX_MAX_K_NARROW);
-    if (int rc = merge_open_input(paths[i], *ins.back(), "mfx_db_join")) return rc;
-  }
-  if (ins[1]->h.k != ins[0]->h.k)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_join: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", paths[1], ins[1]->h.k, paths[0], ins[0]->h.k);
-  const int k = (int)ins[0]->h.k;
-  MergeWindows P;
-  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
-  const size_t cells = kind == JOIN_SPECTRUM ? (size_t)(o->copies + 2u) * (o->max_mult + 1u) : 0;
-  // res: stats word [0] (the k-mers of both), then the 128 piece sums or the image and its entry counter
-  const size_t res_words = 2 + (kind == JOIN_COMPLETENESS ? 128 : cells + 1);
-  std::vector<uint64_t> res(res_words, 0);
-  uint64_t got[2] = {0, 0}, windows = 0;
-  double t_read = 0, t_decode = 0, t_join = 0;
-  if (P.max_pairs) {
-    DeviceBack back;
-    MFX_HIP(hipSetDevice(o->device));
-    // p[0]: one buffer of cap pairs, the k-mers in front of the counts: the decoded runs.  p[1]: the window's blocks.  p[2]: tasks, their below /
-    // above, the inputs' error words.  p[3], p[4]: the window's escapes.  p[5]: the result.  p[6], p[7]: the -prob table.
-    const uint64_t cap = P.max_pairs + 1, small = P.max_tasks * (sizeof(mfx_merge_task) + 8) + 2 * 4 + 64;
-    const size_t np = o->n_prob && kind == JOIN_COMPLETENESS ? o->n_prob : 1;
-    DbDev D;
-    hipError_t e = hipMalloc(&D.p[0], cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&D.p[1], P.max_bytes + 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[2], small);
-    if (e == hipSuccess) e = hipMalloc(&D.p[3], (P.max_esc + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[4], (P.max_esc + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc(&D.p[5], res_words * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[6], np * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[7], np * sizeof(double));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who, (unsigned long)P.max_pairs,
-                      ((double)cap * 12 + (double)P.max_bytes + (double)P.max_esc * 12 + (double)small + (double)res_words * 8) / 1e9, hipGetErrorString(e));
-    }
-    uint64_t *d_keys = (uint64_t *)D.p[0], *d_res = (uint64_t *)D.p[5];
-    uint32_t *d_vals = (uint32_t *)((char *)D.p[0] + cap * 8);
-    MergeDecoder dec;
-    dec.d_words = D.p[1];
-    dec.d_tasks = (mfx_merge_task *)D.p[2];
-    dec.d_below = (uint32_t *)(dec.d_tasks + P.max_tasks); dec.d_above = dec.d_below + P.max_tasks; dec.d_err = dec.d_above + P.max_tasks;
-    dec.d_ek = (uint64_t *)D.p[3]; dec.d_ev = (uint32_t *)D.p[4];
-    MFX_HIP(hipHostMalloc(&dec.pinned, P.max_bytes + 8, hipHostMallocDefault));
-    MFX_HIP(mfx_memset_now(d_res, 0, res_words * 8));
-    if (kind == JOIN_COMPLETENESS && o->n_prob) {
-      MFX_HIP(hipMemcpy(D.p[6], o->probK, o->n_prob * sizeof(uint32_t), hipMemcpyHostToDevice));
-      MFX_HIP(hipMemcpy(D.p[7], o->probP, o->n_prob * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int cus = 0;
-    MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
-    const int grid = (cus > 0 ? cus : 256) * (kind == JOIN_COMPLETENESS ? 4 : 2);      // the workgroups a CU holds at once (mfx_join.hip: LDS)
-    mfx_spectrum_args sa{};
-    if (kind == JOIN_SPECTRUM) {
-      sa.copies = o->copies;
-      sa.max_mult = o->max_mult;
-      sa.lds_cols = mfx_spec_lds_cols(o->copies, o->max_mult);
-      const char *ag = getenv("MFX_SPECTRUM_AGG");                 // as mfx_spectrum_run reads it (docs/KNOBS.md)
-      sa.aggregate = ag ? (atoi(ag) != 0) : MFX_SPEC_AGG_DEFAULT;
-      sa.img = d_res + 2;
-    }
-    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
-    for (size_t wi = 0; wi < P.win.size(); ++wi) {
-      if (P.win[wi].pairs == 0) continue;
-      // ---- read and decode: the read run and the asm run of the window.  (One stream: the blocks of this window are copied behind the join of
-      // the window before it, whose kernel runs while the host reads.)
-      const int rc = merge_decode_window(ins, P, wi, k, who, dec, d_keys, d_vals);
-      t_read += dec.t_read; t_decode += dec.t_decode;
-      if (rc) return rc;
-      const double t0 = db_now();
-      const MergeRun a = dec.runs[0], b = dec.runs[1];
-      got[0] += a.len; got[1] += b.len;
-      if (kind == JOIN_COMPLETENESS)
-        MFX_HIP(mfx_k_join_completeness(d_keys + a.off, d_vals + a.off, a.len, d_keys + b.off, d_vals + b.off, b.len, k, o->peak, o->n_prob, (const uint32_t *)D.p[6],
-                                        (const double *)D.p[7], reinterpret_cast<double *>(d_res + 2), d_res, grid, nullptr));
-      else
-        MFX_HIP(mfx_k_join_spectrum(d_keys + a.off, d_vals + a.off, a.len, d_keys + b.off, d_vals + b.off, b.len, sa, o->minV, o->maxV, d_res, grid, nullptr));
-      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
-      t_join += db_now() - t0;
-      ++windows;
-    }
-    MFX_HIP(hipMemcpy(res.data(), d_res, res_words * 8, hipMemcpyDeviceToHost));
-  }
-  // ---- what the windows held against what the files say, the image against its counter: no partial result is handed out
-  for (int i = 0; i < 2; ++i)
-    if (got[i] != ins[i]->h.n)
-      return mfx_fail(MFX_E_FORMAT, "'%s': the windows hold %lu of its %lu k-mers: the directory does not describe the blocks", paths[i], (unsigned long)got[i], (unsigned long)ins[i]->h.n);
-  const uint64_t n_both = res[0];
-  if (n_both > got[0] || n_both > got[1]) return mfx_fail(MFX_E_HIP, "%s: %lu k-mers in both inputs, more than an input holds", who, (unsigned long)n_both);
-  if (kind == JOIN_SPECTRUM) {
-    uint64_t sum = 0;
-    for (size_t i = 0; i < cells; ++i) sum += res[2 + i];
-    if (sum != res[2 + cells]) return mfx_fail(MFX_E_HIP, "%s: the image sums to %lu, the join counted %lu entries", who, (unsigned long)sum, (unsigned long)res[2 + cells]);
-    const bool filtered = o->minV > 1 || o->maxV < 0xffffffffull;      // (a count is 1 at the least: no other filter makes a pair (0, 0))
-    if (!filtered && sum != got[0] + got[1] - n_both)
-      return mfx_fail(MFX_E_HIP, "%s: the join counted %lu entries, the inputs hold %lu distinct k-mers", who, (unsigned long)sum, (unsigned long)(got[0] + got[1] - n_both));
-    memcpy(img, res.data() + 2, cells * 8);
-    *n_entries = sum;
-  } else {
-    memcpy(total64, res.data() + 2, 64 * sizeof(double));
-    memcpy(undrcpy64, res.data() + 2 + 64, 64 * sizeof(double));
-  }
-  if (st) {
-    st->n_read = got[0]; st->n_asm = got[1]; st->n_both = n_both; st->windows = windows;
-    st->t_read = t_read; st->t_decode = t_decode; st->t_join = t_join; st->t_total = db_now() - t_begin;
-  }
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_join_completeness(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, double *total64, double *undrcpy64, mfx_db_join_stats *st) {
-  try { return db_join_impl(read_path, asm_path, o, JOIN_COMPLETENESS, total64, undrcpy64, nullptr, nullptr, st); }      // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_completeness: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_join_completeness: %s", e.what()); }
-}
-
-extern "C" int mfx_db_join_spectrum(const char *read_path, const char *asm_path, const mfx_db_join_opts *o, uint64_t *img, uint64_t *n_entries, mfx_db_join_stats *st) {
-  try { return db_join_impl(read_path, asm_path, o, JOIN_SPECTRUM, nullptr, nullptr, img, n_entries, st); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_spectrum: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_join_spectrum: %s", e.what()); }
-}
-
-extern "C" void mfx_db_join_grain(uint32_t *per_lane, uint32_t *tile) {
-  if (per_lane) *per_lane = MFX_JOIN_PER;
-  if (tile) *tile = MFX_JOIN_TILE;
-}
-
-extern "C" int mfx_db_join_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *asm_keys, const uint32_t *asm_vals, uint64_t n_asm,
-                                uint64_t *keys, uint32_t *readV, uint32_t *asmV, uint64_t cap, uint64_t *n_pairs) {
-  if ((n_read && (!read_keys || !read_vals)) || (n_asm && (!asm_keys || !asm_vals)) || !n_pairs || (cap && (!keys || !readV || !asmV)))
-    return mfx_fail(MFX_E_INVAL, "mfx_db_join_host: null argument");
-  uint64_t n = 0;
-  try {
-    mfx_join_host(read_keys, read_vals, n_read, asm_keys, asm_vals, n_asm, [&](bool have, uint64_t key, uint32_t rv, uint32_t av) {
-      if (!have) return;
-      if (n < cap) { keys[n] = key; readV[n] = rv; asmV[n] = av; }
-      ++n;
-    });
-  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_join_host: out of memory"); }
-  *n_pairs = n;
-  return MFX_OK;
-}
-
-// ---------------------------------------------------------------------------
-// mfx_db_diploid: two haplotype assemblies against the reads, window by window (include/merfin_amd.h; the rule: mfx_diploid.h; the kernels:
-// mfx_diploid.hip).  mfx_db_merge's windows and decode over the three files; hap1's and hap2's runs are tagged, merged (mfx_merge_pairs_kernel)
-// and compacted into the pair run; the read run stays where the decode left it and is joined against the pair run by mfx_join_kernel.
-// ---------------------------------------------------------------------------
-static void diploid_fill_stats(const uint64_t *c, mfx_db_diploid_stats *st) {
-  mfx_diploid_counts *x[3] = {&st->hap1, &st->hap2, &st->both};
-  for (int i = 0; i < 3; ++i) {
-    const uint64_t *s = c + i * MFX_DIP_PER_X;
-    x[i]->distinct = s[MFX_DIP_DISTINCT]; x[i]->total = s[MFX_DIP_TOTAL]; x[i]->only_distinct = s[MFX_DIP_ONLY_DISTINCT];
-    x[i]->only_total = s[MFX_DIP_ONLY_TOTAL]; x[i]->found = s[MFX_DIP_FOUND];
-  }
-  st->solid = c[MFX_DIP_SOLID]; st->n_read = c[MFX_DIP_N_READ]; st->n_shared = c[MFX_DIP_N_SHARED];
-}
-
-static int diploid_check_opts(const char *who, const mfx_db_join_opts *o, const uint64_t *asm_img, const uint64_t *cn_img, const uint64_t *n_entries,
-                              const mfx_db_diploid_stats *st, const double *total64, const double *undrcpy64) {
-  if (!o || !asm_img || !cn_img || !n_entries || !st) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if ((total64 != nullptr) != (undrcpy64 != nullptr)) return mfx_fail(MFX_E_INVAL, "%s: total64 and undrcpy64 are given together or not at all", who);
-  if (total64 && o->n_prob && (!o->probK || !o->probP)) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (o->copies < MFX_SPEC_MIN_COPIES || o->copies > MFX_SPEC_MAX_COPIES)      // (mfx_spectrum_run's bounds and texts)
-    return mfx_fail(MFX_E_INVAL, "%s: copies = %u is outside [%u, %u]", who, o->copies, MFX_SPEC_MIN_COPIES, MFX_SPEC_MAX_COPIES);
-  if (o->max_mult < MFX_SPEC_MIN_MULT || o->max_mult > MFX_SPEC_MAX_MULT)
-    return mfx_fail(MFX_E_INVAL, "%s: max_mult = %u is outside [%u, %u]", who, o->max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  return MFX_OK;
-}
-
-static int db_diploid_impl(const char *read_path, const char *hap1_path, const char *hap2_path, const mfx_db_join_opts *o, uint64_t *asm_img, uint64_t *cn_img,
-                           uint64_t *n_entries, mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
-  const char *who = "mfx_db_diploid";
-  const double t_begin = db_now();
-  // ---- every check that needs no device
-  if (!read_path || !hap1_path || !hap2_path) return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (int rc = diploid_check_opts(who, o, asm_img, cn_img, n_entries, st, total64, undrcpy64)) return rc;
-  const bool pieces = total64 != nullptr;
-  std::vector<std::unique_ptr<MergeIn>> ins;
-  const char *paths[3] = {read_path, hap1_path, hap2_path};
-  for (int i = 0; i < 3; ++i) {
-    ins.emplace_back(new MergeIn);
-    mfx_db_info info;                                            // (k > 31 has no sorted form: said as that, not as "a plain flat file")
-    if (detect(paths[i]) == MFX_DB_FLAT && mfx_db_probe_impl(paths[i], &info) == MFX_OK && info.k > MFX_MAX_K_NARROW)
-      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %d-mers: the sorted join takes k <= %d", who, paths[i], info.k, MFX_MAX_K_NARROW);
-    if (int rc = merge_open_input(paths[i], *ins.back(), who)) return rc;
-    if (ins[i]->h.k != ins[0]->h.k)
-      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", who, paths[i], ins[i]->h.k, paths[0], ins[0]->h.k);
-  }
-  const int k = (int)ins[0]->h.k;
-  MergeWindows P;
-  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
-  uint64_t max_asm = 0;                                        // the most a window's blocks hold of the two assemblies together
-  for (size_t w = 0; w < P.win.size(); ++w) {
-    uint64_t a = 0;
-    for (uint32_t i = 1; i < 3; ++i) a += mfx_merge_block_pairs(P.pin[i], P.blk[2 * (w * 3 + i)], P.blk[2 * (w * 3 + i) + 1]);
-    max_asm = std::max(max_asm, a);
-  }
-  const uint64_t W = (uint64_t)o->max_mult + 1, cls_cells = MFX_DIP_ROWS * W, cn_cells = (uint64_t)(o->copies + 2u) * W;
-  // res: [0] the k-mers of the reads and of an assembly, [1] spare; the class image and its counter word; the cn image and its counter word;
-  // the 256 piece sums; the copies of the counters
-  const size_t off_cls = 2, off_cn = off_cls + cls_cells + 1, off_sums = off_cn + cn_cells + 1, off_cnt = off_sums + 256, res_words = off_cnt + MFX_DIP_STAT_WORDS;
-  std::vector<uint64_t> res(res_words, 0);
-  uint64_t got[3] = {0, 0, 0}, windows = 0;
-  double t_read = 0, t_decode = 0, t_pair = 0, t_join = 0;
-  if (P.max_pairs) {
-    DeviceBack back;
-    MFX_HIP(hipSetDevice(o->device));
-    // p[0]: one buffer of cap pairs, the k-mers in front of the counts: the decoded runs of the three inputs.  p[1]: the window's blocks.  p[2]: tasks,
-    // their below / above, the inputs' error words, the pair kernel's tile offsets.  p[3], p[4]: the window's escapes.  p[5]: the result.  p[6], p[7]: the
-    // -prob table.  E.p[0]: the tagged merged run of the two assemblies (acap pairs).  E.p[1]: the pair run (acap k-mers, acap words).
-    const uint64_t cap = P.max_pairs + 1, acap = max_asm + 1, tiles = mfx_dip_tiles(max_asm);
-    const uint64_t small = P.max_tasks * (sizeof(mfx_merge_task) + 8) + 3 * 4 + 64 + (tiles + 1) * 8;
-    const size_t np = o->n_prob && pieces ? o->n_prob : 1;
-    DbDev D, E;
-    hipError_t e = hipMalloc(&D.p[0], cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&D.p[1], P.max_bytes + 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[2], small);
-    if (e == hipSuccess) e = hipMalloc(&D.p[3], (P.max_esc + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[4], (P.max_esc + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc(&D.p[5], res_words * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[6], np * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&D.p[7], np * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&E.p[0], acap * 12);
-    if (e == hipSuccess) e = hipMalloc(&E.p[1], acap * 16);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs, %lu of them the assemblies' (%.3f GB) do not fit the device: %s; lower MFX_MERGE_RANGE", who,
-                      (unsigned long)P.max_pairs, (unsigned long)max_asm,
-                      ((double)cap * 12 + (double)acap * 28 + (double)P.max_bytes + (double)P.max_esc * 12 + (double)small + (double)res_words * 8) / 1e9, hipGetErrorString(e));
-    }
-    uint64_t *d_keys = (uint64_t *)D.p[0], *d_res = (uint64_t *)D.p[5];
-    uint32_t *d_vals = (uint32_t *)((char *)D.p[0] + cap * 8);
-    uint64_t *m_keys = (uint64_t *)E.p[0], *p_keys = (uint64_t *)E.p[1], *p_vals = p_keys + acap;
-    uint32_t *m_vals = (uint32_t *)((char *)E.p[0] + acap * 8);
-    MergeDecoder dec;
-    dec.d_words = D.p[1];
-    uint64_t *d_tile = (uint64_t *)D.p[2];
-    dec.d_tasks = (mfx_merge_task *)(d_tile + tiles + 1);
-    dec.d_below = (uint32_t *)(dec.d_tasks + P.max_tasks); dec.d_above = dec.d_below + P.max_tasks; dec.d_err = dec.d_above + P.max_tasks;
-    dec.d_ek = (uint64_t *)D.p[3]; dec.d_ev = (uint32_t *)D.p[4];
-    MFX_HIP(hipHostMalloc(&dec.pinned, P.max_bytes + 8, hipHostMallocDefault));
-    MFX_HIP(mfx_memset_now(d_res, 0, res_words * 8));
-    if (pieces && o->n_prob) {
-      MFX_HIP(hipMemcpy(D.p[6], o->probK, o->n_prob * sizeof(uint32_t), hipMemcpyHostToDevice));
-      MFX_HIP(hipMemcpy(D.p[7], o->probP, o->n_prob * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int cus = 0;
-    MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
-    const int grid = (cus > 0 ? cus : 256) * 2;                  // the workgroups a CU holds at once (mfx_diploid.hip: LDS)
-    mfx_spectrum_args cls{}, cn{};
-    const char *ag = getenv("MFX_SPECTRUM_AGG");                 // as mfx_spectrum_run reads it (docs/KNOBS.md)
-    cls.copies = MFX_DIP_ROWS - 2u; cn.copies = o->copies;
-    cls.max_mult = cn.max_mult = o->max_mult;
-    cls.lds_cols = cn.lds_cols = mfx_dip_lds_cols(o->copies, o->max_mult);
-    cls.aggregate = cn.aggregate = ag ? (atoi(ag) != 0) : MFX_SPEC_AGG_DEFAULT;
-    cls.img = d_res + off_cls; cn.img = d_res + off_cn;
-    const bool timing = getenv("MFX_DB_TIMING") != nullptr;
-    for (size_t wi = 0; wi < P.win.size(); ++wi) {
-      if (P.win[wi].pairs == 0) continue;
-      const int rc = merge_decode_window(ins, P, wi, k, who, dec, d_keys, d_vals);
-      t_read += dec.t_read; t_decode += dec.t_decode;
-      if (rc) return rc;
-      double t0 = db_now();
-      const MergeRun a = dec.runs[0], h1 = dec.runs[1], h2 = dec.runs[2];
-      got[0] += a.len; got[1] += h1.len; got[2] += h2.len;
-      // ---- a. the pair run: the role into the two low bits of the assemblies' k-mers, one merge, the head positions compacted
-      const uint64_t M = h1.len + h2.len;
-      uint64_t n_pairs = 0;
-      if (M > max_asm) return mfx_fail(MFX_E_INVAL, "%s: a window does not match its plan", who);      // (nothing is merged beyond the buffers)
-      if (M) {
-        MFX_HIP(mfx_k_trio_tag(d_keys + h1.off, h1.len, MFX_DIP_HAP1, nullptr));
-        MFX_HIP(mfx_k_trio_tag(d_keys + h2.off, h2.len, MFX_DIP_HAP2, nullptr));
-        MFX_HIP(mfx_k_merge_pairs(d_keys + h1.off, d_vals + h1.off, h1.len, d_keys + h2.off, d_vals + h2.off, h2.len, m_keys, m_vals, nullptr));
-        MFX_HIP(mfx_k_dip_pairs(m_keys, m_vals, M, d_tile, p_keys, p_vals, nullptr));
-        MFX_HIP(hipMemcpyAsync(&n_pairs, d_tile + mfx_dip_tiles(M), 8, hipMemcpyDeviceToHost, nullptr));
-        MFX_HIP(hipStreamSynchronize(nullptr));
-      }
-      if (n_pairs > M || 2 * n_pairs < M) return mfx_fail(MFX_E_HIP, "%s: the pair run of a window is damaged", who);
-      double t1 = db_now();
-      t_pair += t1 - t0;
-      // ---- b. the join of the read run against it
-      MFX_HIP(mfx_k_dip_join(d_keys + a.off, d_vals + a.off, a.len, p_keys, p_vals, n_pairs, cls, cn, o->minV, o->maxV, k, pieces ? 1 : 0, o->peak,
-                             pieces ? o->n_prob : 0u, (const uint32_t *)D.p[6], (const double *)D.p[7], reinterpret_cast<double *>(d_res + off_sums), d_res + off_cnt,
-                             d_res, grid, nullptr));
-      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
-      t_join += db_now() - t1;
-      ++windows;
-    }
-    MFX_HIP(hipMemcpy(res.data(), d_res, res_words * 8, hipMemcpyDeviceToHost));
-  }
-  // ---- what the windows held against what the files say, the counters against the files, the images against their counters: no partial result
-  for (int i = 0; i < 3; ++i)
-    if (got[i] != ins[i]->h.n)
-      return mfx_fail(MFX_E_FORMAT, "'%s': the windows hold %lu of its %lu k-mers: the directory does not describe the blocks", paths[i], (unsigned long)got[i], (unsigned long)ins[i]->h.n);
-  uint64_t c[MFX_DIP_NSTATS];
-  for (uint32_t s = 0; s < MFX_DIP_NSTATS; ++s) {
-    c[s] = 0;
-    for (uint32_t j = 0; j < MFX_DIP_STAT_SHARDS; ++j) c[s] += res[off_cnt + j * MFX_DIP_STAT_STRIDE + s];
-  }
-  const uint64_t d1 = c[MFX_DIP_DISTINCT], d2 = c[MFX_DIP_PER_X + MFX_DIP_DISTINCT], db = c[2 * MFX_DIP_PER_X + MFX_DIP_DISTINCT];
-  if (d1 != got[1] || d2 != got[2] || c[MFX_DIP_N_READ] != got[0] || d1 + d2 - c[MFX_DIP_N_SHARED] != db ||
-      res[0] != db - c[2 * MFX_DIP_PER_X + MFX_DIP_ONLY_DISTINCT])
-    return mfx_fail(MFX_E_HIP, "%s: the join counted %lu, %lu and %lu k-mers of the reads, hap1 and hap2 (%lu shared, %lu of either, %lu of the reads and an assembly): "
-                    "not what databases of %lu, %lu and %lu k-mers give", who, (unsigned long)c[MFX_DIP_N_READ], (unsigned long)d1, (unsigned long)d2,
-                    (unsigned long)c[MFX_DIP_N_SHARED], (unsigned long)db, (unsigned long)res[0], (unsigned long)got[0], (unsigned long)got[1], (unsigned long)got[2]);
-  uint64_t sum_cls = 0, sum_cn = 0;
-  for (size_t i = 0; i < cls_cells; ++i) sum_cls += res[off_cls + i];
-  for (size_t i = 0; i < cn_cells; ++i) sum_cn += res[off_cn + i];
-  if (sum_cls != res[off_cls + cls_cells] || sum_cn != res[off_cn + cn_cells] || sum_cls != sum_cn)
-    return mfx_fail(MFX_E_HIP, "%s: the images sum to %lu and %lu, the join counted %lu and %lu entries", who, (unsigned long)sum_cls, (unsigned long)sum_cn,
-                    (unsigned long)res[off_cls + cls_cells], (unsigned long)res[off_cn + cn_cells]);
-  const bool filtered = o->minV > 1 || o->maxV < 0xffffffffull;      // (a count is 1 at the least: no other filter makes an entry vanish)
-  if (!filtered && sum_cn != got[0] + db - res[0])
-    return mfx_fail(MFX_E_HIP, "%s: the join counted %lu entries, the inputs hold %lu distinct k-mers", who, (unsigned long)sum_cn, (unsigned long)(got[0] + db - res[0]));
-  memcpy(asm_img, res.data() + off_cls, cls_cells * 8);
-  memcpy(cn_img, res.data() + off_cn, cn_cells * 8);
-  *n_entries = sum_cn;
-  if (pieces) {
-    memcpy(total64, res.data() + off_sums, 64 * sizeof(double));
-    memcpy(undrcpy64, res.data() + off_sums + 64, 3 * 64 * sizeof(double));
-  }
-  memset(st, 0, sizeof(*st));
-  diploid_fill_stats(c, st);
-  st->n_hap1 = got[1]; st->n_hap2 = got[2]; st->windows = windows;
-  st->t_read = t_read; st->t_decode = t_decode; st->t_pair = t_pair; st->t_join = t_join; st->t_total = db_now() - t_begin;
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_diploid(const char *read_path, const char *hap1_path, const char *hap2_path, const mfx_db_join_opts *o, uint64_t *asm_img, uint64_t *cn_img,
-                              uint64_t *n_entries, mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
-  try { return db_diploid_impl(read_path, hap1_path, hap2_path, o, asm_img, cn_img, n_entries, st, total64, undrcpy64); }      // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_diploid: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_diploid: %s", e.what()); }
-}
-
-extern "C" int mfx_db_diploid_host(const uint64_t *read_keys, const uint32_t *read_vals, uint64_t n_read, const uint64_t *hap1_keys, const uint32_t *hap1_vals,
-                                   uint64_t n_hap1, const uint64_t *hap2_keys, const uint32_t *hap2_vals, uint64_t n_hap2, int k, const mfx_db_join_opts *o, uint64_t *keys,
-                                   uint32_t *readV, uint32_t *c1V, uint32_t *c2V, uint64_t cap, uint64_t *n_kmers, uint64_t *asm_img, uint64_t *cn_img, uint64_t *n_entries,
-                                   mfx_db_diploid_stats *st, double *total64, double *undrcpy64) {
-  const char *who = "mfx_db_diploid_host";
-  if ((n_read && (!read_keys || !read_vals)) || (n_hap1 && (!hap1_keys || !hap1_vals)) || (n_hap2 && (!hap2_keys || !hap2_vals)) || !n_kmers ||
-      (cap && (!keys || !readV || !c1V || !c2V)))
-    return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (int rc = diploid_check_opts(who, o, asm_img, cn_img, n_entries, st, total64, undrcpy64)) return rc;
-  if (k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "%s: k = %d is outside [1, %d]", who, k, MFX_MAX_K_NARROW);
-  try {
-    mfx_dip_host_result R;
-    uint64_t n = 0;
-    mfx_dip_host(read_keys, read_vals, n_read, hap1_keys, hap1_vals, n_hap1, hap2_keys, hap2_vals, n_hap2, k, o->minV, o->maxV, o->copies, o->max_mult, total64 != nullptr,
-                 [&](uint32_t r) { double rk, pr; mfx_getK_core(o->peak, o->n_prob, o->probK, o->probP, r, rk, pr); return rk; },
-                 [&](uint64_t key, uint32_t r, uint32_t c1, uint32_t c2) {
-                   if (n < cap) { keys[n] = key; readV[n] = r; c1V[n] = c1; c2V[n] = c2; }
-                   ++n;
-                 }, R);
-    if (R.stats[MFX_DIP_DISTINCT] != n_hap1 || R.stats[MFX_DIP_PER_X + MFX_DIP_DISTINCT] != n_hap2 || R.stats[MFX_DIP_N_READ] != n_read)
-      return mfx_fail(MFX_E_INVAL, "%s: the runs do not ascend strictly, or hold a count of 0", who);
-    *n_kmers = n;
-    memcpy(asm_img, R.asm_img.data(), R.asm_img.size() * 8);
-    memcpy(cn_img, R.cn_img.data(), R.cn_img.size() * 8);
-    *n_entries = R.n_entries;
-    if (total64) { memcpy(total64, R.tot, sizeof(R.tot)); memcpy(undrcpy64, R.und, sizeof(R.und)); }
-    memset(st, 0, sizeof(*st));
-    diploid_fill_stats(R.stats, st);
-    st->n_hap1 = n_hap1; st->n_hap2 = n_hap2;
-    return MFX_OK;
-  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "%s: out of memory", who); }
-}
-
-extern "C" int mfx_diploid_write_asm(const uint64_t *img, uint32_t max_mult, const char *path) {
-  if (!img || !path) return mfx_fail(MFX_E_INVAL, "mfx_diploid_write_asm: null argument");
-  if (max_mult < MFX_SPEC_MIN_MULT || max_mult > MFX_SPEC_MAX_MULT)
-    return mfx_fail(MFX_E_INVAL, "mfx_diploid_write_asm: max_mult = %u is outside [%u, %u]", max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  static const char *const label[MFX_DIP_ROWS] = {"read-only", "hap1-only", "hap2-only", "shared"};
-  mfx_file fh = mfx_open_writer(path, false);                    // compressor chosen by suffix (mfx_pipe.h)
-  if (!fh.f) return mfx_fail(MFX_E_IO, "mfx_diploid_write_asm: cannot open '%s' for writing", path);
-  fprintf(fh.f, "Assembly\tkmer_multiplicity\tCount\n");
-  for (uint32_t r = 0; r < MFX_DIP_ROWS; ++r)
-    for (uint32_t m = 0; m <= max_mult; ++m)
-      if (img[(size_t)r * (max_mult + 1u) + m]) fprintf(fh.f, "%s\t%u\t%llu\n", label[r], m, (unsigned long long)img[(size_t)r * (max_mult + 1u) + m]);
-  if (mfx_close(fh)) return mfx_fail(MFX_E_IO, "mfx_diploid_write_asm: writing '%s' failed", path);
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_merge_plan(const uint64_t *const *first, const uint64_t *n, uint32_t n_in, int k, uint64_t R, uint64_t *out, uint64_t cap, uint64_t *n_windows) {
-  if (!first || !n || !n_windows || n_in == 0 || n_in > MFX_MERGE_MAX_INPUTS || k < 1 || k > MFX_MAX_K_NARROW) return mfx_fail(MFX_E_INVAL, "mfx_db_merge_plan: bad argument");
-  try {
-    std::vector<mfx_merge_input> in(n_in);
-    for (uint32_t i = 0; i < n_in; ++i) in[i] = mfx_merge_input{first[i], 1u, (n[i] + MFX_MERGE_BLOCK - 1) / MFX_MERGE_BLOCK, n[i]};
-    std::vector<mfx_merge_window> win;
-    std::vector<uint64_t> blk;
-    mfx_merge_plan(in.data(), n_in, k, R, win, blk);
-    *n_windows = win.size();
-    const uint64_t row = 3 + 2 * (uint64_t)n_in;
-    for (uint64_t w = 0; out && w < win.size() && w < cap; ++w) {
-      out[w * row] = win[w].lo; out[w * row + 1] = win[w].hi; out[w * row + 2] = win[w].pairs;
-      for (uint64_t j = 0; j < 2 * (uint64_t)n_in; ++j) out[w * row + 3 + j] = blk[w * 2 * n_in + j];
-    }
-    return MFX_OK;
-  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_merge_plan: out of memory"); }
-}
-
-// ---------------------------------------------------------------------------
-// mfx_db_trio, mfx_db_trio_hist, mfx_db_histogram: the hap-mer sets of a trio and the k-mer histograms their cutoffs are read off
-// (include/merfin_amd.h; the rule: mfx_trio.h; the kernels: mfx_trio.hip).  mfx_db_merge's windows, pread loop, decode and pairwise merge as
-// they are; between decode and merge every input's k-mers take its role into their two low bits, so that the merged run knows its inputs.
-// Pass 1 (only where a cutoff is automatic, and for the two histogram calls) ends in the image; pass 2 in two compacted outputs, each behind
-// the carry of a streamed writer of its own.
-// ---------------------------------------------------------------------------
-namespace {
-enum TrioKind { TRIO_FULL, TRIO_HIST, TRIO_HISTOGRAM };
-struct TrioTimes { double read = 0, decode = 0, merge = 0, hist = 0, classify = 0, write = 0; };
-}  // namespace
-
-static int trio_impl(TrioKind kind, const char *mat_path, const char *pat_path, const char *child_path, const char *out_a, const char *out_b, const mfx_db_trio_opts *o,
-                     uint64_t *img, mfx_db_trio_stats *st) {
-  const char *who = kind == TRIO_FULL ? "mfx_db_trio" : kind == TRIO_HIST ? "mfx_db_trio_hist" : "mfx_db_histogram";
-  const double t_begin = db_now();
-  if (st) memset(st, 0, sizeof(*st));
-  // ---- every check that needs no device
-  if (!o || (kind != TRIO_HISTOGRAM && (!mat_path || !pat_path)) || (kind == TRIO_HISTOGRAM && !child_path) || (kind == TRIO_FULL ? (!out_a || !out_b) : !img))
-    return mfx_fail(MFX_E_INVAL, "%s: null argument", who);
-  if (o->max_mult < MFX_SPEC_MIN_MULT || o->max_mult > MFX_SPEC_MAX_MULT)
-    return mfx_fail(MFX_E_INVAL, "%s: max_mult = %u is outside [%u, %u]", who, o->max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  if (kind == TRIO_FULL && o->cut_child != 0 && !child_path)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_trio: cut_child = %u without a child database: the child's cutoff has nothing to act on", o->cut_child);
-  const bool has_child = child_path != nullptr;
-  std::vector<const char *> paths;
-  std::vector<uint32_t> roles;
-  if (kind != TRIO_HISTOGRAM) { paths.push_back(mat_path); roles.push_back(MFX_TRIO_MAT); paths.push_back(pat_path); roles.push_back(MFX_TRIO_PAT); }
-  if (has_child) { paths.push_back(child_path); roles.push_back(MFX_TRIO_CHILD); }
-  const uint32_t n_in = (uint32_t)paths.size();
-  std::vector<std::unique_ptr<MergeIn>> ins;
-  for (uint32_t i = 0; i < n_in; ++i) {
-    ins.emplace_back(new MergeIn);
-    mfx_db_info info;                                            // (k > 31 has no sorted form: said as that, not as "a plain flat file")
-    if (detect(paths[i]) == MFX_DB_FLAT && mfx_db_probe_impl(paths[i], &info) == MFX_OK && info.k > MFX_MAX_K_NARROW)
-      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %d-mers: the sorted databases of this call hold k <= %d", who, paths[i], info.k, MFX_MAX_K_NARROW);
-    if (int rc = merge_open_input(paths[i], *ins.back(), who)) return rc;
-    if (ins[i]->h.k != ins[0]->h.k)
-      return mfx_fail(MFX_E_INVAL, "%s: '%s' holds %u-mers, '%s' %u-mers: the inputs are of one k", who, paths[i], ins[i]->h.k, paths[0], ins[0]->h.k);
-  }
-  const int k = (int)ins[0]->h.k;
-  if (kind == TRIO_FULL) {
-    const char *outs[2] = {out_a, out_b};
-    struct stat so[2];
-    bool have[2];
-    for (int j = 0; j < 2; ++j) {
-      have[j] = stat(outs[j], &so[j]) == 0;
-      for (uint32_t i = 0; have[j] && i < n_in; ++i) {
-        struct stat si;
-        if (fstat(ins[i]->fd, &si) == 0 && si.st_dev == so[j].st_dev && si.st_ino == so[j].st_ino)
-          return mfx_fail(MFX_E_INVAL, "mfx_db_trio: the output '%s' is the input '%s'", outs[j], paths[i]);
-      }
-    }
-    if (strcmp(out_a, out_b) == 0 || (have[0] && have[1] && so[0].st_dev == so[1].st_dev && so[0].st_ino == so[1].st_ino))
-      return mfx_fail(MFX_E_INVAL, "mfx_db_trio: the two outputs '%s' and '%s' are the same file", out_a, out_b);
-  }
-  MergeWindows P;
-  if (int rc = merge_plan_windows(ins, k, who, P)) return rc;
-  uint32_t cuts[3] = {o->cut_mat, o->cut_pat, has_child ? o->cut_child : 1u};
-  const bool need_hist = kind != TRIO_FULL || cuts[0] == 0 || cuts[1] == 0 || cuts[2] == 0;
-  const uint64_t W = (uint64_t)o->max_mult + 1, cells = 3 * W;
-  std::vector<uint64_t> image(cells + 1, 0);
-  uint64_t dstats[MFX_TRIO_NSTATS] = {0, 0, 0, 0, 0, 0}, windows = 0;
-  TrioTimes T;
-  // ---- the device: the buffers of the largest window, for both passes
-  std::unique_ptr<DeviceBack> back;
-  DbDev D;
-  StreamDev SA, SB;
-  MergeDecoder dec;
-  mfx_db_writer *wa = nullptr, *wb = nullptr;
-  WriterAbort ga, gb;
-  const uint64_t cap = P.max_pairs + MFX_DELTA_BLOCK, tiles = mfx_trio_tiles(P.max_pairs);
-  uint64_t *bk[2] = {nullptr, nullptr}, *xk = nullptr, *d_tile = nullptr, *d_stats = nullptr, *d_img = nullptr;
-  uint32_t *bv[2] = {nullptr, nullptr}, *xv = nullptr;
-  int grid = 1;
-  mfx_spectrum_args sa{};
-  if (P.max_pairs) {
-    back.reset(new DeviceBack);
-    MFX_HIP(hipSetDevice(o->device));
-    // p[0], p[1]: two buffers of cap pairs, the k-mers in front of the counts: decoded runs, merge levels, set A behind its writer's carry, and
-    // the packed words of the one that is free by then (p[1] only where something is merged or written).  p[2]: the window's blocks.  p[3]: the
-    // classify's tile offsets (two per tile), the copies of the stats, tasks, their below / above, the inputs' error words.  p[4], p[5]: the window's escapes.
-    // p[6]: set B behind its writer's carry.  p[7]: the image and its counter word.
-    const uint64_t small = 2 * (tiles + 1) * 8 + MFX_TRIO_STAT_WORDS * 8 + P.max_tasks * (sizeof(mfx_merge_task) + 8) + n_in * 4 + 64;
-    const bool two = kind == TRIO_FULL || n_in > 1;
-    hipError_t e = hipMalloc(&D.p[0], cap * 12);
-    if (e == hipSuccess && two) e = hipMalloc(&D.p[1], cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&D.p[2], P.max_bytes + 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[3], small);
-    if (e == hipSuccess) e = hipMalloc(&D.p[4], (P.max_esc + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&D.p[5], (P.max_esc + 1) * 4);
-    if (e == hipSuccess && kind == TRIO_FULL) e = hipMalloc(&D.p[6], cap * 12);
-    if (e == hipSuccess && need_hist) e = hipMalloc(&D.p[7], (cells + 1) * 8);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      const double nbuf = kind == TRIO_FULL ? 3 : two ? 2 : 1;
-      // (a writer's own: the plan and offsets of its blocks, 28 bytes per 4096 k-mers, and what a window escapes)
-      return mfx_fail(MFX_E_NOMEM, "%s: the buffers of a window of %lu pairs (%.3f GB: %d of %lu pairs, the second output's among them; the blocks; the block plans "
-                      "of both writers) do not fit the device: %s; lower MFX_MERGE_RANGE", who, (unsigned long)P.max_pairs,
-                      (nbuf * (double)cap * 12 + (double)P.max_bytes + (double)P.max_esc * 12 + (double)small + (double)(cells + 1) * 8 +
-                       (kind == TRIO_FULL ? 2.0 * (double)(cap / MFX_DELTA_BLOCK + 1) * (sizeof(mfx_delta_plan) + 12) : 0.0)) / 1e9,
-                      (int)nbuf, (unsigned long)cap, hipGetErrorString(e));
-    }
-    for (int i = 0; i < 2; ++i) { bk[i] = (uint64_t *)D.p[i]; bv[i] = D.p[i] ? (uint32_t *)((char *)D.p[i] + cap * 8) : nullptr; }
-    xk = (uint64_t *)D.p[6]; xv = D.p[6] ? (uint32_t *)((char *)D.p[6] + cap * 8) : nullptr;
-    d_tile = (uint64_t *)D.p[3]; d_stats = d_tile + 2 * (tiles + 1); d_img = (uint64_t *)D.p[7];
-    dec.d_tasks = (mfx_merge_task *)(d_stats + MFX_TRIO_STAT_WORDS);
-    dec.d_below = (uint32_t *)(dec.d_tasks + P.max_tasks); dec.d_above = dec.d_below + P.max_tasks; dec.d_err = dec.d_above + P.max_tasks;
-    dec.d_words = D.p[2]; dec.d_ek = (uint64_t *)D.p[4]; dec.d_ev = (uint32_t *)D.p[5];
-    MFX_HIP(hipHostMalloc(&dec.pinned, P.max_bytes + 8, hipHostMallocDefault));
-    MFX_HIP(mfx_memset_now(d_stats, 0, MFX_TRIO_STAT_WORDS * 8));
-    if (d_img) MFX_HIP(mfx_memset_now(d_img, 0, (cells + 1) * 8));
-    int cus = 0;
-    MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
-    grid = (cus > 0 ? cus : 256) * 4;                            // 32 KB of LDS bins per workgroup: four workgroups of four waves per CU
-    sa.copies = 1;                                               // an image of copies + 2 = 3 rows
-    sa.max_mult = o->max_mult;
-    sa.lds_cols = mfx_spec_lds_cols(1, o->max_mult);
-    const char *ag = getenv("MFX_SPECTRUM_AGG");                 // as mfx_spectrum_run reads it (docs/KNOBS.md)
-    sa.aggregate = ag ? (atoi(ag) != 0) : MFX_SPEC_AGG_DEFAULT;
-    sa.img = d_img;
-  }
-  const bool timing = getenv("MFX_DB_TIMING") != nullptr;
-  // one pass over the windows: decode, tag, merge, then the histogram (classify == false) or the two sets behind their writers
-  auto run_pass = [&](bool classify) -> int {
-    std::vector<MergeRun> &runs = dec.runs, next;
-    std::vector<uint64_t> got(n_in, 0);
-    const mfx_trio_cuts tc{cuts[0], cuts[1], cuts[2], has_child};
-    windows = 0;
-    for (size_t wi = 0; wi < P.win.size(); ++wi) {
-      if (P.win[wi].pairs == 0) continue;
-      const int rc_dec = merge_decode_window(ins, P, wi, k, who, dec, bk[0], bv[0]);
-      T.read += dec.t_read; T.decode += dec.t_decode;
-      if (rc_dec) return rc_dec;
-      double t0 = db_now(), t1;
-      for (uint32_t i = 0; i < n_in; ++i) {                      // the role into the key's two low bits (mfx_trio.h)
-        got[i] += runs[i].len;
-        MFX_HIP(mfx_k_trio_tag(bk[0] + runs[i].off, runs[i].len, roles[i], nullptr));
-      }
-      int cur = 0;
-      while (runs.size() > 1) {                                  // mfx_db_merge's pairwise tree, from one buffer to the other
-        next.clear();
-        uint64_t at = 0;
-        for (size_t j = 0; j < runs.size(); j += 2) {
-          const MergeRun a = runs[j], b = j + 1 < runs.size() ? runs[j + 1] : MergeRun{0, 0};
-          MFX_HIP(mfx_k_merge_pairs(bk[cur] + a.off, bv[cur] + a.off, a.len, bk[cur] + b.off, bv[cur] + b.off, b.len, bk[cur ^ 1] + at, bv[cur ^ 1] + at, nullptr));
-          next.push_back(MergeRun{at, a.len + b.len});
-          at += a.len + b.len;
-        }
-        runs.swap(next);
-        cur ^= 1;
-      }
-      if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
-      t1 = db_now();
-      T.merge += t1 - t0;
-      const uint64_t M = runs[0].len;
-      ++windows;
-      if (!classify) {
-        MFX_HIP(mfx_k_trio_hist(bk[cur] + runs[0].off, bv[cur] + runs[0].off, M, sa, grid, nullptr));
-        if (timing) MFX_HIP(hipStreamSynchronize(nullptr));
-        T.hist += db_now() - t1;
-        continue;
-      }
-      // ---- classify: set A behind the place of its writer's carry in the other buffer, set B behind its writer's in a buffer of its own
-      const uint64_t ca = wa->ck.size(), cb = wb->ck.size();
-      uint64_t n_out[2] = {0, 0};
-      if (M) {
-        const uint64_t mt = mfx_trio_tiles(M);
-        MFX_HIP(mfx_k_trio_classify(bk[cur] + runs[0].off, bv[cur] + runs[0].off, M, tc, d_tile, bk[cur ^ 1] + ca, bv[cur ^ 1] + ca, xk + cb, xv + cb, d_stats, nullptr));
-        MFX_HIP(hipMemcpyAsync(n_out, d_tile + 2 * mt, 16, hipMemcpyDeviceToHost, nullptr));
-        MFX_HIP(hipStreamSynchronize(nullptr));
-      }
-      t0 = db_now();
-      T.classify += t0 - t1;
-      if (n_out[0] + n_out[1] > M) return mfx_fail(MFX_E_HIP, "%s: the classified pairs of a window are damaged", who);
-      // (the merged run is read by now: its buffer is the scratch of both appends, one after the other -- an append has left the device when it returns)
-      if (n_out[0])
-        if (int rc = stream_append_device(wa, SA, bk[cur ^ 1], bv[cur ^ 1], n_out[0], bk[cur], cap * 12, who, "MFX_MERGE_RANGE")) return rc;
-      if (n_out[1])
-        if (int rc = stream_append_device(wb, SB, xk, xv, n_out[1], bk[cur], cap * 12, who, "MFX_MERGE_RANGE")) return rc;
-      T.write += db_now() - t0;
-    }
-    // what the windows held against what the files say: no partial result is handed out
-    for (uint32_t i = 0; i < n_in; ++i)
-      if (got[i] != ins[i]->h.n)
-        return mfx_fail(MFX_E_FORMAT, "'%s': the windows hold %lu of its %lu k-mers: the directory does not describe the blocks", paths[i], (unsigned long)got[i],
-                        (unsigned long)ins[i]->h.n);
-    return MFX_OK;
-  };
-  const uint64_t n_of[3] = {kind != TRIO_HISTOGRAM ? ins[0]->h.n : 0, kind != TRIO_HISTOGRAM ? ins[1]->h.n : 0, has_child ? ins[n_in - 1]->h.n : 0};
-  // ---- pass 1: the image
-  if (need_hist) {
-    if (P.max_pairs) {
-      if (int rc = run_pass(false)) return rc;
-      MFX_HIP(hipMemcpy(image.data(), d_img, (cells + 1) * 8, hipMemcpyDeviceToHost));
-    }
-    uint64_t sum = 0, row[3] = {0, 0, 0};
-    for (size_t i = 0; i < cells; ++i) { sum += image[i]; row[i / W] += image[i]; }
-    if (sum != image[cells]) return mfx_fail(MFX_E_HIP, "%s: the image sums to %lu, the pass counted %lu entries", who, (unsigned long)sum, (unsigned long)image[cells]);
-    if (row[2] != n_of[2] || row[0] > n_of[0] || row[1] > n_of[1] || n_of[0] - row[0] != n_of[1] - row[1])
-      return mfx_fail(MFX_E_HIP, "%s: the rows of the image hold %lu, %lu and %lu k-mers: not what databases of %lu, %lu and %lu k-mers give", who, (unsigned long)row[0],
-                      (unsigned long)row[1], (unsigned long)row[2], (unsigned long)n_of[0], (unsigned long)n_of[1], (unsigned long)n_of[2]);
-    dstats[MFX_TRIO_S_MAT_ONLY] = row[0]; dstats[MFX_TRIO_S_PAT_ONLY] = row[1]; dstats[MFX_TRIO_S_BOTH] = n_of[0] - row[0];
-  }
-  uint32_t autos[3] = {0, 0, 0};
-  uint64_t n_a = 0, n_b = 0;
-  double t_close = 0;
-  if (kind == TRIO_FULL) {
-    // ---- the automatic cutoffs: the valley of each row, by the rule -peak auto reads its peak with
-    static const char *const what[3] = {"cut_mat (merfin -cutmat <n>)", "cut_pat (merfin -cutpat <n>)", "cut_child (merfin -cutchild <n>)"};
-    for (uint32_t r = 0; r < 3; ++r) {
-      if (cuts[r] != 0) continue;
-      mfx_spectrum_peak_t pk;
-      const int rc = mfx_spectrum_peak(image.data() + r * W, o->max_mult, &pk);
-      if (rc == MFX_E_NODATA) {
-        const std::string why = mfx_last_error();
-        return mfx_fail(MFX_E_NODATA, "mfx_db_trio: no automatic cutoff for '%s': the histogram of %s shows no valley (%s); give %s", paths[r],
-                        r == 2 ? "its k-mers" : "the k-mers the other parent does not hold", why.c_str(), what[r]);
-      }
-      if (rc) return rc;
-      cuts[r] = pk.valley;
-      autos[r] = 1;
-    }
-    // ---- pass 2: the two sets
-    if (int rc = db_open_streamed(out_a, k, &wa)) return rc;
-    ga.w = wa;
-    if (int rc = db_open_streamed(out_b, k, &wb)) return rc;
-    gb.w = wb;
-    if (P.max_pairs) {
-      if (int rc = stream_dev_init(SA, wa, cap, who, "MFX_MERGE_RANGE")) return rc;
-      if (int rc = stream_dev_init(SB, wb, cap, who, "MFX_MERGE_RANGE")) return rc;
-      if (int rc = run_pass(true)) return rc;
-      std::vector<uint64_t> shards(MFX_TRIO_STAT_WORDS);      // the counters' copies, added up
-      MFX_HIP(hipMemcpy(shards.data(), d_stats, MFX_TRIO_STAT_WORDS * 8, hipMemcpyDeviceToHost));
-      for (uint32_t s = 0; s < (uint32_t)MFX_TRIO_NSTATS; ++s) {
-        dstats[s] = 0;
-        for (uint32_t c = 0; c < MFX_TRIO_STAT_SHARDS; ++c) dstats[s] += shards[c * MFX_TRIO_STAT_STRIDE + s];
-      }
-      if (dstats[MFX_TRIO_S_BOTH] + dstats[MFX_TRIO_S_MAT_ONLY] != n_of[0] || dstats[MFX_TRIO_S_BOTH] + dstats[MFX_TRIO_S_PAT_ONLY] != n_of[1])
-        return mfx_fail(MFX_E_HIP, "mfx_db_trio: %lu k-mers of both parents, %lu and %lu of one alone: not what databases of %lu and %lu k-mers give",
-                        (unsigned long)dstats[MFX_TRIO_S_BOTH], (unsigned long)dstats[MFX_TRIO_S_MAT_ONLY], (unsigned long)dstats[MFX_TRIO_S_PAT_ONLY],
-                        (unsigned long)n_of[0], (unsigned long)n_of[1]);
-    }
-    const double tc0 = db_now();
-    ga.w = nullptr;
-    if (int rc = mfx_db_writer_close(wa, &n_a)) return rc;       // (gb: the second writer goes with its spool)
-    gb.w = nullptr;
-    if (int rc = mfx_db_writer_close(wb, &n_b)) { unlink(out_a); return rc; }
-    t_close = db_now() - tc0;
-    if (img && need_hist) memcpy(img, image.data(), cells * 8);
-  } else if (kind == TRIO_HIST) {
-    memcpy(img, image.data(), cells * 8);
-  } else {
-    memcpy(img, image.data() + MFX_TRIO_CHILD * W, W * 8);       // (one row: the file stood in the child's role)
-  }
-  if (st) {
-    st->n_mat = n_of[0]; st->n_pat = n_of[1]; st->n_child = n_of[2];
-    st->n_both = dstats[MFX_TRIO_S_BOTH]; st->n_mat_only = dstats[MFX_TRIO_S_MAT_ONLY]; st->n_pat_only = dstats[MFX_TRIO_S_PAT_ONLY];
-    st->n_mat_only_cut = dstats[MFX_TRIO_S_MAT_CUT]; st->n_pat_only_cut = dstats[MFX_TRIO_S_PAT_CUT]; st->n_child_cut = dstats[MFX_TRIO_S_CHILD_CUT];
-    st->n_a = n_a; st->n_b = n_b; st->windows = windows;
-    if (kind == TRIO_FULL) {
-      st->cut_mat = cuts[0]; st->cut_pat = cuts[1]; st->cut_child = has_child ? cuts[2] : 0;
-      st->auto_mat = autos[0]; st->auto_pat = autos[1]; st->auto_child = has_child ? autos[2] : 0;
-    }
-    st->hist_pass = need_hist ? 1u : 0u;
-    st->t_read = T.read; st->t_decode = T.decode; st->t_merge = T.merge; st->t_hist = T.hist; st->t_classify = T.classify; st->t_write = T.write;
-    st->t_close = t_close; st->t_total = db_now() - t_begin;
-  }
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_trio(const char *mat_path, const char *pat_path, const char *child_path, const char *out_a, const char *out_b, const mfx_db_trio_opts *o, uint64_t *img,
-                           mfx_db_trio_stats *st) {
-  try { return trio_impl(TRIO_FULL, mat_path, pat_path, child_path, out_a, out_b, o, img, st); }      // (nothing leaves the C ABI as an exception)
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_trio: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_trio: %s", e.what()); }
-}
-
-extern "C" int mfx_db_trio_hist(const char *mat_path, const char *pat_path, const char *child_path, uint32_t max_mult, uint64_t *img, mfx_db_trio_stats *st, int device) {
-  const mfx_db_trio_opts o{0, 0, 0, max_mult, device};
-  try { return trio_impl(TRIO_HIST, mat_path, pat_path, child_path, nullptr, nullptr, &o, img, st); }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_trio_hist: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_trio_hist: %s", e.what()); }
-}
-
-extern "C" int mfx_db_histogram(const char *path, uint32_t max_mult, uint64_t *row, uint64_t *n_kmers, int device) {
-  const mfx_db_trio_opts o{0, 0, 0, max_mult, device};
-  mfx_db_trio_stats st;
-  if (n_kmers) *n_kmers = 0;
-  try {
-    if (int rc = trio_impl(TRIO_HISTOGRAM, nullptr, nullptr, path, nullptr, nullptr, &o, row, &st)) return rc;
-    if (n_kmers) *n_kmers = st.n_child;
-    return MFX_OK;
-  }
-  catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_histogram: out of memory"); }
-  catch (const std::exception &e) { return mfx_fail(MFX_E_IO, "mfx_db_histogram: %s", e.what()); }
-}
-
-extern "C" int mfx_db_histogram_write(const uint64_t *row, uint32_t max_mult, const char *path) {
-  if (!row || !path) return mfx_fail(MFX_E_INVAL, "mfx_db_histogram_write: null argument");
-  if (max_mult < MFX_SPEC_MIN_MULT || max_mult > MFX_SPEC_MAX_MULT)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_histogram_write: max_mult = %u is outside [%u, %u]", max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  mfx_file fh = mfx_open_writer(path, false);                    // compressor chosen by suffix (mfx_pipe.h)
-  if (!fh.f) return mfx_fail(MFX_E_IO, "mfx_db_histogram_write: cannot open '%s' for writing", path);
-  for (uint32_t m = 0; m <= max_mult; ++m)
-    if (row[m]) fprintf(fh.f, "%u\t%llu\n", m, (unsigned long long)row[m]);
-  if (mfx_close(fh)) return mfx_fail(MFX_E_IO, "mfx_db_histogram_write: writing '%s' failed", path);
-  return MFX_OK;
-}
-
-extern "C" int mfx_db_trio_host(const uint64_t *mat_keys, const uint32_t *mat_vals, uint64_t n_mat, const uint64_t *pat_keys, const uint32_t *pat_vals, uint64_t n_pat,
-                                const uint64_t *child_keys, const uint32_t *child_vals, uint64_t n_child, int has_child, uint32_t cut_mat, uint32_t cut_pat,
-                                uint32_t cut_child, uint32_t max_mult, uint64_t *a_keys, uint32_t *a_vals, uint64_t *n_a, uint64_t *b_keys, uint32_t *b_vals, uint64_t *n_b,
-                                uint64_t *img, mfx_db_trio_stats *st) {
-  if ((n_mat && (!mat_keys || !mat_vals || !a_keys || !a_vals)) || (n_pat && (!pat_keys || !pat_vals || !b_keys || !b_vals)) || (n_child && (!child_keys || !child_vals)) ||
-      !n_a || !n_b || !img || !st)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_trio_host: null argument");
-  if (max_mult < MFX_SPEC_MIN_MULT || max_mult > MFX_SPEC_MAX_MULT)
-    return mfx_fail(MFX_E_INVAL, "mfx_db_trio_host: max_mult = %u is outside [%u, %u]", max_mult, MFX_SPEC_MIN_MULT, MFX_SPEC_MAX_MULT);
-  if (cut_mat == 0 || cut_pat == 0 || (has_child && cut_child == 0) || (!has_child && n_child))
-    return mfx_fail(MFX_E_INVAL, "mfx_db_trio_host: the cutoffs are 1 at the least, and there are no child k-mers without a child");
-  try {
-    const uint64_t *const keys[3] = {mat_keys, pat_keys, child_keys};
-    const uint32_t *const vals[3] = {mat_vals, pat_vals, child_vals};
-    const uint64_t n[3] = {n_mat, n_pat, n_child};
-    mfx_trio_host_result R;
-    mfx_trio_host(keys, vals, n, mfx_trio_cuts{cut_mat, cut_pat, has_child ? cut_child : 1u, has_child != 0}, max_mult, R);
-    if (R.ak.size() > n_mat || R.bk.size() > n_pat) return mfx_fail(MFX_E_INVAL, "mfx_db_trio_host: the runs do not ascend strictly");
-    if (!R.ak.empty()) { memcpy(a_keys, R.ak.data(), R.ak.size() * 8); memcpy(a_vals, R.av.data(), R.av.size() * 4); }
-    if (!R.bk.empty()) { memcpy(b_keys, R.bk.data(), R.bk.size() * 8); memcpy(b_vals, R.bv.data(), R.bv.size() * 4); }
-    memcpy(img, R.img.data(), R.img.size() * 8);
-    memset(st, 0, sizeof(*st));
-    st->n_mat = n_mat; st->n_pat = n_pat; st->n_child = n_child;
-    st->n_both = R.stats[MFX_TRIO_S_BOTH]; st->n_mat_only = R.stats[MFX_TRIO_S_MAT_ONLY]; st->n_pat_only = R.stats[MFX_TRIO_S_PAT_ONLY];
-    st->n_mat_only_cut = R.stats[MFX_TRIO_S_MAT_CUT]; st->n_pat_only_cut = R.stats[MFX_TRIO_S_PAT_CUT]; st->n_child_cut = R.stats[MFX_TRIO_S_CHILD_CUT];
-    st->n_a = *n_a = R.ak.size(); st->n_b = *n_b = R.bk.size();
-    st->cut_mat = cut_mat; st->cut_pat = cut_pat; st->cut_child = has_child ? cut_child : 0;
-    return MFX_OK;
-  } catch (const std::bad_alloc &) { return mfx_fail(MFX_E_NOMEM, "mfx_db_trio_host: out of memory"); }
-}
 
 
 // ---------------------------------------------------------------------------

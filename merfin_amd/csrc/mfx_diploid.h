@@ -1,4 +1,4 @@
-// mfx_diploid.h -- the rule of mfx_db_diploid (mfx_db.cpp; kernels: mfx_diploid.hip): two haplotype assemblies against the reads in one sorted
+// mfx_diploid.h -- the rule of mfx_db_diploid (mfx_db_join.cpp; kernels: mfx_diploid.hip): two haplotype assemblies against the reads in one sorted
 // join.  Which class a k-mer of the union of the three databases belongs to, what it adds to the two images, to the counters and to the
 // completeness piece sums.  Written once for the host and the device (MFX_MERGE_HD), no HIP call, no library state: the kernels,
 // mfx_db_diploid_host and tools/native/diploid_sanitize.cpp run this text.

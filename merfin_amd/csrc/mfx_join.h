@@ -1,4 +1,4 @@
-// mfx_join.h -- the plain arithmetic of mfx_db_join_* (mfx_db.cpp) and of mfx_join_kernel (mfx_join.hip): how two ascending runs are cut
+// mfx_join.h -- the plain arithmetic of mfx_db_join_* (mfx_db_join.cpp) and of mfx_join_kernel (mfx_join.hip): how two ascending runs are cut
 // into tiles and lane shares of the merged order, and which lane owns a key that both runs hold.  The lane walk below is compiled for the
 // device and for the host from one text: the kernel runs it over a tile staged in LDS, mfx_join_host over plain arrays, tile after tile
 // and lane after lane -- tools/native/db_join_sanitize.cpp drives that under the sanitizers, tests/test_join_cpu.py through

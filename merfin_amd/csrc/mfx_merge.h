@@ -1,4 +1,4 @@
-// mfx_merge.h -- the plain host arithmetic of mfx_db_merge (mfx_db.cpp): the key windows the sorted inputs are merged by, and the slice of
+// mfx_merge.h -- the plain host arithmetic of mfx_db_merge (mfx_db_merge.cpp): the key windows the sorted inputs are merged by, and the slice of
 // an input's escape list that belongs to a window.  No HIP, no library state: tools/native/db_merge_sanitize.cpp drives it under the
 // sanitizers, tests/test_merge_plan_cpu.py through mfx_db_merge_plan.
 //
@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <vector>
 
-constexpr uint64_t MFX_MERGE_BLOCK = 4096;                     // (MFX_DELTA_BLOCK, mfx_delta.h: checked where both are seen, mfx_db.cpp)
+constexpr uint64_t MFX_MERGE_BLOCK = 4096;                     // (MFX_DELTA_BLOCK, mfx_delta.h: checked where both are seen, mfx_db_windows.cpp)
 constexpr uint64_t MFX_MERGE_RANGE_DEFAULT = 1ull << 26;       // pairs decoded per window, summed over the inputs
 constexpr uint32_t MFX_MERGE_MAX_INPUTS = 64;
 

@@ -1,4 +1,4 @@
-// mfx_trio.h -- the class rule of mfx_db_trio (mfx_db.cpp; kernels: mfx_trio.hip): which hap-mer set a k-mer of the parents' and the child's
+// mfx_trio.h -- the class rule of mfx_db_trio (mfx_db_trio.cpp; kernels: mfx_trio.hip): which hap-mer set a k-mer of the parents' and the child's
 // databases belongs to, the count written for it, and what it adds to the three histogram rows.  Written once for the host and the device
 // (MFX_MERGE_HD), no HIP call, no library state: the kernels, mfx_db_trio_host and tools/native/trio_sanitize.cpp run this text.
 //

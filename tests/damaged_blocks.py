@@ -20,7 +20,7 @@ from tests import delta_blocks as db
 
 BLOCK = db.BLOCK
 TEXT = {"order": "k-mers that do not ascend below the next block's first", "escape": "an escaped count that is not in the escape list",
-        "zero": "a count of zero"}                                # the words of mfx_db.cpp for each class
+        "zero": "a count of zero"}                                # the words of mfx_db_windows.cpp for each class
 
 
 # ---- the valid catalogue ----
@@ -52,7 +52,7 @@ def classify(path):
 
 
 def host_problem(path):
-    """what the host checks in front of the merge (mfx_db.cpp: flat_header_problem, merge_open_input, read_delta_directory) refuse in the
+    """what the host checks in front of the merge (mfx_db.cpp: flat_header_problem, read_delta_directory; mfx_db_windows.cpp: merge_open_input) refuse in the
     file, restated; None: they take it.  (db.decode_raw asserts the block count, the offsets and the file's length.)"""
     raw, k, flags, n, n_esc = db.read_flat(path)
     r = db.decode_raw(path, matched=False)

@@ -1,8 +1,8 @@
 """tests/damaged_blocks.py without a device: the valid catalogue decodes to its own arrays and shows no class, every damaged file shows
 exactly the class it is made for and differs from the file it is made from in the fields meant and in nothing else.
 
-What the host takes before a block reaches the decoder of -merge / -join (csrc/mfx_db.cpp: merge_check opens every input with
-merge_open_input, which applies flat_header_problem and read_delta_directory; -join calls merge_open_input itself):
+What the host takes before a block reaches the decoder of -merge / -join (csrc/mfx_db_windows.cpp: every call opens its inputs with
+merge_open_input, which applies mfx_db.cpp's flat_header_problem and read_delta_directory):
   header   magic MFXKMER1, 1 <= k <= 31, the delta flag (4) set and the placed flag (8) clear -- a placed, packed or plain file is refused;
            the canonical flag (1) and the other bits are not looked at; n_escape <= n and both within the file's size
   blocks   ceil(n / 4096) of them; kbits 0 .. 2k and vbits 2 .. 22 per block; offsets 8-byte aligned, each block exactly as long as its

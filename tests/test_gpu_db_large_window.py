@@ -8,7 +8,7 @@ every other test stays below about 36 000, so these paths run nowhere else:
   mfx_trio_hist_kernel   persistent workgroups, CUs x 4 of 256 positions, LDS bins kept from turn to turn: a workgroup takes a third turn
                      above 2 x (CUs x 4) x 256 merged positions
   mfx_join_kernel    persistent workgroups over tiles of MFX_JOIN_TILE = 2048 merged positions (db_join_grain), CUs x 4 of them for
-                     -completeness and CUs x 2 for -spectrum (csrc/mfx_db.cpp): with CUs x 4 x 2048 + 3 x 2048 < positions < 2 x CUs x 4 x
+                     -completeness and CUs x 2 for -spectrum (csrc/mfx_db_join.cpp): with CUs x 4 x 2048 + 3 x 2048 < positions < 2 x CUs x 4 x
                      2048 some workgroups of the completeness launch take a second turn and some do not, and the spectrum launch's take a
                      third
   the encoder        gets a window's survivors in one append: hundreds of blocks a launch instead of a handful

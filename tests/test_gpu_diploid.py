@@ -1,4 +1,4 @@
-"""mfx_db_diploid on the device (csrc/mfx_diploid.hip: the pair-run kernel and mfx_join_kernel with the two-assembly consumer; csrc/mfx_db.cpp:
+"""mfx_db_diploid on the device (csrc/mfx_diploid.hip: the pair-run kernel and mfx_join_kernel with the two-assembly consumer; csrc/mfx_db_join.cpp:
 the windows' driver).  Every result is compared `==` with three references: the numpy reference of tests/diploid_ref.py, the host walk
 (mfx_db_diploid_host: the text the kernels run) and the chain of existing calls the pass replaces -- db_merge([hap1, hap2]) -> M, then
 db_join_spectrum(reads, M) for the cn image and its entry count, and db_join_completeness on hap1, hap2 and M for the piece sums.  readK is

@@ -1,4 +1,4 @@
-"""mfx_db_join_completeness / mfx_db_join_spectrum on the device (csrc/mfx_join.hip: mfx_join_kernel; csrc/mfx_db.cpp: the windows' driver).
+"""mfx_db_join_completeness / mfx_db_join_spectrum on the device (csrc/mfx_join.hip: mfx_join_kernel; csrc/mfx_db_join.cpp: the windows' driver).
 Every result is compared `==` with two references: the oracle applied to the numpy arrays (oracle.pyoracle.completeness_piece per piece,
 tests/spectrum_ref.image) and the table route on a full index loaded from the same two files (Evaluator.completeness_pieces,
 Index.spectrum).  readK is an integer, so the fp64 sums are exact in any order and `==` is the right comparison.

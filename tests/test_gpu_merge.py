@@ -1,4 +1,4 @@
-"""mfx_db_merge on the device (csrc/mfx_merge.hip: decode, merge path, combine; csrc/mfx_db.cpp: the windows' driver and the streamed
+"""mfx_db_merge on the device (csrc/mfx_merge.hip: decode, merge path, combine; csrc/mfx_db_merge.cpp: the windows' driver and the streamed
 writer behind it).  Every result is compared byte for byte with mfx_db_write_flat of a numpy reference -- the inputs concatenated,
 np.unique with its inverse, np.add.at in 64 bits then clipped (np.maximum.at / np.minimum.at; presence counts for intersect), then the
 filter -- and loaded back through the table's decode kernel.  The sizes are the smallest at which the code can go wrong: inputs of 0, 1 and

@@ -1,5 +1,5 @@
 """mfx_db_trio, mfx_db_trio_hist and mfx_db_histogram on the device (csrc/mfx_trio.hip: the role tag, the histogram pass, the classify pass
-with its two compactions; csrc/mfx_db.cpp: the windows' driver and the two streamed writers).  Every output file is compared byte for byte
+with its two compactions; csrc/mfx_db_trio.cpp: the windows' driver and the two streamed writers).  Every output file is compared byte for byte
 with mfx_db_write_flat of the numpy reference (tests/trio_ref.py) and with the chain of existing calls (db_merge_except, db_merge,
 db_merge intersect), the image and the statistics with ==; the inputs are unchanged afterwards and a second run gives the same bytes.
 The sizes are the smallest at which the code can go wrong: databases of 0, 1 and around one block of 4096 k-mers up to five blocks, merged

@@ -1,8 +1,9 @@
 // The host side of mfx_db_join_* that no device enters, under AddressSanitizer + UBSan: the join kernel's tile and lane cuts and its ownership
 // rule as csrc/mfx_join.h restates them for the host (mfx_join_host: the text the kernel's lanes run) on random runs and on runs with an
-// equal pair on every lane and tile boundary, the window trimming (mfx_join_trim), and the input checks of mfx_db_join_* (csrc/mfx_db.cpp)
+// equal pair on every lane and tile boundary, the window trimming (mfx_join_trim), and the input checks of mfx_db_join_* (csrc/mfx_db_join.cpp, mfx_db_windows.cpp)
 // on files written by mfx_db_write_flat -- every such call must be refused with the code it names and the outputs untouched.
-//   hipcc -Xarch_host -fsanitize=address,undefined -g -O1 -std=c++17 tools/native/db_join_sanitize.cpp merfin_amd/csrc/mfx_db.cpp -Imerfin_amd/csrc -Iinclude \
+//   hipcc -Xarch_host -fsanitize=address,undefined -g -O1 -std=c++17 tools/native/db_join_sanitize.cpp merfin_amd/csrc/mfx_db.cpp merfin_amd/csrc/mfx_db_windows.cpp \
+//         merfin_amd/csrc/mfx_db_join.cpp -Imerfin_amd/csrc -Iinclude \
 //         -Lmerfin_amd -lmerfin_amd -Wl,-rpath,$PWD/merfin_amd -Wl,-rpath,/opt/rocm/lib -o /tmp/db_join_sanitize && ASAN_OPTIONS=detect_leaks=0 /tmp/db_join_sanitize /tmp/dbj
 #include <algorithm>
 #include <random>

@@ -1,7 +1,8 @@
 // The host side of mfx_db_merge that no device enters, under AddressSanitizer + UBSan: the window planner and the escape slicing
-// (csrc/mfx_merge.h) on random directories, and the input checks of mfx_db_merge (csrc/mfx_db.cpp) on files written by mfx_db_write_flat
+// (csrc/mfx_merge.h) on random directories, and the input checks of mfx_db_merge (csrc/mfx_db_merge.cpp, mfx_db_windows.cpp) on files written by mfx_db_write_flat
 // and then damaged -- every such call must end in MFX_E_FORMAT (or the refusal it names) with nothing written.
-//   hipcc -fsanitize=address,undefined -g -O1 -std=c++17 tools/native/db_merge_sanitize.cpp merfin_amd/csrc/mfx_db.cpp -Imerfin_amd/csrc -Iinclude \
+//   hipcc -fsanitize=address,undefined -g -O1 -std=c++17 tools/native/db_merge_sanitize.cpp merfin_amd/csrc/mfx_db.cpp merfin_amd/csrc/mfx_db_windows.cpp \
+//         merfin_amd/csrc/mfx_db_merge.cpp -Imerfin_amd/csrc -Iinclude \
 //         -Lmerfin_amd -lmerfin_amd -Wl,-rpath,$PWD/merfin_amd -Wl,-rpath,/opt/rocm/lib -o /tmp/db_merge_sanitize && ASAN_OPTIONS=detect_leaks=0 /tmp/db_merge_sanitize /tmp/dbm
 #include <algorithm>
 #include <random>
