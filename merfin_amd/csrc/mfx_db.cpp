@@ -809,7 +809,7 @@ int load_flat_delta(mfx_index *const *ixs, uint32_t nix, int fd, const char *pat
 
 }  // namespace
 
-// ---- for the staged load (mfx_api.cpp: mfx_db_stage) ----------------------------------------------------------------------
+// ---- for the staged load (mfx_index.cpp: mfx_db_stage) ----------------------------------------------------------------------
 // opens `path` if it is a delta-coded flat database and reads + checks its directory; MFX_E_FORMAT with *fd_out = -1 when it is
 // another kind of database (the caller then takes the ordinary load)
 int mfx_flat_delta_open(const char *path, int *fd_out, mfx_flat_delta_info *info, std::vector<uint64_t> &dir) {
@@ -1342,7 +1342,7 @@ extern "C" int mfx_db_write_flat_placed(const char *path, int k, const uint64_t 
   return db_guard("mfx_db_write_flat_placed", [&] { return mfx_db_write_flat_placed_impl(path, k, pkeys, values, n); });
 }
 
-// P of n canonical k-mers, on the host (mfx_place.h; the device form: mfx_db_place_keys in mfx_api.cpp)
+// P of n canonical k-mers, on the host (mfx_place.h; the device form: mfx_db_place_keys in mfx_index.cpp)
 void mfx_place_keys_host(int k, const uint64_t *kmers, uint64_t n, uint64_t *out, uint8_t *sbits_out) {      // sbits_out: k = 31 (out then holds P >> 1)
   par_blocks((n + 65535) / 65536, [&](uint64_t b) {
     for (uint64_t i = b * 65536, e = std::min<uint64_t>(n, i + 65536); i < e; ++i) {

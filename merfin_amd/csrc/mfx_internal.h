@@ -45,7 +45,7 @@ static inline hipError_t mfx_memset_now(void *p, int v, size_t n) {
 #endif
 }
 
-// flat-binary database -> table, read with parallel pread into the index's staging lanes (mfx_api.cpp)
+// flat-binary database -> table, read with parallel pread into the index's staging lanes (mfx_index.cpp)
 // vals_off == 0: the records at keys_off are PACKED (MFX_PACKED_VBITS), there is no counts array
 int  mfx_index_add_from_file(struct mfx_index *const *ixs, uint32_t nix, int fd, const char *path, uint64_t keys_off, uint64_t vals_off,
                              uint64_t n, int side, uint64_t minV, uint64_t maxV);
@@ -59,7 +59,7 @@ void mfx_index_ingest_release(struct mfx_index *ix);
 // the table's state after a load (probe-limit failures: MFX_E_FULL, damaged records, non-canonical k-mers); bumps ix->version
 int  mfx_index_check(struct mfx_index *ix);
 int  mfx_reads_claim_error(const struct mfx_index *ix, const char *who);     // MFX_E_INVAL: a claim into a k > 31 table after its read counter began
-// a delta-coded flat database opened for the staged load (mfx_db.cpp; mfx_api.cpp: mfx_db_stage)
+// a delta-coded flat database opened for the staged load (mfx_db.cpp; mfx_index.cpp: mfx_db_stage)
 struct mfx_flat_delta_info { int k = 0, placed = 0; uint64_t n = 0, n_escape = 0, nblocks = 0, escapes_off = 0, fsize = 0; };
 void mfx_place_keys_host(int k, const uint64_t *kmers, uint64_t n, uint64_t *out, uint8_t *sbits_out = nullptr);      // mfx_db.cpp: P (mfx_place.h) of canonical k-mers, host threads; k = 31: P >> 1 and the strand bits
 int  mfx_flat_delta_open(const char *path, int *fd_out, mfx_flat_delta_info *info, std::vector<uint64_t> &dir);
@@ -142,7 +142,7 @@ struct mfx_table_view {
   uint64_t  side_nlines;
 };
 
-struct mfx_ingest;              // pinned staging lanes of the host -> table pipeline (mfx_api.cpp)
+struct mfx_ingest;              // pinned staging lanes of the host -> table pipeline (mfx_index.cpp)
 struct WorkerPool;              // parked host threads (mfx_pool.h)
 
 struct mfx_index {
@@ -173,7 +173,7 @@ struct mfx_index {
   uint64_t  side_nlines = 0;    // compact: lines of the side table, which follows the nlines main lines in d_slots
   uint64_t  paths_token = 0;    // seq_only: the k-mers are those of a prepared VCF's PATHS (mfx_index_claim_paths), not a sequence's: the token of that call set
   uint32_t  seq_digest = 0;     // seq_only: content digest of the sequence the k-mers were claimed from (0: not recorded);
-                                // evaluating another sequence on it is refused (mfx_seq_digest32, mfx_api.cpp)
+                                // evaluating another sequence on it is refused (mfx_seq_digest32, mfx_seq.cpp)
   double    max_gb = 0;         // the -memory cap the table was created under (0: none): a table that grows honours it (mfx_reads_begin_all)
   // what a claiming read counter did to the table (mfx_index_growths): growths, their wall time, the rehash kernels' time and the bytes they read + wrote
   uint64_t  grow_count = 0, rehash_bytes = 0;
@@ -238,9 +238,9 @@ inline bool mfx_seq_planes_once(mfx_seq *s, uint64_t plane_words, Alloc alloc, R
 int mfx_seq_digest32(const mfx_seq *s, uint32_t *out);
 // refuses (MFX_E_INVAL) the evaluation of a sequence other than the one a sequence-only index was claimed from
 int mfx_check_seq_of_index(const mfx_index *ix, const mfx_seq *s, const char *who);
-extern thread_local bool t_mfx_path_lookup;       // the calling thread looks the variant modes' own path text up: a path-only index answers (mfx_api.cpp)
+extern thread_local bool t_mfx_path_lookup;       // the calling thread looks the variant modes' own path text up: a path-only index answers (mfx_seq.cpp)
 
-// The paths of a batch of variant clusters inside their packed text, for the device-side varMer::score (mfx_api.cpp:
+// The paths of a batch of variant clusters inside their packed text, for the device-side varMer::score (mfx_paths.cpp:
 // mfx_score_paths; kernel mfx_var_score_kernel): host arrays
 struct mfx_path_table {
   uint64_t        npaths = 0, nvals = 0;
@@ -293,7 +293,7 @@ int  mfx_claim_paths_finish(mfx_index *ix, uint64_t token);          // waits, c
 void mfx_claim_paths_release(int device, uint8_t *scratch);
 
 int mfx_seq_partial_error(const mfx_seq *s, const char *who);     // MFX_E_INVAL: the sequence object holds a part only
-int mfx_seq_ensure_ascii(const mfx_seq *s);      // unpacks the planes into d_bases if a packed upload left them newer (mfx_api.cpp)
+int mfx_seq_ensure_ascii(const mfx_seq *s);      // unpacks the planes into d_bases if a packed upload left them newer (mfx_seq.cpp)
 
 struct mfx_eval {
   const mfx_index *ix = nullptr;
@@ -325,7 +325,7 @@ struct mfx_eval {
   uint8_t  *h_stage[2] = {nullptr, nullptr};   // pinned staging of the streamed upload (pageable sources), kept between calls
   size_t    h_stage_bytes = 0;
   WorkerPool *pool = nullptr;                           // host threads parked between streamed runs (mfx_pool.h)
-  // device scratch of mfx_score_paths_trv (the variant modes score ~40 batches per run, one at a time: their ~20 arrays are carved out of one
+  // device scratch of mfx_score_paths / mfx_score_paths_trv (mfx_paths.cpp, laid out by mfx_var_arena.h; the variant modes score ~40 batches per run, one at a time: their ~20 arrays are carved out of one
   // allocation that is kept from batch to batch)
   uint8_t  *d_var_scratch = nullptr;
   uint64_t  var_scratch_bytes = 0;

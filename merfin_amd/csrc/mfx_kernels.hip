@@ -166,7 +166,7 @@ __device__ __forceinline__ void mfx_mod_place(uint64_t mz, uint32_t jo, uint64_t
 //   line  = (top * nlines) >> 32,   f = low 32 bits of top * nlines      -- two `top` of one line differ in f by >= nlines >= 2^qshift,
 //   fq    = f >> qshift,  qshift = floor(log2(nlines))                      so fq tells them apart in 32 - qshift bits
 //   F0    = {high bits of the minimizer : 2m - 32 | fq : 32 - qshift | strand : 1 | j : 2 | outer bases : 6}   <= 40 bits
-// (the host makes the table large enough for that: nlines >= 2^(2m - 31), mfx_api.cpp).  A slot in candidate line d of its k-mer
+// (the host makes the table large enough for that: nlines >= 2^(2m - 31), mfx_index.cpp).  A slot in candidate line d of its k-mer
 // holds F0 | d << 40 with d <= 2: (line, key field) <-> k-mer is one to one (mfx_q_invert is the way back, used by the export),
 // so a 42-bit compare is an exact match, and the all-ones word (d = 3) stays the empty slot.  A k-mer whose three candidate
 // lines are full lives in the side table under its full key (mfx_c_claim).  Everything else of the layout -- 16 slots per line,
@@ -3756,7 +3756,7 @@ __global__ __launch_bounds__(MFX_BLOCK) void mfx_pack_kernel(const uint8_t *base
 // every 32-base word of the padded buffer -- so that it does not depend on how the sequence is held (one byte per base or
 // packed planes), on letter case or on what the invalid bytes were.  A wrapping sum of per-word hashes: any launch shape
 // and any chunking give the same value.  A sequence-only index records the digest of the sequence it was claimed from and
-// evaluations of another sequence are refused (mfx_api.cpp: seq_digest32).
+// evaluations of another sequence are refused (mfx_seq.cpp: mfx_seq_digest32).
 __device__ __forceinline__ uint64_t mfx_double_bits(uint32_t v) {       // bit b of v -> bits 2b and 2b+1
   uint64_t x = v;
   x = (x | (x << 16)) & 0x0000FFFF0000FFFFULL;
@@ -4290,7 +4290,7 @@ hipError_t mfx_k_gather_rate(const void *table, uint64_t nlines, uint64_t *scrat
 }
 
 // ===========================================================================
-// launch wrappers (called from mfx_api.cpp, which is compiled as plain C++)
+// launch wrappers (called from the host files, which are compiled as plain C++)
 // ===========================================================================
 hipError_t mfx_k_table_init(mfx_slot *slots, uint64_t nslots, hipStream_t st) {
   mfx_table_init_kernel<<<4096, 256, 0, st>>>(slots, nslots);

@@ -10,7 +10,7 @@ from .binding import TILE, hist_words, result_from_counts
 
 def tile_table(lens):
     """[(contig, first start position, n positions)] in global tile order --
-    the same layout mfx_seq builds (csrc/mfx_api.cpp:seq_layout)."""
+    the same layout mfx_seq builds (csrc/mfx_seq.cpp:seq_layout)."""
     out = []
     for c, n in enumerate(lens):
         for p in range(0, n, TILE):

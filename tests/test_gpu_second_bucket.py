@@ -100,7 +100,7 @@ def _index(m, k, env, monkeypatch):
     lf = info["distinct"] / (info["bytes"] / 8.0)
     print("k = %d %r: %d distinct k-mers, load factor %.3f" % (k, env, info["distinct"], lf))
     # a quotient table (k > 21) has at least 2^(2 (k - 3) - 31) lines of 16 slots, whatever the load factor asked for (quot_min_lines in
-    # mfx_api.cpp: 128 lines at k = 22, 4 GB at k = 31): at k = 31 a world of this size cannot fill it, and the displaced queries of that
+    # mfx_index.cpp: 128 lines at k = 22, 4 GB at k = 31): at k = 31 a world of this size cannot fill it, and the displaced queries of that
     # route are those of the satellite array, whose k-mers share their home lines at any table size
     floor_slots = 16 << (2 * (k - 3) - 31) if k > 21 else 0
     if floor_slots < info["distinct"] / 0.5:

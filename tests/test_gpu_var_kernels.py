@@ -105,3 +105,53 @@ def test_the_debug_entries_refuse_tables_that_point_outside():
         ev.debug_score_paths_trv(b.host, t)
     with pytest.raises(m.MfxError):
         ev.debug_score_paths(B.PathTable(b"ACGT\n", [0], [9], [0], [0], [0]))
+
+
+def test_host_form_on_a_used_scratch():
+    """mfx_score_paths lays its batch out in the evaluator's scratch, as mfx_score_paths_trv does: on ONE evaluator the large
+    device-enumerated batch, then host batches of ten clusters whose text is shorter than one 4096-byte tile (what the larger batch
+    left behind their text and tables is still there), then a host batch whose text alone is longer than the whole first scratch (it
+    has to be made again).  Every score bit for bit, with and without totdk."""
+    import merfin_amd as m
+    w, ix, _ = setup(21, True)
+    ev = m.Evaluator(ix, m.KParams(vc.PEAK, w.probK, w.probP))          # its own evaluator: the scratch starts empty
+    b = vc.pack(binding(), w.clusters, w.scored, seed=21)
+    t = b.tables
+    vc.check_scores(b, *[ev.debug_score_paths_trv(b.host, t, need_dk=True)[n] for n in ("numM", "totdk")], "the large batch first")
+    # no more than the scratch it made: a quarter over the sum of its pieces (9 bytes per text byte and 3 tiles, 44 per slot, 12 per
+    # row, the tables, 256 bytes of rounding for each of 21 pieces)
+    scratch = 1.25 * (9 * t.text_end + 3 * 4096 + 256 + 44 * t.path_cap + 12 * t.row_cap + 16 + t.cl.nbytes + t.var.nbytes + t.al.nbytes
+                      + len(t.win) + len(t.alt) + 8 * len(t.cl) + 21 * 256)
+    ok = [i for i, x in enumerate(w.scored) if vc.status_of(w.clusters[i], x) == vc.OK]
+    pick = lambda idx: ([w.clusters[i] for i in idx], [w.scored[i] for i in idx])
+    size = lambda i: sum(len(p) + 1 for p in w.scored[i]["paths"])
+    ten = lambda at: [i for i in ok[at:] if size(i) <= 400][:10]         # ten clusters from ok[at] on whose paths fit in one tile together
+    for at in (0, len(ok) // 2, len(ok) - 40):
+        h = vc.pack(binding(), [], [], *pick(ten(at)), seed=3)
+        assert 0 < len(h.host.text) < 4096 and len(h.host.off) >= 10
+        for need_dk in (True, False):
+            vc.check_scores(h, *ev.debug_score_paths(h.host, need_dk=need_dk), "ten clusters from %d on a used scratch" % at, need_dk=need_dk)
+    one = sum(map(size, ok))
+    h = vc.pack(binding(), [], [], *pick(ok * (int(scratch) // one + 1)), seed=4)
+    assert len(h.host.text) > scratch
+    for need_dk in (True, False):
+        vc.check_scores(h, *ev.debug_score_paths(h.host, need_dk=need_dk), "a host batch beyond the first scratch", need_dk=need_dk)
+    h = vc.pack(binding(), [], [], *pick(ten(7)), seed=5)                   # and a short one again, on the grown scratch
+    vc.check_scores(h, *ev.debug_score_paths(h.host), "ten clusters on the grown scratch")
+
+
+def test_empty_calls_return_ok_and_write_nothing():
+    """no path (npaths == 0) and no text (len == 0): MFX_OK from both debug entry points, numM / totdk as the caller filled them"""
+    w, ix, ev = setup(21, True)
+    B = binding()
+    L = B.load_library()
+    none = B.TraverseTables(np.zeros(0, dtype=B.TRV_CLUSTER_DTYPE), np.zeros(0, dtype=B.TRV_VARIANT_DTYPE), np.zeros(0, dtype=B.TRV_ALLELE_DTYPE), b"", b"", 0, 0, 0)
+    for what, pt, text_end in (("npaths == 0", B.PathTable(b"ACGTACGTACGTACGTACGTACGTA\n"), 26), ("len == 0", B.PathTable(b"", [0, 0], [0, 0], [0, 0], [0, 0], [0, 1]), 0)):
+        for need_dk in (1, 0):
+            numM, totdk = np.full(4, 0xabcdabcd, dtype=np.uint32), np.full(4, -7.5)
+            out = [need_dk, B.C.c_void_p(numM.ctypes.data), B.C.c_void_p(totdk.ctypes.data)]
+            assert L.mfx_debug_score_paths(ev.h, *(pt.args() + out)) == 0, (what, L.mfx_last_error())
+            none.text_end = text_end
+            o, ptrs = B._trv_outputs(none)
+            assert L.mfx_debug_score_paths_trv(ev.h, *(pt.args() + none.args() + out + ptrs)) == 0, (what, L.mfx_last_error())
+            assert numM.tolist() == [0xabcdabcd] * 4 and totdk.tolist() == [-7.5] * 4, what

@@ -90,7 +90,7 @@ def test_the_minimizer_hash_is_a_bijection():
 def test_quotient_round_trip_at_the_smallest_and_at_ordinary_table_sizes(k):
     r = random.Random(k)
     t = ((k + 1) & 3) + 4
-    nmin = 1 << (2 * (k - 3) - 31)                                   # quot_min_lines (mfx_api.cpp)
+    nmin = 1 << (2 * (k - 3) - 31)                                   # quot_min_lines (mfx_index.cpp)
     for nl in (max(nmin, 1024), max(nmin, 1024) + 12345, max(nmin, 845_000_000), (1 << 32) - 17):
         qshift = nl.bit_length() - 1
         seen = {}
